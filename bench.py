@@ -49,7 +49,14 @@ also says how far the kernel is from its ALGORITHM and from the clock the chip r
                   file (profiles/sustained_clock.json); `frac` itself stays against the 2.4 GHz maximum
 The LSM row carries per_date_us (where the 10 us of a date go); cpu_baseline is timed on the metric's
 own configuration (10^6 x 252, GENERATE, all host cores) and price_check.full_config_generate compares
-the two prices on it.
+the two prices on it.  The files these file-sourced figures come from are cited once, in `sources`
+(each VALU entry's own pass is named beside its count in profiles/valu_insts.json); the line is printed without spaces, so that it stays
+short enough to be read whole.
+
+`--dump-outputs DIR` writes what the headline's last timed step computed, for REPLAY and GENERATE:
+the accumulator vector (all-reduced over the ranks) and its finalized price, std_error, sum_payoff,
+sumsq_payoff, as DIR/{replay,generate}_{accumulator,result}.npy (float64).  The inputs depend on the
+arguments only (seeds = global trajectory indices), so two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -93,6 +100,9 @@ def parse(argv=None):
     ap.add_argument("--nsteps", type=int, default=252, help="Euler steps per trajectory")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extra", action="store_true", help="skip everything but the headline lines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write what the headline's last timed step computed (REPLAY and GENERATE: the "
+                         "accumulator vector and the finalized result) as DIR/<name>.npy, float64")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--ramp-ms", type=float, default=30.0,
                     help="GPU time spent on the same kernel before the W warm-up steps, so that the "
@@ -363,6 +373,11 @@ def hbm_roofline(kernel, bytes_per_launch, ms, **extra):
     return r
 
 
+# Where the file-sourced figures of the VALU roofline entries come from: cited once, as the line's `sources`,
+# not in every entry — the line has to stay short enough to be read whole
+SOURCES = {}
+
+
 def valu_roofline(kernel, key, units, ms, table):
     """fp64-VALU issue fraction: SQ_INSTS_VALU x 4 cycles / (1024 SIMDs x 2.4 GHz x time)."""
     ent = table.get(key)
@@ -374,8 +389,10 @@ def valu_roofline(kernel, key, units, ms, table):
     ach = insts * VALU_CYCLES_PER_INST / (ms * 1e-3)
     r = {"bound": "valu", "kernel": kernel, "achieved": ach / 1e9, "peak": SIMD_CYCLES_PEAK / 1e9,
          "unit": "G SIMD-cycles/s", "frac": ach / SIMD_CYCLES_PEAK, "kernel_ms": ms,
-         "valu_insts_per_unit": ent["valu_insts_per_unit"], "unit_of_work": ent.get("unit"),
-         "insts_source": "profiles/valu_insts.json (" + ent.get("source", "rocprofv3 --pmc") + ")"}
+         "valu_insts_per_unit": ent["valu_insts_per_unit"], "unit_of_work": ent.get("unit")}
+    cite = "profiles/valu_insts.json (" + ent.get("source", "rocprofv3 --pmc") + ")"
+    if cite not in SOURCES.setdefault("insts_source", []):
+        SOURCES["insts_source"].append(cite)
     try:  # the clock the chip sustains under this kernel (a PMC pass on file): `frac` is against the 2.4 GHz maximum
         clk = json.load(open(os.path.join(ROOT, "profiles", "sustained_clock.json"))).get(key)
     except Exception:
@@ -383,14 +400,24 @@ def valu_roofline(kernel, key, units, ms, table):
     if clk:
         r["sustained_clock_mhz"] = clk["clock_mhz"]
         r["frac_at_sustained_clock"] = r["frac"] * 2400.0 / clk["clock_mhz"]
-        r["clock_source"] = "profiles/sustained_clock.json (rocprofv3 --pmc GRBM_GUI_ACTIVE / 8 XCDs / kernel duration; not collected in this run)"
+        SOURCES["clock_source"] = "profiles/sustained_clock.json (rocprofv3 --pmc GRBM_GUI_ACTIVE / 8 XCDs / kernel duration; not collected in this run)"
     fl = floor_insts().get(key)
     if fl:  # `frac` grades the kernel against its OWN instruction count; these two against its algorithm's
         r["floor_insts_per_unit"] = fl["floor_insts_per_unit"]
         r["frac_of_floor"] = fl["floor_insts_per_unit"] / ent["valu_insts_per_unit"]
         r["frac_vs_floor"] = r["frac"] * r["frac_of_floor"]
-        r["floor_source"] = "profiles/floor_insts.json (tools/floor_insts.py: essential operations of the shipped algorithm, DESIGN.md §8)"
+        SOURCES["floor_source"] = "profiles/floor_insts.json (tools/floor_insts.py: essential operations of the shipped algorithm, DESIGN.md §8)"
     return r
+
+
+def dump_outputs(out_dir, runs):
+    """--dump-outputs: for each timed run, the accumulator vector its last step left (all-reduced over the
+    ranks) and the result hh_mc_finalize makes of it — what a caller of hh_mc_accumulate receives."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, (acc, r) in runs.items():
+        np.save(os.path.join(out_dir, name + "_accumulator.npy"), np.asarray(acc, dtype=np.float64))
+        np.save(os.path.join(out_dir, name + "_result.npy"),  # price, std_error, sum_payoff, sumsq_payoff
+                np.array([r.price, r.std_error, r.sum_payoff, r.sumsq_payoff], dtype=np.float64))
 
 
 def single_process(args):
@@ -657,6 +684,8 @@ def main():
     dt_rep, kern_rep, acc_rep, ramp_ms = timed(model, cfg_rep, args.steps, args.warmup, args.ramp_ms)
     dt_gen, kern_gen, acc_gen, _ = timed(model, cfg_gen, args.steps, args.warmup, args.ramp_ms)
     res, res_gen = finalize(model, cfg_rep, acc_rep), finalize(model, cfg_gen, acc_gen)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"replay": (acc_rep, res), "generate": (acc_gen, res_gen)})
     total_path_steps = float(n_global) * n_steps
     value = total_path_steps * args.steps / dt_rep
     vt = valu_insts() if rank == 0 else {}
@@ -1115,7 +1144,9 @@ def main():
                       "oracle/hh_oracle.c with OpenMP over paths" % (reps, n_paths, n_steps, el)}
     for c_ in list(_ffi._contexts.values()):  # nothing of the library is left for the interpreter's exit to find
         c_.synchronize()
-    print(json.dumps(out), flush=True)
+    if SOURCES:
+        out["sources"] = SOURCES
+    print(json.dumps(out, separators=(",", ":")), flush=True)
 
 
 if __name__ == "__main__":
