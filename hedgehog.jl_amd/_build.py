@@ -47,8 +47,8 @@ def _run(cmd):
 
 
 def build_library(force: bool = False, extra_flags=(), out: str | None = None) -> str:
-    """extra_flags (-D… variants for A/B builds) go to every compile; they get their own object
-    directory so that the default build's objects stay valid."""
+    """extra_flags (-D… switches of a check build, tests/c/build_bk_check.py) go to every compile;
+    they get their own object directory so that the default build's objects stay valid."""
     lib = out or LIB
     if not force and not extra_flags and out is None and not is_stale():
         return lib

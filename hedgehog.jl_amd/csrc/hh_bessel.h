@@ -356,7 +356,8 @@ HH_MATH_FN LogMul besseli_logmul(const BesselTable& t, const BesselTable& t0, in
 // at a third of the instructions (two real Horner chains of 2 instead of 6 instructions per term, no atan2, no
 // second sine).  The Broadie–Kaya set-up needs exactly that: log I_ν(ν_κ) and the characteristic function at 0
 // (hh_bk.hip, cf_setup) are real evaluations that went through the complex code, a tenth of a trajectory's work.
-// tests/c/bessel_check.cpp compares the two on the host; tools/bk_ab.py on the device (same sums).
+// tests/c/bessel_check.cpp compares the two on the host; tests/test_gpu_bk_forms.py on the device (the
+// HH_BK_COMPLEX_SETUP build, bit for bit).
 struct LogMulRe {
   double lg, mul;
 };

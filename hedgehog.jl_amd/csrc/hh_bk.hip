@@ -41,7 +41,7 @@
 // 248 registers + scratch in the fall-back kernel.  Without the pass the literals stay where they are used:
 // the draw kernels take 92-120 registers with nothing in scratch (bk_draw_grid_kernel 0.173 -> 0.111 ms), and
 // the hot CF kernel — whose Horner constants are SGPR literals already — drops from 122 to 105 registers and
-// runs 2-5 % faster (interleaved A/B, tools/bk_ab.py: config 4 0.499 -> 0.474 ms, exact grid 1.736 -> 1.706).
+// runs 2-5 % faster (interleaved A/B: config 4 0.499 -> 0.474 ms, exact grid 1.736 -> 1.706).
 #include <algorithm>
 #include <atomic>
 #include <cmath>
@@ -60,12 +60,6 @@ constexpr double kPi = kBesselPi;
 constexpr double kTwoPi = kBesselTwoPi, kInvTwoPi = 0.15915494309189533577;
 constexpr double kInvPi = 0.31830988618379067154, kTwoOverPi = 0.63661977236758134308;
 
-#ifndef HH_BK_SLOTS
-#define HH_BK_SLOTS 1536
-#endif
-#ifndef HH_BK_HEAVY_GRID
-#define HH_BK_HEAVY_GRID 64
-#endif
 // Two switches of a TEST build (tests/c/build_bk_check.py, tests/test_gpu_bk_forms.py), which must give the shipped
 // build's samples bit for bit: the trajectory's two real-axis evaluations through the complex code (1), and the
 // bisection ladder run by the failed lane alone, statement for statement as sample_from_cf.jl:123-133 has it (1)
@@ -85,8 +79,8 @@ constexpr double kInvPi = 0.31830988618379067154, kTwoOverPi = 0.636619772367581
 // forced four; with a slot for it, 5 % faster (profiles/r05_h_bk_ab.txt).  A bitmap word is 64 slots, hence 192
 // per XCD.  256 terms of 8 bytes: 0.81 GB for 10^4 and for 10^8 trajectories alike).  A trajectory's terms are only needed again if its secant fails (2 % of
 // them): the ladder kernel re-derives those.
-constexpr int kSlots = HH_BK_SLOTS;
-constexpr int kHeavyGrid = HH_BK_HEAVY_GRID;   // workgroups of the tail kernel (169 registers: it holds the whole-trajectory
+constexpr int kSlots = 1536;
+constexpr int kHeavyGrid = 64;   // workgroups of the tail kernel (169 registers: it holds the whole-trajectory
                                   // code, idle with the reference's controls and the whole job when no series fits the
                                   // term cache; its first kRecStride workgroups then add the records)
 static_assert(kHeavyGrid <= kSlots, "the tail kernel's workgroup b uses slot b");
@@ -852,7 +846,7 @@ __device__ __forceinline__ double cdf_cached(const Terms& t, const double* col, 
 // abscissae, same CDF values, same decisions: the same ∫V, decision word and counters as the sequential loop, bit for
 // bit (HH_BK_SERIAL_LADDER builds that loop; tests/test_gpu_bk_forms.py holds the two against each other).
 // (What it costs: ~20 µs of the 0.32 ms at 10^6 trajectories, however it is organised — one wave per tile in batches
-// of 8, 4 or 2, every wave its own lanes with no barrier in front (tools/variants/bk_ladder_variants.inc), the
+// of 8, 4 or 2, every wave its own lanes with no barrier in front, the
 // walking wave at raised priority: all within 1 % of each other, profiles/r06_g_bk_ab_ladder_forms.txt, r06_k_*.
 // Half of it is the instructions — a turn is one CDF evaluation, ~250 of a tile's 39 000 wave-instructions — the rest
 // the three waves that wait.  The four small kernels this replaced cost 37 µs + their boundaries.)
@@ -862,14 +856,6 @@ __device__ __forceinline__ double cdf_cached(const Terms& t, const double* col, 
 // kept across the ladder, the CF kernel took 128 registers instead of 95 — four waves per SIMD instead of five).
 // thread of the r-th failed trajectory of the tile (r below their number)
 __device__ __forceinline__ uint32_t nth_failed(const LadderShared& sh, uint32_t r) {
-#if defined(HH_BK_LADDER_VARIANTS) && HH_BK_LADDER_PER_WAVE  // every wave its OWN failed lanes (bk_ladder_variants.inc)
-  {
-    const uint32_t wv = threadIdx.x >> 6;
-    unsigned long long mw = sh.fail[wv];
-    for (uint32_t i = 0; i < r; ++i) mw &= mw - 1ull;
-    return wv * 64u + (uint32_t)__ffsll((long long)mw) - 1u;
-  }
-#endif
   uint32_t w = 0;
 #pragma unroll
   for (uint32_t i = 0; i + 1 < (uint32_t)(kTile / 64); ++i) {
@@ -1078,9 +1064,6 @@ __device__ __forceinline__ void invert_phase(const BkArgs& p, const double* coef
     }
     root = sh.iv[tid];
   };
-#ifdef HH_BK_LADDER_VARIANTS  // A/B builds (tools/variants/bk_ladder_variants.inc): other organisations of the same walk
-#include "bk_ladder_variants.inc"
-#else
   if (__syncthreads_or(failed)) {  // (uniform) nearly every tile
 #if HH_BK_SERIAL_LADDER
     if (failed) lane_ladder(p, coef, col, sh);
@@ -1094,7 +1077,6 @@ __device__ __forceinline__ void invert_phase(const BkArgs& p, const double* coef
     __syncthreads();
     if (failed) after_ladder();
   }
-#endif
   if (live && !too_long) finish(root);
   const unsigned long long m_long = __ballot(too_long);
   if ((tid & 63) == 0) p.long_mask[(size_t)tile * (kTile / 64) + (tid >> 6)] = m_long;
@@ -1176,30 +1158,19 @@ __device__ __forceinline__ void give_slot(const BkArgs& p, uint32_t slot) {
 // (occupancy: at its 95 registers five workgroups are resident per CU; capped at 4 / 3 / 2 by an LDS pad the chain
 // takes +2 % / +12 % / +41 % at 10^6 trajectories and +4.5 % / +17 % / +53 % at 10^7 — profiles/r06_o_bk_occupancy.txt;
 // at 6 waves per SIMD it would have to spill 66 registers: 1.5 x the time, round 4)
-#ifndef HH_BK_CF_WAVES
-#define HH_BK_CF_WAVES 0
-#endif
-#if HH_BK_CF_WAVES
-#define HH_BK_CF_OCC __attribute__((amdgpu_waves_per_eu(HH_BK_CF_WAVES, HH_BK_CF_WAVES)))
-#else
-#define HH_BK_CF_OCC
-#endif
 // (DRAW: the trajectory's three draws are made (1: GENERATE) or read from the caller's buffer (2: REPLAY) here — the
 // one-shot law: a tile needs only its own draws, so a launch in front bought nothing but its own fill and drain.
 // 0: they are where a kernel in front left them — the variance kernel of a grid)
 template <int ORD, int DRAW = 0>
-__global__ __launch_bounds__(kTile) HH_BK_CF_OCC void bk_cf_kernel(const BkArgs p, const BkTables* __restrict__ tabs) {
+__global__ __launch_bounds__(kTile) void bk_cf_kernel(const BkArgs p, const BkTables* __restrict__ tabs) {
   const uint32_t tile = blockIdx.x, tid = threadIdx.x;
   const uint64_t path = (uint64_t)tile * kTile + tid;
   const bool live = path < p.n_paths;
   if (tile == 0 && tid == 0) __builtin_memcpy(p.args_dev, &p, sizeof(BkArgs));  // for bk_tail_kernel
-#if defined(HH_BK_TILE_STAMPS) && HH_BK_TILE_STAMPS  // diagnostic build (tools/bk_tile_timeline.py): when a tile ran, and where
-  const unsigned long long stamp0 = __builtin_amdgcn_s_memrealtime();  // 100 MHz
-#endif
   // The tiles of the LAST ROUND — the last occupants of the chip's workgroup slots — issue ahead of the older waves
   // beside them.  The hardware issues oldest-first, so at the end of a chain the final five waves of a SIMD finish one
   // after the other, the last of them alone at a quarter of the issue rate: a drain of 100 µs behind the last start
-  // (tools/bk_tile_timeline.py).  Raised, they take 75 instead of 96 µs each while the round before them gives way:
+  // (a tile timeline of the chain).  Raised, they take 75 instead of 96 µs each while the round before them gives way:
   // -1 … -3.5 % of the chain at every size from 1.1 to 6 rounds, -0.3 % at 30 (profiles/r06_ab_bk_last_round_priority.txt;
   // two rounds raised: +6 %, half a round: a third of the gain, priorities graded by start order or falling with a
   // tile's progress: no better; EVERY tile's priority falling with its progress: +9 % — oldest-first is right until the end).
@@ -1227,17 +1198,6 @@ __global__ __launch_bounds__(kTile) HH_BK_CF_OCC void bk_cf_kernel(const BkArgs 
   if (live && (p.root_form | p.bracket_form | p.caps) == 0) series_phase<ORD>(p, bt, path, col, p.cache_stride, sh, h, j_stop);
   invert_phase<ORD>(p, tabs->coef, tile, tid, path, live, col, sh, h, j_stop);
   give_slot(p, slot);
-#if defined(HH_BK_TILE_STAMPS) && HH_BK_TILE_STAMPS
-  // (in place of the series lengths of the tile's last three trajectories: start, end in 10 ns ticks, XCD | CU id)
-  __syncthreads();
-  if (tid == 0 && (uint64_t)(tile + 1) * kTile <= p.n_paths) {
-    uint32_t* out = p.diag + p.draw_stride + (size_t)tile * kTile + (kTile - 3);
-    out[0] = (uint32_t)stamp0;
-    out[1] = (uint32_t)__builtin_amdgcn_s_memrealtime();
-    out[2] = ((uint32_t)__builtin_amdgcn_s_getreg(((4 - 1) << 11) | (0 << 6) | 20) << 16) |  // XCC_ID
-             ((uint32_t)__builtin_amdgcn_s_getreg(((16 - 1) << 11) | (0 << 6) | 4) & 0xffffu);  // HW_ID: wave, simd, cu, sh, se
-  }
-#endif
 }
 
 // Tail kernel, kHeavyGrid workgroups behind the CF kernel.

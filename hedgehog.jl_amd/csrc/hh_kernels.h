@@ -60,7 +60,7 @@ struct SimArgs {
   uint64_t path_offset;
   uint32_t n_steps;
   uint32_t n_tiles;       // workgroups of the launch = records it leaves (sim_records)
-  uint32_t tail_from;     // REPLAY: tiles from here on pipeline deeper (the grid's tail)
+  uint32_t tail_from;     // unused (0); kept so that the argument layout of every kernel stays as it is
   const uint64_t* seeds;  // device
   const double* replay;   // device, tile-major
   double* terminal;       // device or nullptr
@@ -110,10 +110,7 @@ struct BkTableKey {
 };
 
 // several payoffs on ONE set of terminal samples (basket.jl:35-38, same-expiry payoffs)
-#ifndef HH_BASKET_CHUNK
-#define HH_BASKET_CHUNK 4096
-#endif
-constexpr int kBasketChunk = HH_BASKET_CHUNK;  // trajectories per workgroup of basket_payoff_kernel
+constexpr int kBasketChunk = 4096;  // trajectories per workgroup of basket_payoff_kernel
 struct BasketArgs {
   const double* terminal;    // [n_paths] (+ [n_paths] mirrored)
   const double* terminal_d;  // [P][n_total] or nullptr
@@ -135,12 +132,8 @@ inline uint32_t tiles_for(uint64_t n_paths) { return (uint32_t)((n_paths + kTile
 // chip always has >= 2048 workgroups to run and the reducer at most a few thousand records to add.  The form is
 // a function of the shard's n_paths alone, so a result is reproducible for a given (n_paths, sharding) as
 // everywhere else.
-#ifndef HH_EXACT_PAIRS_SMALL
-#define HH_EXACT_PAIRS_SMALL 4
-#endif
 constexpr int kExactPairs = 8, kExactPairsHuge = 64;
-constexpr int kExactPairsSmall = HH_EXACT_PAIRS_SMALL;  // below 2048·512·8 trajectories (hh_kernels.hip says why)
-// (defined in hh_kernels.hip: $HEDGEHOG_MC_EXACT_PAIRS overrides it for a measurement — tools/exact_pairs_ab.py)
+constexpr int kExactPairsSmall = 4;  // below 2048·512·8 trajectories (profiles/r06_c_exact_pairs_ab.txt)
 int exact_pairs_per_lane(uint64_t n_paths);
 inline uint32_t exact_records(uint64_t n_paths) {
   const uint64_t per = 512ull * (uint64_t)exact_pairs_per_lane(n_paths);

@@ -12,7 +12,6 @@
 // register pipeline; GENERATE draws them in registers from Philox keyed by the trajectory seed.
 // Every workgroup leaves one record of partial sums; a second tiny kernel adds the records in a
 // fixed order, so results are bit-reproducible for a given (n_paths, sharding).
-#include <cstdlib>
 #include <type_traits>
 
 #include "hh_sim.h"
@@ -25,122 +24,70 @@ namespace hh {
 // ------------------------------------------------------------------------------------------
 
 // The shape of the REPLAY pipeline, as measured (profiles/r02_a_replay_occupancy_ab.txt,
-// r02_b_replay_shape_ab.txt, r02_d_replay_counted_waits_ab.txt).  The A/B builds of tools/tune_replay.py
-// (-DHH_REPLAY_VARIANTS -Itools/variants) override these with -D and add the experiment paths that did not
-// ship — two trajectories per lane, the per-wave LDS-DMA ring, the occupancy pad, the antithetic pair
-// split over two lanes — from tools/variants/; this translation unit holds what ships.
-#ifdef HH_REPLAY_VARIANTS
-#include "replay_knobs.h"
-#endif
-#ifndef HH_REPLAY_CHUNK_PRICE
-#define HH_REPLAY_CHUNK_PRICE 4   // steps per register chunk, price-only kernel …
-#endif
-#ifndef HH_REPLAY_CHUNK_PPT1
-#define HH_REPLAY_CHUNK_PPT1 4    // … antithetic and dual-partial kernels (one trajectory per lane: 0.608 vs 0.627 ms
-#endif                            //   antithetic, 0.597 vs 0.611 ms one carried derivative, against two per lane)
-#ifndef HH_REPLAY_CHUNK_TAIL
-#define HH_REPLAY_CHUNK_TAIL 4    // … and of the price-only kernel's last HH_REPLAY_TAIL_TILES workgroups
-#endif
-#ifndef HH_REPLAY_TAIL_TILES
-#define HH_REPLAY_TAIL_TILES 512
-#endif
-#ifndef HH_REPLAY_COUNTED
-#define HH_REPLAY_COUNTED 1       // steady-state loads unguarded, so that the compiler can COUNT its waits
-#endif
+// r02_b_replay_shape_ab.txt, r02_d_replay_counted_waits_ab.txt).  The experiment paths that did not ship — two
+// trajectories per lane, the per-wave LDS-DMA ring, the occupancy pad, the antithetic pair split over two
+// lanes — were measured there; their code is in the history.
+constexpr int kReplayChunk = 4;  // steps per register chunk, every kernel and every workgroup (one trajectory per
+                                 //   lane: 0.608 vs 0.627 ms antithetic, 0.597 vs 0.611 ms one carried derivative,
+                                 //   against two per lane; 8 steps in the grid's last workgroups: 0.5766 vs 0.5780 ms,
+                                 //   noise — docs/HISTORY.md, round 2)
 // Occupancy of the REPLAY kernels.  HBM delivers most when a CU runs few concurrent 1 MB streams
 // (tools/ubench/hbm_read_sweep.hip), so the REPLAY variants are held BELOW what their register count
 // would allow — by the compiler's own occupancy control, amdgpu_waves_per_eu(1, max): the kernel
 // descriptor then reserves ⌊512 / max⌋ registers per lane and the hardware admits at most `max`
 // waves per SIMD, whatever else the kernel declares.
-#ifndef HH_REPLAY_MINW
-#define HH_REPLAY_MINW 1
-#endif
-#ifndef HH_REPLAY_MAXW
-#define HH_REPLAY_MAXW 2          // price-only: 2 waves per SIMD = 2 workgroups of 256 threads = 8 waves per CU
-#endif
-#ifndef HH_REPLAY_MAXW_DUAL
-#define HH_REPLAY_MAXW_DUAL 3     // one carried derivative: 0.597 ms at 3 waves per SIMD against 0.646 at 2
-#endif
-#ifndef HH_REPLAY_MAXW_DUAL_WIDE
-#define HH_REPLAY_MAXW_DUAL_WIDE HH_REPLAY_MAXW_DUAL  // two or more carried derivatives
-#endif
-#ifndef HH_REPLAY_MAXW_ANTI
-#define HH_REPLAY_MAXW_ANTI 8     // antithetic: indifferent (0.629 vs 0.625 ms), left at the register limit
-#endif
+constexpr int kReplayMaxWaves = 2;      // price-only: 2 waves per SIMD = 2 workgroups of 256 threads = 8 waves per CU
+constexpr int kReplayMaxWavesDual = 3;  // carried derivatives: 0.597 ms at 3 waves per SIMD against 0.646 at 2
+constexpr int kReplayMaxWavesAnti = 8;  // antithetic: indifferent (0.629 vs 0.625 ms), left at the register limit
 
 constexpr int replay_max_waves(bool replay, bool anti, int p) {
-  return !replay ? 8 : anti ? HH_REPLAY_MAXW_ANTI : p > 1 ? HH_REPLAY_MAXW_DUAL_WIDE : p > 0 ? HH_REPLAY_MAXW_DUAL : HH_REPLAY_MAXW;
+  return !replay ? 8 : anti ? kReplayMaxWavesAnti : p > 0 ? kReplayMaxWavesDual : kReplayMaxWaves;
 }
-template <class M, int P, bool REPLAY, bool ANTI, int PPT, int RING, bool PIPE>
-__global__ __launch_bounds__(kTile / PPT)
-__attribute__((amdgpu_waves_per_eu(REPLAY ? HH_REPLAY_MINW : 1,
-                                   replay_max_waves(REPLAY, ANTI, P)))) void euler_kernel(
-    const SimArgs<P> a) {
+template <class M, int P, bool REPLAY, bool ANTI>
+__global__ __launch_bounds__(kTile)
+__attribute__((amdgpu_waves_per_eu(1, replay_max_waves(REPLAY, ANTI, P)))) void euler_kernel(const SimArgs<P> a) {
   constexpr int NC = M::NCOMP;
   using State = typename M::State;
-  using Vec = typename VecOf<PPT>::type;
 
   const uint32_t tile = blockIdx.x;
   const uint32_t tid = threadIdx.x;
-  const uint64_t path0 = (uint64_t)tile * kTile + (uint64_t)tid * PPT;
+  const uint64_t path = (uint64_t)tile * kTile + tid;
   const uint32_t n_steps = a.n_steps;
 
-  State st[PPT];
-  State sa[ANTI ? PPT : 1];
-#pragma unroll
-  for (int j = 0; j < PPT; ++j) {
-    M::init(st[j], a);
-    if constexpr (ANTI) M::init(sa[j], a);
-  }
+  State st, sa;
+  M::init(st, a);
+  if constexpr (ANTI) M::init(sa, a);
 
   if constexpr (REPLAY) {
     // the tile's increments: element (step, comp, lane) at ((step*NC + comp)*256 + lane)
-    const double* __restrict__ base =
-        a.replay + (size_t)tile * n_steps * NC * kTile + (size_t)tid * PPT;
-    // steps per chunk: the price-only kernel (one trajectory per lane) moves 4 steps at a time
-#ifdef HH_REPLAY_VARIANTS
-    constexpr int kChunk = (P == 0 && !ANTI && RING == 0) ? HH_REPLAY_CHUNK_PRICE : (PPT == 1 ? HH_REPLAY_CHUNK_PPT1 : HH_REPLAY_CHUNK);
-#else
-    constexpr int kChunk = (P == 0 && !ANTI) ? HH_REPLAY_CHUNK_PRICE : HH_REPLAY_CHUNK_PPT1;
-#endif
+    const double* __restrict__ base = a.replay + (size_t)tile * n_steps * NC * kTile + tid;
     // Two register chunks, load(B) || compute(A), with the occupancy capped by amdgpu_waves_per_eu (see
-    // HH_REPLAY_MAXW above): 8 waves per CU for the price-only kernel, 12 for the dual-partial kernels,
-    // uncapped for the antithetic one (measurements: DESIGN.md §5, tools/tune_replay.py,
-    // tools/replay_sizes.py, tools/ubench/hbm_read_sweep.hip).
-#ifdef HH_REPLAY_VARIANTS
-#include "replay_lds_ring.inc"  // if constexpr (RING > 0 && PPT == 2) { the per-wave LDS-DMA ring } else
-#endif
-    {
-#ifdef HH_REPLAY_VARIANTS
-#include "replay_occupancy_pad.inc"
-#endif
-    // The last workgroups of a grid run while the chip empties: fewer streams are open, so each has
-    // to keep more bytes in flight to hold the bandwidth up — they pipeline HH_REPLAY_CHUNK_TAIL steps
-    // per chunk instead of kChunk (registers are there: the occupancy cap leaves a wave 256).
-    auto pipeline = [&](auto depth) {
-      constexpr int CH = decltype(depth)::value;
-      Vec X[CH][NC], Y[CH][NC];
-      auto ld = [&](Vec(&buf)[CH][NC], uint32_t s0) {
-#pragma unroll
+    // kReplayMaxWaves above): 8 waves per CU for the price-only kernel, 12 for the dual-partial kernels,
+    // uncapped for the antithetic one (measurements: DESIGN.md §5, tools/replay_sizes.py,
+    // tools/ubench/hbm_read_sweep.hip).
+    // (a lambda called in place: the compiler inlines it late, after the step loops have taken their shape —
+    // written straight into the kernel, the same source is scheduled differently and grows the price-only
+    // kernel by ~80 instructions)
+    [&] {
+      constexpr int CH = kReplayChunk;
+      double X[CH][NC], Y[CH][NC];
+      auto ld = [&](double(&buf)[CH][NC], uint32_t s0) {
+  #pragma unroll
         for (int u = 0; u < CH; ++u) {
           if (s0 + u < n_steps) {
-#pragma unroll
-            for (int c = 0; c < NC; ++c)
-              buf[u][c] = stream_load<Vec>(base + ((size_t)(s0 + u) * NC + c) * kTile);
+  #pragma unroll
+            for (int c = 0; c < NC; ++c) buf[u][c] = stream_load(base + ((size_t)(s0 + u) * NC + c) * kTile);
           }
         }
       };
-      auto go = [&](const Vec(&buf)[CH][NC], uint32_t s0) {
-#pragma unroll
+      auto go = [&](const double(&buf)[CH][NC], uint32_t s0) {
+  #pragma unroll
         for (int u = 0; u < CH; ++u) {
           if (s0 + u < n_steps) {
-#pragma unroll
-            for (int j = 0; j < PPT; ++j) {
-              const double d1 = VecOf<PPT>::get(buf[u][0], j);
-              const double d2 = NC > 1 ? VecOf<PPT>::get(buf[u][NC - 1], j) : 0.0;
-              M::step(st[j], a, d1, d2);
-              if constexpr (ANTI) M::step(sa[j], a, -d1, -d2);  // montecarlo.jl:258: -W
-            }
+            const double d1 = buf[u][0];
+            const double d2 = NC > 1 ? buf[u][NC - 1] : 0.0;
+            M::step(st, a, d1, d2);
+            if constexpr (ANTI) M::step(sa, a, -d1, -d2);  // montecarlo.jl:258: -W
           }
         }
       };
@@ -149,27 +96,23 @@ __attribute__((amdgpu_waves_per_eu(REPLAY ? HH_REPLAY_MINW : 1,
       // and waits for ALL of them (s_waitcnt vmcnt(0)/(1) right after issuing Y) — a wave then never
       // overlaps its own loads with its own arithmetic.  Unguarded, the wait is vmcnt(CH·NC): X has
       // landed, Y stays in flight behind the arithmetic of X.
-      auto ldf = [&](Vec(&buf)[CH][NC], uint32_t s0) {
-#pragma unroll
+      auto ldf = [&](double(&buf)[CH][NC], uint32_t s0) {
+  #pragma unroll
         for (int u = 0; u < CH; ++u)
-#pragma unroll
-          for (int c = 0; c < NC; ++c)
-            buf[u][c] = stream_load<Vec>(base + ((size_t)(s0 + u) * NC + c) * kTile);
+  #pragma unroll
+          for (int c = 0; c < NC; ++c) buf[u][c] = stream_load(base + ((size_t)(s0 + u) * NC + c) * kTile);
       };
-      auto gof = [&](const Vec(&buf)[CH][NC]) {
-#pragma unroll
+      auto gof = [&](const double(&buf)[CH][NC]) {
+  #pragma unroll
         for (int u = 0; u < CH; ++u) {
-#pragma unroll
-          for (int j = 0; j < PPT; ++j) {
-            const double d1 = VecOf<PPT>::get(buf[u][0], j);
-            const double d2 = NC > 1 ? VecOf<PPT>::get(buf[u][NC - 1], j) : 0.0;
-            M::step(st[j], a, d1, d2);
-            if constexpr (ANTI) M::step(sa[j], a, -d1, -d2);  // montecarlo.jl:258: -W
-          }
+          const double d1 = buf[u][0];
+          const double d2 = NC > 1 ? buf[u][NC - 1] : 0.0;
+          M::step(st, a, d1, d2);
+          if constexpr (ANTI) M::step(sa, a, -d1, -d2);  // montecarlo.jl:258: -W
         }
       };
       uint32_t s = 0;
-      if (HH_REPLAY_COUNTED && n_steps >= 2u * CH) {
+      if (n_steps >= 2u * CH) {
         ldf(X, 0);
         while (s + 3u * CH <= n_steps) {  // chunks s, s+CH and s+2CH are full
           ldf(Y, s + CH);
@@ -184,7 +127,7 @@ __attribute__((amdgpu_waves_per_eu(REPLAY ? HH_REPLAY_MINW : 1,
         ld(X, s + CH);
         go(Y, s);
         go(X, s + CH);
-      } else {  // short runs (and -DHH_REPLAY_COUNTED=0, the all-guarded form, for A/B)
+      } else {  // short runs
         ld(X, 0);
         while (s < n_steps) {
           ld(Y, s + CH);
@@ -196,45 +139,31 @@ __attribute__((amdgpu_waves_per_eu(REPLAY ? HH_REPLAY_MINW : 1,
           s += CH;
         }
       }
-    };
-    constexpr int kTail = (P == 0 && !ANTI && PPT == 1) ? HH_REPLAY_CHUNK_TAIL : kChunk;
-    if (kTail != kChunk && tile >= a.tail_from)
-      pipeline(std::integral_constant<int, kTail>{});
-    else
-      pipeline(std::integral_constant<int, kChunk>{});
-    }
+    }();
   } else {
-    uint64_t key[PPT];
-#pragma unroll
-    for (int j = 0; j < PPT; ++j) key[j] = (path0 + j < a.n_paths) ? a.seeds[path0 + j] : 0ull;
+    const uint64_t key = path < a.n_paths ? a.seeds[path] : 0ull;
 
     if constexpr (NC == 2) {
       for (uint32_t s = 0; s < n_steps; ++s) {
-#pragma unroll
-        for (int j = 0; j < PPT; ++j) {
-          double z1, z2;
-          normal_pair(key[j], s, 0u, 0u, kDomEuler, z1, z2);
-          const double d1 = a.sqrt_dt * z1;
-          const double d2 = a.sqrt_dt * fma(a.rho, z1, a.rho_c * z2);
-          M::step(st[j], a, d1, d2);
-          if constexpr (ANTI) M::step(sa[j], a, -d1, -d2);
-        }
+        double z1, z2;
+        normal_pair(key, s, 0u, 0u, kDomEuler, z1, z2);
+        const double d1 = a.sqrt_dt * z1;
+        const double d2 = a.sqrt_dt * fma(a.rho, z1, a.rho_c * z2);
+        M::step(st, a, d1, d2);
+        if constexpr (ANTI) M::step(sa, a, -d1, -d2);
       }
     } else {
       // scalar noise: one Philox block feeds two consecutive steps
       for (uint32_t s = 0; s < n_steps; s += 2) {
-#pragma unroll
-        for (int j = 0; j < PPT; ++j) {
-          double z1, z2;
-          normal_pair(key[j], s >> 1, 0u, 0u, kDomEuler, z1, z2);
-          const double d1 = a.sqrt_dt * z1;
-          M::step(st[j], a, d1, 0.0);
-          if constexpr (ANTI) M::step(sa[j], a, -d1, 0.0);
-          if (s + 1 < n_steps) {
-            const double d2 = a.sqrt_dt * z2;
-            M::step(st[j], a, d2, 0.0);
-            if constexpr (ANTI) M::step(sa[j], a, -d2, 0.0);
-          }
+        double z1, z2;
+        normal_pair(key, s >> 1, 0u, 0u, kDomEuler, z1, z2);
+        const double d1 = a.sqrt_dt * z1;
+        M::step(st, a, d1, 0.0);
+        if constexpr (ANTI) M::step(sa, a, -d1, 0.0);
+        if (s + 1 < n_steps) {
+          const double d2 = a.sqrt_dt * z2;
+          M::step(st, a, d2, 0.0);
+          if constexpr (ANTI) M::step(sa, a, -d2, 0.0);
         }
       }
     }
@@ -243,15 +172,10 @@ __attribute__((amdgpu_waves_per_eu(REPLAY ? HH_REPLAY_MINW : 1,
   double acc[4 + P];
 #pragma unroll
   for (int i = 0; i < 4 + P; ++i) acc[i] = 0.0;
-#pragma unroll
-  for (int j = 0; j < PPT; ++j) finish_path<P, ANTI>(st[j], sa[ANTI ? j : 0], a, path0 + j, acc);
-  block_reduce_publish<4 + P, kTile / PPT / 64, 2>(acc, a.records + (size_t)tile * kRecStride, a.accum != nullptr, a.map.n > 0);
-  if (a.accum && reduces_records(tile, a)) finish_records<kTile / PPT, P>(a);
+  finish_path<P, ANTI>(st, sa, a, path, acc);
+  block_reduce_publish<4 + P, kTile / 64, 2>(acc, a.records + (size_t)tile * kRecStride, a.accum != nullptr, a.map.n > 0);
+  if (a.accum && reduces_records(tile, a)) finish_records<kTile, P>(a);
 }
-
-#ifdef HH_REPLAY_VARIANTS
-#include "anti_pair_split.inc"  // euler_pair_split_kernel (-DHH_ANTI_SPLIT=1)
-#endif
 
 // ------------------------------------------------------------------------------------------
 // Euler–Maruyama on the REFERENCE's noise layout: path-major REPLAY
@@ -279,21 +203,13 @@ __attribute__((amdgpu_waves_per_eu(REPLAY ? HH_REPLAY_MINW : 1,
 //
 // Needs S to be a multiple of 16 bytes (n_steps·NCOMP even: every Heston shape); the one remaining
 // case (lognormal, odd n_steps) goes through replay_pack_kernel + the tile-major kernel.
-#ifndef HH_PM_MAXW
-#define HH_PM_MAXW 2   // waves per SIMD of the path-major kernel: 0.622 ms at 2, 0.632-0.634 at 3, 4, 5 (profiles/r03_a_path_major_ab.txt)
-#endif
-#ifndef HH_PM_NT
-#define HH_PM_NT 1
-#endif
-#ifndef HH_PM_PIECES
-#define HH_PM_PIECES 8  // 16-byte pieces per row and chunk: 8 = one 128-byte line, 16 = two
-#endif
-constexpr int kPmPieces = HH_PM_PIECES;
+constexpr int kPmMaxWaves = 2;  // waves per SIMD of the path-major kernel: 0.622 ms at 2, 0.632-0.634 at 3, 4, 5 (profiles/r03_a_path_major_ab.txt)
+constexpr int kPmPieces = 8;    // 16-byte pieces per row and chunk: 8 = one 128-byte line, 16 = two
 static_assert(kPmPieces == 8 || kPmPieces == 16, "one or two 128-byte lines per row and chunk");
 
 template <class M, int P, bool ANTI>
 __global__ __launch_bounds__(kTile)
-__attribute__((amdgpu_waves_per_eu(1, HH_PM_MAXW))) void euler_pm_kernel(const SimArgs<P> a) {
+__attribute__((amdgpu_waves_per_eu(1, kPmMaxWaves))) void euler_pm_kernel(const SimArgs<P> a) {
   constexpr int NC = M::NCOMP;
   constexpr int NP = kPmPieces;            // pieces per row and chunk
   constexpr int ROWB = NP * 16;            // bytes of a row of the LDS image
@@ -365,7 +281,7 @@ __attribute__((amdgpu_waves_per_eu(1, HH_PM_MAXW))) void euler_pm_kernel(const S
       }
       __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
                                        (__attribute__((address_space(3))) void*)&image[wave][i * 128],
-                                       16, 0, HH_PM_NT ? 2 : 0);
+                                       16, 0, 2);  // nontemporal: a read-once stream
       src[i] += ROWB;
     }
   };
@@ -527,10 +443,7 @@ __global__ __launch_bounds__(kTile) void wiener_fill_kernel(double rho, double r
   }
 }
 
-#ifndef HH_PACK_STEPS
-#define HH_PACK_STEPS 4  // steps per workgroup of the path-major -> tile-major repack (4.6 TB/s read+write; 8: 4.2, 16: 2.8)
-#endif
-constexpr int kPackSteps = HH_PACK_STEPS;
+constexpr int kPackSteps = 4;  // steps per workgroup of the path-major -> tile-major repack (4.6 TB/s read+write; 8: 4.2, 16: 2.8)
 
 // src[path][step][comp] -> dst[tile][step][comp][256], transposed through LDS so that both the
 // reads (along step·comp) and the writes (along path) are contiguous per wave.
@@ -609,12 +522,6 @@ static PartialMap classify_partials(const hh_model& m, const hh_config& c) {
 // kExactPairs / kExactPairsHuge in a large / huge one.  A function of n_paths alone — every launcher and every
 // record count in the library asks here.
 int exact_pairs_per_lane(uint64_t n_paths) {
-  static const int forced = [] {
-    const char* e = getenv("HEDGEHOG_MC_EXACT_PAIRS");  // a measurement: 1, 2, 4, 8 or 64 for every size
-    const int v = e ? atoi(e) : 0;
-    return (v == 1 || v == 2 || v == 4 || v == kExactPairs || v == kExactPairsHuge) ? v : 0;
-  }();
-  if (forced) return forced;
   return n_paths >= (uint64_t)2048 * 512 * kExactPairsHuge ? kExactPairsHuge
          : n_paths >= (uint64_t)2048 * 512 * kExactPairs   ? kExactPairs
                                                            : kExactPairsSmall;
@@ -662,7 +569,6 @@ static SimArgs<P> make_args(const hh_model& m, const hh_config& c, const DeviceP
   a.path_offset = c.path_offset;
   a.n_steps = c.n_steps;
   a.n_tiles = sim_records(c);
-  a.tail_from = a.n_tiles > (uint32_t)HH_REPLAY_TAIL_TILES ? a.n_tiles - (uint32_t)HH_REPLAY_TAIL_TILES : 0u;
   a.seeds = p.seeds;
   a.replay = p.replay;
   a.terminal = p.terminal;
@@ -685,24 +591,7 @@ SimArgs<0> make_args0(const hh_model& m, const hh_config& c, const DevicePtrs& p
 
 template <class M, int P, bool REPLAY, bool ANTI>
 static int launch_euler_t(const SimArgs<P>& a, hipStream_t s) {
-#ifdef HH_REPLAY_VARIANTS
-  constexpr int PPT = !REPLAY ? 1 : (P == 0 && !ANTI) ? HH_REPLAY_PPT : (P == 0 ? HH_REPLAY_PPT_ANTI : HH_REPLAY_PPT_DUAL);
-  constexpr int RING = !REPLAY ? 0 : ANTI ? HH_REPLAY_LDS_ANTI : P > 0 ? HH_REPLAY_LDS_DUAL : HH_REPLAY_LDS;
-  constexpr bool PIPE = HH_REPLAY_PIPE != 0;
-  // With the standard ring (32 KiB of LDS per Heston workgroup) a CU holds 4 workgroups, the chip 1024; a
-  // grid of at most half that cannot fill it, so each wave gets a deeper, pipelined ring instead
-  if constexpr (RING > 0 && HH_REPLAY_LDS_DEEP > 0) {
-    if (a.n_tiles <= 512u) {
-      hipLaunchKernelGGL((euler_kernel<M, P, REPLAY, ANTI, PPT, HH_REPLAY_LDS_DEEP, true>), dim3(a.n_tiles),
-                         dim3(kTile / PPT), 0, s, a);
-      return (int)hipGetLastError();
-    }
-  }
-#else
-  constexpr int PPT = 1, RING = 0;  // one trajectory per lane, the register pipeline
-  constexpr bool PIPE = false;
-#endif
-  hipLaunchKernelGGL((euler_kernel<M, P, REPLAY, ANTI, PPT, RING, PIPE>), dim3(a.n_tiles), dim3(kTile / PPT), 0, s, a);
+  hipLaunchKernelGGL((euler_kernel<M, P, REPLAY, ANTI>), dim3(a.n_tiles), dim3(kTile), 0, s, a);
   return (int)hipGetLastError();
 }
 
@@ -716,14 +605,6 @@ static int launch_euler_pm(const SimArgs<P>& a, bool anti, hipStream_t s) {
 template <class M, int P>
 static int launch_euler_m(const SimArgs<P>& a, bool replay, bool anti, hipStream_t s, bool path_major = false) {
   if (replay && path_major) return launch_euler_pm<M, P>(a, anti, s);
-#if defined(HH_REPLAY_VARIANTS) && HH_ANTI_SPLIT
-  if constexpr (P == 0) {
-    if (replay && anti) {
-      hipLaunchKernelGGL((euler_pair_split_kernel<M>), dim3(a.n_tiles), dim3(2 * kTile), 0, s, a);
-      return (int)hipGetLastError();
-    }
-  }
-#endif
   if (replay) return anti ? launch_euler_t<M, P, true, true>(a, s) : launch_euler_t<M, P, true, false>(a, s);
   return anti ? launch_euler_t<M, P, false, true>(a, s) : launch_euler_t<M, P, false, false>(a, s);
 }
@@ -793,13 +674,7 @@ int launch_reduce_records(const double* records, uint32_t n_records, double n_pa
 // are spread such that chunk c is ALWAYS handled on XCD c mod 8, whatever the payoff: each XCD's
 // private L2 then holds one eighth of the samples (1 MB of 8 at 10^6 trajectories) for all payoffs,
 // instead of every L2 streaming all of them.  Placement is for speed only: results do not depend on it.
-#ifndef HH_BASKET_XCD
-#define HH_BASKET_XCD 1
-#endif
-#ifndef HH_BASKET_KB
-#define HH_BASKET_KB 4
-#endif
-constexpr int kBasketKB = HH_BASKET_KB;  // payoffs a workgroup evaluates on each sample it loads
+constexpr int kBasketKB = 4;  // payoffs a workgroup evaluates on each sample it loads
 
 // One workgroup = one chunk of samples x kBasketKB payoffs: a sample (and its tangents) is loaded once
 // and every payoff of the group is evaluated on it from registers, so the re-read of the samples
@@ -807,14 +682,10 @@ constexpr int kBasketKB = HH_BASKET_KB;  // payoffs a workgroup evaluates on eac
 // accumulators, lane order and record, so its sums are those of a one-payoff launch bit for bit.
 template <int P>
 __global__ __launch_bounds__(256) void basket_payoff_kernel(const BasketArgs b, const uint32_t n_payoffs) {
-#if HH_BASKET_XCD
   const uint32_t per_xcd = (b.n_chunks + 7u) / 8u;           // chunks an XCD owns
   const uint32_t xcd = blockIdx.x & 7u, idx = blockIdx.x >> 3;
   const uint32_t grp = idx / per_xcd, chunk = (idx % per_xcd) * 8u + xcd;
   if (chunk >= b.n_chunks) return;                           // padding of the last group of eight
-#else
-  const uint32_t chunk = blockIdx.x, grp = blockIdx.y;
-#endif
   const uint32_t k0 = grp * kBasketKB;
   double strike[kBasketKB], cp[kBasketKB];
 #pragma unroll
@@ -907,11 +778,7 @@ int launch_basket_payoffs(const BasketArgs& b, uint32_t n_payoffs, uint32_t n_ac
   const uint32_t n_groups = (n_payoffs + kBasketKB - 1) / kBasketKB;
   // a 1-D grid: 2^31 workgroups is 3.5·10^13 payoff evaluations; beyond that the caller splits the basket
   if ((uint64_t)((b.n_chunks + 7u) / 8u) * 8u * n_groups > 0x7fffffffull) return (int)hipErrorInvalidConfiguration;
-#if HH_BASKET_XCD
   const dim3 grid(((b.n_chunks + 7u) / 8u) * 8u * n_groups), block(256);
-#else
-  const dim3 grid(b.n_chunks, n_groups), block(256);
-#endif
   switch (pad_partials(n_active_partials)) {
     case 0: hipLaunchKernelGGL(basket_payoff_kernel<0>, grid, block, 0, s, b, n_payoffs); break;
     case 1: hipLaunchKernelGGL(basket_payoff_kernel<1>, grid, block, 0, s, b, n_payoffs); break;

@@ -55,10 +55,7 @@ namespace hh {
 namespace {
 
 constexpr int kLsmFinalChunk = 1024;  // paths per workgroup of the final Σ, Σ² kernel (16-double records)
-#ifndef HH_LSM_WG
-#define HH_LSM_WG 512
-#endif
-constexpr int kLsmWg = HH_LSM_WG;     // threads per workgroup of every kernel that forms canonical sums
+constexpr int kLsmWg = 512;     // threads per workgroup of every kernel that forms canonical sums
 constexpr int kLsmQSmall = 1024 / kLsmWg, kLsmQLarge = 8192 / kLsmWg;  // trajectories per lane
 constexpr int kLsmWaves = kLsmWg / 64;
 constexpr int kLsmMaxDeg = 8;
@@ -94,15 +91,6 @@ inline uint32_t lsm_nch(uint64_t ntot) {
 
 // ---- full path grid -----------------------------------------------------------------------
 
-#ifndef HH_LSM_GRID_NT
-#define HH_LSM_GRID_NT 1  // the grid is written once and read once, 1.6 GB: nontemporal stores (-2 % of the LSM chain)
-#endif
-
-#if HH_LSM_GRID_NT
-#define HH_GRID_STORE(p, v) __builtin_nontemporal_store((v), (p))
-#else
-#define HH_GRID_STORE(p, v) (*(p) = (v))
-#endif
 template <bool ANTI>
 __global__ __launch_bounds__(256) void gbm_grid_kernel(const uint64_t* __restrict__ seeds,
                                                        uint64_t n_paths, uint32_t n_steps,
@@ -124,11 +112,11 @@ __global__ __launch_bounds__(256) void gbm_grid_kernel(const uint64_t* __restric
         // GBM process increment dW = W (exp((μ-σ²/2) dt + σ √dt z) - 1)
         const double e = fm::exp(fma(b, z[h], a));  // hh_math.h: <= 1.5 ulp, a third of the library's instructions
         S = S + S * (e - 1.0);
-        HH_GRID_STORE(&grid[(size_t)(s + h + 1) * ntot + i], S);
+        __builtin_nontemporal_store(S, &grid[(size_t)(s + h + 1) * ntot + i]);
         if (ANTI) {  // flipped σ, same draws (montecarlo.jl:276): exp(a - b z) = exp(2a) / exp(a + b z),
                      // a reciprocal (6 instructions, <= 3.5 ulp) instead of a second exponential (25)
           Sa = Sa + Sa * (e2a * fm::rcp(e) - 1.0);
-          HH_GRID_STORE(&grid[(size_t)(s + h + 1) * ntot + n_paths + i], Sa);
+          __builtin_nontemporal_store(Sa, &grid[(size_t)(s + h + 1) * ntot + n_paths + i]);
         }
       }
     }
@@ -151,18 +139,6 @@ constexpr int log2_of(int p) { return p <= 1 ? 0 : 1 + log2_of(p / 2); }
 // 16 lanes (xor 1, 2: quad_perm; xor 4: row_shl / row_shr by 4 into alternate banks; xor 8: row_ror:8),
 // gfx950's v_permlane16_swap / v_permlane32_swap across rows.  Same partner, same value: the sums do
 // not change by a bit.
-#ifndef HH_LSM_DPP
-#define HH_LSM_DPP 1
-#endif
-#ifndef HH_LSM_SWAP_PAIRS  // A/B switches of round 3's later cuts (tools/lsm_breakdown.py; both bit-identical)
-#define HH_LSM_SWAP_PAIRS 1
-#endif
-#ifndef HH_LSM_EARLY_STATS
-#define HH_LSM_EARLY_STATS 1
-#endif
-#ifndef HH_LSM_GATHER_USED
-#define HH_LSM_GATHER_USED 1
-#endif
 
 template <int OFF>
 __device__ __forceinline__ unsigned xor_lane_u32(unsigned x, int lane) {
@@ -183,13 +159,9 @@ __device__ __forceinline__ unsigned xor_lane_u32(unsigned x, int lane) {
 }
 template <int OFF>
 __device__ __forceinline__ double xor_lane(double x, int lane) {
-#if HH_LSM_DPP
   const unsigned long long b = (unsigned long long)__double_as_longlong(x);
   const unsigned lo = xor_lane_u32<OFF>((unsigned)b, lane), hi = xor_lane_u32<OFF>((unsigned)(b >> 32), lane);
   return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
-#else
-  return __shfl_xor(x, OFF, 64);
-#endif
 }
 
 template <int P2>
@@ -204,7 +176,6 @@ __device__ __forceinline__ void wave_reduce_multi(double (&a)[P2]) {
 #pragma unroll
       for (int i = 0; i < P2 / 2; ++i) {
         if (i < h) {
-#if HH_LSM_DPP && HH_LSM_SWAP_PAIRS
           if constexpr (off == 32 || off == 16) {
             // v_permlane{32,16}_swap IS the exchange of this step: it swaps a[i] of the upper lanes with
             // a[i + h] of their partners, after which every lane holds {what it keeps, what it was sent}
@@ -226,7 +197,6 @@ __device__ __forceinline__ void wave_reduce_multi(double (&a)[P2]) {
                    __longlong_as_double((long long)(((unsigned long long)yh << 32) | yl));
             continue;
           }
-#endif
           // both elements into registers first: written as `upper ? a[i] : a[i + h]` the compiler
           // selects the ADDRESS, which makes `a` a dynamically indexed array in scratch memory
           const double lo = a[i], hi = a[i + h];
@@ -387,51 +357,11 @@ __device__ __forceinline__ double rcp_nr(double x) {
 // coefficients) is dropped, its coefficient 0.  (Until late round 3 the pivot was held against the
 // largest diagonal entry: with heavy-tailed z and degree 7-8 that one, Σ z^16, is 10^13 times the
 // count Σ z^0, and the test dropped the constant and the linear column of a perfectly determined fit.)  Every workgroup of either form runs this on the same
-// sums and so obtains the same coefficients.  One-thread form:
-template <int D>
-__device__ void solve_normal_equations(const double* B, double p0, const double* Pm1, double* coef) {
-  constexpr int N = D + 1;
-  auto Pv = [&](int i) { return i == 0 ? p0 : Pm1[i - 1]; };
-  double M[N][N + 1];
-#pragma unroll
-  for (int j = 0; j < N; ++j) {
-#pragma unroll
-    for (int k = 0; k < N; ++k) M[j][k] = Pv(j + k);
-    M[j][N] = B[j];
-  }
-  double inv[N];
-#pragma unroll
-  for (int c = 0; c < N; ++c) {
-    const bool dead = !(M[c][c] > 1e-13 * Pv(2 * c));
-    inv[c] = dead ? 0.0 : rcp_nr(M[c][c]);
-    if (!dead) {
-#pragma unroll
-      for (int j = 0; j < N; ++j)
-        if (j > c) {
-          const double f = M[j][c] * inv[c];
-#pragma unroll
-          for (int k = 0; k <= N; ++k)
-            if (k >= c) M[j][k] = fma(-f, M[c][k], M[j][k]);
-        }
-    }
-  }
-  double cf[N];
-#pragma unroll
-  for (int c = N - 1; c >= 0; --c) {
-    double s = M[c][N];
-#pragma unroll
-    for (int k = 0; k < N; ++k)
-      if (k > c) s = fma(-M[c][k], cf[k], s);
-    cf[c] = s * inv[c];  // 0 for a dropped column
-  }
-#pragma unroll
-  for (int c = 0; c < N; ++c) coef[c] = cf[c];
-}
-
-// The same elimination with the rows spread over the lanes of one wave (lane j holds row j in
-// registers, the pivot row travels by v_readlane): the same operations on the same operands in the
-// same order per element — bit-identical coefficients — at ~300 instructions, most of them
-// independent across the lanes.  Called by all 64 lanes of a wave; coef written by lane 0.
+// sums and so obtains the same coefficients.
+//
+// The rows are spread over the lanes of one wave (lane j holds row j in registers, the pivot row travels by
+// v_readlane): ~300 instructions, most of them independent across the lanes.  Called by all 64 lanes of a
+// wave; coef written by lane 0.
 __device__ __forceinline__ double readlane_f64(double v, int lane) {
   const long long b = __double_as_longlong(v);
   const int lo = __builtin_amdgcn_readlane((int)(b & 0xffffffffll), lane);
@@ -479,20 +409,8 @@ __device__ void solve_normal_equations_wave(const double* B, double p0, const do
   }
 }
 
-#ifndef HH_LSM_WAVE_SOLVE
-#define HH_LSM_WAVE_SOLVE 1
-#endif
-// timing diagnostics only (results are WRONG with any bit set; tools/lsm_breakdown.py builds variants):
-// 1 = the gather does not wait for granules that fail their check, 2 = no solve, 4 = no partial sums / reductions / publish
-#ifndef HH_LSM_DEBUG
-#define HH_LSM_DEBUG 0
-#endif
-// 1: diagnostic build that stamps the phases of a date (s_memrealtime, 100 MHz) in thread 0 of one
-// workgroup and leaves the totals behind the row counters (tools/lsm_breakdown.py reads them through
-// hh_lsm_debug_read); in the shipped build no stamp executes
-#ifndef HH_LSM_STAMPS
-#define HH_LSM_STAMPS 0
-#endif
+// slots behind the row counters that hh_lsm_debug_read returns (the phase stamps of a diagnostic build that has
+// been removed; profiles/ has its measurements).  Nothing writes them now: their contents are unspecified.
 constexpr int kLsmStampSlots = 8;
 
 // coefficients of row t into LDS (coef[D+1], *have_fit) from the global sums B[0..D], P[0] = n_itm,
@@ -510,16 +428,8 @@ __device__ __forceinline__ void lds_barrier() {
 template <int D>
 __device__ __forceinline__ void fit_row_wave0(double n_itm, const double* B, const double* Pm1, double* coef,
                                               int* have_fit) {
-#if HH_LSM_WAVE_SOLVE
-  if (n_itm > 0.0 && !(HH_LSM_DEBUG & 2))
-    solve_normal_equations_wave<D>(B, n_itm, Pm1, coef);  // isempty(in_the_money) && continue (:120)
+  if (n_itm > 0.0) solve_normal_equations_wave<D>(B, n_itm, Pm1, coef);  // isempty(in_the_money) && continue (:120)
   if (threadIdx.x == 0) *have_fit = n_itm > 0.0 ? 1 : 0;
-#else
-  if (threadIdx.x == 0) {
-    if (n_itm > 0.0) solve_normal_equations<D>(B, n_itm, Pm1, coef);
-    *have_fit = n_itm > 0.0 ? 1 : 0;
-  }
-#endif
 }
 template <int D>
 __device__ __forceinline__ void fit_row(double n_itm, const double* B, const double* Pm1, double* coef,
@@ -865,7 +775,7 @@ __device__ __forceinline__ bool gather_records(const LsmPersistArgs& a, uint32_t
       };
       if (ok) {
         bool bad = sweep(std::integral_constant<int, 0>{});  // through the caches (a volatile access is made sc0 sc1)
-        if (__any(bad) && !(HH_LSM_DEBUG & 1)) {
+        if (__any(bad)) {
           const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
           unsigned spins = 0;
           while (true) {
@@ -998,21 +908,6 @@ __global__ __launch_bounds__(kLsmWg, (Q * kLsmWg > 1024 ? 2 : 4)) void lsm_persi
   if (M >= 5) issue_row(M - 4);
   int cur = 0;  // at date t: xl[cur] = row t-1, xl[cur ^ 1] = row t-2, xin = row t-3
   double regressed = 0.0, skipped = 0.0;
-#if HH_LSM_STAMPS
-  unsigned long long st_acc[kLsmStampSlots] = {}, st_t0 = __builtin_amdgcn_s_memrealtime();
-#ifndef HH_LSM_STAMP_THREAD
-#define HH_LSM_STAMP_THREAD 0  // which thread of the middle workgroup stamps (waves 0-3 and 4-7 differ, below)
-#endif
-  const bool st_me = blockIdx.x == gridDim.x / 2 && threadIdx.x == HH_LSM_STAMP_THREAD;
-#define HH_STAMP(k)                                                  \
-  if (st_me) {                                                       \
-    const unsigned long long now = __builtin_amdgcn_s_memrealtime(); \
-    st_acc[k] += now - st_t0;                                        \
-    st_t0 = now;                                                     \
-  }
-#else
-#define HH_STAMP(k)
-#endif
   // The pipeline of a date t (epoch e = M - t + 1).  What couples the workgroups is one record per
   // date; its two halves travel separately, because only one of them depends on the stopping state:
   //   group A, epoch e   Σ z^k y of row t (k = 0..D; needs the decisions of date t+1)  +  (n, Σx, Σx²) of row t-2
@@ -1108,9 +1003,7 @@ __global__ __launch_bounds__(kLsmWg, (Q * kLsmWg > 1024 ? 2 : 4)) void lsm_persi
     // window, a full date before anybody needs them.
     for (uint32_t t = M - 1; alive && t >= 1; --t) {
       const uint32_t e = M - t + 1;  // epoch whose records hold the sums of row t
-      HH_STAMP(7)
       alive = gather_records<D>(a, e, gscratch, tot, &ok_flag);
-      HH_STAMP(1)  // all-gather: loads, validation, reduction
       if (!alive) break;
       // The solve is one wave's; the other seven use the window for the one piece of the date's arithmetic
       // that needs neither the coefficients nor the stopping state: the statistics of the row that has
@@ -1118,14 +1011,13 @@ __global__ __launch_bounds__(kLsmWg, (Q * kLsmWg > 1024 ? 2 : 4)) void lsm_persi
       double st[3] = {0.0, 0.0, 0.0};
       if (wave == 0) {
         fit_row_wave0<D>(r_cur.n, tot, tot + kGrp, coef, &have_fit);  // Gram: P[0] = n, P[k] = group B
-      } else if (HH_LSM_EARLY_STATS && t >= 4) {
+      } else if (t >= 4) {
 #pragma unroll
         for (int j = 0; j < Q; ++j) add_stats(xin[j], a.cp, a.strike, live(j), st);
       }
       // the power sums date t+1 left in scratch (row t-1): group B of the epoch of date t-1
-      if (t + 2 <= M && t >= 2 && !(HH_LSM_DEBUG & 4)) total_and_publish(e + 1, 1, 4);
+      if (t + 2 <= M && t >= 2) total_and_publish(e + 1, 1, 4);
       lds_barrier();
-      HH_STAMP(2)  // normal equations
       // statistics of row t-2 (two divisions and a square root: a 0.3 µs chain for a wave with nothing
       // else to issue): needed by the power sums at the end of the date, so formed beside the decisions,
       // not in front of the solve
@@ -1140,20 +1032,18 @@ __global__ __launch_bounds__(kLsmWg, (Q * kLsmWg > 1024 ? 2 : 4)) void lsm_persi
           val[j] = ex ? pay : val[j];
         }
       }
-      HH_STAMP(3)  // exercise decisions
       if (t >= 2) {
         // row t-1 moves from LDS into the registers (the next decision row) and its moment sums are
         // formed with the stopping state as of now; row t-3 has landed: it takes the freed LDS slots
         // (a lane only ever touches its own) and leaves its statistics
 #pragma unroll
         for (int j = 0; j < Q; ++j) xs[j] = xl[cur][j * kLsmWg + threadIdx.x];
-        if (!(HH_LSM_DEBUG & 4)) {
         {
           double v[kGrp];
 #pragma unroll
           for (int i = 0; i < kGrp; ++i) v[i] = 0.0;
           if (t >= 4) {
-            if (HH_LSM_EARLY_STATS && wave != 0) {
+            if (wave != 0) {
 #pragma unroll
               for (int j = 0; j < Q; ++j) xl[cur][j * kLsmWg + threadIdx.x] = xin[j];
 #pragma unroll
@@ -1181,17 +1071,10 @@ __global__ __launch_bounds__(kLsmWg, (Q * kLsmWg > 1024 ? 2 : 4)) void lsm_persi
           else moments([&](int k) { return a.disc_pow[k]; });
           wave_part<kGrp, kRecP2>(v, scratch, 0);
         }
-        HH_STAMP(4)  // moment sums + their wave butterfly
         lds_barrier();
-#if HH_LSM_STAMPS > 1
-        HH_STAMP(7)  // (diagnostic: the barrier's wait goes to "loop overhead")
-#endif
         total_and_publish(e + 1, 0, 0);  // wave 0: group A is on its way — the date's critical path ends here
-        HH_STAMP(6)  // workgroup total of A, store issued
-        }
         if (t >= 5) issue_row(t - 4);  // row (t-1)-3: lands, is parked and leaves its statistics at date t-1
-        HH_STAMP(0)  // next row issued
-        if (t >= 3 && !(HH_LSM_DEBUG & 4)) {  // power sums of row t-2 (xl[cur ^ 1]): published from the next window
+        if (t >= 3) {  // power sums of row t-2 (xl[cur ^ 1]): published from the next window
           double w[kGrp];
 #pragma unroll
           for (int i = 0; i < kGrp; ++i) w[i] = 0.0;
@@ -1200,7 +1083,6 @@ __global__ __launch_bounds__(kLsmWg, (Q * kLsmWg > 1024 ? 2 : 4)) void lsm_persi
             add_powers_from1<D>(xl[cur ^ 1][j * kLsmWg + threadIdx.x], a.cp, a.strike, live(j), r_nn, w);
           wave_part<kGrp, kRecP2>(w, scratch, kGrp);
         }
-        HH_STAMP(5)  // power sums + their wave butterfly
         cur ^= 1;
         r_cur = r_next;
         r_next = r_nn;
@@ -1220,12 +1102,7 @@ __global__ __launch_bounds__(kLsmWg, (Q * kLsmWg > 1024 ? 2 : 4)) void lsm_persi
     a.counters[0] = regressed;
     a.counters[1] = skipped;
   }
-#if HH_LSM_STAMPS
-  if (st_me)
-    for (int k = 0; k < kLsmStampSlots; ++k) a.counters[2 + k] = (double)st_acc[k];
-#endif
 }
-#undef HH_STAMP
 
 // ---- launch sequences ---------------------------------------------------------------------------
 
@@ -1469,10 +1346,6 @@ int launch_lsm(const double* grid, uint64_t ntot, uint32_t n_steps, double strik
   int rc = 1;
   if (form == kLsmFormPersistent || form == kLsmFormAuto) {  // one launch whenever the chip can hold the grid
     if (n_steps >= (uint32_t)kDiscLds) table();
-    if (HH_LSM_STAMPS) {  // (the shipped kernel writes both counters itself; the stamps accumulate)
-      const hipError_t e = hipMemsetAsync(L.counters, 0, (2 + kLsmStampSlots) * sizeof(double), s);
-      if (e != hipSuccess) return (int)e;
-    }
 #define HH_CALL(D) run_lsm_persistent<D>(L, a, s, spin_ticks)
     HH_LSM_DISPATCH(degree, HH_CALL)
 #undef HH_CALL

@@ -22,19 +22,16 @@ struct MultiArgs {
   SimArgs<0> m[K];  // everything but the model scalars and the output pointers is the same in all of them
 };
 
-#ifndef HH_MULTI_CHUNK
-#define HH_MULTI_CHUNK 4          // steps per register chunk of the REPLAY pipeline (as euler_kernel)
-#endif
-#ifndef HH_MULTI_MAXW
-#define HH_MULTI_MAXW 3           // waves per SIMD, REPLAY: K path-steps of arithmetic per 16 bytes want more
-#endif                            //   waves than the price-only stream's two
+constexpr int kMultiChunk = 4;     // steps per register chunk of the REPLAY pipeline (as euler_kernel)
+constexpr int kMultiMaxWaves = 3;  // waves per SIMD, REPLAY: K path-steps of arithmetic per 16 bytes want more
+                                   //   waves than the price-only stream's two
 
 // SHARED: the models agree on ρ and dt (what a bump of the spot, the variance, κ, θ, σ, the rate or the strike
 // leaves alone), so the correlated increments are formed once; otherwise each model forms its own from the
 // same two normals.  Same operations on the same numbers either way.
 template <class M, bool REPLAY, bool ANTI, int K, bool SHARED>
 __global__ __launch_bounds__(kTile)
-__attribute__((amdgpu_waves_per_eu(1, REPLAY ? HH_MULTI_MAXW : 8))) void euler_multi_kernel(const MultiArgs<K> a) {
+__attribute__((amdgpu_waves_per_eu(1, REPLAY ? kMultiMaxWaves : 8))) void euler_multi_kernel(const MultiArgs<K> a) {
   constexpr int NC = M::NCOMP;
   using State = typename M::State;
   const SimArgs<0>& a0 = a.m[0];
@@ -61,14 +58,14 @@ __attribute__((amdgpu_waves_per_eu(1, REPLAY ? HH_MULTI_MAXW : 8))) void euler_m
     // the register pipeline of euler_kernel: two chunks, load(Y) || compute(X), steady state unguarded so
     // that the compiler counts its waits
     const double* __restrict__ base = a0.replay + (size_t)tile * n_steps * NC * kTile + tid;
-    constexpr int CH = HH_MULTI_CHUNK;
+    constexpr int CH = kMultiChunk;
     double X[CH][NC], Y[CH][NC];
     auto ld = [&](double(&buf)[CH][NC], uint32_t s0) {
 #pragma unroll
       for (int u = 0; u < CH; ++u) {
         if (s0 + u < n_steps) {
 #pragma unroll
-          for (int c = 0; c < NC; ++c) buf[u][c] = stream_load<double>(base + ((size_t)(s0 + u) * NC + c) * kTile);
+          for (int c = 0; c < NC; ++c) buf[u][c] = stream_load(base + ((size_t)(s0 + u) * NC + c) * kTile);
         }
       }
     };
@@ -81,7 +78,7 @@ __attribute__((amdgpu_waves_per_eu(1, REPLAY ? HH_MULTI_MAXW : 8))) void euler_m
 #pragma unroll
       for (int u = 0; u < CH; ++u)
 #pragma unroll
-        for (int c = 0; c < NC; ++c) buf[u][c] = stream_load<double>(base + ((size_t)(s0 + u) * NC + c) * kTile);
+        for (int c = 0; c < NC; ++c) buf[u][c] = stream_load(base + ((size_t)(s0 + u) * NC + c) * kTile);
     };
     auto gof = [&](const double(&buf)[CH][NC]) {
 #pragma unroll

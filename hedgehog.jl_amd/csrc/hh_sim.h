@@ -18,9 +18,6 @@ namespace hh {
 // heston.jl:7-31.  u = [log S, v];  f = [mu - v+/2, kappa(theta - v+)],  g = [sqrt(v+), sigma sqrt(v+)]
 // with v+ = max(v, 0).  K = u + dt f(u);  u' = K + g(.) dW, g taken at K (SPLIT, the integrator's
 // split-step form) or at u.
-#ifndef HH_LEAN_SQRT
-#define HH_LEAN_SQRT 1
-#endif
 // sqrt of the clipped variance w >= 0.  The library routine is v_rsq_f64 + one coupled Newton step
 // + two residual corrections, wrapped in a 2^±256 range scaling for arguments below 2^-767 and a
 // class test for 0/inf: 18 instructions, more than half of a Heston path-step.  This is the same
@@ -31,7 +28,6 @@ namespace hh {
 // the result; the two instructions are 4 of the antithetic kernel's 47 per pair-step.)  A clipped
 // variance between 0 and 2^-767 cannot change any later state.
 __device__ __forceinline__ double sqrt_clipped(double w) {
-#if HH_LEAN_SQRT
   const double y = __builtin_fmin(__builtin_amdgcn_rsq(w), 0x1p1000);
   double g = w * y, h = 0.5 * y;
   const double r = fma(-h, g, 0.5);
@@ -39,9 +35,6 @@ __device__ __forceinline__ double sqrt_clipped(double w) {
   h = fma(h, r, h);
   g = fma(fma(-g, g, w), h, g);
   return fma(fma(-g, g, w), h, g);
-#else
-  return sqrt(w);
-#endif
 }
 
 template <int P, bool SPLIT>
@@ -284,9 +277,6 @@ __device__ __forceinline__ void exact_pair_normals(const SimArgs<P>& a, uint64_t
 // REPLAY kernel at two workgroups per CU, and 3907 adds to one address are 45 µs on an 8 µs exact-law kernel;
 // a resident grid of workgroups looping over tiles (one ticket each) loses 3.5-4 % to the fixed assignment.
 
-#ifndef HH_FINISH_STAMPS
-#define HH_FINISH_STAMPS 0
-#endif
 // which workgroup reduces: SimArgs::reducer_tile — the last tile's; the FIRST one's under HH_OPT_FINISH_TILE_FIRST
 // (a diagnostic: it then has to wait for nearly every record)
 template <class Args>
@@ -472,9 +462,6 @@ __device__ __forceinline__ void finish_records(const Args& a) {
   const unsigned long long spin_ticks = a.finish_spin_ticks;
   __shared__ double sm[4 * 256];
   __shared__ unsigned int gave_up;
-#if HH_FINISH_STAMPS  // a diagnostic build (tools/finish_stamps.py): where the tail's time goes, in accum[11..15]
-  const unsigned long long st0 = wall_clock64();
-#endif
   // (a give-up of an earlier launch the host has not dealt with yet: this buffer cannot be trusted — the sums are NaN
   // whatever it holds, and a wait for a record that looks missing ends at once: keep_waiting asks too)
   const unsigned int state_in_flight = scalar_load_begin(a.finish_state);
@@ -496,9 +483,6 @@ __device__ __forceinline__ void finish_records(const Args& a) {
       store_through(records + (size_t)i * kRecStride + kRecItmS + 1, poison);
     }
   }
-#if HH_FINISH_STAMPS
-  const unsigned long long st1 = wall_clock64();
-#endif
   __syncthreads();
   double s[4] = {0.0, 0.0, 0.0, 0.0}, d[P > 0 ? P : 1];
   if (threadIdx.x < 64) {
@@ -538,11 +522,6 @@ __device__ __forceinline__ void finish_records(const Args& a) {
       if (map->dK[k] != 0.0) out -= map->dK[k] * s[3];
     }
     if (slot == HH_ACC_NPATHS) out = n_paths;
-#if HH_FINISH_STAMPS
-    if (slot == 11) out = (double)st0;               // this workgroup's own record is out
-    if (slot == 12) out = (double)st1;               // thread `slot` has all its records
-    if (slot == 13) out = (double)wall_clock64();    // sums done
-#endif
     const bool dirty = scalar_load_end(state_in_flight) != 0u;
     accum[slot] = (gave_up || dirty) ? __longlong_as_double(0x7FF8000000000000ll) : out;
     if (slot == 0 && gave_up) __hip_atomic_store(a.finish_state, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -553,29 +532,7 @@ __device__ __forceinline__ void finish_records(const Args& a) {
 // REPLAY stream loads
 // ------------------------------------------------------------------------------------------
 
-template <int PPT>
-struct VecOf;
-template <>
-struct VecOf<1> {
-  using type = double;
-  __device__ static __forceinline__ double get(const type& v, int) { return v; }
-};
-template <>
-struct VecOf<2> {
-  using type = double __attribute__((ext_vector_type(2)));
-  __device__ static __forceinline__ double get(const type& v, int j) { return j ? v.y : v.x; }
-};
-
-#ifndef HH_REPLAY_NT
-#define HH_REPLAY_NT 1            // the increments are a read-once stream: nontemporal loads
-#endif
-template <class Vec>
-__device__ __forceinline__ Vec stream_load(const double* p) {
-#if HH_REPLAY_NT
-  return __builtin_nontemporal_load(reinterpret_cast<const Vec*>(p));  // read-once stream
-#else
-  return *reinterpret_cast<const Vec*>(p);
-#endif
-}
+// the increments are a read-once stream: nontemporal loads
+__device__ __forceinline__ double stream_load(const double* p) { return __builtin_nontemporal_load(p); }
 
 }  // namespace hh

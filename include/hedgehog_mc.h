@@ -535,8 +535,10 @@ int hh_lsm_shard_phase(hh_ctx* ctx, int32_t phase, uint32_t t, const double* in_
 int hh_lsm_shard_finish(hh_ctx* ctx, double* accum_dev, int32_t* stop_time, double* stop_value,
                         double* spot_grid, uint32_t* rows_regressed, uint32_t* rows_skipped);
 int hh_lsm_finalize(const double* accum_host, hh_lsm_result* out);
-/* Diagnostics: the 8 phase totals (ticks of the 100 MHz constant clock) that a library built with
- * -DHH_LSM_STAMPS=1 leaves behind a persistent LSM solve of that shape; zeros from the shipped build. */
+/* Retired diagnostic, kept for ABI compatibility: copies the 8 doubles behind the row counters of an LSM
+ * solve of that shape.  They held the phase totals of a diagnostic build that is no longer part of the
+ * library; nothing writes them now, so their contents are unspecified (zeros after some forms, whatever the
+ * reused scratch held after others). */
 int hh_lsm_debug_read(hh_ctx* ctx, uint64_t n_paths_total, uint32_t n_steps, int32_t degree,
                       double* out8);
 

@@ -341,20 +341,6 @@ def test_rate_curve_against_the_reference_test_vectors():
     assert hh.df(flat, t1) == pytest.approx(math.exp(-r * tau), abs=g["atol"])              # :62
 
 
-@pytest.mark.skipif(__import__("shutil").which("hipcc") is None, reason="needs hipcc")
-def test_optional_ring_form_of_the_replay_kernel_still_compiles(tmp_path):
-    """The LDS-DMA ring form of the price-only REPLAY kernel is kept behind compile-time knobs for
-    A/B runs (tools/tune_replay.py): it must keep compiling for gfx950."""
-    import subprocess
-    src = os.path.join(ROOT, "hedgehog.jl_amd", "csrc", "hh_kernels.hip")
-    out = tmp_path / "ring.o"
-    proc = subprocess.run(["hipcc", "-c", "-O1", "-std=c++17", "--offload-arch=gfx950",
-                           "-ffp-contract=off", "-DHH_REPLAY_LDS=4", "-DHH_REPLAY_PPT=2",
-                           "-DHH_REPLAY_PAD_KIB=0", src, "-o", str(out)],
-                          capture_output=True, text=True)
-    assert proc.returncode == 0, proc.stderr[-2000:]
-
-
 def test_full_path_entry_points_refuse_duals_instead_of_dropping_them():
     """float(Dual) is defined (value part), so a host layer that packs plain doubles would silently return a
     price without partials: LSM and the exact Heston paths carry none, and say so."""

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Bitwise comparison of Broadie–Kaya terminal samples between the shipped library and variants
 (hedgehog.jl_amd/lib/variants/libhh_bk_*.so): hh_mc_solve on the parameter sets of tests/test_gpu_bk.py, one small
-ensemble each, every sample compared as a 64-bit pattern.  What tools/bk_ab.py's `same_sum` cannot show.  GPU box only."""
+ensemble each, every sample compared as a 64-bit pattern.  What a comparison of sums cannot show.  GPU box only."""
 import ctypes as C
 import glob
 import os

@@ -16,7 +16,7 @@ import json
 import os
 import sys
 
-KERNEL = "euler_kernel<hh::HestonModel<0, true>, 0, true, false, 1, 0, false>"  # price-only REPLAY (256 threads)
+KERNEL = "euler_kernel<hh::HestonModel<0, true>, 0, true, false>"  # price-only REPLAY (256 threads)
 
 
 def per_kernel(path, counter):
@@ -32,7 +32,7 @@ PM_KERNEL = "euler_pm_kernel<hh::HestonModel<0, true>, 0, false>"  # path-major 
 
 def path_major(fetch_csv, write_csv, tag):
     """usage: tools/pmc_traffic.py pm <fetch csv> <write csv> [tag] — adds the path-major kernel's
-    traffic (PMC passes of `tools/tune_pm.py run 1` with HH_VARIANTS='{"main": []}') to the JSON.
+    traffic (PMC passes of a price-only path-major REPLAY run) to the JSON.
     Its reads are 16 B per lane LDS-DMA of whole aligned 128-B lines: the x2 of the guide's gfx950 note."""
     fetch, write = per_kernel(fetch_csv, "FETCH_SIZE"), per_kernel(write_csv, "WRITE_SIZE")
     fk = next(k for k in fetch if PM_KERNEL in k)
@@ -48,7 +48,7 @@ def path_major(fetch_csv, write_csv, tag):
         "path_major_hbm_bytes_per_launch": 2.0 * f_kib * 1024.0 + w_kib * 1024.0,
         "path_major_same_pass_tile_major_FETCH_SIZE_KiB_raw": fetch[tile][0] if tile else None,
         "path_major_source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) -- python3 "
-                             "tools/tune_pm.py run 1 (HH_VARIANTS={\"main\": []}); round " + tag})
+                             "a price-only path-major REPLAY run; round " + tag})
     json.dump(out, open(dst, "w"), indent=1)
     print(json.dumps({k: v for k, v in out.items() if k.startswith("path_major")}, indent=1))
 
