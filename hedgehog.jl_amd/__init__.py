@@ -15,7 +15,8 @@ from .greeks import (BatchGreekProblem, FDBackward, FDCentral, FDForward, Finite
                      ForwardAD, GreekProblem, GreekResult, PropertyLens, SecondOrderGreekProblem, SpotLens,
                      VolLens,
                      ZeroRateSpineLens, optic, set)
-from .lsm import LSM, HestonExactPaths, LSMSolution, simulate_heston_exact_paths, solve_lsm
+from .lsm import (LSM, EulerPaths, HestonExactPaths, LSMSolution, simulate_euler_paths,
+                  simulate_heston_exact_paths, solve_lsm)
 from .montecarlo import (AbstractPricingMethod, Antithetic, BlackScholesExact, EulerMaruyama,
                          HestonBroadieKaya, HestonDynamics, LognormalDynamics, MethodError,
                          MonteCarlo, NoVarianceReduction, NormalLaw, SimulationConfig, marginal_law,

@@ -19,6 +19,7 @@ HH_LOGNORMAL, HH_HESTON = 0, 1
 HH_EULER_MARUYAMA, HH_EXACT_LAW, HH_BROADIE_KAYA = 0, 1, 2
 HH_NOISE_GENERATE, HH_NOISE_REPLAY = 0, 1
 HH_REPLAY_TILE_MAJOR, HH_REPLAY_PATH_MAJOR = 0, 1
+HH_PATH_SPOT, HH_PATH_LOG = 0, 1
 
 HH_OK, HH_ERR_INVALID, HH_ERR_UNSUPPORTED, HH_ERR_HIP, HH_ERR_NOMEM, HH_ERR_RCCL, HH_ERR_DEVICE_TIMEOUT = 0, -1, -2, -3, -4, -5, -6
 HH_MGPU_AUTO, HH_MGPU_HOST_SUM, HH_MGPU_RCCL = 0, 1, 2
@@ -125,6 +126,9 @@ SYMBOLS = [
     ("hh_lsm_solve", C.c_int, [_vp, C.POINTER(hh_model), C.POINTER(hh_config), C.c_int32, C.c_double, C.POINTER(hh_lsm_result), _vp, _vp, _vp]),
     ("hh_lsm_solve_grid", C.c_int, [_vp, C.POINTER(hh_model), _vp, C.c_uint64, C.c_uint32, C.c_int32, C.c_double, C.POINTER(hh_lsm_result), _vp, _vp]),
     ("hh_heston_exact_grid", C.c_int, [_vp, C.POINTER(hh_model), C.POINTER(hh_config), _vp, _vp, C.c_int32, C.POINTER(hh_result)]),
+    ("hh_euler_grid", C.c_int, [_vp, C.POINTER(hh_model), C.POINTER(hh_config), C.c_int32, _vp, _vp, C.c_int32, C.POINTER(hh_result)]),
+    ("hh_lsm_solve_euler", C.c_int, [_vp, C.POINTER(hh_model), C.POINTER(hh_config), C.c_int32, C.c_int32, C.c_double,
+                                     C.POINTER(hh_lsm_result), _vp, _vp, _vp]),
     ("hh_lsm_shard_xchg_elems", C.c_size_t, [C.c_uint32, C.c_int32]),
     ("hh_lsm_shard_begin", C.c_int, [_vp, C.POINTER(hh_model), C.POINTER(hh_config), C.c_int32, C.c_double, _vp]),
     ("hh_lsm_shard_phase", C.c_int, [_vp, C.c_int32, C.c_uint32, _vp, _vp]),

@@ -1253,6 +1253,90 @@ int hh_lsm_solve(hh_ctx* ctx, const hh_model* m, const hh_config* c, int32_t deg
   return HH_OK;
 }
 
+// ---- Euler–Maruyama path grids (GENERATE) -------------------------------------------------------------
+
+// The Euler states of every date into ctx->lsm_grid (spot or log-spot rows, hh_path_state) and, want_var, the
+// Heston variance rows into ctx->heston_var.  The grid is [n_steps+1][n_paths·(1+antithetic)] (hh_lsm_grid_elems).
+static int run_euler_grid(hh_ctx* ctx, const hh_model* m, const hh_config* c, int32_t path_state, bool want_var) {
+  if (path_state != HH_PATH_SPOT && path_state != HH_PATH_LOG)
+    return fail(ctx, HH_ERR_INVALID, "path_state must be HH_PATH_SPOT (0) or HH_PATH_LOG (1)");
+  const bool hest = c->dynamics == HH_HESTON;
+  if (c->strategy != HH_EULER_MARUYAMA || (c->dynamics != HH_LOGNORMAL && !hest))
+    return fail(ctx, HH_ERR_UNSUPPORTED, "Euler grid needs LognormalDynamics or HestonDynamics + EulerMaruyama");
+  if (c->noise_mode != HH_NOISE_GENERATE || c->n_partials != 0)
+    return fail(ctx, HH_ERR_UNSUPPORTED, "Euler grid: GENERATE noise, no dual partials");
+  if (want_var && !hest)
+    return fail(ctx, HH_ERR_UNSUPPORTED, "Euler grid: variance rows belong to HestonDynamics");
+  if (c->n_paths == 0 || c->n_steps == 0 || c->n_paths > kMaxPaths / 2 || c->n_steps > kMaxGridSteps)
+    return fail(ctx, HH_ERR_INVALID, "Euler grid: 1 <= n_paths <= 2^31 - 128, 1 <= n_steps <= %u", kMaxGridSteps);
+  if (!(m->S0 > 0.0) || !(m->T > 0.0) || !std::isfinite(m->S0) || !std::isfinite(m->T) ||
+      !std::isfinite(m->sigma) || !std::isfinite(m->r_drift) ||
+      (hest && (!(std::fabs(m->rho) <= 1.0) || !std::isfinite(m->V0) || !std::isfinite(m->kappa) ||
+                !std::isfinite(m->theta))))
+    return fail(ctx, HH_ERR_INVALID, "Euler grid: S0, T > 0, |rho| <= 1, model scalars finite");
+  const size_t elems = hh_lsm_grid_elems(c->n_paths, c->n_steps, c->antithetic);
+  int rc;
+  if ((rc = ensure(ctx, ctx->lsm_grid, ctx->lsm_grid_cap, elems))) return rc;
+  if (want_var && (rc = ensure(ctx, ctx->heston_var, ctx->heston_var_cap, elems))) return rc;
+  const uint64_t* seeds_dev = nullptr;
+  if ((rc = stage_path_seeds(ctx, c, &seeds_dev))) return rc;
+  HH_HIP(ctx, hh::launch_euler_grid(*m, *c, seeds_dev, path_state == HH_PATH_LOG, ctx->lsm_grid,
+                                    want_var ? ctx->heston_var : nullptr, ctx->stream));
+  return HH_OK;
+}
+
+int hh_euler_grid(hh_ctx* ctx, const hh_model* m, const hh_config* c, int32_t path_state, double* spot_grid,
+                  double* var_grid, int32_t grids_on_device, hh_result* out) {
+  if (!ctx) return HH_ERR_INVALID;
+  std::lock_guard<std::recursive_mutex> lock__(ctx->mu);
+  if (!m || !c) return fail(ctx, HH_ERR_INVALID, "hh_euler_grid: NULL argument");
+  const auto t0 = std::chrono::steady_clock::now();
+  HH_HIP(ctx, hipSetDevice(ctx->device));
+  HH_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+  int rc = run_euler_grid(ctx, m, c, path_state, var_grid != nullptr);
+  if (rc) return rc;
+  HH_HIP(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+  const size_t bytes = hh_lsm_grid_elems(c->n_paths, c->n_steps, c->antithetic) * sizeof(double);
+  const hipMemcpyKind kind = grids_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+  if (spot_grid) HH_HIP(ctx, hipMemcpyAsync(spot_grid, ctx->lsm_grid, bytes, kind, ctx->stream));
+  if (var_grid) HH_HIP(ctx, hipMemcpyAsync(var_grid, ctx->heston_var, bytes, kind, ctx->stream));
+  HH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  if (out) {
+    std::memset(out, 0, sizeof(*out));
+    out->n_paths_done = c->n_paths;
+    float ms = 0.f;
+    HH_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
+    out->kernel_ms = ms;
+    out->total_ms =
+        std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  }
+  return HH_OK;
+}
+
+int hh_lsm_solve_euler(hh_ctx* ctx, const hh_model* m, const hh_config* c, int32_t path_state, int32_t degree,
+                       double step_discount, hh_lsm_result* out, int32_t* stop_time, double* stop_value,
+                       double* spot_grid) {
+  if (!ctx) return HH_ERR_INVALID;
+  std::lock_guard<std::recursive_mutex> lock__(ctx->mu);
+  if (!m || !c || !out) return fail(ctx, HH_ERR_INVALID, "hh_lsm_solve_euler: NULL argument");
+  const auto t0 = std::chrono::steady_clock::now();
+  int rc = lsm_check_scalars(ctx, m, c, degree, step_discount);
+  if (rc) return rc;
+  HH_HIP(ctx, hipSetDevice(ctx->device));
+  HH_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+  if ((rc = run_euler_grid(ctx, m, c, path_state, false))) return rc;
+  const uint64_t ntot = c->n_paths * (c->antithetic ? 2 : 1);
+  rc = lsm_on_grid(ctx, ctx->lsm_grid, ntot, c->n_steps, m, degree, step_discount, out, stop_time, stop_value, t0);
+  if (rc) return rc;
+  if (spot_grid) {
+    HH_HIP(ctx, hipMemcpyAsync(spot_grid, ctx->lsm_grid,
+                               hh_lsm_grid_elems(c->n_paths, c->n_steps, c->antithetic) * sizeof(double),
+                               hipMemcpyDeviceToHost, ctx->stream));
+    HH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  }
+  return HH_OK;
+}
+
 // ---- LSM on an ensemble sharded over several devices ------------------------------------------------
 
 size_t hh_lsm_shard_xchg_elems(uint32_t n_steps, int32_t degree) {

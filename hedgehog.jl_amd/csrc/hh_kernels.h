@@ -238,6 +238,11 @@ int launch_lsm_phase(int phase, uint32_t t, const double* grid, uint64_t ntot, u
                      double* vec_out, hipStream_t s);
 int launch_gbm_grid(const uint64_t* seeds_dev, uint64_t n_paths, uint32_t n_steps, double S0,
                     double r, double sigma, double T, int anti, double* grid, hipStream_t s);
+// Euler–Maruyama states at every date (GENERATE; c: dynamics, em_split, antithetic, n_paths, n_steps) into the
+// step-major grid [n_steps+1][n_paths·(1+antithetic)]: exp(log S), or log S when log_state; the Heston variance
+// state into var_grid when it is not NULL (lognormal: ignored).
+int launch_euler_grid(const hh_model& m, const hh_config& c, const uint64_t* seeds_dev, bool log_state,
+                      double* grid, double* var_grid, hipStream_t s);
 // form: kLsmFormPersistent = the whole backward induction in ONE launch when the ensemble fits the
 // chip (else it falls back by itself), kLsmFormPerDate = one launch per exercise date.  *form_used
 // says which was enqueued; after a persistent launch the caller synchronises and reads the word at

@@ -145,10 +145,8 @@ __attribute__((amdgpu_waves_per_eu(1, replay_max_waves(REPLAY, ANTI, P)))) void 
 
     if constexpr (NC == 2) {
       for (uint32_t s = 0; s < n_steps; ++s) {
-        double z1, z2;
-        normal_pair(key, s, 0u, 0u, kDomEuler, z1, z2);
-        const double d1 = a.sqrt_dt * z1;
-        const double d2 = a.sqrt_dt * fma(a.rho, z1, a.rho_c * z2);
+        double d1, d2;
+        euler_pair_increments(key, s, a, d1, d2);
         M::step(st, a, d1, d2);
         if constexpr (ANTI) M::step(sa, a, -d1, -d2);
       }
@@ -156,7 +154,7 @@ __attribute__((amdgpu_waves_per_eu(1, replay_max_waves(REPLAY, ANTI, P)))) void 
       // scalar noise: one Philox block feeds two consecutive steps
       for (uint32_t s = 0; s < n_steps; s += 2) {
         double z1, z2;
-        normal_pair(key, s >> 1, 0u, 0u, kDomEuler, z1, z2);
+        euler_scalar_normals(key, s >> 1, z1, z2);
         const double d1 = a.sqrt_dt * z1;
         M::step(st, a, d1, 0.0);
         if constexpr (ANTI) M::step(sa, a, -d1, 0.0);

@@ -48,6 +48,7 @@
 #include "hh_kernels.h"
 #include "hh_math.h"
 #include "hh_rng.h"
+#include "hh_sim.h"
 #include <atomic>
 
 namespace hh {
@@ -117,6 +118,75 @@ __global__ __launch_bounds__(256) void gbm_grid_kernel(const uint64_t* __restric
                      // a reciprocal (6 instructions, <= 3.5 ulp) instead of a second exponential (25)
           Sa = Sa + Sa * (e2a * fm::rcp(e) - 1.0);
           __builtin_nontemporal_store(Sa, &grid[(size_t)(s + h + 1) * ntot + n_paths + i]);
+        }
+      }
+    }
+  }
+}
+
+// The state of an Euler–Maruyama trajectory (heston.jl:7-52, GENERATE noise) at every date: what
+// simulate_paths(sde_problem(prob, dynamics, EulerMaruyama()), …) holds per trajectory, the state [log S, V]
+// (LogHestonProblem / LogGBMProblem, montecarlo.jl:161-207).  The draws, the correlation and the step are
+// euler_kernel's (hh_sim.h: euler_pair_increments / euler_scalar_normals, M::step), so row n_steps of the spot
+// grid is hh_mc_solve's terminal bit for bit: S = exp(x) as finish_path forms it.  LOG: x itself.  Row 0 is the
+// caller's S0 (log S0).  Antithetic: the mirrored path (-dW, the same lane) in column n_paths + i.  WRITE_V: the
+// variance state after each step into vgrid, V0 in row 0.  One row of a wave is a coalesced 512-byte line; the
+// grid is written once and read once by the induction, far beyond what the caches hold: nontemporal stores.
+template <class M, bool ANTI, bool LOG, bool WRITE_V>
+__global__ __launch_bounds__(256) void euler_grid_kernel(const SimArgs<0> a, double row0,
+                                                         double* __restrict__ grid,
+                                                         double* __restrict__ vgrid) {
+  using State = typename M::State;
+  constexpr int NC = M::NCOMP;
+  static_assert(!WRITE_V || NC == 2, "variance rows belong to the Heston state");
+  const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= a.n_paths) return;
+  const uint64_t ntot = ANTI ? 2 * a.n_paths : a.n_paths;
+  const uint32_t n_steps = a.n_steps;
+  auto put = [&](uint32_t row, const State& s, uint64_t col) {
+    const double v = LOG ? s.x.v : exp(s.x.v);
+    __builtin_nontemporal_store(v, &grid[(size_t)row * ntot + col]);
+    if constexpr (WRITE_V) __builtin_nontemporal_store(s.v.v, &vgrid[(size_t)row * ntot + col]);
+  };
+  State st, sa;
+  M::init(st, a);
+  if constexpr (ANTI) M::init(sa, a);
+  grid[i] = row0;
+  if constexpr (ANTI) grid[a.n_paths + i] = row0;
+  if constexpr (WRITE_V) {
+    vgrid[i] = a.v0.v;
+    if constexpr (ANTI) vgrid[a.n_paths + i] = a.v0.v;
+  }
+  const uint64_t key = a.seeds[i];  // montecarlo.jl:331
+  if constexpr (NC == 2) {
+    for (uint32_t s = 0; s < n_steps; ++s) {
+      double d1, d2;
+      euler_pair_increments(key, s, a, d1, d2);
+      M::step(st, a, d1, d2);
+      put(s + 1, st, i);
+      if constexpr (ANTI) {
+        M::step(sa, a, -d1, -d2);  // montecarlo.jl:258: -W
+        put(s + 1, sa, a.n_paths + i);
+      }
+    }
+  } else {
+    for (uint32_t s = 0; s < n_steps; s += 2) {
+      double z1, z2;
+      euler_scalar_normals(key, s >> 1, z1, z2);
+      const double d1 = a.sqrt_dt * z1;
+      M::step(st, a, d1, 0.0);
+      put(s + 1, st, i);
+      if constexpr (ANTI) {
+        M::step(sa, a, -d1, 0.0);
+        put(s + 1, sa, a.n_paths + i);
+      }
+      if (s + 1 < n_steps) {
+        const double d2 = a.sqrt_dt * z2;
+        M::step(st, a, d2, 0.0);
+        put(s + 2, st, i);
+        if constexpr (ANTI) {
+          M::step(sa, a, -d2, 0.0);
+          put(s + 2, sa, a.n_paths + i);
         }
       }
     }
@@ -1308,6 +1378,38 @@ int launch_gbm_grid(const uint64_t* seeds_dev, uint64_t n_paths, uint32_t n_step
   else
     hipLaunchKernelGGL(gbm_grid_kernel<false>, g, blk, 0, s, seeds_dev, n_paths, n_steps, S0, a, b,
                        1.0, grid);
+  return (int)hipGetLastError();
+}
+
+int launch_euler_grid(const hh_model& m, const hh_config& c, const uint64_t* seeds_dev, bool log_state,
+                      double* grid, double* var_grid, hipStream_t s) {
+  DevicePtrs p{};
+  p.seeds = seeds_dev;
+  const SimArgs<0> a = make_args0(m, c, p);
+  const double row0 = log_state ? a.x0.v : m.S0;
+  const dim3 g((unsigned)((c.n_paths + 255) / 256)), blk(256);
+  auto go = [&](auto model, auto anti, auto log, auto write_v) {
+    hipLaunchKernelGGL((euler_grid_kernel<decltype(model), decltype(anti)::value, decltype(log)::value,
+                                          decltype(write_v)::value>),
+                       g, blk, 0, s, a, row0, grid, var_grid);
+  };
+  auto with_v = [&](auto model, auto anti, auto log) {
+    if constexpr (decltype(model)::NCOMP == 2) {
+      if (var_grid) return go(model, anti, log, std::true_type{});
+    }
+    go(model, anti, log, std::false_type{});
+  };
+  auto with_log = [&](auto model, auto anti) {
+    if (log_state) with_v(model, anti, std::true_type{});
+    else with_v(model, anti, std::false_type{});
+  };
+  auto with_anti = [&](auto model) {
+    if (c.antithetic) with_log(model, std::true_type{});
+    else with_log(model, std::false_type{});
+  };
+  if (c.dynamics == HH_LOGNORMAL) with_anti(GbmModel<0>{});
+  else if (c.em_split) with_anti(HestonModel<0, true>{});
+  else with_anti(HestonModel<0, false>{});
   return (int)hipGetLastError();
 }
 

@@ -120,6 +120,27 @@ struct GbmModel {
 };
 
 // ------------------------------------------------------------------------------------------
+// GENERATE noise of an Euler trajectory (montecarlo.jl:331: its draws are keyed by its seed)
+// ------------------------------------------------------------------------------------------
+// Every kernel that draws Euler increments in registers takes them from here, so that a grid of states and the
+// terminal of the same trajectory see the same increments.  The loops stay in the kernels: written as one helper
+// with the step as a callback, the compiler schedules euler_kernel differently.
+
+// two components (Heston): one Philox pair per step, correlated (heston.jl:7-31 with the noise's ρ)
+template <int P>
+__device__ __forceinline__ void euler_pair_increments(uint64_t key, uint32_t s, const SimArgs<P>& a, double& d1,
+                                                      double& d2) {
+  double z1, z2;
+  normal_pair(key, s, 0u, 0u, kDomEuler, z1, z2);
+  d1 = a.sqrt_dt * z1;
+  d2 = a.sqrt_dt * fma(a.rho, z1, a.rho_c * z2);
+}
+// one component (lognormal): one Philox pair per two steps — step 2h takes sqrt(dt)·z1, step 2h+1 sqrt(dt)·z2
+__device__ __forceinline__ void euler_scalar_normals(uint64_t key, uint32_t h, double& z1, double& z2) {
+  normal_pair(key, h, 0u, 0u, kDomEuler, z1, z2);
+}
+
+// ------------------------------------------------------------------------------------------
 // payoff + reduction
 // ------------------------------------------------------------------------------------------
 

@@ -5,8 +5,11 @@
 reference's LSM is used with (test/agreement/american_options.jl), and HestonDynamics +
 HestonBroadieKaya (per-date exact transitions, montecarlo.jl:209-231), regressed on the SPOT rows.
 For every log-state problem (the Euler ones, and HestonNoise) the reference's extract_spot_grid
-(:47-85) hands the regression log-prices; that as-run behaviour is not reproduced: the Euler
-combinations raise MethodError here, and the exact Heston paths are exponentiated first."""
+(:47-85) hands the regression log-prices.  The exact Heston paths are exponentiated first.  The Euler
+combinations (LognormalDynamics or HestonDynamics + EulerMaruyama, `hh_lsm_solve_euler`) are reached
+only when the caller names the path state: path_state="spot" regresses on exp(log S) as for the exact
+Heston paths, path_state="log" hands log S to the regression and the payoff, the reference as run.
+Without it they raise MethodError."""
 from __future__ import annotations
 
 import ctypes as C
@@ -19,8 +22,10 @@ from . import _ffi
 from .dates import MILLISECONDS_IN_YEAR_365, yearfrac
 from .domain import (American, BlackScholesInputs, HestonInputs, PricingProblem, VanillaOption, df,
                      get_vol, zero_rate)
-from .montecarlo import (AbstractPricingMethod, Antithetic, BlackScholesExact, HestonBroadieKaya,
-                         HestonDynamics, LognormalDynamics, MethodError, MonteCarlo)
+from .montecarlo import (AbstractPricingMethod, Antithetic, BlackScholesExact, EulerMaruyama,
+                         HestonBroadieKaya, HestonDynamics, LognormalDynamics, MethodError, MonteCarlo)
+
+_PATH_STATES = {"spot": _ffi.HH_PATH_SPOT, "log": _ffi.HH_PATH_LOG}
 
 
 @dataclass(frozen=True)
@@ -54,8 +59,19 @@ class LSMSolution:
     result: Any = field(default=None, compare=False, repr=False)
 
 
-def _lsm_structs(prob: PricingProblem, mc: MonteCarlo):
-    """hh_model / hh_config of the path source behind an LSM solve (or a bare path simulation)."""
+def _is_euler(mc: MonteCarlo) -> bool:
+    return isinstance(mc.strategy, EulerMaruyama) and isinstance(mc.dynamics, (LognormalDynamics, HestonDynamics))
+
+
+def _path_state_code(path_state) -> int:
+    if path_state not in _PATH_STATES:
+        raise ValueError(f'path_state must be "spot" or "log", not {path_state!r}')
+    return _PATH_STATES[path_state]
+
+
+def _lsm_structs(prob: PricingProblem, mc: MonteCarlo, euler: bool = False):
+    """hh_model / hh_config of the path source behind an LSM solve (or a bare path simulation).
+    euler: the Euler sources are admitted (the caller has named a path state)."""
     payoff, m = prob.payoff, prob.market_inputs
     cfg = mc.config
     from .dual import n_partials
@@ -79,6 +95,17 @@ def _lsm_structs(prob: PricingProblem, mc: MonteCarlo):
         model.V0, model.kappa, model.theta = float(m.V0), float(m.κ), float(m.θ)
         model.sigma, model.rho = float(m.σ), float(m.ρ)
         c.dynamics, c.strategy = _ffi.HH_HESTON, _ffi.HH_BROADIE_KAYA
+    elif euler and isinstance(mc.strategy, EulerMaruyama) and isinstance(mc.dynamics, LognormalDynamics) \
+            and isinstance(m, BlackScholesInputs):
+        model.sigma = float(get_vol(m.sigma, None, None))
+        c.dynamics, c.strategy = _ffi.HH_LOGNORMAL, _ffi.HH_EULER_MARUYAMA
+        c.em_split = int(mc.em_split)                                   # as montecarlo.py packs it
+    elif euler and isinstance(mc.strategy, EulerMaruyama) and isinstance(mc.dynamics, HestonDynamics) \
+            and isinstance(m, HestonInputs):
+        model.V0, model.kappa, model.theta = float(m.V0), float(m.κ), float(m.θ)
+        model.sigma, model.rho = float(m.σ), float(m.ρ)
+        c.dynamics, c.strategy = _ffi.HH_HESTON, _ffi.HH_EULER_MARUYAMA
+        c.em_split = int(mc.em_split)
     else:
         raise MethodError("full-path simulation on the HIP path: LognormalDynamics + BlackScholesExact "
                           "on BlackScholesInputs, or HestonDynamics + HestonBroadieKaya on HestonInputs")
@@ -94,12 +121,18 @@ def _lsm_structs(prob: PricingProblem, mc: MonteCarlo):
 
 
 def solve_lsm(prob: PricingProblem, method: LSM, spot_paths: bool = False,
-              stopping_info: bool = True) -> LSMSolution:
+              stopping_info: bool = True, path_state=None) -> LSMSolution:
+    """path_state: None (the exact sources only), "spot" or "log" (module docstring).  On an exact source
+    "spot" is what it does anyway and "log" raises MethodError.  With path_state="log", spot_paths holds log S."""
     payoff, m = prob.payoff, prob.market_inputs
     if not (isinstance(payoff, VanillaOption) and isinstance(payoff.exercise_style, American)):
         raise MethodError("solve(::PricingProblem, ::LSM) needs an American VanillaOption")
     mc = method.mc_method
-    model, c, T = _lsm_structs(prob, mc)
+    state = None if path_state is None else _path_state_code(path_state)
+    euler = state is not None and _is_euler(mc)
+    if state == _ffi.HH_PATH_LOG and not euler:
+        raise MethodError('path_state="log" applies to the Euler path sources only')
+    model, c, T = _lsm_structs(prob, mc, euler=euler)
     cfg = mc.config
     nsteps = cfg.steps
     # discount = df(rate, add_yearfrac(referenceDate, T / nsteps))      # :107
@@ -110,6 +143,8 @@ def solve_lsm(prob: PricingProblem, method: LSM, spot_paths: bool = False,
     grid = np.empty((nsteps + 1, ntot)) if spot_paths else None
     res = _ffi.hh_lsm_result()
     if mc.devices is not None:  # ONE call, the trajectories sharded over these GPUs inside the library
+        if euler:
+            raise MethodError("LSM on Euler paths is not sharded over several GPUs")
         if spot_paths:
             raise ValueError("spot_paths is not returned by the multi-GPU form")
         mg = _ffi.get_multi_gpu(tuple(mc.devices))
@@ -119,11 +154,14 @@ def solve_lsm(prob: PricingProblem, method: LSM, spot_paths: bool = False,
         return LSMSolution(prob, method, res.price, (tau, val) if stopping_info else None, None,
                            std_error=res.std_error, result=res)
     ctx = _ffi.get_context(mc.device)
-    ctx.check(ctx.lib.hh_lsm_solve(ctx.handle, C.byref(model), C.byref(c), method.degree,
-                                   step_discount, C.byref(res),
-                                   tau.ctypes.data if stopping_info else None,
-                                   val.ctypes.data if stopping_info else None,
-                                   grid.ctypes.data if spot_paths else None))
+    outs = (tau.ctypes.data if stopping_info else None, val.ctypes.data if stopping_info else None,
+            grid.ctypes.data if spot_paths else None)
+    if euler:
+        ctx.check(ctx.lib.hh_lsm_solve_euler(ctx.handle, C.byref(model), C.byref(c), state, method.degree,
+                                             step_discount, C.byref(res), *outs))
+    else:
+        ctx.check(ctx.lib.hh_lsm_solve(ctx.handle, C.byref(model), C.byref(c), method.degree,
+                                       step_discount, C.byref(res), *outs))
     return LSMSolution(prob, method, res.price, (tau, val) if stopping_info else None, grid,
                        std_error=res.std_error, result=res)
 
@@ -157,3 +195,33 @@ def simulate_heston_exact_paths(prob: PricingProblem, mc: MonteCarlo) -> HestonE
     ctx.check(ctx.lib.hh_heston_exact_grid(ctx.handle, C.byref(model), C.byref(c), spot.ctypes.data,
                                            var.ctypes.data, 0, C.byref(res)))
     return HestonExactPaths(spot, var, np.linspace(0.0, T, steps + 1), res)
+
+
+@dataclass(frozen=True)
+class EulerPaths:
+    """What simulate_paths(sde_problem(prob, dynamics, EulerMaruyama()), method, variance_reduction) holds per
+    trajectory (montecarlo.jl:161-207, 342-375), as (steps+1, n) matrices: `spot` in the path state asked for
+    (exp(log S), or log S itself), `variance` the Heston variance state (None for lognormal dynamics).  Antithetic:
+    n = 2·trajectories, the mirrored path of trajectory i in column trajectories + i."""
+    spot: Any
+    variance: Any
+    times: Any
+    result: Any = field(default=None, compare=False, repr=False)
+
+
+def simulate_euler_paths(prob: PricingProblem, mc: MonteCarlo, path_state: str = "spot") -> EulerPaths:
+    """Euler–Maruyama paths (GENERATE) through hh_euler_grid: the draws of solve(prob, mc) on the same seeds, so
+    the last spot row is that solve's terminal sample."""
+    state = _path_state_code(path_state)
+    if not _is_euler(mc):
+        raise MethodError("simulate_euler_paths needs LognormalDynamics or HestonDynamics + EulerMaruyama")
+    model, c, T = _lsm_structs(prob, mc, euler=True)
+    steps = mc.config.steps
+    ntot = mc.config.trajectories * (2 if c.antithetic else 1)
+    spot = np.empty((steps + 1, ntot))
+    var = np.empty((steps + 1, ntot)) if c.dynamics == _ffi.HH_HESTON else None
+    res = _ffi.hh_result()
+    ctx = _ffi.get_context(mc.device)
+    ctx.check(ctx.lib.hh_euler_grid(ctx.handle, C.byref(model), C.byref(c), state, spot.ctypes.data,
+                                    var.ctypes.data if var is not None else None, 0, C.byref(res)))
+    return EulerPaths(spot, var, np.linspace(0.0, T, steps + 1), res)

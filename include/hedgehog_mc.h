@@ -506,6 +506,38 @@ int hh_lsm_solve_grid(hh_ctx* ctx, const hh_model* model, const double* spot_gri
                       hh_lsm_result* out, int32_t* stop_time, double* stop_value);
 
 /*
+ * Euler–Maruyama paths at every date, and LSM on them (opt-in).
+ *   simulate_paths(sde_problem(prob, dynamics, EulerMaruyama()), …)   (montecarlo.jl:161-207, 342-375)
+ * cfg: dynamics = HH_LOGNORMAL or HH_HESTON, strategy = HH_EULER_MARUYAMA, noise_mode = HH_NOISE_GENERATE,
+ * n_partials = 0; em_split and antithetic as for hh_mc_solve.  Seeds: one per trajectory (seeds_len, when set,
+ * >= n_paths), trajectory i keyed by seeds[i] (montecarlo.jl:331) and drawn exactly as hh_mc_solve draws it, so
+ * row n_steps of the HH_PATH_SPOT grid is hh_mc_solve's terminal output bit for bit.  Antithetic: the mirrored
+ * path (-dW) of trajectory i in column n_paths + i.  path_offset is not read — as in every Euler solve, trajectory i
+ * takes seeds[i] whatever the offset; a shard passes its own slice of the seeds.
+ *
+ * Path state.  The state of these problems is [log S, V] (LogGBMProblem, LogHestonProblem); the reference's
+ * extract_spot_grid takes its first component (least_squares_montecarlo.jl:47-85), so as run the reference
+ * regresses on log S and applies the payoff to log S.  The caller names the reading:
+ *   HH_PATH_SPOT  rows exp(log S) — this library's reading, as for the Broadie–Kaya paths (hh_lsm_solve)
+ *   HH_PATH_LOG   rows log S — handed to the regression and to the payoff as they are: the reference as run
+ * hh_lsm_solve keeps refusing Euler configurations (HH_ERR_UNSUPPORTED): only these entry points reach them.
+ *
+ * hh_euler_grid: spot_grid (rows in the path state) and var_grid (Heston only: V0 in row 0, then the variance
+ * state after each step) are nullable, hh_lsm_grid_elems(n_paths, n_steps, antithetic) doubles each, step-major;
+ * host memory, or device memory when grids_on_device.  out (nullable): n_paths_done, kernel_ms, total_ms.
+ * hh_lsm_solve_euler: the grid in device memory, then the backward induction of hh_lsm_solve_grid on it (the
+ * same forms, fall-backs and HH_OPT_LSM_FORM); the outputs as for hh_lsm_solve.
+ * REPLAY noise, dual partials, other strategies and var_grid on lognormal dynamics: HH_ERR_UNSUPPORTED.
+ * Not provided: a sharded / multi-GPU Euler LSM (no hh_lsm_shard_begin counterpart).
+ */
+enum hh_path_state { HH_PATH_SPOT = 0, HH_PATH_LOG = 1 };
+int hh_euler_grid(hh_ctx* ctx, const hh_model* model, const hh_config* cfg, int32_t path_state,
+                  double* spot_grid, double* var_grid, int32_t grids_on_device, hh_result* out);
+int hh_lsm_solve_euler(hh_ctx* ctx, const hh_model* model, const hh_config* cfg, int32_t path_state,
+                       int32_t degree, double step_discount, hh_lsm_result* out, int32_t* stop_time,
+                       double* stop_value, double* spot_grid);
+
+/*
  * The same solve for an ensemble SHARDED over several devices (one process and one hh_ctx per
  * device, trajectories split by contiguous ranges as for hh_mc_accumulate).  The backward induction
  * needs sums over ALL trajectories at three points — the in-the-money statistics of every row, the

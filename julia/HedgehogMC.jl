@@ -14,7 +14,7 @@
 # keywords), hh_mc_solve_multi / hh_mgpu_solve_multi (prices_hip: the solves of a bumped Greek on shared draws),
 # hh_seeds_cache (the library's own seed cache), hh_mgpu_create / hh_mgpu_solve (solve_hip(...; devices = 0:7): several GPUs behind the one
 # call), hh_mc_accumulate + hh_mc_finalize (solve_sharded_hip: one process per GPU), hh_mc_solve_basket, hh_carr_madan,
-# hh_carr_madan_basket (+ _grad), hh_ctx_set_option, hh_lsm_solve, hh_heston_exact_grid, hh_replay_elems, the device-memory helpers.  The struct mirrors
+# hh_carr_madan_basket (+ _grad), hh_ctx_set_option, hh_lsm_solve, hh_heston_exact_grid, hh_euler_grid + hh_lsm_solve_euler (opt-in), hh_replay_elems, the device-memory helpers.  The struct mirrors
 # below are checked field by field against the C header by tests/test_julia_layout.py (offsets from
 # a compiled offsetof dump), so a drift between the two shows up on the CPU, without Julia.
 module HedgehogMC
@@ -34,6 +34,7 @@ const HH_ACC_LEN = 16
 const HH_ABI_VERSION = 6
 const HH_NOISE_GENERATE, HH_NOISE_REPLAY = Int32(0), Int32(1)
 const HH_REPLAY_TILE_MAJOR, HH_REPLAY_PATH_MAJOR = Int32(0), Int32(1)
+const HH_PATH_SPOT, HH_PATH_LOG = Int32(0), Int32(1)   # rows of an Euler grid: exp(log S) / log S (hh_path_state)
 
 # ---- C structs (layout of include/hedgehog_mc.h) ---------------------------------------------
 struct HHModel
@@ -533,7 +534,7 @@ end
 
 # (a docstring must sit DIRECTLY above its function: nothing between the closing quotes and `function`)
 """
-    solve_lsm_hip(prob, method::LSM; devices = nothing)
+    solve_lsm_hip(prob, method::LSM{<:MonteCarlo{<:Any,BlackScholesExact}}; devices = nothing)
 
 `hh_lsm_solve`: GBM-process paths of (LognormalDynamics, BlackScholesExact), backward induction with
 polynomial regression of degree `method.degree`.  Returns an `LSMSolution` whose `stopping_info` is
@@ -542,9 +543,14 @@ rebuilt from the (time, value) arrays and whose `spot_paths` is the (nsteps+1) x
 `devices = 0:7`: the same solve with the trajectories sharded over those GPUs inside the library
 (`hh_mgpu_lsm_solve`: the phased induction on every device, its per-date sums all-reduced in the library);
 the spot grid is then not returned (`spot_paths` of the solution is an empty matrix).
+
+`method` names its strategy so that this method and the EulerMaruyama one below are disjoint in the method
+argument: with a bare `::LSM` here, a BlackScholesInputs problem with an Euler LSM would match both (this one
+more specific in the problem, that one in the method) and Julia would throw an ambiguity error.
 """
 function solve_lsm_hip(prob::PricingProblem{VanillaOption{TS,TE,Hedgehog.American,C,S},I},
-                       method::Hedgehog.LSM; devices = nothing) where {TS,TE,C,S,I<:BlackScholesInputs}
+                       method::Hedgehog.LSM{<:MonteCarlo{<:Any,BlackScholesExact}};
+                       devices = nothing) where {TS,TE,C,S,I<:BlackScholesInputs}
     mc, m, payoff = method.mc_method, prob.market_inputs, prob.payoff
     (mc.dynamics isa LognormalDynamics && mc.strategy isa BlackScholesExact) ||
         throw(MethodError(Hedgehog.solve, (prob, method)))
@@ -620,6 +626,102 @@ function heston_exact_paths_hip(prob::PricingProblem{P,I}, method::MonteCarlo) w
         rc == 0 || error("hh_heston_exact_grid failed ($rc): $(last_error(ctx))")
     end
     return permutedims(spot), permutedims(var)
+end
+
+# ---- Euler–Maruyama paths and LSM on them (opt-in: the caller names the path state) ----------------
+_path_state(s::Symbol) = s === :spot ? HH_PATH_SPOT : s === :log ? HH_PATH_LOG :
+    throw(ArgumentError("path_state must be :spot or :log"))
+
+# hh_model / hh_config of (LognormalDynamics | HestonDynamics) + EulerMaruyama, GENERATE; the caller preserves `seeds`
+function _euler_structs(prob, mc::MonteCarlo, seeds::Vector{UInt64}, em_split::Bool)
+    m, payoff, cfg = prob.market_inputs, prob.payoff, mc.config
+    T = yearfrac(m.referenceDate, payoff.expiry)                                   # montecarlo.jl:173,197
+    r = Float64(zero_rate(m.rate, 0.0))                                            # montecarlo.jl:176,200
+    heston = mc.dynamics isa HestonDynamics
+    model = heston ?
+        HHModel(Float64(m.spot), Float64(m.V0), Float64(m.κ), Float64(m.θ), Float64(m.σ), Float64(m.ρ), r, 1.0,
+                Float64(T), Float64(payoff.strike), payoff.call_put(), ntuple(_ -> Ptr{Cdouble}(C_NULL), 8)...) :
+        HHModel(Float64(m.spot), 0.0, 0.0, 0.0, Float64(get_vol(m.sigma, nothing, nothing)), 0.0, r, 1.0,
+                Float64(T), Float64(payoff.strike), payoff.call_put(), ntuple(_ -> Ptr{Cdouble}(C_NULL), 8)...)
+    anti = cfg.variance_reduction isa Antithetic
+    config = HHConfig(Int32(heston ? 1 : 0), Int32(0), Int32(anti), Int32(em_split), Int32(0), Int32(0), Int32(0),
+                      Int32(0), Int32(0), Int32(0), UInt32(cfg.steps), UInt32(0), UInt64(cfg.trajectories),
+                      UInt64(0), pointer(seeds), Ptr{Cdouble}(C_NULL), 0.0, 0.0, 0.0, 0.0, Int32(0), Int32(0),
+                      Int32(0), Int32(0), Int32(0), Int32(0), UInt64(length(seeds)), UInt64(0))
+    return model, config, T, anti
+end
+
+"""
+    solve_lsm_hip(prob, method::LSM{<:MonteCarlo{<:Any,EulerMaruyama}}; path_state = :spot, em_split = true)
+
+`hh_lsm_solve_euler`: LSM on Euler–Maruyama paths of LognormalDynamics or HestonDynamics (GENERATE, the
+draws of `solve(prob, method.mc_method)` on the same seeds).  The reference's state is `[log S, V]` and its
+`extract_spot_grid` hands the regression and the payoff log S (least_squares_montecarlo.jl:47-85):
+`path_state = :log` reproduces that as run, `:spot` (this library's reading) regresses on exp(log S).  Not
+routed by `install!`: the reading is the caller's choice.  `spot_paths` holds the rows in the path state.
+"""
+function solve_lsm_hip(prob::PricingProblem{VanillaOption{TS,TE,Hedgehog.American,C,S},I},
+                       method::Hedgehog.LSM{MonteCarlo{D,EulerMaruyama,CF}}; path_state::Symbol = :spot,
+                       em_split::Bool = true) where {TS,TE,C,S,I<:Union{BlackScholesInputs,HestonInputs},
+                                                     D<:Union{LognormalDynamics,HestonDynamics},CF}
+    mc, m, payoff = method.mc_method, prob.market_inputs, prob.payoff
+    ((D <: HestonDynamics) == (I <: HestonInputs)) || throw(MethodError(Hedgehog.solve, (prob, method)))
+    state = _path_state(path_state)
+    cfg = mc.config
+    nsteps = Int(cfg.steps)
+    seeds = convert(Vector{UInt64}, cfg.seeds .% UInt64)
+    anti = cfg.variance_reduction isa Antithetic
+    n = Int(cfg.trajectories); ntot = anti ? 2n : n
+    tau = Vector{Int32}(undef, ntot); val = Vector{Float64}(undef, ntot)
+    grid = Matrix{Float64}(undef, ntot, nsteps + 1)          # column-major: [path, step] = C [step][path]
+    res = Ref{HHLsmResult}()
+    ctx = context()
+    GC.@preserve seeds tau val grid begin
+        model, config, T, _ = _euler_structs(prob, mc, seeds, em_split)
+        step_discount = df(m.rate, Hedgehog.add_yearfrac(m.referenceDate, T / nsteps))   # :107
+        rc = ccall((:hh_lsm_solve_euler, LIB[]), Cint,
+                   (Ptr{Cvoid}, Ref{HHModel}, Ref{HHConfig}, Int32, Int32, Cdouble, Ref{HHLsmResult},
+                    Ptr{Int32}, Ptr{Cdouble}, Ptr{Cdouble}),
+                   ctx.handle, model, config, state, Int32(method.degree), Float64(step_discount), res,
+                   pointer(tau), pointer(val), pointer(grid))
+        rc == 0 || error("hh_lsm_solve_euler failed ($rc): $(last_error(ctx))")
+    end
+    stopping_info = [(Int(tau[p]), val[p]) for p in 1:ntot]
+    return Hedgehog.LSMSolution(prob, method, res[].price, stopping_info, permutedims(grid))
+end
+
+"""
+    euler_paths_hip(prob, method::MonteCarlo; path_state = :spot, em_split = true) -> (spot, variance)
+
+`hh_euler_grid`: what `simulate_paths(sde_problem(prob, dynamics, EulerMaruyama()), method, …)`
+(montecarlo.jl:161-207, 342-375) holds per trajectory, as (nsteps+1) x npaths matrices (x 2npaths antithetic,
+the mirrored path of trajectory i in column npaths + i): the first state component as exp(log S) (`:spot`) or
+log S (`:log`), and the Heston variance state (`nothing` for LognormalDynamics).
+"""
+function euler_paths_hip(prob::PricingProblem, method::MonteCarlo; path_state::Symbol = :spot,
+                         em_split::Bool = true)
+    (method.strategy isa EulerMaruyama &&
+     (method.dynamics isa HestonDynamics ? prob.market_inputs isa HestonInputs :
+      method.dynamics isa LognormalDynamics && prob.market_inputs isa BlackScholesInputs)) ||
+        throw(MethodError(euler_paths_hip, (prob, method)))
+    state = _path_state(path_state)
+    cfg = method.config
+    nsteps = Int(cfg.steps)
+    seeds = convert(Vector{UInt64}, cfg.seeds .% UInt64)
+    heston = method.dynamics isa HestonDynamics
+    ntot = (cfg.variance_reduction isa Antithetic ? 2 : 1) * Int(cfg.trajectories)
+    spot = Matrix{Float64}(undef, ntot, nsteps + 1)
+    var = heston ? Matrix{Float64}(undef, ntot, nsteps + 1) : Matrix{Float64}(undef, 0, 0)
+    ctx = context()
+    GC.@preserve seeds spot var begin
+        model, config, _, _ = _euler_structs(prob, method, seeds, em_split)
+        rc = ccall((:hh_euler_grid, LIB[]), Cint,
+                   (Ptr{Cvoid}, Ref{HHModel}, Ref{HHConfig}, Int32, Ptr{Cdouble}, Ptr{Cdouble}, Int32, Ptr{Cvoid}),
+                   ctx.handle, model, config, state, pointer(spot), heston ? pointer(var) : Ptr{Cdouble}(C_NULL),
+                   Int32(0), C_NULL)
+        rc == 0 || error("hh_euler_grid failed ($rc): $(last_error(ctx))")
+    end
+    return permutedims(spot), heston ? permutedims(var) : nothing
 end
 
 const DEVICES = Ref{Any}(nothing)   # install!(devices = 0:7): every routed solve is sharded over these GPUs
