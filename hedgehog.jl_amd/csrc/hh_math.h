@@ -238,7 +238,9 @@ HH_MATH_FN double log(double x) {
   return fma(de, 6.93147180369123816490e-01, fma(2.0, s, t));       // e·ln2_hi exact
 }
 
-// atan2(y, x) for finite arguments, not both zero
+// atan2(y, x) for finite arguments, not both zero.  A zero y counts as +0 whatever its sign: (-0, x < 0) gives +π,
+// not libm's -π, and (-0, x > 0) gives +0 — the angle of the upper side, which is also the side besseli_logmul
+// (hh_bessel.h) reflects such an argument to (pinned on the device by tests/test_gpu_math_device.py)
 // The angle of (|x|, |y|) in the first quadrant is H + atan(n/d) with ONE division and one break point: with
 // m = min, M = max of |x|, |y| and t = m/M in [0, 1],
 //   t <  7/16:  |y| <= |x|: atan(|y|/|x|)                       (H = 0,   n = |y|,  d = |x|)

@@ -10,6 +10,7 @@ import subprocess
 import pytest
 
 from tests.conftest import host_cxxflags, host_env
+from tests.math_bars import BARS
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -22,10 +23,7 @@ def test_hh_math_against_long_double_libm(tmp_path):
                     os.path.join(ROOT, "tests", "c", "math_check.cpp"), "-o", str(exe)], check=True)
     out = subprocess.run([str(exe)], check=True, capture_output=True, text=True, env=host_env()).stdout
     err = {ln.split()[0]: float(ln.split()[2]) for ln in out.strip().splitlines()}
-    assert set(err) == {"sin", "cos", "log", "atan2", "exp", "wsin", "wcos", "nquant"}
-    # exp <= 1.5 ulp; the wide sincos (|x| <= 2^45, three-term reduction) as good as the narrow one
-    assert err["exp"] < 1.5 and err["wsin"] < 2.0 and err["wcos"] < 2.0, err
-    # ulp of the fp64 result (sin/cos: absolute 2^-73 where the value is below 1e-6)
-    assert err["sin"] < 2.0 and err["cos"] < 2.0 and err["log"] < 2.5 and err["atan2"] < 2.5, err
-    # the normal quantile (AS 241): a rational approximation good to 1e-16 before rounding; it seeds a root search
-    assert err["nquant"] < 8.0, err
+    assert set(err) == set(BARS) == {"sin", "cos", "log", "atan2", "exp", "wsin", "wcos", "nquant"}
+    # sin/cos < 2, log/atan2 < 2.5, exp < 1.5, wide sincos < 2, normal quantile < 8 ulp (tests/math_bars.py)
+    for name, bar in BARS.items():
+        assert err[name] < bar, (name, err)
