@@ -1,7 +1,6 @@
 // C-ABI of libhedgehog_mc.so (include/hedgehog_mc.h): context, argument checking, staging of
 // caller buffers, kernel sequencing.  No arithmetic of the pricing path happens on the host except
 // hh_mc_finalize's discount·mean (montecarlo.jl:489-490) on the reduced accumulator vector.
-#include <chrono>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -182,6 +181,22 @@ size_t replay_elems(uint64_t n_paths, uint32_t n_steps, int dynamics) {
   return (size_t)hh::tiles_for(n_paths) * n_steps * ncomp_of(dynamics) * hh::kTile;
 }
 
+// the times of a solve: kernel_ms from ctx->ev0 to ctx->ev1 (the stream has passed ev1), total_ms on the clock
+int solve_times(hh_ctx* ctx, const WallClock& clock, double* kernel_ms, double* total_ms) {
+  float ms = 0.f;
+  HH_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
+  *kernel_ms = ms;
+  *total_ms = clock.ms();
+  return HH_OK;
+}
+
+// mean and sample variance (0 for a single trajectory, clamped at 0) of the payoffs an accumulator vector sums over n
+void payoff_moments(const double* acc, double n, double* mean, double* var) {
+  *mean = acc[HH_ACC_SUM] / n;
+  *var = n > 1.0 ? (acc[HH_ACC_SUMSQ] - n * *mean * *mean) / (n - 1.0) : 0.0;
+  if (!(*var > 0.0)) *var = 0.0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -348,12 +363,8 @@ int hh_replay_pack(hh_ctx* ctx, int32_t dynamics, uint64_t n_paths, uint32_t n_s
   const double* src_dev = src;
   if (!src_on_device) {
     const size_t n = (size_t)n_paths * n_steps * nc;
-    int rc = ensure(ctx, ctx->replay_src, ctx->replay_src_cap, n);
+    const int rc = stage_host(ctx, ctx->replay_src, ctx->replay_src_cap, n, src, n, &src_dev);
     if (rc) return rc;
-    HH_HIP(ctx, hipMemcpyAsync(ctx->replay_src, src, n * sizeof(double), hipMemcpyHostToDevice,
-                               ctx->stream));
-    if ((rc = note_host_copy(ctx))) return rc;
-    src_dev = ctx->replay_src;
   }
   HH_HIP(ctx, hh::launch_replay_pack(nc, n_paths, n_steps, src_dev, dst, ctx->stream));
   return release_host_operands(ctx);
@@ -369,12 +380,8 @@ int hh_wiener_fill(hh_ctx* ctx, int32_t dynamics, double rho, double T, uint32_t
   HH_HIP(ctx, hipSetDevice(ctx->device));
   const uint64_t* seeds_dev = seeds;
   if (!seeds_on_device) {
-    int rc = ensure(ctx, ctx->seeds, ctx->seeds_cap, (size_t)n_paths);
+    const int rc = stage_host(ctx, ctx->seeds, ctx->seeds_cap, (size_t)n_paths, seeds, (size_t)n_paths, &seeds_dev);
     if (rc) return rc;
-    HH_HIP(ctx, hipMemcpyAsync(ctx->seeds, seeds, n_paths * sizeof(uint64_t),
-                               hipMemcpyHostToDevice, ctx->stream));
-    if ((rc = note_host_copy(ctx))) return rc;
-    seeds_dev = ctx->seeds;
   }
   const double dt = T / (double)n_steps;
   HH_HIP(ctx, hh::launch_wiener_fill(dynamics, rho, std::sqrt(dt), n_steps, n_paths, seeds_dev, dst,
@@ -394,29 +401,17 @@ static int stage_noise(hh_ctx* ctx, const hh_config* c, hh::DevicePtrs& p, bool 
   // seeds: per-trajectory for Euler (montecarlo.jl:331), seeds[1] only for the exact laws (:456)
   if (c->noise_mode == HH_NOISE_GENERATE) {
     const size_t need = (c->strategy == HH_EULER_MARUYAMA) ? (size_t)c->n_paths : 1;
-    if (c->seeds_on_device) {
+    if (c->seeds_on_device)
       p.seeds = c->seeds;
-    } else {
-      rc = ensure(ctx, ctx->seeds, ctx->seeds_cap, need);
-      if (rc) return rc;
-      HH_HIP(ctx, hipMemcpyAsync(ctx->seeds, c->seeds, need * sizeof(uint64_t),
-                                 hipMemcpyHostToDevice, ctx->stream));
-      if ((rc = note_host_copy(ctx))) return rc;
-      p.seeds = ctx->seeds;
-    }
+    else if ((rc = stage_host(ctx, ctx->seeds, ctx->seeds_cap, need, c->seeds, need, &p.seeds)))
+      return rc;
   } else if (bk) {
     // the trajectory's three draws [V_T | u | Z], n_paths each (heston.jl:246-259 order)
     const size_t n3 = (size_t)3 * c->n_paths;
-    if (c->replay_on_device) {
+    if (c->replay_on_device)
       p.replay = c->replay;
-    } else {
-      rc = ensure(ctx, ctx->replay, ctx->replay_cap, n3);
-      if (rc) return rc;
-      HH_HIP(ctx, hipMemcpyAsync(ctx->replay, c->replay, n3 * sizeof(double), hipMemcpyHostToDevice,
-                                 ctx->stream));
-      if ((rc = note_host_copy(ctx))) return rc;
-      p.replay = ctx->replay;
-    }
+    else if ((rc = stage_host(ctx, ctx->replay, ctx->replay_cap, n3, c->replay, n3, &p.replay)))
+      return rc;
   } else {
     const uint32_t steps = (c->strategy == HH_EULER_MARUYAMA) ? c->n_steps : 1;
     const int dyn = (c->strategy == HH_EULER_MARUYAMA) ? c->dynamics : HH_LOGNORMAL;
@@ -424,17 +419,11 @@ static int stage_noise(hh_ctx* ctx, const hh_config* c, hh::DevicePtrs& p, bool 
     if (c->replay_layout == HH_REPLAY_PATH_MAJOR && c->strategy == HH_EULER_MARUYAMA && !tile_major_only &&
         hh::replay_direct_path_major(steps, ncomp_of(dyn))) {
       // the reference's layout, streamed as it stands (euler_pm_kernel): no repack pass
-      if (c->replay_on_device) {
+      const size_t n = (size_t)c->n_paths * steps * ncomp_of(dyn);
+      if (c->replay_on_device)
         p.replay = c->replay;
-      } else {
-        const size_t n = (size_t)c->n_paths * steps * ncomp_of(dyn);
-        rc = ensure(ctx, ctx->replay_src, ctx->replay_src_cap, n);
-        if (rc) return rc;
-        HH_HIP(ctx, hipMemcpyAsync(ctx->replay_src, c->replay, n * sizeof(double), hipMemcpyHostToDevice,
-                                   ctx->stream));
-        if ((rc = note_host_copy(ctx))) return rc;
-        p.replay = ctx->replay_src;
-      }
+      else if ((rc = stage_host(ctx, ctx->replay_src, ctx->replay_src_cap, n, c->replay, n, &p.replay)))
+        return rc;
       p.replay_path_major = true;
     } else if (c->replay_layout == HH_REPLAY_PATH_MAJOR) {
       rc = ensure(ctx, ctx->replay, ctx->replay_cap, tile_elems);
@@ -450,12 +439,8 @@ static int stage_noise(hh_ctx* ctx, const hh_config* c, hh::DevicePtrs& p, bool 
         // the kernel guards the tail); Euler: the padded tile-major buffer of hh_replay_elems()
         const size_t host_elems =
             (c->strategy == HH_EULER_MARUYAMA) ? tile_elems : (size_t)c->n_paths;
-        rc = ensure(ctx, ctx->replay, ctx->replay_cap, tile_elems);
+        rc = stage_host(ctx, ctx->replay, ctx->replay_cap, tile_elems, c->replay, host_elems, &p.replay);
         if (rc) return rc;
-        HH_HIP(ctx, hipMemcpyAsync(ctx->replay, c->replay, host_elems * sizeof(double),
-                                   hipMemcpyHostToDevice, ctx->stream));
-        if ((rc = note_host_copy(ctx))) return rc;
-        p.replay = ctx->replay;
       }
     } else {
       return fail(ctx, HH_ERR_INVALID, "unknown replay_layout %d", c->replay_layout);
@@ -677,7 +662,7 @@ int hh_mc_solve_multi(hh_ctx* ctx, const hh_model* models, uint32_t n_models, co
   std::lock_guard<std::recursive_mutex> lock__(ctx->mu);
   if (!out || !models || n_models == 0 || n_models > HH_MAX_MODELS)
     return fail(ctx, HH_ERR_INVALID, "hh_mc_solve_multi: 1 .. %d models and their results", HH_MAX_MODELS);
-  const auto t0 = std::chrono::steady_clock::now();
+  const WallClock clock;
   HH_HIP(ctx, hipSetDevice(ctx->device));
   const size_t n_acc = (size_t)n_models * HH_ACC_LEN;
   int rc = ensure(ctx, ctx->basket_accum, ctx->basket_accum_cap, n_acc);
@@ -688,16 +673,10 @@ int hh_mc_solve_multi(hh_ctx* ctx, const hh_model* models, uint32_t n_models, co
   double host[HH_MAX_MODELS * HH_ACC_LEN];
   HH_HIP(ctx, hipMemcpyAsync(host, ctx->basket_accum, n_acc * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   HH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  float ms = 0.f;
-  HH_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
-  const double total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  for (uint32_t k = 0; k < n_models; ++k) {
-    std::memset(&out[k], 0, sizeof(hh_result));
-    if ((rc = hh_mc_finalize(&models[k], c, host + (size_t)k * HH_ACC_LEN, &out[k]))) return finalize_failed(ctx, rc);
-    out[k].kernel_ms = ms;
-    out[k].total_ms = total;
-  }
-  return HH_OK;
+  double kernel_ms, total_ms;
+  if ((rc = solve_times(ctx, clock, &kernel_ms, &total_ms))) return rc;
+  rc = finalize_results(models, 1, c, host, n_models, kernel_ms, total_ms, out);
+  return rc ? finalize_failed(ctx, rc) : HH_OK;
 }
 
 int hh_mc_accumulate_basket(hh_ctx* ctx, const hh_model* m, const hh_config* c,
@@ -722,21 +701,19 @@ int hh_mc_accumulate_basket(hh_ctx* ctx, const hh_model* m, const hh_config* c,
   b.n_paths = c->n_paths;
   b.n_chunks = hh::basket_chunks(c->n_paths);
   b.antithetic = c->antithetic;
-  rc = ensure(ctx, ctx->payoffs, ctx->payoffs_cap, (size_t)2 * n_payoffs);
+  std::vector<double> payoffs(strikes, strikes + n_payoffs);  // strikes | cps
+  payoffs.insert(payoffs.end(), cps, cps + n_payoffs);
+  const double* payoffs_dev = nullptr;
+  rc = stage_host(ctx, ctx->payoffs, ctx->payoffs_cap, payoffs.size(), payoffs.data(), payoffs.size(), &payoffs_dev);
   if (rc) return rc;
-  HH_HIP(ctx, hipMemcpyAsync(ctx->payoffs, strikes, n_payoffs * sizeof(double),
-                             hipMemcpyHostToDevice, ctx->stream));
-  HH_HIP(ctx, hipMemcpyAsync(ctx->payoffs + n_payoffs, cps, n_payoffs * sizeof(double),
-                             hipMemcpyHostToDevice, ctx->stream));
-  if ((rc = note_host_copy(ctx))) return rc;
   rc = ensure(ctx, ctx->basket_records, ctx->basket_records_cap,
               (size_t)n_payoffs * b.n_chunks * hh::kRecStride);
   if (rc) return rc;
   b.terminal = term_dev;
   const int n_active = c->n_partials ? hh::count_active_partials(*m, *c) : 0;
   b.terminal_d = n_active ? ctx->terminal_d : nullptr;
-  b.strikes = ctx->payoffs;
-  b.cps = ctx->payoffs + n_payoffs;
+  b.strikes = payoffs_dev;
+  b.cps = payoffs_dev + n_payoffs;
   b.records = ctx->basket_records;
   HH_HIP(ctx, hh::launch_basket_payoffs(b, n_payoffs, (uint32_t)n_active, ctx->stream));
   HH_HIP(ctx, hh::launch_reduce_records(ctx->basket_records, b.n_chunks, (double)c->n_paths,
@@ -753,7 +730,7 @@ int hh_mc_solve_basket(hh_ctx* ctx, const hh_model* m, const hh_config* c, const
   if (!ctx) return HH_ERR_INVALID;
   std::lock_guard<std::recursive_mutex> lock__(ctx->mu);
   if (!out) return fail(ctx, HH_ERR_INVALID, "result is NULL");
-  const auto t0 = std::chrono::steady_clock::now();
+  const WallClock clock;
   HH_HIP(ctx, hipSetDevice(ctx->device));
   const size_t n_acc = (size_t)n_payoffs * HH_ACC_LEN;
   int rc = ensure(ctx, ctx->basket_accum, ctx->basket_accum_cap, n_acc);
@@ -766,31 +743,21 @@ int hh_mc_solve_basket(hh_ctx* ctx, const hh_model* m, const hh_config* c, const
   HH_HIP(ctx, hipMemcpyAsync(host.data(), ctx->basket_accum, n_acc * sizeof(double),
                              hipMemcpyDeviceToHost, ctx->stream));
   HH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  float ms = 0.f;
-  HH_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
-  const double total =
-      std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  for (uint32_t k = 0; k < n_payoffs; ++k) {
-    std::memset(&out[k], 0, sizeof(hh_result));
-    rc = hh_mc_finalize(m, c, host.data() + (size_t)k * HH_ACC_LEN, &out[k]);
-    if (rc) return finalize_failed(ctx, rc);
-    out[k].kernel_ms = ms;
-    out[k].total_ms = total;
-  }
-  return HH_OK;
+  double kernel_ms, total_ms;
+  if ((rc = solve_times(ctx, clock, &kernel_ms, &total_ms))) return rc;
+  rc = finalize_results(m, 0, c, host.data(), n_payoffs, kernel_ms, total_ms, out);
+  return rc ? finalize_failed(ctx, rc) : HH_OK;
 }
 
 int hh_mc_finalize(const hh_model* m, const hh_config* c, const double* acc, hh_result* out) {
   if (!m || !c || !acc || !out) return HH_ERR_INVALID;
   const double n = acc[HH_ACC_NPATHS];
   if (!(n >= 1.0)) return HH_ERR_INVALID;
-  const double mean = acc[HH_ACC_SUM] / n;
+  double mean, var;
+  payoff_moments(acc, n, &mean, &var);
   out->sum_payoff = acc[HH_ACC_SUM];
   out->sumsq_payoff = acc[HH_ACC_SUMSQ];
   out->price = m->discount * mean;  // montecarlo.jl:489-490
-  double var = 0.0;
-  if (n > 1.0) var = (acc[HH_ACC_SUMSQ] - n * mean * mean) / (n - 1.0);
-  if (!(var > 0.0)) var = 0.0;
   out->std_error = m->discount * std::sqrt(var / n);
   for (uint32_t k = 0; k < HH_MAX_PARTIALS; ++k) {
     double d = 0.0;
@@ -813,7 +780,7 @@ int hh_mc_solve(hh_ctx* ctx, const hh_model* m, const hh_config* c, hh_result* o
   if (!ctx) return HH_ERR_INVALID;
   std::lock_guard<std::recursive_mutex> lock__(ctx->mu);
   if (!out) return fail(ctx, HH_ERR_INVALID, "result is NULL");
-  const auto t0 = std::chrono::steady_clock::now();
+  const WallClock clock;
   std::memset(out, 0, sizeof(*out));
   HH_HIP(ctx, hipSetDevice(ctx->device));
   HH_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
@@ -825,12 +792,7 @@ int hh_mc_solve(hh_ctx* ctx, const hh_model* m, const hh_config* c, hh_result* o
   HH_HIP(ctx, hipStreamSynchronize(ctx->stream));
   rc = hh_mc_finalize(m, c, ctx->accum_host, out);
   if (rc) return finalize_failed(ctx, rc);
-  float ms = 0.f;
-  HH_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
-  out->kernel_ms = ms;
-  out->total_ms =
-      std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  return HH_OK;
+  return solve_times(ctx, clock, &out->kernel_ms, &out->total_ms);
 }
 
 int hh_ctx_check_last(hh_ctx* ctx) {
@@ -879,6 +841,28 @@ int hh_carr_madan(hh_ctx* ctx, const hh_model* m, int32_t dynamics, int32_t comp
   return HH_OK;
 }
 
+// The payoffs of a Carr–Madan basket (`who`: the entry point, for the messages) checked, packed as log K | T | r_drift |
+// discount into host[0 .. 4n) and uploaded into ctx->payoffs, which is made to hold 4n + out_len doubles.
+static int cm_upload_payoffs(hh_ctx* ctx, const char* who, const double* strikes, const double* cps, const double* Ts,
+                             const double* r_drifts, const double* discounts, size_t n, size_t out_len,
+                             std::vector<double>& host) {
+  for (size_t k = 0; k < n; ++k) {
+    if (!(strikes[k] > 0.0) || !(Ts[k] > 0.0) || (cps[k] != 1.0 && cps[k] != -1.0) ||
+        !std::isfinite(r_drifts[k]) || !(discounts[k] > 0.0))
+      return fail(ctx, HH_ERR_INVALID, "%s: payoff %zu: strike, T, discount > 0, cp = +-1", who, k);
+    host[k] = std::log(strikes[k]);
+    host[n + k] = Ts[k];
+    host[2 * n + k] = r_drifts[k];
+    host[3 * n + k] = discounts[k];
+  }
+  HH_HIP(ctx, hipSetDevice(ctx->device));
+  int rc = ensure(ctx, ctx->payoffs, ctx->payoffs_cap, 4 * n + out_len);
+  if (rc) return rc;
+  HH_HIP(ctx, hipMemcpyAsync(ctx->payoffs, host.data(), 4 * n * sizeof(double), hipMemcpyHostToDevice,
+                             ctx->stream));
+  return HH_OK;
+}
+
 int hh_carr_madan_basket(hh_ctx* ctx, const hh_model* m, int32_t dynamics, int32_t compat_sqrt_alpha,
                          double alpha, double bound, const double* strikes, const double* cps,
                          const double* Ts, const double* r_drifts, const double* discounts,
@@ -895,20 +879,8 @@ int hh_carr_madan_basket(hh_ctx* ctx, const hh_model* m, int32_t dynamics, int32
     return fail(ctx, HH_ERR_INVALID, "hh_carr_madan_basket: bad scalars");
   const size_t n = n_payoffs;
   std::vector<double> host(5 * n);  // log K | T | r_drift | discount | (out)
-  for (size_t k = 0; k < n; ++k) {
-    if (!(strikes[k] > 0.0) || !(Ts[k] > 0.0) || (cps[k] != 1.0 && cps[k] != -1.0) ||
-        !std::isfinite(r_drifts[k]) || !(discounts[k] > 0.0))
-      return fail(ctx, HH_ERR_INVALID, "hh_carr_madan_basket: payoff %zu: strike, T, discount > 0, cp = +-1", k);
-    host[k] = std::log(strikes[k]);
-    host[n + k] = Ts[k];
-    host[2 * n + k] = r_drifts[k];
-    host[3 * n + k] = discounts[k];
-  }
-  HH_HIP(ctx, hipSetDevice(ctx->device));
-  int rc = ensure(ctx, ctx->payoffs, ctx->payoffs_cap, 5 * n);
+  const int rc = cm_upload_payoffs(ctx, "hh_carr_madan_basket", strikes, cps, Ts, r_drifts, discounts, n, n, host);
   if (rc) return rc;
-  HH_HIP(ctx, hipMemcpyAsync(ctx->payoffs, host.data(), 4 * n * sizeof(double), hipMemcpyHostToDevice,
-                             ctx->stream));
   HH_HIP(ctx, hh::launch_carr_madan_basket(*m, dynamics, compat_sqrt_alpha, alpha, bound, ctx->payoffs,
                                            n_payoffs, ctx->payoffs + 4 * n, ctx->stream));
   HH_HIP(ctx, hipMemcpyAsync(host.data() + 4 * n, ctx->payoffs + 4 * n, n * sizeof(double),
@@ -939,21 +911,10 @@ int hh_carr_madan_basket_grad(hh_ctx* ctx, const hh_model* m, int32_t dynamics,
     return fail(ctx, HH_ERR_INVALID, "hh_carr_madan_basket_grad: bad scalars (Heston: sigma, theta != 0)");
   const size_t n = n_payoffs;
   std::vector<double> host(4 * n + HH_CM_GRAD_LEN * n);  // log K | T | r_drift | discount | out [n][8]
-  for (size_t k = 0; k < n; ++k) {
-    if (!(strikes[k] > 0.0) || !(Ts[k] > 0.0) || (cps[k] != 1.0 && cps[k] != -1.0) ||
-        !std::isfinite(r_drifts[k]) || !(discounts[k] > 0.0))
-      return fail(ctx, HH_ERR_INVALID, "hh_carr_madan_basket_grad: payoff %zu: strike, T, discount > 0, cp = +-1", k);
-    host[k] = std::log(strikes[k]);
-    host[n + k] = Ts[k];
-    host[2 * n + k] = r_drifts[k];
-    host[3 * n + k] = discounts[k];
-  }
-  HH_HIP(ctx, hipSetDevice(ctx->device));
-  int rc = ensure(ctx, ctx->payoffs, ctx->payoffs_cap, 4 * n + HH_CM_GRAD_LEN * n);
+  const int rc = cm_upload_payoffs(ctx, "hh_carr_madan_basket_grad", strikes, cps, Ts, r_drifts, discounts, n,
+                                   HH_CM_GRAD_LEN * n, host);
   if (rc) return rc;
   double* out_dev = ctx->payoffs + 4 * n;
-  HH_HIP(ctx, hipMemcpyAsync(ctx->payoffs, host.data(), 4 * n * sizeof(double), hipMemcpyHostToDevice,
-                             ctx->stream));
   HH_HIP(ctx, hh::launch_carr_madan_grad(*m, dynamics, compat_sqrt_alpha, alpha, bound, ctx->payoffs,
                                          n_payoffs, out_dev, ctx->stream));
   HH_HIP(ctx, hipMemcpyAsync(host.data() + 4 * n, out_dev, HH_CM_GRAD_LEN * n * sizeof(double),
@@ -979,19 +940,40 @@ size_t hh_lsm_grid_elems(uint64_t n_paths, uint32_t n_steps, int32_t antithetic)
   return (size_t)(n_steps + 1) * n_paths * (antithetic ? 2 : 1);
 }
 
+// the buffers of a backward induction over ntot trajectories
+static int ensure_lsm_buffers(hh_ctx* ctx, uint64_t ntot, uint32_t n_steps, int32_t degree) {
+  int rc;
+  if ((rc = ensure(ctx, ctx->lsm_val, ctx->lsm_val_cap, (size_t)ntot))) return rc;
+  if ((rc = ensure(ctx, ctx->lsm_tau, ctx->lsm_tau_cap, (size_t)ntot))) return rc;
+  if ((rc = ensure(ctx, ctx->lsm_scratch, ctx->lsm_scratch_cap, hh::lsm_scratch_doubles(ntot, n_steps, degree))))
+    return rc;
+  return ensure(ctx, ctx->records, ctx->records_cap, (size_t)hh::lsm_chunks(ntot) * hh::kRecStride);
+}
+
+// queue the copies back of an induction's row counters (regressed, skipped) into counters[0 .. 2) and, where the
+// caller asked for them, of its stopping times and values
+static int copy_back_lsm(hh_ctx* ctx, uint64_t ntot, uint32_t n_steps, int32_t degree, double* counters,
+                         int32_t* stop_time, double* stop_value) {
+  const size_t nscr = hh::lsm_scratch_doubles(ntot, n_steps, degree);
+  HH_HIP(ctx, hipMemcpyAsync(counters, ctx->lsm_scratch + nscr - 2 - hh::kLsmStampSlotsApi, 2 * sizeof(double),
+                             hipMemcpyDeviceToHost, ctx->stream));
+  if (stop_time)
+    HH_HIP(ctx, hipMemcpyAsync(stop_time, ctx->lsm_tau, ntot * sizeof(int32_t),
+                               hipMemcpyDeviceToHost, ctx->stream));
+  if (stop_value)
+    HH_HIP(ctx, hipMemcpyAsync(stop_value, ctx->lsm_val, ntot * sizeof(double),
+                               hipMemcpyDeviceToHost, ctx->stream));
+  return HH_OK;
+}
+
 // Backward induction on a spot grid already in device memory (rows = dates, ntot trajectories):
 // launches, reduction and the copies back.  The caller recorded ctx->ev0 before producing the grid.
 static int lsm_on_grid(hh_ctx* ctx, const double* grid_dev, uint64_t ntot, uint32_t n_steps,
                        const hh_model* m, int32_t degree, double step_discount, hh_lsm_result* out,
-                       int32_t* stop_time, double* stop_value,
-                       std::chrono::steady_clock::time_point t0) {
+                       int32_t* stop_time, double* stop_value, const WallClock& clock) {
   const uint32_t ch = hh::lsm_chunks(ntot);
   int rc;
-  if ((rc = ensure(ctx, ctx->lsm_val, ctx->lsm_val_cap, (size_t)ntot))) return rc;
-  if ((rc = ensure(ctx, ctx->lsm_tau, ctx->lsm_tau_cap, (size_t)ntot))) return rc;
-  const size_t nscr = hh::lsm_scratch_doubles(ntot, n_steps, degree);
-  if ((rc = ensure(ctx, ctx->lsm_scratch, ctx->lsm_scratch_cap, nscr))) return rc;
-  if ((rc = ensure(ctx, ctx->records, ctx->records_cap, (size_t)ch * hh::kRecStride))) return rc;
+  if ((rc = ensure_lsm_buffers(ctx, ntot, n_steps, degree))) return rc;
   // enqueue the induction, the final reduction and every copy back, then synchronise ONCE; the
   // one-launch form leaves a word behind when its workgroups could not all be resident together
   // (another kernel held CUs): nothing was written then, and the launch-per-date form runs instead
@@ -1016,36 +998,19 @@ static int lsm_on_grid(hh_ctx* ctx, const double* grid_dev, uint64_t ntot, uint3
                                  sizeof(gave_up), hipMemcpyDeviceToHost, ctx->stream));
     HH_HIP(ctx, hipMemcpyAsync(ctx->accum_host, ctx->accum, HH_ACC_LEN * sizeof(double),
                                hipMemcpyDeviceToHost, ctx->stream));
-    HH_HIP(ctx, hipMemcpyAsync(counters, ctx->lsm_scratch + nscr - 2 - hh::kLsmStampSlotsApi,
-                               2 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    if (stop_time)
-      HH_HIP(ctx, hipMemcpyAsync(stop_time, ctx->lsm_tau, ntot * sizeof(int32_t),
-                                 hipMemcpyDeviceToHost, ctx->stream));
-    if (stop_value)
-      HH_HIP(ctx, hipMemcpyAsync(stop_value, ctx->lsm_val, ntot * sizeof(double),
-                                 hipMemcpyDeviceToHost, ctx->stream));
+    if ((rc = copy_back_lsm(ctx, ntot, n_steps, degree, counters, stop_time, stop_value))) return rc;
     HH_HIP(ctx, hipStreamSynchronize(ctx->stream));
     if (!gave_up) break;
     ++ctx->lsm_persistent_fallbacks;
     ++fallbacks;
   }
-  const double n = (double)ntot, mean = ctx->accum_host[HH_ACC_SUM] / n;
-  double var = n > 1.0 ? (ctx->accum_host[HH_ACC_SUMSQ] - n * mean * mean) / (n - 1.0) : 0.0;
-  if (!(var > 0.0)) var = 0.0;
-  std::memset(out, 0, sizeof(*out));
-  out->price = mean;  // price = mean(discount^t * val) (least_squares_montecarlo.jl:133-134)
-  out->std_error = std::sqrt(var / n);
-  out->n_paths_total = ntot;
+  // the reduction wrote (double)ntot into slot HH_ACC_NPATHS
+  if ((rc = hh_lsm_finalize(ctx->accum_host, out))) return finalize_failed(ctx, rc);
   out->rows_regressed = (uint32_t)counters[0];
   out->rows_skipped = (uint32_t)counters[1];
   out->form = form_used;
   out->persistent_fallbacks = fallbacks;
-  float ms = 0.f;
-  HH_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
-  out->kernel_ms = ms;
-  out->total_ms =
-      std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  return HH_OK;
+  return solve_times(ctx, clock, &out->kernel_ms, &out->total_ms);
 }
 
 static int lsm_check_scalars(hh_ctx* ctx, const hh_model* m, const hh_config* c, int32_t degree,
@@ -1068,15 +1033,8 @@ static int stage_path_seeds(hh_ctx* ctx, const hh_config* c, const uint64_t** ou
     return fail(ctx, HH_ERR_INVALID, "Number of seeds (%llu) must be >= number of trajectories (%llu)",
                 (unsigned long long)c->seeds_len, (unsigned long long)c->n_paths);
   *out = c->seeds;
-  if (!c->seeds_on_device) {
-    int rc = ensure(ctx, ctx->seeds, ctx->seeds_cap, (size_t)c->n_paths);
-    if (rc) return rc;
-    HH_HIP(ctx, hipMemcpyAsync(ctx->seeds, c->seeds, c->n_paths * sizeof(uint64_t),
-                               hipMemcpyHostToDevice, ctx->stream));
-    if ((rc = note_host_copy(ctx))) return rc;
-    *out = ctx->seeds;
-  }
-  return HH_OK;
+  if (c->seeds_on_device) return HH_OK;
+  return stage_host(ctx, ctx->seeds, ctx->seeds_cap, (size_t)c->n_paths, c->seeds, (size_t)c->n_paths, out);
 }
 
 // The n_steps Broadie–Kaya transitions of length T/n_steps into ctx->lsm_grid (spot rows) and
@@ -1176,49 +1134,44 @@ static int heston_grid_counters(hh_ctx* ctx, uint32_t n_steps, uint64_t* newton_
   return HH_OK;
 }
 
-int hh_heston_exact_grid(hh_ctx* ctx, const hh_model* m, const hh_config* c, double* spot_grid,
-                         double* var_grid, int32_t grids_on_device, hh_result* out) {
-  if (!ctx) return HH_ERR_INVALID;
-  std::lock_guard<std::recursive_mutex> lock__(ctx->mu);
-  if (!m || !c) return fail(ctx, HH_ERR_INVALID, "hh_heston_exact_grid: NULL argument");
-  const auto t0 = std::chrono::steady_clock::now();
-  HH_HIP(ctx, hipSetDevice(ctx->device));
-  HH_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-  int rc = run_heston_grid(ctx, m, c);
-  if (rc) return rc;
-  HH_HIP(ctx, hipEventRecord(ctx->ev1, ctx->stream));
-  const size_t bytes = (size_t)(c->n_steps + 1) * c->n_paths * sizeof(double);
+// The end of a grid entry point, once ctx->ev1 is recorded behind the grid: the spot and variance rows into the
+// caller's buffers (device or host memory), then *out — with the summed Broadie–Kaya counters of the transitions
+// for the exact Heston grid (bk_counters).
+static int grid_results(hh_ctx* ctx, const hh_config* c, double* spot_grid, double* var_grid,
+                        int32_t grids_on_device, bool bk_counters, hh_result* out, const WallClock& clock) {
+  const size_t bytes = hh_lsm_grid_elems(c->n_paths, c->n_steps, c->antithetic) * sizeof(double);
   const hipMemcpyKind kind = grids_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
   if (spot_grid) HH_HIP(ctx, hipMemcpyAsync(spot_grid, ctx->lsm_grid, bytes, kind, ctx->stream));
   if (var_grid) HH_HIP(ctx, hipMemcpyAsync(var_grid, ctx->heston_var, bytes, kind, ctx->stream));
   HH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  if (out) {
-    std::memset(out, 0, sizeof(*out));
-    if ((rc = heston_grid_counters(ctx, c->n_steps, &out->bk_newton_fail, &out->bk_bisect_fallback,
-                                   &out->bk_maxguess_fallback, &out->bk_cf_terms)))
-      return rc;
-    out->n_paths_done = c->n_paths;
-    float ms = 0.f;
-    HH_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
-    out->kernel_ms = ms;
-    out->total_ms =
-        std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  }
+  if (!out) return HH_OK;
+  std::memset(out, 0, sizeof(*out));
+  int rc;
+  if (bk_counters && (rc = heston_grid_counters(ctx, c->n_steps, &out->bk_newton_fail, &out->bk_bisect_fallback,
+                                                &out->bk_maxguess_fallback, &out->bk_cf_terms)))
+    return rc;
+  out->n_paths_done = c->n_paths;
+  return solve_times(ctx, clock, &out->kernel_ms, &out->total_ms);
+}
+
+// the spot grid an LSM solve regressed on, into the caller's host buffer (when given)
+static int copy_back_spot_grid(hh_ctx* ctx, const hh_config* c, double* spot_grid) {
+  if (!spot_grid) return HH_OK;
+  HH_HIP(ctx, hipMemcpyAsync(spot_grid, ctx->lsm_grid,
+                             hh_lsm_grid_elems(c->n_paths, c->n_steps, c->antithetic) * sizeof(double),
+                             hipMemcpyDeviceToHost, ctx->stream));
+  HH_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return HH_OK;
 }
 
-int hh_lsm_solve(hh_ctx* ctx, const hh_model* m, const hh_config* c, int32_t degree,
-                 double step_discount, hh_lsm_result* out, int32_t* stop_time, double* stop_value,
-                 double* spot_grid) {
-  if (!ctx) return HH_ERR_INVALID;
-  std::lock_guard<std::recursive_mutex> lock__(ctx->mu);
-  if (!m || !c || !out) return fail(ctx, HH_ERR_INVALID, "hh_lsm_solve: NULL argument");
-  const auto t0 = std::chrono::steady_clock::now();
-  // The reference's LSM regresses on the first state component of simulate_paths' solution
-  // (least_squares_montecarlo.jl:53,76).  Path sources: the GBM noise process of (LognormalDynamics,
-  // BlackScholesExact) (montecarlo.jl:140-159), whose state IS the spot, and the per-date exact
-  // Heston transitions of (HestonDynamics, HestonBroadieKaya) (montecarlo.jl:209-231), whose spot
-  // rows exp(log S) are used here (the reference hands its regression the log-state).
+// The paths of an LSM solve into ctx->lsm_grid, after the checks.  The reference's LSM regresses on the first state
+// component of simulate_paths' solution (least_squares_montecarlo.jl:53,76).  Path sources: the GBM noise process of
+// (LognormalDynamics, BlackScholesExact) (montecarlo.jl:140-159), whose state IS the spot, and the per-date exact
+// Heston transitions of (HestonDynamics, HestonBroadieKaya) (montecarlo.jl:209-231), whose spot rows exp(log S) are
+// used here (the reference hands its regression the log-state).  start (when given) is recorded in
+// front of the grid.
+static int lsm_paths(hh_ctx* ctx, const hh_model* m, const hh_config* c, int32_t degree, double step_discount,
+                     hipEvent_t start) {
   const bool gbm = c->dynamics == HH_LOGNORMAL && c->strategy == HH_EXACT_LAW;
   const bool heston = c->dynamics == HH_HESTON && c->strategy == HH_BROADIE_KAYA;
   if (!gbm && !heston)
@@ -1230,27 +1183,45 @@ int hh_lsm_solve(hh_ctx* ctx, const hh_model* m, const hh_config* c, int32_t deg
   int rc = lsm_check_scalars(ctx, m, c, degree, step_discount);
   if (rc) return rc;
   HH_HIP(ctx, hipSetDevice(ctx->device));
-  const uint64_t ntot = c->n_paths * (c->antithetic ? 2 : 1);
-  const size_t grid_elems = hh_lsm_grid_elems(c->n_paths, c->n_steps, c->antithetic);
-  HH_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-  if (gbm) {
-    if ((rc = ensure(ctx, ctx->lsm_grid, ctx->lsm_grid_cap, grid_elems))) return rc;
-    const uint64_t* seeds_dev = nullptr;
-    if ((rc = stage_path_seeds(ctx, c, &seeds_dev))) return rc;
-    HH_HIP(ctx, hh::launch_gbm_grid(seeds_dev, c->n_paths, c->n_steps, m->S0, m->r_drift, m->sigma,
-                                    m->T, c->antithetic, ctx->lsm_grid, ctx->stream));
-  } else {
-    if ((rc = run_heston_grid(ctx, m, c))) return rc;
-  }
-  rc = lsm_on_grid(ctx, ctx->lsm_grid, ntot, c->n_steps, m, degree, step_discount, out, stop_time,
-                   stop_value, t0);
-  if (rc) return rc;
-  if (spot_grid) {
-    HH_HIP(ctx, hipMemcpyAsync(spot_grid, ctx->lsm_grid, grid_elems * sizeof(double),
-                               hipMemcpyDeviceToHost, ctx->stream));
-    HH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  }
+  if (start) HH_HIP(ctx, hipEventRecord(start, ctx->stream));
+  if (heston) return run_heston_grid(ctx, m, c);
+  if ((rc = ensure(ctx, ctx->lsm_grid, ctx->lsm_grid_cap, hh_lsm_grid_elems(c->n_paths, c->n_steps, c->antithetic))))
+    return rc;
+  const uint64_t* seeds_dev = nullptr;
+  if ((rc = stage_path_seeds(ctx, c, &seeds_dev))) return rc;
+  HH_HIP(ctx, hh::launch_gbm_grid(seeds_dev, c->n_paths, c->n_steps, m->S0, m->r_drift, m->sigma,
+                                  m->T, c->antithetic, ctx->lsm_grid, ctx->stream));
   return HH_OK;
+}
+
+int hh_heston_exact_grid(hh_ctx* ctx, const hh_model* m, const hh_config* c, double* spot_grid,
+                         double* var_grid, int32_t grids_on_device, hh_result* out) {
+  if (!ctx) return HH_ERR_INVALID;
+  std::lock_guard<std::recursive_mutex> lock__(ctx->mu);
+  if (!m || !c) return fail(ctx, HH_ERR_INVALID, "hh_heston_exact_grid: NULL argument");
+  const WallClock clock;
+  HH_HIP(ctx, hipSetDevice(ctx->device));
+  HH_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+  int rc = run_heston_grid(ctx, m, c);
+  if (rc) return rc;
+  HH_HIP(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+  return grid_results(ctx, c, spot_grid, var_grid, grids_on_device, /*bk_counters=*/true, out, clock);
+}
+
+int hh_lsm_solve(hh_ctx* ctx, const hh_model* m, const hh_config* c, int32_t degree,
+                 double step_discount, hh_lsm_result* out, int32_t* stop_time, double* stop_value,
+                 double* spot_grid) {
+  if (!ctx) return HH_ERR_INVALID;
+  std::lock_guard<std::recursive_mutex> lock__(ctx->mu);
+  if (!m || !c || !out) return fail(ctx, HH_ERR_INVALID, "hh_lsm_solve: NULL argument");
+  const WallClock clock;
+  int rc = lsm_paths(ctx, m, c, degree, step_discount, ctx->ev0);
+  if (rc) return rc;
+  const uint64_t ntot = c->n_paths * (c->antithetic ? 2 : 1);
+  rc = lsm_on_grid(ctx, ctx->lsm_grid, ntot, c->n_steps, m, degree, step_discount, out, stop_time,
+                   stop_value, clock);
+  if (rc) return rc;
+  return copy_back_spot_grid(ctx, c, spot_grid);
 }
 
 // ---- Euler–Maruyama path grids (GENERATE) -------------------------------------------------------------
@@ -1290,27 +1261,13 @@ int hh_euler_grid(hh_ctx* ctx, const hh_model* m, const hh_config* c, int32_t pa
   if (!ctx) return HH_ERR_INVALID;
   std::lock_guard<std::recursive_mutex> lock__(ctx->mu);
   if (!m || !c) return fail(ctx, HH_ERR_INVALID, "hh_euler_grid: NULL argument");
-  const auto t0 = std::chrono::steady_clock::now();
+  const WallClock clock;
   HH_HIP(ctx, hipSetDevice(ctx->device));
   HH_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
   int rc = run_euler_grid(ctx, m, c, path_state, var_grid != nullptr);
   if (rc) return rc;
   HH_HIP(ctx, hipEventRecord(ctx->ev1, ctx->stream));
-  const size_t bytes = hh_lsm_grid_elems(c->n_paths, c->n_steps, c->antithetic) * sizeof(double);
-  const hipMemcpyKind kind = grids_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-  if (spot_grid) HH_HIP(ctx, hipMemcpyAsync(spot_grid, ctx->lsm_grid, bytes, kind, ctx->stream));
-  if (var_grid) HH_HIP(ctx, hipMemcpyAsync(var_grid, ctx->heston_var, bytes, kind, ctx->stream));
-  HH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  if (out) {
-    std::memset(out, 0, sizeof(*out));
-    out->n_paths_done = c->n_paths;
-    float ms = 0.f;
-    HH_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
-    out->kernel_ms = ms;
-    out->total_ms =
-        std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  }
-  return HH_OK;
+  return grid_results(ctx, c, spot_grid, var_grid, grids_on_device, /*bk_counters=*/false, out, clock);
 }
 
 int hh_lsm_solve_euler(hh_ctx* ctx, const hh_model* m, const hh_config* c, int32_t path_state, int32_t degree,
@@ -1319,22 +1276,16 @@ int hh_lsm_solve_euler(hh_ctx* ctx, const hh_model* m, const hh_config* c, int32
   if (!ctx) return HH_ERR_INVALID;
   std::lock_guard<std::recursive_mutex> lock__(ctx->mu);
   if (!m || !c || !out) return fail(ctx, HH_ERR_INVALID, "hh_lsm_solve_euler: NULL argument");
-  const auto t0 = std::chrono::steady_clock::now();
+  const WallClock clock;
   int rc = lsm_check_scalars(ctx, m, c, degree, step_discount);
   if (rc) return rc;
   HH_HIP(ctx, hipSetDevice(ctx->device));
   HH_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
   if ((rc = run_euler_grid(ctx, m, c, path_state, false))) return rc;
   const uint64_t ntot = c->n_paths * (c->antithetic ? 2 : 1);
-  rc = lsm_on_grid(ctx, ctx->lsm_grid, ntot, c->n_steps, m, degree, step_discount, out, stop_time, stop_value, t0);
+  rc = lsm_on_grid(ctx, ctx->lsm_grid, ntot, c->n_steps, m, degree, step_discount, out, stop_time, stop_value, clock);
   if (rc) return rc;
-  if (spot_grid) {
-    HH_HIP(ctx, hipMemcpyAsync(spot_grid, ctx->lsm_grid,
-                               hh_lsm_grid_elems(c->n_paths, c->n_steps, c->antithetic) * sizeof(double),
-                               hipMemcpyDeviceToHost, ctx->stream));
-    HH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  }
-  return HH_OK;
+  return copy_back_spot_grid(ctx, c, spot_grid);
 }
 
 // ---- LSM on an ensemble sharded over several devices ------------------------------------------------
@@ -1357,35 +1308,10 @@ int hh_lsm_shard_begin(hh_ctx* ctx, const hh_model* m, const hh_config* c, int32
   std::lock_guard<std::recursive_mutex> lock__(ctx->mu);
   ctx->shard.active = false;
   if (!m || !c || !xchg_dev) return fail(ctx, HH_ERR_INVALID, "hh_lsm_shard_begin: NULL argument");
-  const bool gbm = c->dynamics == HH_LOGNORMAL && c->strategy == HH_EXACT_LAW;
-  const bool heston = c->dynamics == HH_HESTON && c->strategy == HH_BROADIE_KAYA;
-  if (!gbm && !heston)
-    return fail(ctx, HH_ERR_UNSUPPORTED,
-                "LSM needs LognormalDynamics + BlackScholesExact or HestonDynamics + "
-                "HestonBroadieKaya paths");
-  if (c->noise_mode != HH_NOISE_GENERATE || c->n_partials != 0)
-    return fail(ctx, HH_ERR_UNSUPPORTED, "LSM: GENERATE noise, no dual partials");
-  int rc = lsm_check_scalars(ctx, m, c, degree, step_discount);
+  int rc = lsm_paths(ctx, m, c, degree, step_discount, nullptr);
   if (rc) return rc;
-  HH_HIP(ctx, hipSetDevice(ctx->device));
   const uint64_t ntot = c->n_paths * (c->antithetic ? 2 : 1);
-  if (gbm) {
-    const size_t grid_elems = hh_lsm_grid_elems(c->n_paths, c->n_steps, c->antithetic);
-    if ((rc = ensure(ctx, ctx->lsm_grid, ctx->lsm_grid_cap, grid_elems))) return rc;
-    const uint64_t* seeds_dev = nullptr;
-    if ((rc = stage_path_seeds(ctx, c, &seeds_dev))) return rc;
-    HH_HIP(ctx, hh::launch_gbm_grid(seeds_dev, c->n_paths, c->n_steps, m->S0, m->r_drift, m->sigma,
-                                    m->T, c->antithetic, ctx->lsm_grid, ctx->stream));
-  } else {
-    if ((rc = run_heston_grid(ctx, m, c))) return rc;
-  }
-  if ((rc = ensure(ctx, ctx->lsm_val, ctx->lsm_val_cap, (size_t)ntot))) return rc;
-  if ((rc = ensure(ctx, ctx->lsm_tau, ctx->lsm_tau_cap, (size_t)ntot))) return rc;
-  if ((rc = ensure(ctx, ctx->lsm_scratch, ctx->lsm_scratch_cap,
-                   hh::lsm_scratch_doubles(ntot, c->n_steps, degree))))
-    return rc;
-  if ((rc = ensure(ctx, ctx->records, ctx->records_cap, (size_t)hh::lsm_chunks(ntot) * hh::kRecStride)))
-    return rc;
+  if ((rc = ensure_lsm_buffers(ctx, ntot, c->n_steps, degree))) return rc;
   ctx->shard.m = *m;
   ctx->shard.ntot = ntot;
   ctx->shard.n_steps = c->n_steps;
@@ -1424,16 +1350,8 @@ int hh_lsm_shard_finish(hh_ctx* ctx, double* accum_dev, int32_t* stop_time, doub
   if (rc) return rc;
   HH_HIP(ctx, hh::launch_reduce_records(ctx->records, hh::lsm_chunks(sh.ntot), (double)sh.ntot,
                                         accum_dev, ctx->stream));
-  const size_t nscr = hh::lsm_scratch_doubles(sh.ntot, sh.n_steps, sh.degree);
   double counters[2] = {0, 0};
-  HH_HIP(ctx, hipMemcpyAsync(counters, ctx->lsm_scratch + nscr - 2 - hh::kLsmStampSlotsApi, 2 * sizeof(double),
-                             hipMemcpyDeviceToHost, ctx->stream));
-  if (stop_time)
-    HH_HIP(ctx, hipMemcpyAsync(stop_time, ctx->lsm_tau, sh.ntot * sizeof(int32_t),
-                               hipMemcpyDeviceToHost, ctx->stream));
-  if (stop_value)
-    HH_HIP(ctx, hipMemcpyAsync(stop_value, ctx->lsm_val, sh.ntot * sizeof(double),
-                               hipMemcpyDeviceToHost, ctx->stream));
+  if ((rc = copy_back_lsm(ctx, sh.ntot, sh.n_steps, sh.degree, counters, stop_time, stop_value))) return rc;
   if (spot_grid)
     HH_HIP(ctx, hipMemcpyAsync(spot_grid, ctx->lsm_grid,
                                (size_t)(sh.n_steps + 1) * sh.ntot * sizeof(double),
@@ -1463,9 +1381,8 @@ int hh_lsm_finalize(const double* acc, hh_lsm_result* out) {
   if (!acc || !out) return HH_ERR_INVALID;
   const double n = acc[HH_ACC_NPATHS];
   if (!(n >= 1.0)) return HH_ERR_INVALID;
-  const double mean = acc[HH_ACC_SUM] / n;
-  double var = n > 1.0 ? (acc[HH_ACC_SUMSQ] - n * mean * mean) / (n - 1.0) : 0.0;
-  if (!(var > 0.0)) var = 0.0;
+  double mean, var;
+  payoff_moments(acc, n, &mean, &var);
   std::memset(out, 0, sizeof(*out));
   out->price = mean;  // price = mean(discount^t * val) (least_squares_montecarlo.jl:133-134)
   out->std_error = std::sqrt(var / n);
@@ -1480,7 +1397,7 @@ int hh_lsm_solve_grid(hh_ctx* ctx, const hh_model* m, const double* spot_grid_de
   std::lock_guard<std::recursive_mutex> lock__(ctx->mu);
   if (!m || !spot_grid_dev || !out)
     return fail(ctx, HH_ERR_INVALID, "hh_lsm_solve_grid: NULL argument");
-  const auto t0 = std::chrono::steady_clock::now();
+  const WallClock clock;
   hh_config c{};
   c.n_paths = n_paths;
   c.n_steps = n_steps;
@@ -1489,7 +1406,7 @@ int hh_lsm_solve_grid(hh_ctx* ctx, const hh_model* m, const double* spot_grid_de
   HH_HIP(ctx, hipSetDevice(ctx->device));
   HH_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
   return lsm_on_grid(ctx, spot_grid_dev, n_paths, n_steps, m, degree, step_discount, out, stop_time,
-                     stop_value, t0);
+                     stop_value, clock);
 }
 
 int hh_ctx_enable_timing(hh_ctx* ctx, int32_t on) {

@@ -1,8 +1,10 @@
 // The context object behind the C-ABI's opaque hh_ctx, and the helpers every host translation unit
 // (hh_api.hip, hh_mgpu.hip) shares.  Internal; the public surface is include/hedgehog_mc.h.
 #pragma once
+#include <chrono>
 #include <cstdarg>
 #include <cstdio>
+#include <cstring>
 #include <mutex>
 
 #include "hh_kernels.h"
@@ -131,6 +133,17 @@ int ensure(hh_ctx* ctx, T*& buf, size_t& cap, size_t need) {
   ctx->staged_host = true;
   return HH_OK;
 }
+// n elements of a caller's host buffer into the ctx buffer buf, which is made to hold need >= n elements first (the
+// padded tile-major increments are copied short); *dev: where the kernels read them
+template <class T>
+int stage_host(hh_ctx* ctx, T*& buf, size_t& cap, size_t need, const T* src, size_t n, const T** dev) {
+  int rc = ensure(ctx, buf, cap, need);
+  if (rc) return rc;
+  HH_HIP(ctx, hipMemcpyAsync(buf, src, n * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
+  if ((rc = note_host_copy(ctx))) return rc;
+  *dev = buf;
+  return HH_OK;
+}
 // Before an ASYNCHRONOUS entry point returns: every copy it queued from the caller's host memory has read its
 // source (pageable memory is staged by the runtime before hipMemcpyAsync returns, PINNED memory is read by the
 // DMA engine whenever the stream gets there) — only the copies are waited for, the kernels behind them run on.
@@ -149,6 +162,28 @@ int ensure(hh_ctx* ctx, T*& buf, size_t& cap, size_t need) {
   const int rc = ensure(ctx, ctx->bk_scratch, ctx->bk_scratch_cap, need);
   if (ctx->bk_scratch_cap != before) ctx->bk_table_key = hh::BkTableKey{};
   return rc;
+}
+
+// the wall time of an entry point (hh_result / hh_lsm_result::total_ms), from where it is declared
+struct WallClock {
+  std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+  double ms() const { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
+};
+
+// out[0 .. k) from k accumulator vectors of HH_ACC_LEN doubles: result i is of models[i * model_stride] (1: a model
+// per result, 0: one model for every payoff of a basket), zeroed, finalized and stamped with the solve's times.
+// hh_mc_finalize's status when it refuses one: the caller says why.
+[[maybe_unused]] int finalize_results(const hh_model* models, size_t model_stride, const hh_config* c,
+                                      const double* acc, uint32_t k, double kernel_ms, double total_ms,
+                                      hh_result* out) {
+  for (uint32_t i = 0; i < k; ++i) {
+    std::memset(&out[i], 0, sizeof(hh_result));
+    const int rc = hh_mc_finalize(&models[i * model_stride], c, acc + (size_t)i * HH_ACC_LEN, &out[i]);
+    if (rc) return rc;
+    out[i].kernel_ms = kernel_ms;
+    out[i].total_ms = total_ms;
+  }
+  return HH_OK;
 }
 
 }  // namespace

@@ -720,7 +720,7 @@ int hh_mgpu_solve_shards(hh_mgpu* mg, const hh_model* m, const hh_config* cfgs, 
   if (!mg) return HH_ERR_INVALID;
   std::lock_guard<std::mutex> lock__(mg->mu);
   if (!m || !cfgs || !out) return mfail(mg, HH_ERR_INVALID, "hh_mgpu_solve_shards: NULL argument");
-  const auto t0 = std::chrono::steady_clock::now();
+  const WallClock clock;
   int first = -1;
   for (int g = 0; g < mg->n && first < 0; ++g)
     if (cfgs[g].n_paths) first = g;
@@ -732,17 +732,23 @@ int hh_mgpu_solve_shards(hh_mgpu* mg, const hh_model* m, const hh_config* cfgs, 
   rc = hh_mc_finalize(m, &cfgs[first], mg->host, out);  // reads n_partials and the discount seeds only
   if (rc) return mfinalize_failed(mg, rc);
   out->kernel_ms = kernel_ms;
-  out->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  out->total_ms = clock.ms();
   return HH_OK;
 }
+
+// a whole-ensemble config cut into one per device
+struct Shards {
+  std::vector<hh_config> cfg;
+  std::vector<double*> terminal;  // device buffers of the shards' terminal samples (when asked for)
+  std::vector<uint64_t> start;    // the shard's first trajectory in the ensemble
+};
 
 // Shards of a whole-ensemble config with host buffers.  Host slices go to hh_mc_accumulate as they are
 // (it stages them on the shard's stream, from the shard's thread) unless the kernels' operand rules say
 // otherwise: BK REPLAY draws [V_T | u | Z] are three slices per shard, and a slice that does not start on
 // a 16-byte boundary (one double per trajectory — the exact law, lognormal Euler with one step — or an
 // odd row length, cut at an odd trajectory) is staged here into the shard ctx's own buffer.
-static int cut_config(hh_mgpu* mg, const hh_config* cfg, bool want_terminal, std::vector<hh_config>& cs,
-                      std::vector<double*>& term_dev, std::vector<uint64_t>& starts) {
+static int cut_config(hh_mgpu* mg, const hh_config* cfg, bool want_terminal, Shards& sh) {
   if (cfg->n_paths == 0) return mfail(mg, HH_ERR_INVALID, "n_paths must be >= 1");
   if (cfg->seeds_on_device || cfg->replay_on_device || cfg->terminal_on_device)
     return mfail(mg, HH_ERR_INVALID,
@@ -766,15 +772,15 @@ static int cut_config(hh_mgpu* mg, const hh_config* cfg, bool want_terminal, std
   if (!replay && cfg->seeds_len && cfg->seeds_len < (euler ? N : 1))
     return mfail(mg, HH_ERR_INVALID, "Number of seeds (%llu) must be >= number of trajectories (%llu)",
                  (unsigned long long)cfg->seeds_len, (unsigned long long)(euler ? N : 1));
-  cs.assign(mg->n, *cfg);
-  term_dev.assign(mg->n, nullptr);
-  starts.assign(mg->n, 0);
+  sh.cfg.assign(mg->n, *cfg);
+  sh.terminal.assign(mg->n, nullptr);
+  sh.start.assign(mg->n, 0);
   for (int g = 0; g < mg->n; ++g) {
     uint64_t a, b;
     shard_range(N, mg->n, g, tile, &a, &b);
-    hh_config& c = cs[g];
+    hh_config& c = sh.cfg[g];
     hh_ctx* x = mg->ctx[g];
-    starts[g] = a;
+    sh.start[g] = a;
     c.n_paths = b - a;
     c.path_offset = cfg->path_offset + a;
     c.seeds_len = c.replay_len = 0;
@@ -806,7 +812,7 @@ static int cut_config(hh_mgpu* mg, const hh_config* cfg, bool want_terminal, std
     if (want_terminal) {
       int rc = ensure(x, x->terminal, x->terminal_cap, (size_t)c.n_paths * (c.antithetic ? 2 : 1));
       if (rc) return mfail(mg, rc, "%s", x->err);
-      term_dev[g] = x->terminal;
+      sh.terminal[g] = x->terminal;
       c.terminal_on_device = 1;
     }
   }
@@ -817,26 +823,24 @@ int hh_mgpu_solve(hh_mgpu* mg, const hh_model* m, const hh_config* cfg, hh_resul
   if (!mg) return HH_ERR_INVALID;
   std::lock_guard<std::mutex> lock__(mg->mu);
   if (!m || !cfg || !out) return mfail(mg, HH_ERR_INVALID, "hh_mgpu_solve: NULL argument");
-  const auto t0 = std::chrono::steady_clock::now();
-  std::vector<hh_config> cs;
-  std::vector<double*> term_dev;
-  std::vector<uint64_t> starts;
-  int rc = cut_config(mg, cfg, terminal != nullptr, cs, term_dev, starts);
+  const WallClock clock;
+  Shards sh;
+  int rc = cut_config(mg, cfg, terminal != nullptr, sh);
   if (rc) return drain(mg, rc);
   std::memset(out, 0, sizeof(*out));
   double kernel_ms = 0.0;
-  rc = run_shards(mg, m, cs.data(), nullptr, terminal ? term_dev.data() : nullptr, &kernel_ms);
+  rc = run_shards(mg, m, sh.cfg.data(), nullptr, terminal ? sh.terminal.data() : nullptr, &kernel_ms);
   if (rc) return rc;
   if (terminal) {  // the shards' samples into the caller's whole-ensemble layout [N] (+ [N] mirrored)
     for (int g = 0; g < mg->n; ++g) {
-      const uint64_t n = cs[g].n_paths;
+      const uint64_t n = sh.cfg[g].n_paths;
       if (!n) continue;
       HH_MHIP_DRAIN(mg, hipSetDevice(mg->devices[g]));
-      HH_MHIP_DRAIN(mg, hipMemcpyAsync(terminal + starts[g], term_dev[g], n * sizeof(double), hipMemcpyDeviceToHost,
-                                       mg->ctx[g]->stream));
+      HH_MHIP_DRAIN(mg, hipMemcpyAsync(terminal + sh.start[g], sh.terminal[g], n * sizeof(double),
+                                       hipMemcpyDeviceToHost, mg->ctx[g]->stream));
       if (cfg->antithetic)
-        HH_MHIP_DRAIN(mg, hipMemcpyAsync(terminal + cfg->n_paths + starts[g], term_dev[g] + n, n * sizeof(double),
-                                         hipMemcpyDeviceToHost, mg->ctx[g]->stream));
+        HH_MHIP_DRAIN(mg, hipMemcpyAsync(terminal + cfg->n_paths + sh.start[g], sh.terminal[g] + n,
+                                         n * sizeof(double), hipMemcpyDeviceToHost, mg->ctx[g]->stream));
     }
     for (int g = 0; g < mg->n; ++g) {
       HH_MHIP_DRAIN(mg, hipSetDevice(mg->devices[g]));
@@ -846,7 +850,7 @@ int hh_mgpu_solve(hh_mgpu* mg, const hh_model* m, const hh_config* cfg, hh_resul
   rc = hh_mc_finalize(m, cfg, mg->host, out);
   if (rc) return mfinalize_failed(mg, rc);
   out->kernel_ms = kernel_ms;
-  out->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  out->total_ms = clock.ms();
   return HH_OK;
 }
 
@@ -856,25 +860,16 @@ int hh_mgpu_solve_multi(hh_mgpu* mg, const hh_model* models, uint32_t n_models, 
   std::lock_guard<std::mutex> lock__(mg->mu);
   if (!models || !cfg || !out || n_models == 0 || n_models > HH_MAX_MODELS)
     return mfail(mg, HH_ERR_INVALID, "hh_mgpu_solve_multi: 1 .. %d models and their results", HH_MAX_MODELS);
-  const auto t0 = std::chrono::steady_clock::now();
-  std::vector<hh_config> cs;
-  std::vector<double*> term_dev;
-  std::vector<uint64_t> starts;
-  int rc = cut_config(mg, cfg, false, cs, term_dev, starts);
+  const WallClock clock;
+  Shards sh;
+  int rc = cut_config(mg, cfg, false, sh);
   if (rc) return drain(mg, rc);
   Basket b{nullptr, nullptr, 0, n_models};
   double kernel_ms = 0.0;
-  rc = run_shards(mg, models, cs.data(), &b, nullptr, &kernel_ms);
+  rc = run_shards(mg, models, sh.cfg.data(), &b, nullptr, &kernel_ms);
   if (rc) return rc;
-  const double total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  for (uint32_t k = 0; k < n_models; ++k) {
-    std::memset(&out[k], 0, sizeof(hh_result));
-    rc = hh_mc_finalize(&models[k], cfg, mg->host + (size_t)k * HH_ACC_LEN, &out[k]);
-    if (rc) return mfinalize_failed(mg, rc);
-    out[k].kernel_ms = kernel_ms;
-    out[k].total_ms = total;
-  }
-  return HH_OK;
+  rc = finalize_results(models, 1, cfg, mg->host, n_models, kernel_ms, clock.ms(), out);
+  return rc ? mfinalize_failed(mg, rc) : HH_OK;
 }
 
 int hh_mgpu_solve_basket(hh_mgpu* mg, const hh_model* m, const hh_config* cfg, const double* strikes,
@@ -883,25 +878,16 @@ int hh_mgpu_solve_basket(hh_mgpu* mg, const hh_model* m, const hh_config* cfg, c
   std::lock_guard<std::mutex> lock__(mg->mu);
   if (!m || !cfg || !out || !strikes || !cps || n_payoffs == 0 || n_payoffs > 65535)
     return mfail(mg, HH_ERR_INVALID, "hh_mgpu_solve_basket: bad arguments");
-  const auto t0 = std::chrono::steady_clock::now();
-  std::vector<hh_config> cs;
-  std::vector<double*> term_dev;
-  std::vector<uint64_t> starts;
-  int rc = cut_config(mg, cfg, false, cs, term_dev, starts);
+  const WallClock clock;
+  Shards sh;
+  int rc = cut_config(mg, cfg, false, sh);
   if (rc) return drain(mg, rc);
   const Basket b{strikes, cps, n_payoffs};
   double kernel_ms = 0.0;
-  rc = run_shards(mg, m, cs.data(), &b, nullptr, &kernel_ms);
+  rc = run_shards(mg, m, sh.cfg.data(), &b, nullptr, &kernel_ms);
   if (rc) return rc;
-  const double total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  for (uint32_t k = 0; k < n_payoffs; ++k) {
-    std::memset(&out[k], 0, sizeof(hh_result));
-    rc = hh_mc_finalize(m, cfg, mg->host + (size_t)k * HH_ACC_LEN, &out[k]);
-    if (rc) return mfinalize_failed(mg, rc);
-    out[k].kernel_ms = kernel_ms;
-    out[k].total_ms = total;
-  }
-  return HH_OK;
+  rc = finalize_results(m, 0, cfg, mg->host, n_payoffs, kernel_ms, clock.ms(), out);
+  return rc ? mfinalize_failed(mg, rc) : HH_OK;
 }
 
 // SUM all-reduce of the first n doubles of every device's exchange vector, in place.  HH_ERR_RCCL: the
@@ -949,7 +935,7 @@ static int lsm_exchange(hh_mgpu* mg, size_t n) {
 // One pass of the sharded induction in the context's current reduce mode.  HH_ERR_RCCL: see lsm_exchange.
 static int lsm_attempt(hh_mgpu* mg, const hh_model* m, const hh_config* cfg, int32_t degree, double step_discount,
                        hh_lsm_result* out, int32_t* stop_time, double* stop_value) {
-  const auto t0 = std::chrono::steady_clock::now();
+  const WallClock clock;
   const uint64_t N = cfg->n_paths;
   const uint32_t steps = cfg->n_steps;
   const size_t rows = (size_t)steps + 1, nv = 2 * (size_t)degree + 1, nb = (size_t)degree + 1;
@@ -1040,7 +1026,7 @@ static int lsm_attempt(hh_mgpu* mg, const hh_model* m, const hh_config* cfg, int
   out->rows_skipped = sk[0];
   out->form = HH_LSM_FORM_PER_DATE;
   out->kernel_ms = worst;
-  out->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  out->total_ms = clock.ms();
   return HH_OK;
 }
 
