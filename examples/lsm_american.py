@@ -21,6 +21,7 @@ sol = hh.solve(prob, hh.LSM(hh.LognormalDynamics(), hh.BlackScholesExact(), cfg,
 T = hh.yearfrac(ref, expiry)
 print(f"LSM  {sol.price:.5f} +- {sol.std_error:.5f}  ({sol.result.kernel_ms:.2f} ms for "
       f"{sol.result.n_paths_total} paths x 100 dates)")
-print("CRR  6.09711  (2000-step Cox-Ross-Rubinstein tree, T = 366/365; computed by tests' oracle/analytic.py)")
+crr = hh.solve(prob, hh.CoxRossRubinsteinMethod(2000))
+print(f"CRR  {crr.price:.5f}  (2000-step Cox-Ross-Rubinstein tree on the device, T = {T:.6f})")
 tau, val = sol.stopping_info
 print("exercised early on", f"{np.mean(tau < 100) * 100:.1f}% of the paths")

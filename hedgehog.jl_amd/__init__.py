@@ -9,6 +9,7 @@ from ._ffi import Context, HedgehogMCError, get_context, load_library
 from .analytic import (AnalyticSolution, BlackScholesAnalytic, CarrMadan, solve_black_scholes,
                        solve_carr_madan)
 from .basket import BasketPricingProblem, BasketPricingSolution, solve_basket
+from .trees import CoxRossRubinsteinMethod, CRRSolution, solve_crr, solve_crr_basket
 from .dates import Date, DateTime, add_years, to_ticks, yearfrac
 from .dual import Dual, partials_of, value_of
 from .greeks import (BatchGreekProblem, FDBackward, FDCentral, FDForward, FiniteDifference,
@@ -38,6 +39,8 @@ def solve(*args, **kw):
         solve(prob::BasketPricingProblem, method::MonteCarlo | ::CarrMadan)  basket.jl:35
         solve(prob, ::CarrMadan) / solve(prob, ::BlackScholesAnalytic)       carr_madan.jl:47, black_scholes.jl:38
         solve(prob::PricingProblem{<:VanillaOption{…,American,…}}, ::LSM)     least_squares_montecarlo.jl:99
+        solve(prob::PricingProblem{<:VanillaOption}, ::CoxRossRubinsteinMethod) cox_ross_rubinstein.jl:99
+        solve(prob::BasketPricingProblem, ::CoxRossRubinsteinMethod)         basket.jl:35
     """
     from . import greeks as _g
     if len(args) == 2 and isinstance(args[0], PricingProblem) and isinstance(args[1], MonteCarlo):
@@ -49,7 +52,10 @@ def solve(*args, **kw):
         return solve_black_scholes(args[0], args[1])
     if len(args) == 2 and isinstance(args[0], PricingProblem) and isinstance(args[1], LSM):
         return solve_lsm(args[0], args[1], **kw)
-    if len(args) == 2 and isinstance(args[0], BasketPricingProblem) and isinstance(args[1], (MonteCarlo, CarrMadan)):
+    if len(args) == 2 and isinstance(args[0], PricingProblem) and isinstance(args[1], CoxRossRubinsteinMethod):
+        return solve_crr(args[0], args[1])
+    if len(args) == 2 and isinstance(args[0], BasketPricingProblem) and \
+            isinstance(args[1], (MonteCarlo, CarrMadan, CoxRossRubinsteinMethod)):
         return solve_basket(args[0], args[1], **kw)
     if len(args) == 3 and isinstance(args[0], GreekProblem):
         if isinstance(args[1], ForwardAD):

@@ -35,9 +35,14 @@ class BasketPricingSolution:
 
 
 def solve_basket(prob: BasketPricingProblem, method, ensemble: bool = False):
-    """basket.jl:35-38 for a MonteCarlo method (one simulation per expiry group) or CarrMadan (every
-    Fourier integral in one launch)."""
+    """basket.jl:35-38 for a MonteCarlo method (one simulation per expiry group), CarrMadan (every
+    Fourier integral in one launch) or CoxRossRubinsteinMethod (every tree in one launch)."""
     from .analytic import AnalyticSolution, CarrMadan, solve_carr_madan_basket
+    from .trees import CoxRossRubinsteinMethod, CRRSolution, solve_crr_basket
+    if isinstance(method, CoxRossRubinsteinMethod):
+        prices = solve_crr_basket(prob.payoffs, prob.market_inputs, method)
+        return BasketPricingSolution(prob, [CRRSolution(PricingProblem(p, prob.market_inputs), method, float(x))
+                                            for p, x in zip(prob.payoffs, prices)])
     if isinstance(method, CarrMadan):
         prices = solve_carr_madan_basket(prob.payoffs, prob.market_inputs, method)
         return BasketPricingSolution(prob, [AnalyticSolution(PricingProblem(p, prob.market_inputs), method,

@@ -223,6 +223,15 @@ int launch_carr_madan_grad(const hh_model& m, int dynamics, int compat_sqrt_alph
 int launch_carr_madan_basket(const hh_model& m, int dynamics, int compat_sqrt_alpha, double alpha,
                              double bound, const double* per_payoff_dev, uint32_t n_payoffs,
                              double* out_dev, hipStream_t s);
+// Cox–Ross–Rubinstein trees (hh_crr.hip): one tree's scalars as hh_crr_solve stages them (8 doubles)
+struct CrrTree {
+  double F, K, cp, u, p, q, disc;  // forward, strike, ±1, up factor, p = 1/(1+u), q = 1 − p, per-step discount
+  int32_t style;                   // enum hh_crr_style
+  uint32_t row;                    // spot-factor row (HH_CRR_AMERICAN_SPOT)
+};
+// one workgroup per tree; spot_factors_dev: rows of `steps` doubles (NULL when no tree reads one)
+int launch_crr(const CrrTree* trees_dev, const double* spot_factors_dev, int steps, uint32_t n_trees,
+               double* out_dev, hipStream_t s);
 // LSM (hh_lsm.hip)
 uint32_t lsm_chunks(uint64_t ntot);
 size_t lsm_scratch_doubles(uint64_t ntot, uint32_t n_steps, int degree);

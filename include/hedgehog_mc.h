@@ -472,6 +472,32 @@ int hh_carr_madan_basket_grad(hh_ctx* ctx, const hh_model* model, int32_t dynami
                               double* prices_out, double* grad_out);
 
 /*
+ * Cox–Ross–Rubinstein binomial trees — solve(prob, ::CoxRossRubinsteinMethod) for a European or American
+ * VanillaOption on BlackScholesInputs (src/pricing_methods/cox_ross_rubinstein.jl:99-141), and a basket of them
+ * (basket.jl:35-38) in ONE launch, one tree per payoff, all with the same number of steps.  Per tree k:
+ *   forwards[k]  = spot / df(rate, expiry)
+ *   strikes[k], cps[k] (+1 call / -1 put)
+ *   ups[k]       = u = exp(σ·√ΔT), ΔT = yearfrac(referenceDate, expiry) / steps  (p = 1/(1+u) is formed here)
+ *   discounts[k] = exp(−zero_rate(rate, expiry)·ΔT), the per-step discount, the same at every step
+ *   styles[k]    = enum hh_crr_style
+ * HH_CRR_AMERICAN_SPOT trees exercise on sf_i·F·u^k: spot_factors holds n_spot_rows rows of `steps` doubles,
+ * sf_i = exp(−zero_rate(rate, tᵢ)·(steps − i)·ΔT) at element i (cox_ross_rubinstein.jl:75-81), and tree k reads
+ * row spot_row_of_tree[k] — a surface uploads one row per expiry.  spot_factors, spot_row_of_tree and
+ * n_spot_rows (1 .. n_trees) are read only when some tree has that style (NULL / 0 otherwise).
+ * 1 <= steps <= HH_CRR_MAX_STEPS, 1 .. 2^20 trees per call; prices_out[n_trees].  Synchronous.  The node
+ * factors u^k follow the fixed IEEE sequence of csrc/hh_crr.hip, so prices are reproducible bit for bit, and the
+ * kernel form depends on `steps` alone: a tree prices the same alone or in a basket.  Scalars are not checked —
+ * every loop is bounded by `steps`, NaN / infinite inputs give NaN / infinite prices.
+ */
+#define HH_CRR_MAX_STEPS 32768         /* most steps per tree                                        */
+#define HH_CRR_FORM_A_MAX_STEPS 2047   /* up to here one wave prices a tree, beyond it a workgroup     */
+enum hh_crr_style { HH_CRR_EUROPEAN = 0, HH_CRR_AMERICAN_FORWARD = 1, HH_CRR_AMERICAN_SPOT = 2 };
+int hh_crr_solve(hh_ctx* ctx, int32_t steps, uint32_t n_trees, const double* forwards, const double* strikes,
+                 const double* cps, const double* ups, const double* discounts, const int32_t* styles,
+                 const double* spot_factors, uint32_t n_spot_rows, const uint32_t* spot_row_of_tree,
+                 double* prices_out);
+
+/*
  * Longstaff–Schwartz American pricing on the full path grid:
  *   solve(::PricingProblem{VanillaOption{…,American,…}}, ::LSM)
  *                              (src/pricing_methods/least_squares_montecarlo.jl:99-165)
@@ -650,7 +676,8 @@ int hh_wiener_fill(hh_ctx* ctx, int32_t dynamics, double rho, double T, uint32_t
  * enabled, every hh_mc_accumulate / hh_mc_solve brackets EVERYTHING IT ENQUEUES — the simulation
  * kernels and, where it is a kernel of its own, the record reduction; not the staging copies in front —
  * with HIP events on the ctx stream (one slot per call; hh_mc_accumulate_multi on Broadie–Kaya: one per
- * model — a chain's, then each finish pass's); hh_ctx_read_timings
+ * model — a chain's, then each finish pass's); hh_crr_solve brackets its one tree kernel (one slot per
+ * call, neither the upload nor the copy back); hh_ctx_read_timings
  * synchronizes the stream and returns the elapsed ms of the slots recorded since the last read
  * (at most 256 are kept).
  */

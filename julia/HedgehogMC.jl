@@ -471,6 +471,75 @@ function carr_madan_basket_hip(prob::Hedgehog.BasketPricingProblem, method::Hedg
     return Hedgehog.BasketPricingSolution(prob, sols)
 end
 
+# ---- Cox–Ross–Rubinstein trees on the device (src/pricing_methods/cox_ross_rubinstein.jl:99-141) -------------
+const HH_CRR_MAX_STEPS = 32768
+const HH_CRR_FORM_A_MAX_STEPS = 2047
+const HH_CRR_EUROPEAN, HH_CRR_AMERICAN_FORWARD, HH_CRR_AMERICAN_SPOT = Int32(0), Int32(1), Int32(2)
+
+"""
+    crr_basket_hip(prob::BasketPricingProblem, method::CoxRossRubinsteinMethod)
+
+`hh_crr_solve`: every payoff's tree in ONE launch, one tree per payoff, the scalars formed as
+cox_ross_rubinstein.jl:107-132 forms them (the Spot American trees read one row of per-step spot factors per
+expiry, :75-81).  Dual inputs are refused: the kernel carries no partials — use FiniteDifference.
+"""
+function crr_basket_hip(prob::Hedgehog.BasketPricingProblem, method::Hedgehog.CoxRossRubinsteinMethod)
+    m, N = prob.market_inputs, method.steps
+    m isa BlackScholesInputs || throw(MethodError(crr_basket_hip, (prob, method)))
+    1 <= N <= HH_CRR_MAX_STEPS || throw(ArgumentError("CoxRossRubinsteinMethod: steps must lie in 1 .. $HH_CRR_MAX_STEPS"))
+    n = length(prob.payoffs)
+    forwards, strikes, cps, ups, discs = (Vector{Float64}(undef, n) for _ in 1:5)
+    styles, row_of = Vector{Int32}(undef, n), zeros(UInt32, n)
+    rows, keys = Vector{Vector{Float64}}(), Dict{Any,Int}()
+    for (k, p) in enumerate(prob.payoffs)
+        σ = get_vol(m.sigma, p.expiry, p.strike)
+        scal = (m.spot, σ, zero_rate(m.rate, p.expiry), p.strike)
+        _dualtype(scal...) === nothing ||
+            error("ForwardAD through CoxRossRubinsteinMethod is not carried; use FiniteDifference")
+        T = yearfrac(m.referenceDate, p.expiry)
+        ΔT = T / N
+        forwards[k] = m.spot / df(m.rate, p.expiry)
+        strikes[k], cps[k] = p.strike, p.call_put()
+        ups[k] = exp(σ * sqrt(ΔT))
+        discs[k] = exp(-zero_rate(m.rate, p.expiry) * ΔT)
+        if p.exercise_style isa Hedgehog.European
+            styles[k] = HH_CRR_EUROPEAN
+        elseif p.underlying isa Hedgehog.Forward
+            styles[k] = HH_CRR_AMERICAN_FORWARD
+        else
+            styles[k] = HH_CRR_AMERICAN_SPOT
+            row = get!(keys, p.expiry) do
+                push!(rows, [exp(-zero_rate(m.rate, Hedgehog.add_yearfrac(m.rate.reference_date, i * ΔT)) * (N - i) * ΔT)
+                             for i in 0:N-1])
+                length(rows)
+            end
+            row_of[k] = UInt32(row - 1)
+        end
+    end
+    sf = isempty(rows) ? Float64[] : reduce(vcat, rows)
+    out = Vector{Float64}(undef, n)
+    ctx = context()
+    rc = ccall((:hh_crr_solve, LIB[]), Cint,
+               (Ptr{Cvoid}, Int32, UInt32, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble},
+                Ptr{Int32}, Ptr{Cdouble}, UInt32, Ptr{UInt32}, Ptr{Cdouble}),
+               ctx.handle, Int32(N), UInt32(n), forwards, strikes, cps, ups, discs, styles, sf,
+               UInt32(length(rows)), row_of, out)
+    rc == 0 || error("hh_crr_solve failed ($rc): $(last_error(ctx))")
+    return Hedgehog.BasketPricingSolution(prob, [Hedgehog.CRRSolution(PricingProblem(p, m), method, out[k])
+                                                 for (k, p) in enumerate(prob.payoffs)])
+end
+
+"""
+    crr_hip(prob, method::CoxRossRubinsteinMethod)
+
+`solve(prob, ::CoxRossRubinsteinMethod)` for a European or American VanillaOption on BlackScholesInputs, on the
+device: a basket of one (`crr_basket_hip`), so its price equals the same payoff's price in any basket.
+"""
+function crr_hip(prob::PricingProblem{<:VanillaOption}, method::Hedgehog.CoxRossRubinsteinMethod)
+    basket = Hedgehog.BasketPricingProblem([prob.payoff], prob.market_inputs)
+    return crr_basket_hip(basket, method).solutions[1]
+end
+
 # ---- same-expiry baskets (src/calibration/basket.jl:35-38) ---------------------------------------
 """
     solve_basket_hip(prob::BasketPricingProblem, method::MonteCarlo)
