@@ -18,7 +18,10 @@ SOURCES = ["hh_api.hip", "hh_mgpu.hip", "hh_kernels.hip", "hh_multi.hip", "hh_bk
 UNITS = [(s, s.replace(".hip", ".o"), ["-mllvm", "-disable-machine-licm"] if s == "hh_bk.hip" else []) for s in SOURCES]
 CFLAGS = ["-fPIC", "-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off", "-Wall",
           "-Wno-unused-function"]
-LDFLAGS = ["-shared", "-fPIC", "--offload-arch=gfx950", "-ldl"]  # RCCL is bound with dlopen (hh_mgpu.hip)
+# the library exports the header's hh_* functions and nothing else; an undefined symbol fails the link, not a dlopen
+MAP = os.path.join(CSRC, "hedgehog_mc.map")
+LDFLAGS = ["-shared", "-fPIC", "--offload-arch=gfx950", "-ldl",  # RCCL is bound with dlopen (hh_mgpu.hip)
+           "-Wl,--version-script=" + MAP, "-Wl,-z,defs"]
 
 
 def _hipcc() -> str:
@@ -31,12 +34,16 @@ def _headers():
     return deps
 
 
+def link_deps():
+    """What a built library is older than when it must be remade; the map relinks but recompiles nothing."""
+    return [os.path.join(CSRC, s) for s in SOURCES] + _headers() + [MAP]
+
+
 def is_stale() -> bool:
     if not os.path.exists(LIB):
         return True
     t = os.path.getmtime(LIB)
-    deps = [os.path.join(CSRC, s) for s in SOURCES] + _headers()
-    return any(os.path.getmtime(d) > t for d in deps)
+    return any(os.path.getmtime(d) > t for d in link_deps())
 
 
 def _run(cmd):

@@ -18,8 +18,7 @@ def build_bk_check():
     spec = importlib.util.spec_from_file_location("_hh_build", os.path.join(ROOT, "hedgehog.jl_amd", "_build.py"))
     mod = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mod)
-    deps = [os.path.join(mod.CSRC, s) for s in mod.SOURCES] + mod._headers()
-    if os.path.exists(OUT) and all(os.path.getmtime(d) <= os.path.getmtime(OUT) for d in deps):
+    if os.path.exists(OUT) and all(os.path.getmtime(d) <= os.path.getmtime(OUT) for d in mod.link_deps()):
         return OUT
     return mod.build_library(extra_flags=FLAGS, out=OUT)
 

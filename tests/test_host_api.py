@@ -157,11 +157,15 @@ def test_monte_carlo_solution_is_a_plain_frozen_dataclass():
         gone.ensemble
 
 
+def _declared_functions():
+    hdr = open(os.path.join(ROOT, "include", "hedgehog_mc.h")).read()
+    return set(re.findall(r"^\s*(?:int|void|size_t|uint64_t|const char\*|hh_ctx\*)\s+(hh_\w+)\s*\(", hdr, re.M))
+
+
 def test_cabi_header_and_library_agree():
     """Every function include/hedgehog_mc.h declares is bound in _ffi.SYMBOLS and exported by the
     built library (no compute call is made here)."""
-    hdr = open(os.path.join(ROOT, "include", "hedgehog_mc.h")).read()
-    declared = set(re.findall(r"^\s*(?:int|void|size_t|uint64_t|const char\*|hh_ctx\*)\s+(hh_\w+)\s*\(", hdr, re.M))
+    declared = _declared_functions()
     bound = {s[0] for s in _ffi.SYMBOLS}
     assert declared == bound, declared ^ bound
     lib = hh.load_library()
@@ -174,6 +178,18 @@ def test_cabi_header_and_library_agree():
     assert C.sizeof(_ffi.hh_model) == 11 * 8 + 8 * 8
     assert C.sizeof(_ffi.hh_result) == 4 * 8 + 8 * 8 + 5 * 8 + 2 * 8
     assert C.sizeof(_ffi.hh_config) == 10 * 4 + 2 * 4 + 2 * 8 + 2 * 8 + 4 * 8 + 2 * 4 + 4 * 4 + 2 * 8
+
+
+def test_library_exports_exactly_the_header():
+    """The dynamic symbol table of the library (csrc/hedgehog_mc.map) is the header's functions, no more and no
+    fewer: no hh:: function, kernel handle or weak std:: instantiation for another library in the process to bind
+    to or to replace.  The same holds for the check build of tests/c/build_bk_check.py, linked alike."""
+    import subprocess
+    declared = _declared_functions()
+    check = os.path.join(ROOT, "tests", "c", "libhh_bk_check.so")
+    for path in [_ffi.LIB_PATH] + ([check] if os.path.exists(check) else []):
+        nm = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True)
+        assert {line.split()[-1] for line in nm.stdout.splitlines()} == declared, path
 
 
 def test_marginal_law_is_the_reference_formula_quirk_included():
