@@ -16,7 +16,7 @@ test-cpu-asan:
 	$(MAKE) -C oracle -s asan
 	HH_SANITIZE=1 LD_PRELOAD=$(ASAN_RT) ASAN_OPTIONS=detect_leaks=0:abort_on_error=1 UBSAN_OPTIONS=halt_on_error=1:print_stacktrace=1 \
 	  python -m pytest tests/test_oracle_pins.py tests/test_properties.py tests/test_math_host.py tests/test_bessel_host.py \
-	  tests/test_rng_host.py -q -m "not gpu" -p no:cacheprovider
+	  tests/test_rng_host.py tests/test_scratch_layout_host.py -q -m "not gpu" -p no:cacheprovider
 
 test-gpu: build
 	python -m pytest tests -q -m gpu

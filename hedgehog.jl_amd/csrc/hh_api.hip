@@ -122,12 +122,12 @@ int validate(hh_ctx* ctx, const hh_model* m, const hh_config* c) {
 // the record buffer of the launches that reduce their own records: every word kPoison (hh_sim.h) from the
 // allocation on — each launch's reducer leaves it that way again
 int ensure_poisoned(hh_ctx* ctx, size_t need) {
-  if (need <= ctx->frecords_cap) return HH_OK;
-  int rc = ensure(ctx, ctx->frecords, ctx->frecords_cap, need);
+  if (need <= ctx->frecords.cap) return HH_OK;
+  int rc = ensure(ctx, ctx->frecords, need);
   if (rc) return rc;
   static_assert((hh::kPoison >> 32) == (hh::kPoison & 0xffffffffull), "hipMemsetD32 writes the pattern");
   HH_HIP(ctx, hipMemsetD32Async((hipDeviceptr_t)ctx->frecords, (int)(hh::kPoison & 0xffffffffull),
-                                ctx->frecords_cap * 2, ctx->stream));
+                                ctx->frecords.cap * 2, ctx->stream));
   return HH_OK;
 }
 
@@ -158,9 +158,9 @@ int recover_finish(hh_ctx* ctx) {
   HH_HIP(ctx, hipStreamSynchronize(ctx->stream));
   HH_HIP(ctx, hipMemcpy(&state, ctx->finish_state, sizeof(state), hipMemcpyDeviceToHost));
   if (state == 0u) return HH_OK;
-  if (ctx->frecords_cap)
+  if (ctx->frecords.cap)
     HH_HIP(ctx, hipMemsetD32Async((hipDeviceptr_t)ctx->frecords, (int)(hh::kPoison & 0xffffffffull),
-                                  ctx->frecords_cap * 2, ctx->stream));
+                                  ctx->frecords.cap * 2, ctx->stream));
   HH_HIP(ctx, hipMemsetAsync(ctx->finish_state, 0, 2 * sizeof(unsigned int), ctx->stream));
   HH_HIP(ctx, hipStreamSynchronize(ctx->stream));
   const long long ticks = ctx->finish_spin_ticks < 0 ? (long long)hh::kFinishSpinTicksDefault : ctx->finish_spin_ticks;
@@ -236,26 +236,9 @@ void hh_ctx_destroy(hh_ctx* ctx) {
   // a borrowed stream may be gone already: wait for the device (hipFree below synchronises anyway)
   if (ctx->own_stream) (void)hipStreamSynchronize(ctx->own_stream);
   (void)hipDeviceSynchronize();
-  if (ctx->records) (void)hipFree(ctx->records);
-  if (ctx->seeds) (void)hipFree(ctx->seeds);
-  if (ctx->replay) (void)hipFree(ctx->replay);
-  if (ctx->replay_src) (void)hipFree(ctx->replay_src);
-  if (ctx->terminal) (void)hipFree(ctx->terminal);
-  if (ctx->terminal_d) (void)hipFree(ctx->terminal_d);
-  if (ctx->payoffs) (void)hipFree(ctx->payoffs);
-  if (ctx->basket_records) (void)hipFree(ctx->basket_records);
-  if (ctx->basket_accum) (void)hipFree(ctx->basket_accum);
-  if (ctx->bk_scratch) (void)hipFree(ctx->bk_scratch);
-  if (ctx->bk_sort) (void)hipFree(ctx->bk_sort);
-  if (ctx->lsm_grid) (void)hipFree(ctx->lsm_grid);
-  if (ctx->heston_var) (void)hipFree(ctx->heston_var);
-  if (ctx->lsm_val) (void)hipFree(ctx->lsm_val);
-  if (ctx->lsm_tau) (void)hipFree(ctx->lsm_tau);
-  if (ctx->lsm_scratch) (void)hipFree(ctx->lsm_scratch);
   for (auto& e : ctx->seed_cache)
     if (e.dev) (void)hipFree(e.dev);
   if (ctx->accum) (void)hipFree(ctx->accum);
-  if (ctx->frecords) (void)hipFree(ctx->frecords);
   if (ctx->finish_state) (void)hipFree(ctx->finish_state);
   if (ctx->accum_host) (void)hipHostFree(ctx->accum_host);
   for (auto& pr : ctx->tev)
@@ -363,7 +346,7 @@ int hh_replay_pack(hh_ctx* ctx, int32_t dynamics, uint64_t n_paths, uint32_t n_s
   const double* src_dev = src;
   if (!src_on_device) {
     const size_t n = (size_t)n_paths * n_steps * nc;
-    const int rc = stage_host(ctx, ctx->replay_src, ctx->replay_src_cap, n, src, n, &src_dev);
+    const int rc = stage_host(ctx, ctx->replay_src, n, src, n, &src_dev);
     if (rc) return rc;
   }
   HH_HIP(ctx, hh::launch_replay_pack(nc, n_paths, n_steps, src_dev, dst, ctx->stream));
@@ -380,7 +363,7 @@ int hh_wiener_fill(hh_ctx* ctx, int32_t dynamics, double rho, double T, uint32_t
   HH_HIP(ctx, hipSetDevice(ctx->device));
   const uint64_t* seeds_dev = seeds;
   if (!seeds_on_device) {
-    const int rc = stage_host(ctx, ctx->seeds, ctx->seeds_cap, (size_t)n_paths, seeds, (size_t)n_paths, &seeds_dev);
+    const int rc = stage_host(ctx, ctx->seeds, (size_t)n_paths, seeds, (size_t)n_paths, &seeds_dev);
     if (rc) return rc;
   }
   const double dt = T / (double)n_steps;
@@ -403,14 +386,14 @@ static int stage_noise(hh_ctx* ctx, const hh_config* c, hh::DevicePtrs& p, bool 
     const size_t need = (c->strategy == HH_EULER_MARUYAMA) ? (size_t)c->n_paths : 1;
     if (c->seeds_on_device)
       p.seeds = c->seeds;
-    else if ((rc = stage_host(ctx, ctx->seeds, ctx->seeds_cap, need, c->seeds, need, &p.seeds)))
+    else if ((rc = stage_host(ctx, ctx->seeds, need, c->seeds, need, &p.seeds)))
       return rc;
   } else if (bk) {
     // the trajectory's three draws [V_T | u | Z], n_paths each (heston.jl:246-259 order)
     const size_t n3 = (size_t)3 * c->n_paths;
     if (c->replay_on_device)
       p.replay = c->replay;
-    else if ((rc = stage_host(ctx, ctx->replay, ctx->replay_cap, n3, c->replay, n3, &p.replay)))
+    else if ((rc = stage_host(ctx, ctx->replay, n3, c->replay, n3, &p.replay)))
       return rc;
   } else {
     const uint32_t steps = (c->strategy == HH_EULER_MARUYAMA) ? c->n_steps : 1;
@@ -422,11 +405,11 @@ static int stage_noise(hh_ctx* ctx, const hh_config* c, hh::DevicePtrs& p, bool 
       const size_t n = (size_t)c->n_paths * steps * ncomp_of(dyn);
       if (c->replay_on_device)
         p.replay = c->replay;
-      else if ((rc = stage_host(ctx, ctx->replay_src, ctx->replay_src_cap, n, c->replay, n, &p.replay)))
+      else if ((rc = stage_host(ctx, ctx->replay_src, n, c->replay, n, &p.replay)))
         return rc;
       p.replay_path_major = true;
     } else if (c->replay_layout == HH_REPLAY_PATH_MAJOR) {
-      rc = ensure(ctx, ctx->replay, ctx->replay_cap, tile_elems);
+      rc = ensure(ctx, ctx->replay, tile_elems);
       if (rc) return rc;
       rc = hh_replay_pack(ctx, dyn, c->n_paths, steps, c->replay, c->replay_on_device, ctx->replay);
       if (rc) return rc;
@@ -439,7 +422,7 @@ static int stage_noise(hh_ctx* ctx, const hh_config* c, hh::DevicePtrs& p, bool 
         // the kernel guards the tail); Euler: the padded tile-major buffer of hh_replay_elems()
         const size_t host_elems =
             (c->strategy == HH_EULER_MARUYAMA) ? tile_elems : (size_t)c->n_paths;
-        rc = stage_host(ctx, ctx->replay, ctx->replay_cap, tile_elems, c->replay, host_elems, &p.replay);
+        rc = stage_host(ctx, ctx->replay, tile_elems, c->replay, host_elems, &p.replay);
         if (rc) return rc;
       }
     } else {
@@ -460,8 +443,7 @@ static int run_simulation(hh_ctx* ctx, const hh_model* m, const hh_config* c, do
   int rc = HH_OK;
   const uint32_t n_tiles = hh::tiles_for(c->n_paths);
   const bool bk = c->strategy == HH_BROADIE_KAYA;
-  rc = ensure(ctx, ctx->records, ctx->records_cap,
-              (size_t)(bk ? hh::bk_record_count(c->n_paths) : n_tiles) * hh::kRecStride);
+  rc = ensure(ctx, ctx->records, (size_t)(bk ? hh::bk_record_count(c->n_paths) : n_tiles) * hh::kRecStride);
   if (rc) return rc;
 
   hh::DevicePtrs p{};
@@ -491,14 +473,13 @@ static int run_simulation(hh_ctx* ctx, const hh_model* m, const hh_config* c, do
   if (terminal && c->terminal_on_device) {
     p.terminal = terminal;
   } else if (terminal || need_terminal_dev) {
-    rc = ensure(ctx, ctx->terminal, ctx->terminal_cap, n_term);
+    rc = ensure(ctx, ctx->terminal, n_term);
     if (rc) return rc;
     p.terminal = ctx->terminal;
   }
   const int n_active = c->n_partials ? hh::count_active_partials(*m, *c) : 0;
   if (need_terminal_dev && n_active) {
-    rc = ensure(ctx, ctx->terminal_d, ctx->terminal_d_cap,
-                n_term * (size_t)hh::pad_partials((uint32_t)n_active));
+    rc = ensure(ctx, ctx->terminal_d, n_term * (size_t)hh::pad_partials((uint32_t)n_active));
     if (rc) return rc;
     p.terminal_d = ctx->terminal_d;
   }
@@ -575,7 +556,7 @@ int hh_mc_accumulate_multi(hh_ctx* ctx, const hh_model* models, uint32_t n_model
     // runs the chain, the others are finished from the ∫V it left (bk_refinish_kernel, ~10 µs each), with the records —
     // hence the sums — of a chain of their own.  A bumped κ, θ, σ, V0 or T is another chain.
     const uint32_t count = hh::bk_record_count(c->n_paths);
-    if ((rc = ensure(ctx, ctx->records, ctx->records_cap, 2 * (size_t)count * hh::kRecStride))) return rc;  // BEFORE a chain runs
+    if ((rc = ensure(ctx, ctx->records, 2 * (size_t)count * hh::kRecStride))) return rc;  // BEFORE a chain runs
     std::vector<int> leader(n_models, -1);
     for (uint32_t k = 0; k < n_models; ++k)
       for (uint32_t j = 0; j < k; ++j)
@@ -598,7 +579,7 @@ int hh_mc_accumulate_multi(hh_ctx* ctx, const hh_model* models, uint32_t n_model
         if (terminal && c->terminal_on_device) {
           p.terminal = terminal;
         } else if (terminal) {
-          if ((rc = ensure(ctx, ctx->terminal, ctx->terminal_cap, (size_t)c->n_paths))) return rc;
+          if ((rc = ensure(ctx, ctx->terminal, (size_t)c->n_paths))) return rc;
           p.terminal = ctx->terminal;
         }
         if (ctx->timing) HH_HIP(ctx, hipEventRecord(ctx->tev[ctx->t_count % hh_ctx::kTimingSlots][0], ctx->stream));
@@ -616,7 +597,7 @@ int hh_mc_accumulate_multi(hh_ctx* ctx, const hh_model* models, uint32_t n_model
   const size_t rec_elems = (size_t)n_tiles * hh::kRecStride;
   const bool fuse = fuse_for(ctx, c);
   if (fuse) rc = ensure_poisoned(ctx, (size_t)n_models * rec_elems);
-  else rc = ensure(ctx, ctx->records, ctx->records_cap, (size_t)n_models * rec_elems);
+  else rc = ensure(ctx, ctx->records, (size_t)n_models * rec_elems);
   if (rc) return rc;
   hh::DevicePtrs base{};
   if (fuse) fused_controls(ctx, base);
@@ -626,7 +607,7 @@ int hh_mc_accumulate_multi(hh_ctx* ctx, const hh_model* models, uint32_t n_model
   bool any_host_terminal = false;
   if (terminals && !c->terminal_on_device) {
     for (uint32_t k = 0; k < n_models; ++k) any_host_terminal = any_host_terminal || terminals[k] != nullptr;
-    if (any_host_terminal && (rc = ensure(ctx, ctx->terminal, ctx->terminal_cap, (size_t)n_models * n_term))) return rc;
+    if (any_host_terminal && (rc = ensure(ctx, ctx->terminal, (size_t)n_models * n_term))) return rc;
   }
   std::vector<hh::DevicePtrs> p(n_models, base);
   for (uint32_t k = 0; k < n_models; ++k) {
@@ -665,7 +646,7 @@ int hh_mc_solve_multi(hh_ctx* ctx, const hh_model* models, uint32_t n_models, co
   const WallClock clock;
   HH_HIP(ctx, hipSetDevice(ctx->device));
   const size_t n_acc = (size_t)n_models * HH_ACC_LEN;
-  int rc = ensure(ctx, ctx->basket_accum, ctx->basket_accum_cap, n_acc);
+  int rc = ensure(ctx, ctx->basket_accum, n_acc);
   if (rc) return rc;
   HH_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
   if ((rc = hh_mc_accumulate_multi(ctx, models, n_models, c, ctx->basket_accum, terminals))) return rc;
@@ -704,10 +685,9 @@ int hh_mc_accumulate_basket(hh_ctx* ctx, const hh_model* m, const hh_config* c,
   std::vector<double> payoffs(strikes, strikes + n_payoffs);  // strikes | cps
   payoffs.insert(payoffs.end(), cps, cps + n_payoffs);
   const double* payoffs_dev = nullptr;
-  rc = stage_host(ctx, ctx->payoffs, ctx->payoffs_cap, payoffs.size(), payoffs.data(), payoffs.size(), &payoffs_dev);
+  rc = stage_host(ctx, ctx->payoffs, payoffs.size(), payoffs.data(), payoffs.size(), &payoffs_dev);
   if (rc) return rc;
-  rc = ensure(ctx, ctx->basket_records, ctx->basket_records_cap,
-              (size_t)n_payoffs * b.n_chunks * hh::kRecStride);
+  rc = ensure(ctx, ctx->basket_records, (size_t)n_payoffs * b.n_chunks * hh::kRecStride);
   if (rc) return rc;
   b.terminal = term_dev;
   const int n_active = c->n_partials ? hh::count_active_partials(*m, *c) : 0;
@@ -733,7 +713,7 @@ int hh_mc_solve_basket(hh_ctx* ctx, const hh_model* m, const hh_config* c, const
   const WallClock clock;
   HH_HIP(ctx, hipSetDevice(ctx->device));
   const size_t n_acc = (size_t)n_payoffs * HH_ACC_LEN;
-  int rc = ensure(ctx, ctx->basket_accum, ctx->basket_accum_cap, n_acc);
+  int rc = ensure(ctx, ctx->basket_accum, n_acc);
   if (rc) return rc;
   HH_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
   rc = hh_mc_accumulate_basket(ctx, m, c, strikes, cps, n_payoffs, ctx->basket_accum, terminal);
@@ -856,7 +836,7 @@ static int cm_upload_payoffs(hh_ctx* ctx, const char* who, const double* strikes
     host[3 * n + k] = discounts[k];
   }
   HH_HIP(ctx, hipSetDevice(ctx->device));
-  int rc = ensure(ctx, ctx->payoffs, ctx->payoffs_cap, 4 * n + out_len);
+  int rc = ensure(ctx, ctx->payoffs, 4 * n + out_len);
   if (rc) return rc;
   HH_HIP(ctx, hipMemcpyAsync(ctx->payoffs, host.data(), 4 * n * sizeof(double), hipMemcpyHostToDevice,
                              ctx->stream));
@@ -943,19 +923,18 @@ size_t hh_lsm_grid_elems(uint64_t n_paths, uint32_t n_steps, int32_t antithetic)
 // the buffers of a backward induction over ntot trajectories
 static int ensure_lsm_buffers(hh_ctx* ctx, uint64_t ntot, uint32_t n_steps, int32_t degree) {
   int rc;
-  if ((rc = ensure(ctx, ctx->lsm_val, ctx->lsm_val_cap, (size_t)ntot))) return rc;
-  if ((rc = ensure(ctx, ctx->lsm_tau, ctx->lsm_tau_cap, (size_t)ntot))) return rc;
-  if ((rc = ensure(ctx, ctx->lsm_scratch, ctx->lsm_scratch_cap, hh::lsm_scratch_doubles(ntot, n_steps, degree))))
-    return rc;
-  return ensure(ctx, ctx->records, ctx->records_cap, (size_t)hh::lsm_chunks(ntot) * hh::kRecStride);
+  if ((rc = ensure(ctx, ctx->lsm_val, (size_t)ntot))) return rc;
+  if ((rc = ensure(ctx, ctx->lsm_tau, (size_t)ntot))) return rc;
+  if ((rc = ensure(ctx, ctx->lsm_scratch, hh::lsm_scratch_doubles(ntot, n_steps, degree)))) return rc;
+  return ensure(ctx, ctx->records, (size_t)hh::lsm_chunks(ntot) * hh::kRecStride);
 }
 
 // queue the copies back of an induction's row counters (regressed, skipped) into counters[0 .. 2) and, where the
 // caller asked for them, of its stopping times and values
 static int copy_back_lsm(hh_ctx* ctx, uint64_t ntot, uint32_t n_steps, int32_t degree, double* counters,
                          int32_t* stop_time, double* stop_value) {
-  const size_t nscr = hh::lsm_scratch_doubles(ntot, n_steps, degree);
-  HH_HIP(ctx, hipMemcpyAsync(counters, ctx->lsm_scratch + nscr - 2 - hh::kLsmStampSlotsApi, 2 * sizeof(double),
+  const hh::LsmScratch at(ntot, n_steps, degree);
+  HH_HIP(ctx, hipMemcpyAsync(counters, ctx->lsm_scratch + at.counters, 2 * sizeof(double),
                              hipMemcpyDeviceToHost, ctx->stream));
   if (stop_time)
     HH_HIP(ctx, hipMemcpyAsync(stop_time, ctx->lsm_tau, ntot * sizeof(int32_t),
@@ -972,6 +951,7 @@ static int lsm_on_grid(hh_ctx* ctx, const double* grid_dev, uint64_t ntot, uint3
                        const hh_model* m, int32_t degree, double step_discount, hh_lsm_result* out,
                        int32_t* stop_time, double* stop_value, const WallClock& clock) {
   const uint32_t ch = hh::lsm_chunks(ntot);
+  const hh::LsmScratch at(ntot, n_steps, degree);
   int rc;
   if ((rc = ensure_lsm_buffers(ctx, ntot, n_steps, degree))) return rc;
   // enqueue the induction, the final reduction and every copy back, then synchronise ONCE; the
@@ -994,7 +974,7 @@ static int lsm_on_grid(hh_ctx* ctx, const double* grid_dev, uint64_t ntot, uint3
     HH_HIP(ctx, hipEventRecord(ctx->ev1, ctx->stream));
     gave_up = 0;
     if (form_used == hh::kLsmFormPersistent)
-      HH_HIP(ctx, hipMemcpyAsync(&gave_up, hh::lsm_persistent_status(ctx->lsm_scratch),
+      HH_HIP(ctx, hipMemcpyAsync(&gave_up, hh::lsm_persistent_status(ctx->lsm_scratch, at),
                                  sizeof(gave_up), hipMemcpyDeviceToHost, ctx->stream));
     HH_HIP(ctx, hipMemcpyAsync(ctx->accum_host, ctx->accum, HH_ACC_LEN * sizeof(double),
                                hipMemcpyDeviceToHost, ctx->stream));
@@ -1034,7 +1014,7 @@ static int stage_path_seeds(hh_ctx* ctx, const hh_config* c, const uint64_t** ou
                 (unsigned long long)c->seeds_len, (unsigned long long)c->n_paths);
   *out = c->seeds;
   if (c->seeds_on_device) return HH_OK;
-  return stage_host(ctx, ctx->seeds, ctx->seeds_cap, (size_t)c->n_paths, c->seeds, (size_t)c->n_paths, out);
+  return stage_host(ctx, ctx->seeds, (size_t)c->n_paths, c->seeds, (size_t)c->n_paths, out);
 }
 
 // The n_steps Broadie–Kaya transitions of length T/n_steps into ctx->lsm_grid (spot rows) and
@@ -1060,12 +1040,10 @@ static int run_heston_grid(hh_ctx* ctx, const hh_model* m, const hh_config* c) {
   const size_t grid_elems = (size_t)(c->n_steps + 1) * n;
   // dates per kernel chain: given the variance rows, the CF inversions of different dates are
   // independent, so a batch of dates runs as ONE chain over its (date, trajectory) pairs
-  uint32_t per_chain = ctx->grid_form == HH_GRID_FORM_BATCHED
-                           ? hh::bk_grid_dates_per_chain(n, c->n_steps, ctx->bk_term_cache)
-                           : 1u;
+  uint32_t per_chain = ctx->grid_form == HH_GRID_FORM_BATCHED ? hh::bk_grid_dates_per_chain(n, c->n_steps) : 1u;
   int rc;
-  if ((rc = ensure(ctx, ctx->lsm_grid, ctx->lsm_grid_cap, grid_elems))) return rc;
-  if ((rc = ensure(ctx, ctx->heston_var, ctx->heston_var_cap, grid_elems))) return rc;
+  if ((rc = ensure(ctx, ctx->lsm_grid, grid_elems))) return rc;
+  if ((rc = ensure(ctx, ctx->heston_var, grid_elems))) return rc;
   // a chain's scratch is 48 bytes per (date, trajectory) pair beside the fixed term cache: on a device
   // that cannot spare it (shared with another allocator) the dates go into shorter chains, down to one
   // chain per date — same bits either way
@@ -1076,17 +1054,15 @@ static int run_heston_grid(hh_ctx* ctx, const hh_model* m, const hh_config* c) {
     n_chain = n * per_chain;
   }
   if (rc) return rc;
-  if ((rc = ensure(ctx, ctx->records, ctx->records_cap, (size_t)hh::bk_record_count(n_chain) * hh::kRecStride)))
-    return rc;
-  if ((rc = ensure(ctx, ctx->basket_accum, ctx->basket_accum_cap, (size_t)c->n_steps * HH_ACC_LEN)))
-    return rc;
+  if ((rc = ensure(ctx, ctx->records, (size_t)hh::bk_record_count(n_chain) * hh::kRecStride))) return rc;
+  if ((rc = ensure(ctx, ctx->basket_accum, (size_t)c->n_steps * HH_ACC_LEN))) return rc;
   hh::DevicePtrs p{};
   p.records = ctx->records;
   p.bk_scratch = ctx->bk_scratch;
   p.bk_table_key = &ctx->bk_table_key;
   p.bk_term_cache = ctx->bk_term_cache;
   if (per_chain > 1 && ctx->grid_order) {  // the batched chains run their pairs in the order of their Bessel arguments
-    if ((rc = ensure(ctx, ctx->bk_sort, ctx->bk_sort_cap, hh::bk_grid_sort_bytes(n_chain)))) return rc;
+    if ((rc = ensure(ctx, ctx->bk_sort, hh::bk_grid_sort_bytes(n_chain)))) return rc;
     p.bk_sort = ctx->bk_sort;
   }
   if ((rc = stage_path_seeds(ctx, c, &p.seeds))) return rc;
@@ -1185,8 +1161,7 @@ static int lsm_paths(hh_ctx* ctx, const hh_model* m, const hh_config* c, int32_t
   HH_HIP(ctx, hipSetDevice(ctx->device));
   if (start) HH_HIP(ctx, hipEventRecord(start, ctx->stream));
   if (heston) return run_heston_grid(ctx, m, c);
-  if ((rc = ensure(ctx, ctx->lsm_grid, ctx->lsm_grid_cap, hh_lsm_grid_elems(c->n_paths, c->n_steps, c->antithetic))))
-    return rc;
+  if ((rc = ensure(ctx, ctx->lsm_grid, hh_lsm_grid_elems(c->n_paths, c->n_steps, c->antithetic)))) return rc;
   const uint64_t* seeds_dev = nullptr;
   if ((rc = stage_path_seeds(ctx, c, &seeds_dev))) return rc;
   HH_HIP(ctx, hh::launch_gbm_grid(seeds_dev, c->n_paths, c->n_steps, m->S0, m->r_drift, m->sigma,
@@ -1247,8 +1222,8 @@ static int run_euler_grid(hh_ctx* ctx, const hh_model* m, const hh_config* c, in
     return fail(ctx, HH_ERR_INVALID, "Euler grid: S0, T > 0, |rho| <= 1, model scalars finite");
   const size_t elems = hh_lsm_grid_elems(c->n_paths, c->n_steps, c->antithetic);
   int rc;
-  if ((rc = ensure(ctx, ctx->lsm_grid, ctx->lsm_grid_cap, elems))) return rc;
-  if (want_var && (rc = ensure(ctx, ctx->heston_var, ctx->heston_var_cap, elems))) return rc;
+  if ((rc = ensure(ctx, ctx->lsm_grid, elems))) return rc;
+  if (want_var && (rc = ensure(ctx, ctx->heston_var, elems))) return rc;
   const uint64_t* seeds_dev = nullptr;
   if ((rc = stage_path_seeds(ctx, c, &seeds_dev))) return rc;
   HH_HIP(ctx, hh::launch_euler_grid(*m, *c, seeds_dev, path_state == HH_PATH_LOG, ctx->lsm_grid,
@@ -1368,12 +1343,11 @@ int hh_lsm_debug_read(hh_ctx* ctx, uint64_t n_paths_total, uint32_t n_steps, int
   if (!ctx || !out8) return HH_ERR_INVALID;
   std::lock_guard<std::recursive_mutex> lock__(ctx->mu);
   HH_HIP(ctx, hipSetDevice(ctx->device));
-  const size_t nscr = hh::lsm_scratch_doubles(n_paths_total, n_steps, degree);
-  if (!ctx->lsm_scratch || ctx->lsm_scratch_cap < nscr)
+  const hh::LsmScratch at(n_paths_total, n_steps, degree);
+  if (!ctx->lsm_scratch || ctx->lsm_scratch.cap < at.total)
     return fail(ctx, HH_ERR_INVALID, "hh_lsm_debug_read: no LSM solve of that shape has run");
   HH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  HH_HIP(ctx, hipMemcpy(out8, ctx->lsm_scratch + nscr - hh::kLsmStampSlotsApi,
-                        hh::kLsmStampSlotsApi * sizeof(double), hipMemcpyDeviceToHost));
+  HH_HIP(ctx, hipMemcpy(out8, ctx->lsm_scratch + at.stamps, hh::kLsmStampSlots * sizeof(double), hipMemcpyDeviceToHost));
   return HH_OK;
 }
 

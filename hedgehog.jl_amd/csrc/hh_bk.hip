@@ -71,19 +71,7 @@ constexpr double kInvPi = 0.31830988618379067154, kTwoOverPi = 0.636619772367581
 #endif
 
 
-// Columns of cached series terms.  A lane's column belongs to a workgroup SLOT that a workgroup of the
-// CF kernel (or of the ladder kernel behind it) takes when it starts and gives back when it is done —
-// not to the trajectory: the cache is kSlots x 256 columns however many trajectories the chain has
-// (1536 slots: the CF kernel takes 95 registers since its real-axis evaluations, so FIVE of its workgroups are
-// resident per CU, 1280 in all — with 1024 slots the fifth spun for a slot and the kernel ran 3 % slower than at a
-// forced four; with a slot for it, 5 % faster (profiles/r05_h_bk_ab.txt).  A bitmap word is 64 slots, hence 192
-// per XCD.  256 terms of 8 bytes: 0.81 GB for 10^4 and for 10^8 trajectories alike).  A trajectory's terms are only needed again if its secant fails (2 % of
-// them): the ladder kernel re-derives those.
-constexpr int kSlots = 1536;
-constexpr int kHeavyGrid = 64;   // workgroups of the tail kernel (169 registers: it holds the whole-trajectory
-                                  // code, idle with the reference's controls and the whole job when no series fits the
-                                  // term cache; its first kRecStride workgroups then add the records)
-static_assert(kHeavyGrid <= kSlots, "the tail kernel's workgroup b uses slot b");
+// kSlots, kHeavyGrid and the term cache they size: hh_layout.h
 static_assert(kHeavyGrid >= kRecStride, "one workgroup of the tail kernel per accumulator slot");
 
 // The weight of term j of the CDF series (sample_from_cf.jl:86: (2/π)·sin(h j x)·Re ϕ(h j)/j) is (2/π)/j — an
@@ -1094,7 +1082,7 @@ __device__ __forceinline__ void invert_phase(const BkArgs& p, const double* coef
 //    somebody else was faster), the slot goes to the other waves through LDS and is given back (atomic
 //    AND) at the end.  A slot's holder never waits for anything, so a workgroup that finds every slot
 //    taken only waits for another one to finish: no deadlock however the hardware places workgroups.
-constexpr int kXcds = 8, kSlotsPerXcd = kSlots / kXcds, kSlotLineWords = 16;  // 128-byte line per XCD
+constexpr int kSlotsPerXcd = kSlots / kXcds;  // (kXcds, kSlotLineWords: a 128-byte line per XCD, hh_layout.h)
 static_assert(kSlotsPerXcd % 64 == 0 && kSlotsPerXcd / 64 <= kSlotLineWords, "whole bitmap words, one line per XCD");
 __device__ __forceinline__ uint32_t take_slot(const BkArgs& p, uint32_t own) {
   if (p.static_slots) return own;  // uniform
@@ -1547,7 +1535,6 @@ __global__ __launch_bounds__(256) void fill_rows_kernel(double* __restrict__ spo
 // same digit in front of it in the run (the lanes with its digit found by eight ballots, the running count per digit
 // in LDS).  Stable: equal keys stay in pair order — the order a stable radix sort of (key, pair) gives.
 // (measured, 2.4·10^6 pairs: runs of 2048 the same 31 µs, 512: 47, 256: 86 — the [digit][run] table of counts is what costs)
-constexpr int kSortRun = 1024;                           // consecutive pairs per wave
 constexpr int kSortWaves = kTile / 64;
 static_assert(kSortRun % 64 == 0, "whole rounds of a wave");
 
@@ -1673,25 +1660,8 @@ constexpr uint64_t kGridOrderMinPairs = 1ull << 20;
 
 }  // namespace
 
-constexpr size_t kSlotBitmapBytes = 8 * 128 + 128;  // one 128-byte line per XCD (kXcds = 8) + the line of BkArgs::counters
-
-// series terms cached per column: term_cache (HH_OPT_BK_TERM_CACHE; 0 = kBkTermCacheDefault).  The columns
-// belong to workgroup slots, so the cache does not grow with the ensemble.
-static int phi_cache_cap(int term_cache) { return term_cache > 0 ? term_cache : kBkTermCacheDefault; }
-
-// The head of the scratch buffer:
-//   ballots of the too-long trajectories [n_tiles][4] | (128-byte boundary) slot bitmaps, 8 lines | counters, 1 line |
-//   (256-byte boundary) device copy of the argument block | (256) Bessel tables and ϕ(0) constants
-static size_t bk_masks_bytes(size_t n_tiles) { return n_tiles * (kTile / 64) * sizeof(unsigned long long); }
-static size_t bk_lines_offset(size_t n_tiles) { return (bk_masks_bytes(n_tiles) + 127) & ~(size_t)127; }
-static size_t bk_args_offset(size_t n_tiles) { return (bk_lines_offset(n_tiles) + kSlotBitmapBytes + 255) & ~(size_t)255; }
-static size_t bk_tables_offset(size_t n_tiles) { return bk_args_offset(n_tiles) + ((sizeof(BkArgs) + 255) & ~(size_t)255); }
-static size_t bk_flags_bytes(size_t n_tiles) { return bk_tables_offset(n_tiles) + ((sizeof(BkTables) + 255) & ~(size_t)255); }
-// columns of cached terms: one per lane of a workgroup slot (fewer slots than tiles are never needed)
-static size_t bk_cache_columns(size_t n_tiles) {
-  const size_t slots = n_tiles < (size_t)kHeavyGrid ? (size_t)kHeavyGrid : n_tiles < (size_t)kSlots ? n_tiles : (size_t)kSlots;
-  return slots * kTile;
-}
+// where a chain over n_chain trajectories (or pairs) has its pieces of the scratch buffer
+static BkScratch bk_scratch_at(uint64_t n_chain, int term_cache) { return {n_chain, term_cache, sizeof(BkArgs), sizeof(BkTables)}; }
 
 int launch_fill_rows(double* spot0, double* var0, uint64_t n, double S0, double V0, hipStream_t s) {
   hipLaunchKernelGGL(fill_rows_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, s, spot0,
@@ -1705,17 +1675,11 @@ uint32_t bk_record_count(uint64_t n_paths) {
 // … of which a chain fills the first *bk_live_records(): the tail kernel's workgroups leave records only when
 // they had trajectories to run (BkArgs::counters[1], written by the tail kernel)
 const uint32_t* bk_live_records(const void* scratch, uint64_t n_paths) {
-  const unsigned char* base = static_cast<const unsigned char*>(scratch);
-  return reinterpret_cast<const uint32_t*>(base + bk_lines_offset(tiles_for(n_paths)) + 8 * 128) + 1;
+  // (the head of the scratch does not depend on the term cache)
+  return reinterpret_cast<const uint32_t*>(static_cast<const unsigned char*>(scratch) + bk_scratch_at(n_paths, 0).counters) + 1;
 }
 
-size_t bk_scratch_bytes(uint64_t n_paths, int term_cache) {
-  const size_t n_tiles = tiles_for(n_paths);
-  // head | cached series terms [cap][columns] (per workgroup SLOT: independent of n_paths) |
-  // per trajectory: draws [4] | ∫V [1] | decision word, series length (2 x uint32)
-  return bk_flags_bytes(n_tiles) + bk_cache_columns(n_tiles) * (size_t)phi_cache_cap(term_cache) * sizeof(double) +
-         n_tiles * kTile * sizeof(double) * 6;
-}
+size_t bk_scratch_bytes(uint64_t n_paths, int term_cache) { return bk_scratch_at(n_paths, term_cache).total; }
 
 namespace {
 
@@ -1757,25 +1721,24 @@ int bk_prepare(const hh_model& m, const hh_config& c, const DevicePtrs& ptr, uin
   a.seeds = ptr.seeds;
   a.terminal = ptr.terminal;
   a.records = ptr.records;
-  const uint32_t n_tiles = tiles_for(n_chain);
-  const size_t lanes = (size_t)n_tiles * kTile;
+  const BkScratch at = bk_scratch_at(n_chain, ptr.bk_term_cache);
   unsigned char* base = reinterpret_cast<unsigned char*>(ptr.bk_scratch);
-  a.long_mask = reinterpret_cast<unsigned long long*>(base);
-  L.n_tiles = n_tiles;
-  a.slot_busy = reinterpret_cast<uint32_t*>(base + bk_lines_offset(n_tiles));  // 128-byte lines
-  a.counters = a.slot_busy + 8 * 32;                                            // the line behind the eight slot bitmaps
-  a.args_dev = base + bk_args_offset(n_tiles);
-  L.tabs_dev = reinterpret_cast<BkTables*>(base + bk_tables_offset(n_tiles));
+  a.long_mask = reinterpret_cast<unsigned long long*>(base + at.long_mask);
+  L.n_tiles = at.n_tiles;
+  a.slot_busy = reinterpret_cast<uint32_t*>(base + at.slot_lines);
+  a.counters = reinterpret_cast<uint32_t*>(base + at.counters);
+  a.args_dev = base + at.args;
+  L.tabs_dev = reinterpret_cast<BkTables*>(base + at.tables);
   a.tabs_dev = L.tabs_dev;
-  a.n_tiles = n_tiles;
-  a.cache_cap = phi_cache_cap(ptr.bk_term_cache);
-  a.phi_cache = reinterpret_cast<double*>(base + bk_flags_bytes(n_tiles));
-  a.cache_stride = bk_cache_columns(n_tiles);
-  a.static_slots = n_tiles <= (uint32_t)kSlots ? 1u : 0u;
-  a.draws = a.phi_cache + a.cache_stride * (size_t)a.cache_cap;
-  a.iv_store = a.draws + 4 * lanes;  // ∫V per pair of a grid chain / per trajectory of the one-shot law (iv_keep)
-  a.diag = reinterpret_cast<uint32_t*>(a.iv_store + lanes);  // 2 x uint32 per lane
-  a.draw_stride = lanes;
+  a.n_tiles = at.n_tiles;
+  a.cache_cap = at.cache_cap;
+  a.phi_cache = reinterpret_cast<double*>(base + at.phi_cache);
+  a.cache_stride = at.cache_columns;
+  a.static_slots = at.n_tiles <= (uint32_t)kSlots ? 1u : 0u;
+  a.draws = reinterpret_cast<double*>(base + at.draws);
+  a.iv_store = reinterpret_cast<double*>(base + at.iv);  // ∫V per pair of a grid chain / per trajectory of the one-shot law (iv_keep)
+  a.diag = reinterpret_cast<uint32_t*>(base + at.diag);
+  a.draw_stride = at.lanes;
   return 0;
 }
 
@@ -1790,7 +1753,7 @@ int bk_tables(const BkArgs& a, const BkLayout& L, const DevicePtrs& ptr, hipStre
   if (upload_tables) {
     // … and the slot bitmaps and the counters beside them start from zero; after that every chain leaves them so
     // (a workgroup gives its slot back, bk_tail_kernel resets what it counted with): no 5 µs fill per solve
-    (void)hipMemsetAsync(a.slot_busy, 0, kSlotBitmapBytes, s);
+    (void)hipMemsetAsync(a.slot_busy, 0, bk_scratch_at(a.n_paths, 0).zeroed_bytes, s);
     BkBessel tabs;
     if (!bessel_table(a.nu, tabs.t[0]) || !bessel_table(a.nu - a.n_int, tabs.t[1]))
       return (int)hipErrorInvalidValue;  // the series table of hh_bessel.h does not reach |z| = 13: not for ν > -1
@@ -1879,11 +1842,10 @@ int launch_bk_refinish(const hh_model& m, const hh_config& c, const DevicePtrs& 
   return (int)hipGetLastError();
 }
 
-uint32_t bk_grid_dates_per_chain(uint64_t n_paths, uint32_t n_steps, int term_cache) {
+uint32_t bk_grid_dates_per_chain(uint64_t n_paths, uint32_t n_steps) {
   // The term cache no longer grows with the pairs of a chain; what does is 48 bytes per pair (draws, ∫V,
   // decision words).  2^22 pairs fill the chip more than twenty times over and keep that at 0.2 GB: a
   // longer grid is cut into several chains, the dates spread evenly over them.
-  (void)term_cache;
   const uint64_t pairs_max = (uint64_t)1 << 22;
   const uint64_t per = n_paths ? pairs_max / n_paths : 1;
   if (per <= 1) return 1;
@@ -1894,22 +1856,14 @@ uint32_t bk_grid_dates_per_chain(uint64_t n_paths, uint32_t n_steps, int term_ca
 // where a chain over n_paths trajectories left its decision words / series lengths inside `scratch`
 void bk_diag_ptrs(const void* scratch, uint64_t n_paths, int term_cache, const uint32_t** decisions,
                   const uint32_t** series_len) {
-  const size_t n_tiles = tiles_for(n_paths), lanes = n_tiles * kTile;
-  const unsigned char* base = reinterpret_cast<const unsigned char*>(scratch);
-  const double* cache = reinterpret_cast<const double*>(base + bk_flags_bytes(n_tiles));
-  const double* draws = cache + bk_cache_columns(n_tiles) * (size_t)phi_cache_cap(term_cache);
-  const uint32_t* diag = reinterpret_cast<const uint32_t*>(draws + 5 * lanes);
+  const BkScratch at = bk_scratch_at(n_paths, term_cache);
+  const uint32_t* diag = reinterpret_cast<const uint32_t*>(static_cast<const unsigned char*>(scratch) + at.diag);
   *decisions = diag;
-  *series_len = diag + lanes;
+  *series_len = diag + at.lanes;
 }
 
-// device scratch of the ordered form of a grid chain over n_chain pairs:
-//   the order [lanes] x uint32 | counts [256][n_runs] x uint32 | totals [256] x uint32 | keys [lanes] x uint8
-static uint32_t grid_sort_runs(uint64_t n_chain) { return (uint32_t)((n_chain + kSortRun - 1) / kSortRun); }
-size_t bk_grid_sort_bytes(uint64_t n_chain) {
-  const size_t lanes = (size_t)tiles_for(n_chain) * kTile;
-  return lanes * sizeof(uint32_t) + ((size_t)256 * grid_sort_runs(n_chain) + 256) * sizeof(uint32_t) + lanes + 256;
-}
+// device scratch of the ordered form of a grid chain over n_chain pairs
+size_t bk_grid_sort_bytes(uint64_t n_chain) { return BkSortScratch(n_chain).total; }
 
 int launch_bk_grid(const hh_model& m, const hh_config& c, const DevicePtrs& ptr, hipStream_t s,
                    double* spot_rows, double* var_rows, uint32_t k0, uint32_t n_dates, bool upload_tables) {
@@ -1925,20 +1879,20 @@ int launch_bk_grid(const hh_model& m, const hh_config& c, const DevicePtrs& ptr,
   if ((rc = bk_tables(a, L, ptr, s, upload_tables))) return rc;
   const dim3 rows(tiles_for(n_row)), b(kTile);
   const bool ordered = ptr.bk_sort && n_chain >= kGridOrderMinPairs && n_chain < (1ull << 31);
-  const size_t lanes = (size_t)L.n_tiles * kTile;
-  const uint32_t n_runs = grid_sort_runs(n_chain);
-  uint32_t* perm = reinterpret_cast<uint32_t*>(ptr.bk_sort);
-  uint32_t* counts = perm + lanes;
-  uint32_t* totals = counts + (size_t)256 * n_runs;
-  uint8_t* keys = reinterpret_cast<uint8_t*>(totals + 256);
+  const BkSortScratch sort(n_chain);
+  unsigned char* sort_base = static_cast<unsigned char*>(ptr.bk_sort);
+  uint32_t* perm = reinterpret_cast<uint32_t*>(sort_base + sort.perm);
+  uint32_t* counts = reinterpret_cast<uint32_t*>(sort_base + sort.counts);
+  uint32_t* totals = reinterpret_cast<uint32_t*>(sort_base + sort.totals);
+  uint8_t* keys = sort_base + sort.keys;
   hipLaunchKernelGGL(bk_draw_grid_kernel, rows, b, 0, s, a, n_row, k0, n_dates, var_rows, ordered ? keys : nullptr);
   if (ordered) {  // the pairs in the order of their Bessel arguments (grid_order_key)
-    const dim3 sort_grid((n_runs + kSortWaves - 1) / kSortWaves);
+    const dim3 sort_grid((sort.n_runs + kSortWaves - 1) / kSortWaves);
     hipLaunchKernelGGL(grid_sort_count_kernel, sort_grid, b, 0, s, static_cast<const uint8_t*>(keys), (uint32_t)n_chain,
-                       n_runs, counts);
-    hipLaunchKernelGGL(grid_sort_scan_kernel, dim3(256), b, 0, s, counts, n_runs, totals);
+                       sort.n_runs, counts);
+    hipLaunchKernelGGL(grid_sort_scan_kernel, dim3(256), b, 0, s, counts, sort.n_runs, totals);
     hipLaunchKernelGGL(grid_sort_scatter_kernel, sort_grid, b, 0, s, static_cast<const uint8_t*>(keys), (uint32_t)n_chain,
-                       n_runs, static_cast<const uint32_t*>(counts), static_cast<const uint32_t*>(totals), perm);
+                       sort.n_runs, static_cast<const uint32_t*>(counts), static_cast<const uint32_t*>(totals), perm);
     // The chain reads each pair's draws and start variance, and writes its ∫V, THROUGH the order (BkArgs::order): a
     // pair's 48 bytes, fetched at random by a kernel that then computes for 0.3 µs per pair, hide behind the other
     // waves' arithmetic.  Copying them into the order first (a gather by destination 0.19 ms; by source through the

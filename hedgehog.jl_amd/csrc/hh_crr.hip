@@ -236,7 +236,7 @@ int hh_crr_solve(hh_ctx* ctx, int32_t steps, uint32_t n_trees, const double* for
   if (n_sf) std::memcpy(host.data() + n_par, spot_factors, n_sf * sizeof(double));
   HH_HIP(ctx, hipSetDevice(ctx->device));
   const double* dev = nullptr;
-  int rc = stage_host(ctx, ctx->payoffs, ctx->payoffs_cap, n_par + n_sf + n, host.data(), n_par + n_sf, &dev);
+  int rc = stage_host(ctx, ctx->payoffs, n_par + n_sf + n, host.data(), n_par + n_sf, &dev);
   if (rc) return rc;
   double* out_dev = ctx->payoffs + n_par + n_sf;
   if (ctx->timing) HH_HIP(ctx, hipEventRecord(ctx->tev[ctx->t_count % hh_ctx::kTimingSlots][0], ctx->stream));

@@ -9,6 +9,19 @@
 
 #include "hh_kernels.h"
 
+// A device buffer of the context that grows on demand (ensure) and reads as its pointer.  The context's destructor
+// frees it: hh_ctx_destroy deletes the context with its device current and the device idle.
+template <class T>
+struct DevBuf {
+  T* p = nullptr;
+  size_t cap = 0;  // in elements
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;  // one owner
+  DevBuf& operator=(const DevBuf&) = delete;
+  ~DevBuf() { if (p) (void)hipFree(p); }
+  operator T*() const { return p; }
+};
+
 struct hh_ctx {
   int device = 0;
   hipStream_t own_stream = nullptr;
@@ -18,37 +31,22 @@ struct hh_ctx {
   // point has to wait for it (release_host_operands) before it returns — the caller owns its buffers again then
   hipEvent_t ev_stage = nullptr;
   bool staged_host = false;
-  double* records = nullptr;
-  size_t records_cap = 0;  // in records
-  uint64_t* seeds = nullptr;
-  size_t seeds_cap = 0;  // in elements
-  double* replay = nullptr;  // tile-major staging
-  size_t replay_cap = 0;
-  double* replay_src = nullptr;  // path-major staging
-  size_t replay_src_cap = 0;
-  double* terminal = nullptr;
-  size_t terminal_cap = 0;
-  double* terminal_d = nullptr;  // [P][n_total] terminal partials (basket Greeks)
-  size_t terminal_d_cap = 0;
-  double* payoffs = nullptr;  // [2][n_payoffs]: strikes, cps
-  size_t payoffs_cap = 0;
-  double* basket_records = nullptr;
-  size_t basket_records_cap = 0;
-  double* basket_accum = nullptr;
-  size_t basket_accum_cap = 0;
-  unsigned char* bk_scratch = nullptr;
-  size_t bk_scratch_cap = 0;
+  DevBuf<double> records;  // capacities in elements
+  DevBuf<uint64_t> seeds;
+  DevBuf<double> replay;      // tile-major staging
+  DevBuf<double> replay_src;  // path-major staging
+  DevBuf<double> terminal;
+  DevBuf<double> terminal_d;  // [P][n_total] terminal partials (basket Greeks)
+  DevBuf<double> payoffs;     // [2][n_payoffs]: strikes, cps
+  DevBuf<double> basket_records;
+  DevBuf<double> basket_accum;
+  DevBuf<unsigned char> bk_scratch;
   hh::BkTableKey bk_table_key{};  // Bessel tables resident in bk_scratch (dropped by ensure_bk_scratch)
-  double* lsm_grid = nullptr;  // [n_steps+1][ntot]
-  size_t lsm_grid_cap = 0;
-  double* heston_var = nullptr;  // [n_steps+1][n_paths] variance rows of the exact Heston grid
-  size_t heston_var_cap = 0;
-  double* lsm_val = nullptr;
-  size_t lsm_val_cap = 0;
-  int32_t* lsm_tau = nullptr;
-  size_t lsm_tau_cap = 0;
-  double* lsm_scratch = nullptr;
-  size_t lsm_scratch_cap = 0;
+  DevBuf<double> lsm_grid;    // [n_steps+1][ntot]
+  DevBuf<double> heston_var;  // [n_steps+1][n_paths] variance rows of the exact Heston grid
+  DevBuf<double> lsm_val;
+  DevBuf<int32_t> lsm_tau;
+  DevBuf<double> lsm_scratch;
   // sharded LSM in progress (hh_lsm_shard_begin .. hh_lsm_shard_finish)
   struct {
     bool active = false;
@@ -64,12 +62,10 @@ struct hh_ctx {
   int bk_last_cache = 0;            // … and the term cache it ran with
   int grid_form = HH_GRID_FORM_BATCHED;  // hh_ctx_set_option(HH_OPT_GRID_FORM)
   int grid_order = 1;                    // hh_ctx_set_option(HH_OPT_GRID_ORDER): 1 = a chain's pairs sorted by their Bessel arguments
-  unsigned char* bk_sort = nullptr;      // scratch of the ordered form (hh::bk_grid_sort_bytes)
-  size_t bk_sort_cap = 0;
+  DevBuf<unsigned char> bk_sort;         // scratch of the ordered form (hh::bk_grid_sort_bytes)
   uint64_t lsm_persistent_fallbacks = 0;  // persistent launches that gave up and were redone per date
   long long lsm_spin_ticks = -1;          // hh_ctx_set_option(HH_OPT_LSM_SPIN_TICKS); < 0 = the default (1 s)
-  double* frecords = nullptr;      // records of the launches that reduce them themselves: kPoison between launches (hh_sim.h)
-  size_t frecords_cap = 0;         // in doubles
+  DevBuf<double> frecords;         // records of the launches that reduce them themselves: kPoison between launches (hh_sim.h)
   int fuse_reduce = 2;             // hh_ctx_set_option(HH_OPT_FUSE_REDUCE): 0 a second kernel, 1 in the simulation kernel, 2 by size
   unsigned int* finish_state = nullptr;  // device word: a reducer inside a simulation kernel gave up (hh_sim.h); cleared by recover_finish
   long long finish_spin_ticks = -1;      // hh_ctx_set_option(HH_OPT_FINISH_SPIN_TICKS); < 0 = the default (5 s)
@@ -114,16 +110,16 @@ namespace {
   } while (0)
 
 template <class T>
-int ensure(hh_ctx* ctx, T*& buf, size_t& cap, size_t need) {
-  if (need <= cap) return HH_OK;
-  if (buf) HH_HIP(ctx, hipFree(buf));
-  buf = nullptr;
-  cap = 0;
-  hipError_t e = hipMalloc((void**)&buf, need * sizeof(T));
+int ensure(hh_ctx* ctx, DevBuf<T>& buf, size_t need) {
+  if (need <= buf.cap) return HH_OK;
+  if (buf.p) HH_HIP(ctx, hipFree(buf.p));
+  buf.p = nullptr;
+  buf.cap = 0;
+  hipError_t e = hipMalloc((void**)&buf.p, need * sizeof(T));
   if (e != hipSuccess)
     return fail(ctx, HH_ERR_NOMEM, "hipMalloc(%zu bytes) failed: %s", need * sizeof(T),
                 hipGetErrorString(e));
-  cap = need;
+  buf.cap = need;
   return HH_OK;
 }
 
@@ -136,8 +132,8 @@ int ensure(hh_ctx* ctx, T*& buf, size_t& cap, size_t need) {
 // n elements of a caller's host buffer into the ctx buffer buf, which is made to hold need >= n elements first (the
 // padded tile-major increments are copied short); *dev: where the kernels read them
 template <class T>
-int stage_host(hh_ctx* ctx, T*& buf, size_t& cap, size_t need, const T* src, size_t n, const T** dev) {
-  int rc = ensure(ctx, buf, cap, need);
+int stage_host(hh_ctx* ctx, DevBuf<T>& buf, size_t need, const T* src, size_t n, const T** dev) {
+  int rc = ensure(ctx, buf, need);
   if (rc) return rc;
   HH_HIP(ctx, hipMemcpyAsync(buf, src, n * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
   if ((rc = note_host_copy(ctx))) return rc;
@@ -158,9 +154,9 @@ int stage_host(hh_ctx* ctx, T*& buf, size_t& cap, size_t need, const T* src, siz
 // come back at the SAME address (hipFree + hipMalloc of a larger block), so the key is dropped with
 // the old block and the tables are uploaded again.
 [[maybe_unused]] inline int ensure_bk_scratch(hh_ctx* ctx, size_t need) {
-  const size_t before = ctx->bk_scratch_cap;
-  const int rc = ensure(ctx, ctx->bk_scratch, ctx->bk_scratch_cap, need);
-  if (ctx->bk_scratch_cap != before) ctx->bk_table_key = hh::BkTableKey{};
+  const size_t before = ctx->bk_scratch.cap;
+  const int rc = ensure(ctx, ctx->bk_scratch, need);
+  if (ctx->bk_scratch.cap != before) ctx->bk_table_key = hh::BkTableKey{};
   return rc;
 }
 

@@ -6,10 +6,10 @@
 #include <stdint.h>
 
 #include "../../include/hedgehog_mc.h"
+#include "hh_layout.h"
 
 namespace hh {
 
-constexpr int kTile = HH_TILE_PATHS;  // paths per tile == paths per workgroup
 constexpr int kRecStride = HH_ACC_LEN;
 // internal record slots of the simulation / basket kernels (never part of the public vector)
 // what every word of the self-reducing launches' record buffer holds between launches (hh_sim.h, finish_records):
@@ -125,7 +125,6 @@ inline uint32_t basket_chunks(uint64_t n_paths) {
   return (uint32_t)((n_paths + kBasketChunk - 1) / kBasketChunk);
 }
 
-inline uint32_t tiles_for(uint64_t n_paths) { return (uint32_t)((n_paths + kTile - 1) / kTile); }
 // The exact-law kernels (one normal, one exp per trajectory — no time loop to amortise a workgroup's reduction
 // over) give a lane ONE pair of trajectories in a small ensemble and kExactPairs / kExactPairsHuge pairs in a
 // large / huge one: a workgroup of 256 lanes then leaves ONE record per 512 / 4096 / 32768 trajectories, the
@@ -185,9 +184,8 @@ int launch_bk(const hh_model& m, const hh_config& c, const DevicePtrs& p, hipStr
 int launch_bk_grid(const hh_model& m, const hh_config& c, const DevicePtrs& p, hipStream_t s,
                    double* spot_rows, double* var_rows, uint32_t k0, uint32_t n_dates, bool upload_tables);
 // dates per chain for a grid of n_steps dates: all of them unless the pairs' term cache would pass its budget
-uint32_t bk_grid_dates_per_chain(uint64_t n_paths, uint32_t n_steps, int term_cache);
+uint32_t bk_grid_dates_per_chain(uint64_t n_paths, uint32_t n_steps);
 size_t bk_grid_sort_bytes(uint64_t n_chain);
-constexpr int kBkTermCacheDefault = 256;
 size_t bk_scratch_bytes(uint64_t n_paths, int term_cache = 0);
 // where the last chain over n_paths trajectories left, per trajectory, its decision word (BkDecision bits:
 // secant evaluations | branch << 8 | bisection iterations << 16 | long-series bit 31) and its series length
@@ -255,7 +253,7 @@ int launch_euler_grid(const hh_model& m, const hh_config& c, const uint64_t* see
 // form: kLsmFormPersistent = the whole backward induction in ONE launch when the ensemble fits the
 // chip (else it falls back by itself), kLsmFormPerDate = one launch per exercise date.  *form_used
 // says which was enqueued; after a persistent launch the caller synchronises and reads the word at
-// lsm_persistent_status(scratch): non-zero = a workgroup gave up waiting (the grid was not
+// lsm_persistent_status(scratch, its layout): non-zero = a workgroup gave up waiting (the grid was not
 // co-resident) and nothing was written — run the per-date form instead.  Both forms give
 // bit-identical results.
 enum { kLsmFormPerDate = 0, kLsmFormPersistent = 1, kLsmFormAuto = 2 };  // auto: persistent above 2^18 trajectories
@@ -263,8 +261,7 @@ int launch_lsm(const double* grid, uint64_t ntot, uint32_t n_steps, double strik
                double step_discount, int degree, int32_t* tau, double* val, double* scratch,
                double* records, hipStream_t s, int form, int* form_used,
                unsigned long long spin_ticks = 100000000ull /* 1 s of the 100 MHz constant clock */);
-const unsigned int* lsm_persistent_status(const double* scratch);
-constexpr int kLsmStampSlotsApi = 8;  // doubles behind the two row counters at the end of the scratch
+const unsigned int* lsm_persistent_status(const double* scratch, const LsmScratch& at);
 int launch_wiener_fill(int dynamics, double rho, double sqrt_dt, uint32_t n_steps, uint64_t n_paths,
                        const uint64_t* seeds_dev, double* dst, hipStream_t s);
 int launch_replay_pack(int ncomp, uint64_t n_paths, uint32_t n_steps, const double* src_dev,

@@ -56,26 +56,11 @@ namespace hh {
 namespace {
 
 constexpr int kLsmFinalChunk = 1024;  // paths per workgroup of the final Σ, Σ² kernel (16-double records)
-constexpr int kLsmWg = 512;     // threads per workgroup of every kernel that forms canonical sums
-constexpr int kLsmQSmall = 1024 / kLsmWg, kLsmQLarge = 8192 / kLsmWg;  // trajectories per lane
+// kLsmWg (threads per workgroup of every kernel that forms canonical sums), the chunk rule lsm_q() / lsm_nch(), the
+// record ring and the scratch layout they size: hh_layout.h
 constexpr int kLsmWaves = kLsmWg / 64;
 constexpr int kLsmMaxDeg = 8;
-constexpr uint64_t kLsmQ1Max = 1ull << 18;  // up to here chunks of 1024 trajectories, beyond it 8192
-constexpr int kLsmMaxResident = 256;        // chunks the persistent form handles (one per workgroup)
-constexpr int kLsmRing = 16;                // record slots of the persistent all-gather (2 suffice for
-                                            // correctness; 16 dates between two uses of a slot make it all
-                                            // but certain that no L2 still holds the slot's previous lines)
 
-// Trajectories per lane: the smallest of 2, 4, 8, 16 (x 512 lanes = chunks of 1024 … 8192) with which
-// the ensemble fits 256 chunks — one workgroup per CU in the persistent form, whose date is bounded by
-// what ONE workgroup has to do (a 10^6-trajectory induction in chunks of 8192 would keep half the chip
-// idle and every busy CU twice as long).  The chunk size is part of the summation tree: both forms of
-// the induction (and every phase of the sharded one) use lsm_q() of the same ensemble.
-inline int lsm_q(uint64_t ntot) {
-  int q = kLsmQSmall;
-  for (uint64_t cap = kLsmQ1Max; q < kLsmQLarge && ntot > cap; cap <<= 1) q <<= 1;
-  return q;
-}
 // f(std::integral_constant<int, Q>) for the Q that lsm_q() returned
 template <class F>
 inline auto with_q(int q, F&& f) {
@@ -84,10 +69,6 @@ inline auto with_q(int q, F&& f) {
   if (q == 2 * kLsmQSmall) return f(std::integral_constant<int, 2 * kLsmQSmall>{});
   if (q == 4 * kLsmQSmall) return f(std::integral_constant<int, 4 * kLsmQSmall>{});
   return f(std::integral_constant<int, kLsmQLarge>{});
-}
-inline uint32_t lsm_nch(uint64_t ntot) {
-  const uint64_t per = (uint64_t)kLsmWg * lsm_q(ntot);
-  return (uint32_t)((ntot + per - 1) / per);
 }
 
 // ---- full path grid -----------------------------------------------------------------------
@@ -478,10 +459,6 @@ __device__ void solve_normal_equations_wave(const double* B, double p0, const do
     for (int c = 0; c < N; ++c) coef[c] = cf[c];
   }
 }
-
-// slots behind the row counters that hh_lsm_debug_read returns (the phase stamps of a diagnostic build that has
-// been removed; profiles/ has its measurements).  Nothing writes them now: their contents are unspecified.
-constexpr int kLsmStampSlots = 8;
 
 // coefficients of row t into LDS (coef[D+1], *have_fit) from the global sums B[0..D], P[0] = n_itm,
 // P[1..2D] = Pm1[0..]; all threads call it
@@ -1176,38 +1153,24 @@ __global__ __launch_bounds__(kLsmWg, (Q * kLsmWg > 1024 ? 2 : 4)) void lsm_persi
 
 // ---- launch sequences ---------------------------------------------------------------------------
 
-// where the pieces of the caller's scratch buffer are (lsm_scratch_doubles() doubles)
+// where the pieces of the caller's scratch buffer are: its base + the offsets of LsmScratch (hh_layout.h)
 struct LsmLayout {
-  double* rec_stats;  // [rows][nch][3]
-  RowStat* rs;        // [rows]
-  double* rec_pow;    // [rows][nch][2D+1]
-  double* P;          // [rows][2D+1]
-  double* recB;       // [rows][nch][D+1]
-  double* disc_pow;   // [rows]
-  double* sync;       // persistent form: status word, then the record ring (both zeroed per launch)
-  double* counters;   // [2]
-  uint32_t rows, nch;
-  int q;
+  LsmScratch at;
+  double *sync, *ring, *rec_stats, *rec_pow, *P, *recB, *disc_pow, *counters;
+  RowStat* rs;
 };
-
-constexpr size_t kSyncDoubles = 2;                                           // uint32 status word, padded to 16 bytes
-constexpr size_t kRingDoubles = (size_t)kLsmRing * kLsmMaxResident * 32 * 2; // records of 32 granules of 16 bytes
+static_assert(sizeof(RowStat) == 3 * sizeof(double), "LsmScratch::rowstat counts 3 doubles per row");
 
 LsmLayout lsm_layout(double* scratch, uint64_t ntot, uint32_t n_steps, int degree) {
-  const size_t rows = (size_t)n_steps + 1, ch = lsm_nch(ntot), nv = 2 * (size_t)degree + 1;
-  LsmLayout L{};
-  L.sync = scratch;  // at the allocation's start: the per-launch memset covers exactly this block
-  L.rec_stats = L.sync + kSyncDoubles + kRingDoubles;
-  L.rs = reinterpret_cast<RowStat*>(L.rec_stats + rows * ch * 3);
-  L.rec_pow = reinterpret_cast<double*>(L.rs) + rows * 3;  // RowStat = 3 doubles
-  L.P = L.rec_pow + rows * ch * nv;
-  L.recB = L.P + rows * nv;
-  L.disc_pow = L.recB + rows * ch * (degree + 1);
-  L.counters = L.disc_pow + rows;
-  L.rows = (uint32_t)rows;
-  L.nch = (uint32_t)ch;
-  L.q = lsm_q(ntot);
-  return L;
+  const LsmScratch at(ntot, n_steps, degree);
+  return LsmLayout{at, scratch + at.sync, scratch + at.ring, scratch + at.rec_stats, scratch + at.rec_pow,
+                   scratch + at.P, scratch + at.recB, scratch + at.disc_pow, scratch + at.counters,
+                   reinterpret_cast<RowStat*>(scratch + at.rowstat)};
+}
+
+// the row counters and the stamp slots behind them start an induction from zero
+hipError_t zero_counters(const LsmLayout& L, hipStream_t s) {
+  return hipMemsetAsync(L.counters, 0, (L.at.total - L.at.counters) * sizeof(double), s);
 }
 
 LsmStepArgs lsm_step_args(const LsmLayout& L, const double* grid, uint64_t ntot, uint32_t n_steps,
@@ -1216,35 +1179,35 @@ LsmStepArgs lsm_step_args(const LsmLayout& L, const double* grid, uint64_t ntot,
   a.grid = grid; a.ntot = ntot; a.strike = strike; a.cp = cp; a.ln_disc = log(step_discount);
   a.n_steps = n_steps; a.tau = tau; a.val = val; a.rs = L.rs; a.P = L.P; a.recB = L.recB;
   a.disc_pow = L.disc_pow; a.counters = L.counters;
-  a.n_chunks = L.nch;
+  a.n_chunks = L.at.nch;
   return a;
 }
 
 void launch_stats(const LsmLayout& L, const LsmStepArgs& a, hipStream_t s) {
-  const dim3 g(L.nch, L.rows), b(kLsmWg);
-  with_q(L.q, [&](auto qc) {
-    hipLaunchKernelGGL(lsm_stats_kernel<decltype(qc)::value>, g, b, 0, s, a.grid, a.ntot, a.strike, a.cp, L.nch, L.rec_stats);
+  const dim3 g(L.at.nch, L.at.rows), b(kLsmWg);
+  with_q(L.at.q, [&](auto qc) {
+    hipLaunchKernelGGL(lsm_stats_kernel<decltype(qc)::value>, g, b, 0, s, a.grid, a.ntot, a.strike, a.cp, L.at.nch, L.rec_stats);
   });
 }
 
 template <int D>
 void launch_pow(const LsmLayout& L, const LsmStepArgs& a, hipStream_t s) {
-  const dim3 g(L.nch, L.rows), b(kLsmWg);
-  with_q(L.q, [&](auto qc) {
-    hipLaunchKernelGGL((lsm_pow_kernel<D, decltype(qc)::value>), g, b, 0, s, a.grid, a.ntot, a.strike, a.cp, L.nch, a.rs, L.rec_pow);
+  const dim3 g(L.at.nch, L.at.rows), b(kLsmWg);
+  with_q(L.at.q, [&](auto qc) {
+    hipLaunchKernelGGL((lsm_pow_kernel<D, decltype(qc)::value>), g, b, 0, s, a.grid, a.ntot, a.strike, a.cp, L.at.nch, a.rs, L.rec_pow);
   });
 }
 
 template <int D>
 void launch_init(const LsmLayout& L, const LsmStepArgs& a, hipStream_t s) {
-  with_q(L.q, [&](auto qc) {
+  with_q(L.at.q, [&](auto qc) {
     hipLaunchKernelGGL((lsm_init_kernel<D, decltype(qc)::value>), dim3(a.n_chunks), dim3(kLsmWg), 0, s, a);
   });
 }
 
 template <int D>
 void launch_step(const LsmLayout& L, const LsmStepArgs& a, uint32_t t, hipStream_t s) {
-  with_q(L.q, [&](auto qc) {
+  with_q(L.at.q, [&](auto qc) {
     hipLaunchKernelGGL((lsm_step_kernel<D, decltype(qc)::value>), dim3(a.n_chunks), dim3(kLsmWg), 0, s, a, t);
   });
 }
@@ -1253,10 +1216,10 @@ void launch_step(const LsmLayout& L, const LsmStepArgs& a, uint32_t t, hipStream
 template <int D>
 int run_lsm(const LsmLayout& L, const LsmStepArgs& a, hipStream_t s) {
   launch_stats(L, a, s);
-  hipLaunchKernelGGL(lsm_rowstat_kernel, dim3(L.rows), dim3(kLsmWg), 0, s, L.rec_stats, L.nch, L.rs);
+  hipLaunchKernelGGL(lsm_rowstat_kernel, dim3(L.at.rows), dim3(kLsmWg), 0, s, L.rec_stats, L.at.nch, L.rs);
   launch_pow<D>(L, a, s);
-  hipLaunchKernelGGL(lsm_sum_records_kernel<2 * D + 1>, dim3(L.rows), dim3(kLsmWg), 0, s, L.rec_pow,
-                     L.nch, L.P);
+  hipLaunchKernelGGL(lsm_sum_records_kernel<2 * D + 1>, dim3(L.at.rows), dim3(kLsmWg), 0, s, L.rec_pow,
+                     L.at.nch, L.P);
   launch_init<D>(L, a, s);
   for (uint32_t t = a.n_steps - 1; t >= 1; --t)  // for i = nsteps:-1:2, t = i-1 (:112-113)
     launch_step<D>(L, a, t, s);
@@ -1301,21 +1264,21 @@ std::atomic<unsigned int> g_lsm_launches{0};  // numbers the persistent launches
 // runtime cannot guarantee that the grid is resident)
 template <int D>
 int run_lsm_persistent(const LsmLayout& L, const LsmStepArgs& s_args, hipStream_t s, unsigned long long spin_ticks) {
-  if (L.nch > (uint32_t)kLsmMaxResident) return 1;
+  if (L.at.nch > (uint32_t)kLsmMaxResident) return 1;
   LsmPersistArgs a{};
   a.grid = s_args.grid; a.ntot = s_args.ntot; a.strike = s_args.strike; a.cp = s_args.cp;
-  a.n_steps = s_args.n_steps; a.n_chunks = L.nch; a.tau = s_args.tau; a.val = s_args.val;
+  a.n_steps = s_args.n_steps; a.n_chunks = L.at.nch; a.tau = s_args.tau; a.val = s_args.val;
   a.disc_pow = L.disc_pow; a.counters = L.counters; a.ln_disc = s_args.ln_disc;
   a.status = reinterpret_cast<unsigned int*>(L.sync);
-  a.rec = reinterpret_cast<unsigned long long*>(L.sync + kSyncDoubles);
+  a.rec = reinterpret_cast<unsigned long long*>(L.ring);
   a.spin_ticks = spin_ticks;  // default 1 s of the 100 MHz constant clock
   do a.nonce = ++g_lsm_launches; while (a.nonce == 0);
-  const bool fits = with_q(L.q, [&](auto qc) { return grid_fits(lsm_persistent_kernel<D, decltype(qc)::value>, L.nch); });
+  const bool fits = with_q(L.at.q, [&](auto qc) { return grid_fits(lsm_persistent_kernel<D, decltype(qc)::value>, L.at.nch); });
   if (!fits) return 1;
   // status word and the whole record ring (2 MiB): a granule of an earlier launch must not validate
-  hipError_t e = hipMemsetAsync(L.sync, 0, (kSyncDoubles + kRingDoubles) * sizeof(double), s);
+  hipError_t e = hipMemsetAsync(L.sync, 0, (L.at.rec_stats - L.at.sync) * sizeof(double), s);
   if (e != hipSuccess) return (int)e;
-  return with_q(L.q, [&](auto qc) { return launch_cooperative(lsm_persistent_kernel<D, decltype(qc)::value>, L.nch, a, s); });
+  return with_q(L.at.q, [&](auto qc) { return launch_cooperative(lsm_persistent_kernel<D, decltype(qc)::value>, L.at.nch, a, s); });
 }
 
 // one phase of the sharded induction (see hh_kernels.h); vec_in / vec_out are device vectors
@@ -1325,14 +1288,14 @@ int run_lsm_phase(const LsmLayout& L, LsmStepArgs a, int phase, uint32_t t, cons
   constexpr int N = D + 1, NV = 2 * D + 1;
   switch (phase) {
     case kLsmPhasePow:  // global row sums in -> row statistics; local power sums out
-      hipLaunchKernelGGL(lsm_rowstat_from_sums_kernel, dim3((L.rows + 255) / 256), dim3(256), 0, s,
-                         vec_in, L.rows, L.rs);
+      hipLaunchKernelGGL(lsm_rowstat_from_sums_kernel, dim3((L.at.rows + 255) / 256), dim3(256), 0, s,
+                         vec_in, L.at.rows, L.rs);
       launch_pow<D>(L, a, s);
-      hipLaunchKernelGGL(lsm_sum_records_kernel<NV>, dim3(L.rows), dim3(kLsmWg), 0, s, L.rec_pow,
-                         L.nch, vec_out);
+      hipLaunchKernelGGL(lsm_sum_records_kernel<NV>, dim3(L.at.rows), dim3(kLsmWg), 0, s, L.rec_pow,
+                         L.at.nch, vec_out);
       break;
     case kLsmPhaseInit: {  // global power sums in; stopping at expiry; local moment sums of row n-1 out
-      hipError_t e = hipMemcpyAsync(L.P, vec_in, (size_t)L.rows * NV * sizeof(double),
+      hipError_t e = hipMemcpyAsync(L.P, vec_in, (size_t)L.at.rows * NV * sizeof(double),
                                     hipMemcpyDeviceToDevice, s);
       if (e != hipSuccess) return (int)e;
       launch_init<D>(L, a, s);
@@ -1358,14 +1321,7 @@ int run_lsm_phase(const LsmLayout& L, LsmStepArgs a, int phase, uint32_t t, cons
 uint32_t lsm_chunks(uint64_t ntot) { return (uint32_t)((ntot + kLsmFinalChunk - 1) / kLsmFinalChunk); }
 
 // scratch sizes in doubles, for the caller (hh_api.hip) to allocate
-size_t lsm_scratch_doubles(uint64_t ntot, uint32_t n_steps, int degree) {
-  const size_t rows = (size_t)n_steps + 1, ch = lsm_nch(ntot);
-  const size_t nv = 2 * (size_t)degree + 1;
-  // sync | ring | rec_stats [rows][ch][3] | rowstat [rows][3] | rec_pow [rows][ch][nv] | P [rows][nv] |
-  // recB [rows][ch][degree+1] | disc_pow [rows] | counters [2] | phase stamps of a diagnostic build [8]
-  return kSyncDoubles + kRingDoubles + rows * ch * 3 + rows * 3 + rows * ch * nv + rows * nv +
-         rows * ch * (degree + 1) + rows + 2 + kLsmStampSlots;
-}
+size_t lsm_scratch_doubles(uint64_t ntot, uint32_t n_steps, int degree) { return LsmScratch(ntot, n_steps, degree).total; }
 
 int launch_gbm_grid(const uint64_t* seeds_dev, uint64_t n_paths, uint32_t n_steps, double S0,
                     double r, double sigma, double T, int anti, double* grid, hipStream_t s) {
@@ -1427,7 +1383,7 @@ int launch_euler_grid(const hh_model& m, const hh_config& c, const uint64_t* see
 
 // Backward induction on a device-resident grid.  `scratch` has lsm_scratch_doubles() doubles,
 // `records` lsm_chunks() x kRecStride; on return `records` holds the per-workgroup Σ, Σ² of the
-// discounted stopped values and scratch's last two doubles the regressed / skipped row counts.
+// discounted stopped values and scratch's counters (LsmScratch::counters) the regressed / skipped row counts.
 // form: kLsmFormPersistent enqueues the one-launch form when the ensemble fits it (*form_used tells;
 // the caller must then check lsm_persistent_status after synchronising) — kLsmFormPerDate never does.
 int launch_lsm(const double* grid, uint64_t ntot, uint32_t n_steps, double strike, double cp,
@@ -1442,7 +1398,7 @@ int launch_lsm(const double* grid, uint64_t ntot, uint32_t n_steps, double strik
   bool table_out = false;
   auto table = [&]() {
     if (!table_out)
-      hipLaunchKernelGGL(lsm_disc_kernel, dim3((L.rows + 255) / 256), b, 0, s, a.ln_disc, n_steps, L.disc_pow);
+      hipLaunchKernelGGL(lsm_disc_kernel, dim3((L.at.rows + 255) / 256), b, 0, s, a.ln_disc, n_steps, L.disc_pow);
     table_out = true;
   };
   int rc = 1;
@@ -1455,7 +1411,7 @@ int launch_lsm(const double* grid, uint64_t ntot, uint32_t n_steps, double strik
   }
   if (form_used) *form_used = rc == 0 ? kLsmFormPersistent : kLsmFormPerDate;
   if (rc == 1) {
-    const hipError_t e = hipMemsetAsync(L.counters, 0, (2 + kLsmStampSlots) * sizeof(double), s);
+    const hipError_t e = zero_counters(L, s);
     if (e != hipSuccess) return (int)e;
     table();
 #define HH_CALL(D) run_lsm<D>(L, a, s)
@@ -1469,8 +1425,8 @@ int launch_lsm(const double* grid, uint64_t ntot, uint32_t n_steps, double strik
 }
 
 // device address of the word the persistent form sets when a workgroup gave up waiting
-const unsigned int* lsm_persistent_status(const double* scratch) {
-  return reinterpret_cast<const unsigned int*>(scratch);
+const unsigned int* lsm_persistent_status(const double* scratch, const LsmScratch& at) {
+  return reinterpret_cast<const unsigned int*>(scratch + at.sync);
 }
 
 // Sharded induction, one phase per call (hh_kernels.h).  kLsmPhaseStats: local row sums
@@ -1485,12 +1441,12 @@ int launch_lsm_phase(int phase, uint32_t t, const double* grid, uint64_t ntot, u
   const LsmStepArgs a = lsm_step_args(L, grid, ntot, n_steps, strike, cp, step_discount, tau, val);
   const dim3 b(256);
   if (phase == kLsmPhaseStats) {
-    hipError_t e = hipMemsetAsync(L.counters, 0, (2 + kLsmStampSlots) * sizeof(double), s);
+    hipError_t e = zero_counters(L, s);
     if (e != hipSuccess) return (int)e;
     launch_stats(L, a, s);
-    hipLaunchKernelGGL(lsm_sum_records_kernel<3>, dim3(L.rows), dim3(kLsmWg), 0, s, L.rec_stats, L.nch,
+    hipLaunchKernelGGL(lsm_sum_records_kernel<3>, dim3(L.at.rows), dim3(kLsmWg), 0, s, L.rec_stats, L.at.nch,
                        vec_out);
-    hipLaunchKernelGGL(lsm_disc_kernel, dim3((L.rows + 255) / 256), b, 0, s, a.ln_disc, n_steps,
+    hipLaunchKernelGGL(lsm_disc_kernel, dim3((L.at.rows + 255) / 256), b, 0, s, a.ln_disc, n_steps,
                        L.disc_pow);
     return (int)hipGetLastError();
   }

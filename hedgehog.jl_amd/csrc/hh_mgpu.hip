@@ -789,7 +789,7 @@ static int cut_config(hh_mgpu* mg, const hh_config* cfg, bool want_terminal, Sha
     if (replay && !bk) c.replay = cfg->replay + a * per_path;  // a is a multiple of 256 for tile-major data
     HH_MHIP(mg, hipSetDevice(mg->devices[g]));
     if (replay && bk) {
-      int rc = ensure(x, x->replay, x->replay_cap, (size_t)3 * c.n_paths);
+      int rc = ensure(x, x->replay, (size_t)3 * c.n_paths);
       if (rc) return mfail(mg, rc, "%s", x->err);
       for (int k = 0; k < 3; ++k)
         HH_MHIP(mg, hipMemcpyAsync(x->replay + (size_t)k * c.n_paths, cfg->replay + (size_t)k * N + a,
@@ -801,8 +801,8 @@ static int cut_config(hh_mgpu* mg, const hh_config* cfg, bool want_terminal, Sha
       // kernel and the repack read from there); one normal per trajectory of the exact law likewise
       const bool pm = cfg->replay_layout == HH_REPLAY_PATH_MAJOR;
       const size_t n_el = (size_t)c.n_paths * per_path;
-      int rc = pm ? ensure(x, x->replay_src, x->replay_src_cap, n_el)
-                  : ensure(x, x->replay, x->replay_cap, (size_t)hh::tiles_for(c.n_paths) * hh::kTile);
+      int rc = pm ? ensure(x, x->replay_src, n_el)
+                  : ensure(x, x->replay, (size_t)hh::tiles_for(c.n_paths) * hh::kTile);
       if (rc) return mfail(mg, rc, "%s", x->err);
       double* dst = pm ? x->replay_src : x->replay;
       HH_MHIP(mg, hipMemcpyAsync(dst, c.replay, n_el * sizeof(double), hipMemcpyHostToDevice, x->stream));
@@ -810,7 +810,7 @@ static int cut_config(hh_mgpu* mg, const hh_config* cfg, bool want_terminal, Sha
       c.replay_on_device = 1;
     }
     if (want_terminal) {
-      int rc = ensure(x, x->terminal, x->terminal_cap, (size_t)c.n_paths * (c.antithetic ? 2 : 1));
+      int rc = ensure(x, x->terminal, (size_t)c.n_paths * (c.antithetic ? 2 : 1));
       if (rc) return mfail(mg, rc, "%s", x->err);
       sh.terminal[g] = x->terminal;
       c.terminal_on_device = 1;

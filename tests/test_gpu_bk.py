@@ -175,12 +175,23 @@ def test_bk_replay_of_the_callers_draws(hhlib, name, on_device):
     del dev
 
 
-def test_bk_sharding_is_invisible(hhlib):
+@pytest.mark.parametrize("n_a,n_b", [(300, 700), (16384, 256), (393216, 256)])
+def test_bk_sharding_is_invisible(hhlib, n_a, n_b):
+    """An ensemble in one solve and in two, bit for bit: the samples, and — read back after each solve for that
+    solve's own trajectory count — the decision words and series lengths, which lie behind the term cache in the
+    scratch buffer.  The cache has one column per lane of max(64, min(tiles, 1536)) workgroup slots: 64 tiles | 1
+    tile and 1536 tiles | 1 tile are the smallest ensembles on both sides of the two branches of that rule."""
     prm = PARAMS["h252"]
-    full = gpu_bk(hhlib, prm, 1000, 11)[1]
-    a = gpu_bk(hhlib, prm, 300, 11)[1]
-    b = gpu_bk(hhlib, prm, 700, 11, offset=300)[1]
+    full = gpu_bk(hhlib, prm, n_a + n_b, 11)[1]
+    dec, ln = gpu_decisions(hhlib, n_a + n_b)
+    a = gpu_bk(hhlib, prm, n_a, 11)[1]
+    dec_a, ln_a = gpu_decisions(hhlib, n_a)
+    b = gpu_bk(hhlib, prm, n_b, 11, offset=n_a)[1]
+    dec_b, ln_b = gpu_decisions(hhlib, n_b)
     np.testing.assert_array_equal(full, np.concatenate([a, b]))
+    np.testing.assert_array_equal(dec, np.concatenate([dec_a, dec_b]))
+    np.testing.assert_array_equal(ln, np.concatenate([ln_a, ln_b]))
+    assert ln.min() >= 1  # a CDF series has its first term at least: the words were read where the chain wrote them
 
 
 @pytest.mark.parametrize("name,cm_bound", [("h252", 400.0), ("q2", 32.0), ("intended", 200.0)])
