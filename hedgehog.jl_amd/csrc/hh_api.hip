@@ -799,6 +799,10 @@ int hh_bk_decisions(hh_ctx* ctx, uint64_t n_paths, uint32_t* decisions, uint32_t
   return HH_OK;
 }
 
+// the quadrature cuts each of its 256 panels into at most hh::kCarrMadanMaxSubpanels (hh_fourier.hip)
+#define HH_CM_BOUND_MSG "%s: bound/alpha must be <= 196608 (1024 sub-panels of half-width 0.75 alpha per lane)"
+static_assert(hh::kCarrMadanMaxSubpanels * 192 == 196608, "HH_CM_BOUND_MSG names the limit");
+
 int hh_carr_madan(hh_ctx* ctx, const hh_model* m, int32_t dynamics, int32_t compat_sqrt_alpha,
                   double alpha, double bound, double* price_out) {
   if (!ctx) return HH_ERR_INVALID;
@@ -809,6 +813,7 @@ int hh_carr_madan(hh_ctx* ctx, const hh_model* m, int32_t dynamics, int32_t comp
   if (!(m->S0 > 0.0) || !(m->strike > 0.0) || !(m->T > 0.0) || !(alpha > 0.0) || !(bound > 0.0) ||
       (m->cp != 1.0 && m->cp != -1.0) || (dynamics == HH_HESTON && m->sigma == 0.0))
     return fail(ctx, HH_ERR_INVALID, "hh_carr_madan: bad scalars");
+  if (!hh::carr_madan_subpanels(alpha, bound)) return fail(ctx, HH_ERR_INVALID, HH_CM_BOUND_MSG, "hh_carr_madan");
   HH_HIP(ctx, hipSetDevice(ctx->device));
   HH_HIP(ctx, hh::launch_carr_madan(*m, dynamics, compat_sqrt_alpha, alpha, bound, ctx->accum,
                                     ctx->stream));
@@ -857,6 +862,8 @@ int hh_carr_madan_basket(hh_ctx* ctx, const hh_model* m, int32_t dynamics, int32
     return fail(ctx, HH_ERR_INVALID, "hh_carr_madan_basket: 1 .. 2^20 payoffs per call");
   if (!(m->S0 > 0.0) || !(alpha > 0.0) || !(bound > 0.0) || (dynamics == HH_HESTON && m->sigma == 0.0))
     return fail(ctx, HH_ERR_INVALID, "hh_carr_madan_basket: bad scalars");
+  if (!hh::carr_madan_subpanels(alpha, bound))
+    return fail(ctx, HH_ERR_INVALID, HH_CM_BOUND_MSG, "hh_carr_madan_basket");
   const size_t n = n_payoffs;
   std::vector<double> host(5 * n);  // log K | T | r_drift | discount | (out)
   const int rc = cm_upload_payoffs(ctx, "hh_carr_madan_basket", strikes, cps, Ts, r_drifts, discounts, n, n, host);
@@ -889,6 +896,8 @@ int hh_carr_madan_basket_grad(hh_ctx* ctx, const hh_model* m, int32_t dynamics,
   if (!(m->S0 > 0.0) || !(alpha > 0.0) || !(bound > 0.0) ||
       (dynamics == HH_HESTON && (m->sigma == 0.0 || m->theta == 0.0)))
     return fail(ctx, HH_ERR_INVALID, "hh_carr_madan_basket_grad: bad scalars (Heston: sigma, theta != 0)");
+  if (!hh::carr_madan_subpanels(alpha, bound))
+    return fail(ctx, HH_ERR_INVALID, HH_CM_BOUND_MSG, "hh_carr_madan_basket_grad");
   const size_t n = n_payoffs;
   std::vector<double> host(4 * n + HH_CM_GRAD_LEN * n);  // log K | T | r_drift | discount | out [n][8]
   const int rc = cm_upload_payoffs(ctx, "hh_carr_madan_basket_grad", strikes, cps, Ts, r_drifts, discounts, n,

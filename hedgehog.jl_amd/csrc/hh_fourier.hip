@@ -6,8 +6,21 @@
 // :88-92, Heston log-price CF src/distributions/heston.jl:307-319, Normal-law CF
 // src/distributions/sample_from_cf.jl:14-16, parity_transform src/payoffs/payoffs.jl:172-193.
 // The reference integrates over (-bound, bound) with adaptive Gauss–Kronrod (QuadGK, third party);
-// here 256 panels x 16-point Gauss–Legendre, one panel per lane — the integrand is entire and the
-// panels are 2·bound/256 wide, so the rule is exact to rounding for the bounds the reference uses.
+// here 256 panels, one per lane, each cut into m equal sub-panels of 16-point Gauss–Legendre.
+//
+// The integrand is NOT entire: the damped transform has a pole at v = iα (the zero of α² + α − v² +
+// iv(2α+1); the other one is at v = −i(α+1)), with residue ∝ ϕ(−i)·D = S0 whatever the model, strike and
+// expiry.  A Gauss–Legendre panel of half-width h next to v = 0 therefore misses by about S0·f(h/α):
+// rounding level (≤ 5e-14 at S0 = 100) for h/α ≤ 0.78, 2.4e-13 at 1.04, 6.2e-11 at 1.56, 4.5e-6 at 3.9
+// (tests/test_carr_madan_exact_host.py pins these against the 40-digit integral).  So
+//   m = carr_madan_subpanels(α, bound) = the smallest integer with bound/(256·m) ≤ 0.75·α,
+// which is 1 — the plain 256-panel rule, bit for bit — for every setting the reference itself uses
+// (α = 1, bound 16 and 32), and the entry points refuse bound/α > 192·kCarrMadanMaxSubpanels.
+//
+// Stated limit (not handled): for Heston the strip of analyticity of ϕ must contain Im u = −(α+1) for
+// the expiry at hand; κ − ρσ(α+1) > 0 and (κ − ρσ(α+1))² ≥ σ²·α(α+1) make the (α+1)-th moment finite
+// for every T.  Outside it the transform's own singularities approach the real line and no fixed rule
+// converges; the kernels do not detect this.
 #include <cmath>
 
 #include "hh_kernels.h"
@@ -57,6 +70,7 @@ struct FourierArgs {
   // log K, T, r_drift, discount; NULL = the fields above
   const double* per_payoff;
   uint32_t n_payoffs, compat_sqrt_alpha;
+  uint32_t m_sub;   // sub-panels per lane (carr_madan_subpanels)
   double sigma_ln;  // lognormal volatility (law_mu / law_sd are formed per payoff)
 };
 
@@ -100,6 +114,15 @@ __constant__ double kGLw[8] = {0.1894506104550684962853967, 0.182603415044923588
                                0.1691565193950025381893121, 0.1495959888165767320815017,
                                0.1246289712555338720524763, 0.0951585116824927848099251,
                                0.0622535239386478928628438, 0.0271524594117540948517806};
+
+// Centre of sub-panel j of this lane's panel (centre `mid`, m sub-panels of half-width hsub).  m = 1: the panel itself,
+// with `mid` as the plain rule forms it, −bound + (lane + ½)·w — bit for bit.  m > 1: an exact integer times hsub.
+// `mid` is rounded at the size of the bound, 1e-13 at bound 1000; next to v = 0, where the integrand is S0/(2πα) high and
+// α wide, panels displaced by that much against each other cost (bound/α)·2e-17·S0 — 5e-12 at α = 0.1, bound 1000.
+__device__ __forceinline__ double subpanel_centre(double mid, double hsub, uint32_t m, uint32_t j) {
+  if (m == 1) return mid;
+  return (double)(2 * (int)(threadIdx.x * m + j) + 1 - 256 * (int)m) * hsub;
+}
 
 // ---- gradient of the price: complex numbers carrying P complex partials --------------------------
 // The reference differentiates its calibration objective with ForwardDiff, i.e. pushes Duals through
@@ -260,10 +283,15 @@ __global__ __launch_bounds__(256) void carr_madan_grad_kernel(const FourierArgs 
 #pragma unroll
     for (int i = 0; i < 7; ++i) acc[1 + i] += (base * dl[i]).re;
   };
+  const double hsub = half / (double)a.m_sub;
 #pragma unroll 1
-  for (int k = 0; k < 8; ++k) {
-    node(mid - half * kGLx[k], kGLw[k] * half);
-    node(mid + half * kGLx[k], kGLw[k] * half);
+  for (uint32_t j = 0; j < a.m_sub; ++j) {
+    const double msub = subpanel_centre(mid, hsub, a.m_sub, j);
+#pragma unroll 1
+    for (int k = 0; k < 8; ++k) {
+      node(msub - hsub * kGLx[k], kGLw[k] * hsub);
+      node(msub + hsub * kGLx[k], kGLw[k] * hsub);
+    }
   }
   __shared__ double sm[4][kGradVals];
 #pragma unroll
@@ -293,11 +321,17 @@ __global__ __launch_bounds__(256) void carr_madan_kernel(const FourierArgs a0) {
   }
   const double w = 2.0 * a.bound / 256.0;  // panel width
   const double mid = -a.bound + (threadIdx.x + 0.5) * w, half = 0.5 * w;
+  const double hsub = half / (double)a.m_sub;
   double s = 0.0;
 #pragma unroll 1
-  for (int k = 0; k < 8; ++k)
-    s += kGLw[k] * (integrand(a, mid - half * kGLx[k]) + integrand(a, mid + half * kGLx[k]));
-  s *= half;
+  for (uint32_t j = 0; j < a.m_sub; ++j) {
+    const double msub = subpanel_centre(mid, hsub, a.m_sub, j);
+    double sj = 0.0;
+#pragma unroll 1
+    for (int k = 0; k < 8; ++k)
+      sj += kGLw[k] * (integrand(a, msub - hsub * kGLx[k]) + integrand(a, msub + hsub * kGLx[k]));
+    s += sj * hsub;
+  }
   for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
   __shared__ double sm[4];
   if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = s;
@@ -307,6 +341,20 @@ __global__ __launch_bounds__(256) void carr_madan_kernel(const FourierArgs a0) {
 
 }  // namespace
 
+uint32_t carr_madan_subpanels(double alpha, double bound) {
+  const double m = ceil(bound / (256.0 * 0.75 * alpha));
+  if (!(m <= (double)kCarrMadanMaxSubpanels)) return 0;
+  return m < 1.0 ? 1u : (uint32_t)m;
+}
+
+// The rule of a launch: α, the bound and the sub-panels they ask for.  Refused where carr_madan_subpanels refuses: a
+// rule of no sub-panels would write 0.0 as the price.
+static int set_rule(FourierArgs& a, double alpha, double bound) {
+  a.alpha = alpha; a.bound = bound;
+  a.m_sub = carr_madan_subpanels(alpha, bound);
+  return a.m_sub ? (int)hipSuccess : (int)hipErrorInvalidValue;
+}
+
 int launch_carr_madan_basket(const hh_model& m, int dynamics, int compat_sqrt_alpha, double alpha,
                              double bound, const double* per_payoff_dev, uint32_t n_payoffs,
                              double* out_dev, hipStream_t s) {
@@ -315,11 +363,11 @@ int launch_carr_madan_basket(const hh_model& m, int dynamics, int compat_sqrt_al
   a.logS0 = log(m.S0); a.V0 = m.V0; a.kappa = m.kappa; a.theta = m.theta; a.sigma = m.sigma;
   a.rho = m.rho;
   a.sigma_ln = m.sigma;
-  a.alpha = alpha; a.bound = bound;
   a.out = out_dev;
   a.per_payoff = per_payoff_dev;
   a.n_payoffs = n_payoffs;
   a.compat_sqrt_alpha = (uint32_t)(compat_sqrt_alpha != 0);
+  if (const int rc = set_rule(a, alpha, bound)) return rc;
   hipLaunchKernelGGL(carr_madan_kernel, dim3(n_payoffs), dim3(256), 0, s, a);
   return (int)hipGetLastError();
 }
@@ -332,11 +380,11 @@ int launch_carr_madan_grad(const hh_model& m, int dynamics, int compat_sqrt_alph
   a.logS0 = log(m.S0); a.V0 = m.V0; a.kappa = m.kappa; a.theta = m.theta; a.sigma = m.sigma;
   a.rho = m.rho;
   a.sigma_ln = m.sigma;
-  a.alpha = alpha; a.bound = bound;
   a.out = out_dev;
   a.per_payoff = per_payoff_dev;
   a.n_payoffs = n_payoffs;
   a.compat_sqrt_alpha = (uint32_t)(compat_sqrt_alpha != 0);
+  if (const int rc = set_rule(a, alpha, bound)) return rc;
   hipLaunchKernelGGL(carr_madan_grad_kernel, dim3(n_payoffs), dim3(256), 0, s, a);
   return (int)hipGetLastError();
 }
@@ -350,8 +398,9 @@ int launch_carr_madan(const hh_model& m, int dynamics, int compat_sqrt_alpha, do
   const double sqT = sqrt(m.T), tmul = compat_sqrt_alpha ? sqT : m.T;
   a.law_mu = a.logS0 + (m.r_drift - 0.5 * m.sigma * m.sigma) * tmul;  // montecarlo.jl:302
   a.law_sd = m.sigma * sqT;
-  a.alpha = alpha; a.bound = bound; a.logK = log(m.strike); a.discount = m.discount;
+  a.logK = log(m.strike); a.discount = m.discount;
   a.out = out_dev;
+  if (const int rc = set_rule(a, alpha, bound)) return rc;
   hipLaunchKernelGGL(carr_madan_kernel, dim3(1), dim3(256), 0, s, a);
   return (int)hipGetLastError();
 }

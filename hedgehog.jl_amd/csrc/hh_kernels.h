@@ -209,6 +209,11 @@ int count_active_partials(const hh_model& m, const hh_config& c);
 int launch_basket_payoffs(const BasketArgs& b, uint32_t n_payoffs, uint32_t n_active_partials,
                           hipStream_t s);
 // Carr–Madan on the device (hh_fourier.hip)
+// Sub-panels per lane: the smallest m with bound/(256·m) <= 0.75·alpha, which keeps the pole of the damped
+// transform at v = i·alpha far enough from every Gauss–Legendre panel for the rule to be exact to rounding.
+// 0 = more than kCarrMadanMaxSubpanels would be needed (bound/alpha > 196608): the entry points refuse it.
+constexpr uint32_t kCarrMadanMaxSubpanels = 1024;
+uint32_t carr_madan_subpanels(double alpha, double bound);
 int launch_carr_madan(const hh_model& m, int dynamics, int compat_sqrt_alpha, double alpha,
                       double bound, double* out_dev, hipStream_t s);
 // n_payoffs Carr–Madan integrals in one launch (one workgroup each); per_payoff_dev = [4][n_payoffs]:

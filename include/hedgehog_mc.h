@@ -439,6 +439,11 @@ int hh_mc_solve_basket(hh_ctx* ctx, const hh_model* model, const hh_config* cfg,
  * value the reference's MC tests compare against; model->r_drift = zero_rate(rate, expiry),
  * model->T = yearfrac(rate.reference_date, expiry), model->discount = df(rate, expiry).
  * alpha = damping factor, bound = integration bound (CarrMadan(α, bound, dynamics)).
+ * The quadrature is fixed: 256 panels over (-bound, bound), each cut into the fewest equal sub-panels of
+ * half-width <= 0.75 alpha (one for alpha = 1, bound <= 192), 16-point Gauss–Legendre on each; that keeps the
+ * transform's pole at v = i alpha resolved to rounding.  bound/alpha > 196608 (more than 1024 sub-panels) is
+ * HH_ERR_INVALID, for all three entry points.  Heston: the (alpha+1)-th moment of S_T must be finite (for every T:
+ * kappa - rho sigma (alpha+1) > 0 and its square >= sigma^2 alpha (alpha+1)); this is not checked.
  */
 int hh_carr_madan(hh_ctx* ctx, const hh_model* model, int32_t dynamics, int32_t compat_sqrt_alpha,
                   double alpha, double bound, double* price_out);

@@ -18,6 +18,7 @@ EULER, EXACT, BK = _ffi.HH_EULER_MARUYAMA, _ffi.HH_EXACT_LAW, _ffi.HH_BROADIE_KA
 SEEDS = np.arange(1, 11, dtype=np.uint64)
 LSM_RANGE = "LSM: n_paths, n_steps >= 1, 1 <= degree <= 8"
 LSM_PAIR = "LSM needs LognormalDynamics + BlackScholesExact or HestonDynamics + HestonBroadieKaya paths"
+CM_BOUND = "%s: bound/alpha must be <= 196608 (1024 sub-panels of half-width 0.75 alpha per lane)"
 NULL = None
 
 
@@ -109,17 +110,22 @@ def rows():
     add("mc_solve_basket.pair", lambda e: e.lib.hh_mc_solve_basket(e.h, ref(m_()), ref(cfg(HEST, EXACT, steps=1)),
                                                                    k.ctypes.data, s.ctypes.data, 2, e.res, NULL),
         UNS, "no simulation method for dynamics 1 with strategy 1")
+    # Carr–Madan: more than 1024 sub-panels per lane would be needed (bound/alpha = 196608 itself is accepted)
+    add("hh_carr_madan.bound_over_alpha",
+        lambda e: e.lib.hh_carr_madan(e.h, ref(m_()), HEST, 0, 0.5, 98304.5, e.host.ctypes.data_as(C.POINTER(C.c_double))),
+        INV, CM_BOUND % "hh_carr_madan")
     # Carr–Madan baskets
     for fn, grad in (("hh_carr_madan_basket", False), ("hh_carr_madan_basket_grad", True)):
-        def call(e, fn=fn, grad=grad, model=True, dyn=HEST, alpha=1.5, **kw):
+        def call(e, fn=fn, grad=grad, model=True, dyn=HEST, alpha=1.5, bound=1000.0, **kw):
             g = [e.host.ctypes.data] if grad else []
-            return getattr(e.lib, fn)(e.h, ref(m_()) if model else NULL, dyn, 0, alpha, 1000.0, *cm_args(e, **kw),
+            return getattr(e.lib, fn)(e.h, ref(m_()) if model else NULL, dyn, 0, alpha, bound, *cm_args(e, **kw),
                                       e.host.ctypes.data, *g)
         add(f"{fn}.null", lambda e, call=call: call(e, model=False), INV, f"{fn}: NULL argument")
         add(f"{fn}.dynamics", lambda e, call=call: call(e, dyn=5), INV, "unknown dynamics 5")
         add(f"{fn}.n_payoffs", lambda e, call=call: call(e, n=0), INV, f"{fn}: 1 .. 2^20 payoffs per call")
         add(f"{fn}.scalars", lambda e, call=call: call(e, alpha=0.0), INV,
             f"{fn}: bad scalars" + (" (Heston: sigma, theta != 0)" if grad else ""))
+        add(f"{fn}.bound_over_alpha", lambda e, call=call: call(e, alpha=0.5, bound=98304.5), INV, CM_BOUND % fn)
         add(f"{fn}.payoff_strike", lambda e, call=call: call(e, strikes=(90.0, 100.0, -1.0)), INV,
             f"{fn}: payoff 2: strike, T, discount > 0, cp = +-1")
         add(f"{fn}.payoff_cp", lambda e, call=call: call(e, cps=(1.0, 0.0, 1.0)), INV,

@@ -14,14 +14,17 @@ def heston_prob(params, r, ref, expiry, K=100.0, cp=None):
     return hh.PricingProblem(payoff, hh.HestonInputs(ref, r, 100.0, *params))
 
 
-@pytest.mark.parametrize("params,r,ref,expiry,bound,target", [
+TARGETS = [
     ((0.04, 2.0, 0.04, 0.3, -0.7), 0.03, hh.Date(2020, 1, 1), hh.Date(2021, 1, 1), 32.0,
      9.257069529912402),                                   # montecarlo_heston.jl:13-49
     ((0.04, 2.0, 0.04, 0.3, -0.7), 0.03, hh.Date(2021, 1, 1), hh.Date(2022, 1, 1), 400.0,
      9.242521073959068),                                   # H252
     ((1.5, 0.04, 0.3, -0.6, 0.04), 0.05, hh.Date(2025, 1, 1), hh.Date(2025, 12, 31), 32.0,
      46.31412390823014),                                   # montecarlo_heston.jl:161-170 as run (Q2)
-])
+]
+
+
+@pytest.mark.parametrize("params,r,ref,expiry,bound,target", TARGETS)
 def test_carr_madan_heston_targets(params, r, ref, expiry, bound, target):
     prob = heston_prob(params, r, ref, expiry)
     price = hh.solve(prob, hh.CarrMadan(1.0, bound, hh.HestonDynamics())).price
@@ -33,6 +36,40 @@ def test_carr_madan_heston_targets(params, r, ref, expiry, bound, target):
     put = hh.solve(heston_prob(params, r, ref, expiry, cp=hh.Put()),
                    hh.CarrMadan(1.0, bound, hh.HestonDynamics())).price
     assert put == pytest.approx(price - 100.0 + 100.0 * np.exp(-r * T), rel=1e-12)
+
+
+# TARGETS[0] (α = 1, bound 32: one sub-panel per lane) as the library returned it on an MI355X BEFORE the panels
+# were cut into sub-panels (carr_madan_subpanels): the call through `solve`, through hh_carr_madan_basket, and from
+# hh_carr_madan_basket_grad the price and its partials along S0, V0, κ, θ, σ, ρ, r_drift and the discount factor.
+PLAIN_RULE_FIRST_TARGET = dict(
+    solve="0x1.2839e9e0f8b2fp+3",
+    basket="0x1.2839e9e0f8b2fp+3",
+    grad=["0x1.2839e9e0f8b27p+3", "0x1.4fbc60344db94p-1", "0x1.45839eca422a1p+5",
+          "0x1.5738dcfaba095p-4", "0x1.b96d848734801p+5", "-0x1.441d0484b5ffep+0",
+          "0x1.d0613f2731828p-6", "0x1.07032228f961cp+6", "0x1.3145d2b65123fp+3"],
+)
+
+
+def first_target_on_the_device():
+    params, r, ref, expiry, bound, _ = TARGETS[0]
+    from hedgehog_jl_amd import _ffi
+    T = hh.yearfrac(ref, expiry)
+    V0, kappa, theta, sigma, rho = params
+    kw = dict(S0=100.0, V0=V0, kappa=kappa, theta=theta, sigma=sigma, rho=rho)
+    args = (hh.get_context(0), kw, _ffi.HH_HESTON, [100.0], [1.0], [T], [r])
+    solve = hh.solve(heston_prob(params, r, ref, expiry), hh.CarrMadan(1.0, bound, hh.HestonDynamics())).price
+    basket = _cm_basket(*args, bound=bound)
+    gprice, grad = _cm_basket(*args, bound=bound, grad=True)
+    return dict(solve=float(solve).hex(), basket=float(basket[0]).hex(),
+                grad=[float(x).hex() for x in (gprice[0], *grad[0])])
+
+
+def test_one_subpanel_per_lane_is_the_plain_rule_bit_for_bit():
+    """m = 1 — every setting the reference itself uses — must compute what the rule without sub-panels computed, in
+    all three kernels' shared panel loop: `==` on values recorded from the library before the loop was cut up."""
+    got = first_target_on_the_device()
+    assert got == PLAIN_RULE_FIRST_TARGET
+    assert got["basket"] == got["solve"]
 
 
 def test_carr_madan_lognormal_equals_black_scholes():
@@ -72,8 +109,8 @@ if given is not None:
               phases=[Phase.explicit, Phase.generate], suppress_health_check=[HealthCheck.too_slow])
     @given(V0=st.floats(0.005, 0.5), kappa=st.floats(0.1, 5.0), theta=st.floats(0.005, 0.3),
            sigma=st.floats(0.05, 1.2), rho=st.floats(-0.95, 0.95), r=st.floats(-0.01, 0.1),
-           days=st.integers(20, 1500), moneyness=st.floats(0.6, 1.6), alpha=st.sampled_from([0.75, 1.0, 1.5]),
-           bound=st.sampled_from([32.0, 100.0, 400.0]), put=st.booleans())
+           days=st.integers(20, 1500), moneyness=st.floats(0.6, 1.6), alpha=st.sampled_from([0.25, 0.75, 1.0, 1.5]),
+           bound=st.sampled_from([32.0, 100.0, 400.0, 1000.0]), put=st.booleans())
     def test_carr_madan_random_heston(V0, kappa, theta, sigma, rho, r, days, moneyness, alpha, bound, put):
         """Random Heston parameters, damping and integration bounds: the device quadrature against the
         scipy restatement of carr_madan.jl:47-92 (same integrand, adaptive quadrature).  Absolute bar
