@@ -3,7 +3,8 @@
 Tolerances (fp64; the BASELINE bar is 1e-4 relative on the price):
   * REPLAY (identical Wiener increments): per-path samples 1e-12 rel, price 1e-12 rel
   * GENERATE (same Philox stream, different libm for log/sincospi): per-path 1e-11 rel
-  * dual partials: 1e-10 rel on the accumulated Greeks
+  * dual partials: per path and slot against a 50-digit tangent, at the bars of tests/euler_tangent_cases.py
+    (tests/test_gpu_euler_tangent_exact.py); here the accumulated Greeks against the oracle's, 1e-10 rel
 """
 import ctypes as C
 
