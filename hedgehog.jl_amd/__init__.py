@@ -21,17 +21,20 @@ from .lsm import (LSM, EulerPaths, HestonExactPaths, LSMSolution, simulate_euler
 from .montecarlo import (AbstractPricingMethod, Antithetic, BlackScholesExact, EulerMaruyama,
                          HestonBroadieKaya, HestonDynamics, LognormalDynamics, MethodError,
                          MonteCarlo, NoVarianceReduction, NormalLaw, SimulationConfig, marginal_law,
-                         solve_montecarlo, solve_montecarlo_many)
+                         solve_montecarlo, solve_montecarlo_many, solve_path_payoffs)
 from .distributed import rank_device, shard_range, solve_lsm_sharded, solve_sharded
-from .domain import (American, BlackScholesInputs, Call, European, FlatRateCurve, FlatVolSurface,
-                    Forward, HestonInputs, MonteCarloSolution, PricingProblem, Put, RateCurve, Spot,
-                    VanillaOption, df, df_yf, get_vol, spine_zeros, zero_rate, zero_rate_yf)
+from .domain import (American, ArithmeticAverage, AsianOption, AssetOrNothing, BarrierOption, BlackScholesInputs,
+                    Call, CashOrNothing, DigitalOption, DownAndIn, DownAndOut, European, FlatRateCurve,
+                    FlatVolSurface, Forward, GeometricAverage, HestonInputs, Monitoring, MonteCarloSolution,
+                    PricingProblem, Put, RateCurve, Spot, UpAndIn, UpAndOut, VanillaOption, df, df_yf, get_vol,
+                    spine_zeros, zero_rate, zero_rate_yf)
 
 
 def solve(*args, **kw):
     """The reference's single verb (src/Hedgehog.jl:59-98), for the methods on the hot path:
 
         solve(prob::PricingProblem, method::MonteCarlo)                      montecarlo.jl:478
+        solve(prob::PricingProblem{AsianOption | BarrierOption | DigitalOption}, method::MonteCarlo)  (Euler paths)
         solve(gprob::GreekProblem, ::ForwardAD, method)                      greeks_problem.jl:249
         solve(gprob::GreekProblem, ::FiniteDifference, method)               greeks_problem.jl:318
         solve(gprob::SecondOrderGreekProblem, ::FiniteDifference, method)    greeks_problem.jl:396

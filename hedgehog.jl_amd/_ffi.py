@@ -20,6 +20,12 @@ HH_EULER_MARUYAMA, HH_EXACT_LAW, HH_BROADIE_KAYA = 0, 1, 2
 HH_NOISE_GENERATE, HH_NOISE_REPLAY = 0, 1
 HH_REPLAY_TILE_MAJOR, HH_REPLAY_PATH_MAJOR = 0, 1
 HH_PATH_SPOT, HH_PATH_LOG = 0, 1
+HH_PAYOFF_VANILLA, HH_PAYOFF_ASIAN_ARITH, HH_PAYOFF_ASIAN_GEOM = 0, 1, 2
+HH_PAYOFF_BARRIER, HH_PAYOFF_DIGITAL_CASH, HH_PAYOFF_DIGITAL_ASSET = 3, 4, 5
+HH_BARRIER_UP_OUT, HH_BARRIER_UP_IN, HH_BARRIER_DOWN_OUT, HH_BARRIER_DOWN_IN = 0, 1, 2, 3
+HH_STAT_SUM_S, HH_STAT_SUM_X, HH_STAT_MAX_S, HH_STAT_MIN_S, HH_STAT_S_T = 0, 1, 2, 3, 4
+HH_PATH_STATS = 5
+HH_MAX_PATH_PAYOFFS = 1024
 
 HH_OK, HH_ERR_INVALID, HH_ERR_UNSUPPORTED, HH_ERR_HIP, HH_ERR_NOMEM, HH_ERR_RCCL, HH_ERR_DEVICE_TIMEOUT = 0, -1, -2, -3, -4, -5, -6
 HH_MGPU_AUTO, HH_MGPU_HOST_SUM, HH_MGPU_RCCL = 0, 1, 2
@@ -72,6 +78,11 @@ class hh_lsm_result(C.Structure):
                 ("rows_regressed", C.c_uint32), ("rows_skipped", C.c_uint32),
                 ("kernel_ms", C.c_double), ("total_ms", C.c_double),
                 ("form", C.c_int32), ("persistent_fallbacks", C.c_int32)]
+
+
+class hh_path_payoff(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("barrier_type", C.c_int32), ("strike", C.c_double), ("cp", C.c_double),
+                ("barrier", C.c_double), ("rebate", C.c_double), ("cash", C.c_double)]
 
 
 HH_BK_ROOT_SECANT, HH_BK_ROOT_ORDER2 = 0, 1
@@ -132,6 +143,10 @@ SYMBOLS = [
     ("hh_euler_grid", C.c_int, [_vp, C.POINTER(hh_model), C.POINTER(hh_config), C.c_int32, _vp, _vp, C.c_int32, C.POINTER(hh_result)]),
     ("hh_lsm_solve_euler", C.c_int, [_vp, C.POINTER(hh_model), C.POINTER(hh_config), C.c_int32, C.c_int32, C.c_double,
                                      C.POINTER(hh_lsm_result), _vp, _vp, _vp]),
+    ("hh_mc_path_stats", C.c_int, [_vp, C.POINTER(hh_model), C.POINTER(hh_config), C.c_uint32, C.c_int32, _vp, C.c_int32,
+                                   C.POINTER(hh_result)]),
+    ("hh_mc_solve_path", C.c_int, [_vp, C.POINTER(hh_model), C.POINTER(hh_config), C.c_uint32, C.c_int32,
+                                   C.POINTER(hh_path_payoff), C.c_uint32, C.POINTER(hh_result), _vp, _vp]),
     ("hh_lsm_shard_xchg_elems", C.c_size_t, [C.c_uint32, C.c_int32]),
     ("hh_lsm_shard_begin", C.c_int, [_vp, C.POINTER(hh_model), C.POINTER(hh_config), C.c_int32, C.c_double, _vp]),
     ("hh_lsm_shard_phase", C.c_int, [_vp, C.c_int32, C.c_uint32, _vp, _vp]),

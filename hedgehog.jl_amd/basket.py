@@ -15,9 +15,10 @@ from typing import Any
 import numpy as np
 
 from . import _ffi
-from .domain import MonteCarloSolution, PricingProblem
+from .domain import PATH_PAYOFFS, European, MonteCarloSolution, PricingProblem, Spot, VanillaOption
 from .dual import Dual
-from .montecarlo import MonteCarlo, _model_and_config, _price_from, solve_montecarlo
+from .montecarlo import (MonteCarlo, _model_and_config, _price_from, path_monitoring, solve_montecarlo,
+                         solve_path_payoffs)
 
 
 @dataclass(frozen=True)
@@ -32,6 +33,28 @@ class BasketPricingSolution:
     """basket.jl:24-27."""
     problem: BasketPricingProblem
     solutions: Any
+
+
+def path_groups(payoffs, steps):
+    """The path solves of a basket: [((expiry, monitoring), [indices])], in order of first appearance.  Path-dependent
+    payoffs are grouped by (expiry, monitoring).  A payoff that reads the state at expiry alone — a digital, a European
+    vanilla on the spot — rides along with the first group of its expiry; digitals of an expiry without one form a
+    group of their own (monitored at expiry), vanillas of such an expiry are left to the terminal-sample basket."""
+    groups: dict = {}
+    for i, p in enumerate(payoffs):
+        if isinstance(p, PATH_PAYOFFS) and path_monitoring(p, steps) is not None:
+            groups.setdefault((p.expiry, path_monitoring(p, steps)), []).append(i)
+    for i, p in enumerate(payoffs):
+        vanilla = isinstance(p, VanillaOption) and isinstance(p.exercise_style, European) and \
+            isinstance(p.underlying, Spot) and not isinstance(p.strike, Dual)
+        if not (vanilla or (isinstance(p, PATH_PAYOFFS) and path_monitoring(p, steps) is None)):
+            continue
+        key = next((k for k in groups if k[0] == p.expiry and k[1] is not None), None)
+        if key is None and not vanilla:
+            key = (p.expiry, None)
+        if key is not None:
+            groups.setdefault(key, []).append(i)
+    return [(k, sorted(idx)) for k, idx in groups.items()]
 
 
 def solve_basket(prob: BasketPricingProblem, method, ensemble: bool = False):
@@ -51,7 +74,13 @@ def solve_basket(prob: BasketPricingProblem, method, ensemble: bool = False):
     payoffs = list(prob.payoffs)
     sols: list = [None] * len(payoffs)
     groups: dict = {}
+    if any(isinstance(p, PATH_PAYOFFS) for p in payoffs):  # one hh_mc_solve_path call per (expiry, monitoring)
+        for _, idx in path_groups(payoffs, method.config.steps):
+            for i, sol in zip(idx, solve_path_payoffs([payoffs[i] for i in idx], prob.market_inputs, method, ensemble)):
+                sols[i] = sol
     for i, p in enumerate(payoffs):
+        if sols[i] is not None:
+            continue
         if isinstance(getattr(p, "strike", None), Dual):  # strike partials: plain per-payoff solve
             sols[i] = solve_montecarlo(PricingProblem(p, prob.market_inputs), method, ensemble)
         else:

@@ -1272,6 +1272,122 @@ int hh_lsm_solve_euler(hh_ctx* ctx, const hh_model* m, const hh_config* c, int32
   return copy_back_spot_grid(ctx, c, spot_grid);
 }
 
+// ---- path-dependent payoffs on Euler–Maruyama paths (GENERATE) ---------------------------------------------
+
+// the call's next kernels go into a timing slot of their own (closed by end_timing)
+static int begin_timing(hh_ctx* ctx) {
+  if (ctx->timing) HH_HIP(ctx, hipEventRecord(ctx->tev[ctx->t_count % hh_ctx::kTimingSlots][0], ctx->stream));
+  return HH_OK;
+}
+
+// The checks of both entry points, then the statistics of every trajectory into ctx->path_stats (one timing slot).
+static int run_path_stats(hh_ctx* ctx, const char* who, const hh_model* m, const hh_config* c, uint32_t monitor_every,
+                          int32_t include_start) {
+  const bool hest = c->dynamics == HH_HESTON;
+  if (c->strategy != HH_EULER_MARUYAMA || (c->dynamics != HH_LOGNORMAL && !hest))
+    return fail(ctx, HH_ERR_UNSUPPORTED, "%s needs LognormalDynamics or HestonDynamics + EulerMaruyama", who);
+  if (c->noise_mode == HH_NOISE_REPLAY || c->n_partials != 0)
+    return fail(ctx, HH_ERR_UNSUPPORTED, "%s: GENERATE noise, no dual partials", who);
+  if (c->noise_mode != HH_NOISE_GENERATE) return fail(ctx, HH_ERR_INVALID, "unknown noise_mode %d", c->noise_mode);
+  if (c->n_paths == 0 || c->n_steps == 0 || c->n_paths > kMaxPaths / 2 || c->n_steps > kMaxEulerSteps)
+    return fail(ctx, HH_ERR_INVALID, "%s: 1 <= n_paths <= 2^31 - 128, 1 <= n_steps <= %u", who, kMaxEulerSteps);
+  if (monitor_every == 0 || c->n_steps % monitor_every != 0)
+    return fail(ctx, HH_ERR_INVALID, "%s: monitor_every (%u) must be >= 1 and divide n_steps (%u)", who, monitor_every,
+                c->n_steps);
+  if (!(m->S0 > 0.0) || !(m->T > 0.0) || !std::isfinite(m->S0) || !std::isfinite(m->T) ||
+      !std::isfinite(m->sigma) || !std::isfinite(m->r_drift) || !std::isfinite(m->discount) ||
+      (hest && (!(std::fabs(m->rho) <= 1.0) || !std::isfinite(m->V0) || !std::isfinite(m->kappa) ||
+                !std::isfinite(m->theta))))
+    return fail(ctx, HH_ERR_INVALID, "%s: S0, T > 0, |rho| <= 1, model scalars finite", who);
+  int rc;
+  if ((rc = ensure(ctx, ctx->path_stats, hh::PathStatsLayout(c->n_paths, c->antithetic != 0).total))) return rc;
+  const uint64_t* seeds_dev = nullptr;
+  if ((rc = stage_path_seeds(ctx, c, &seeds_dev))) return rc;
+  if ((rc = begin_timing(ctx))) return rc;
+  HH_HIP(ctx, hh::launch_path_stats(*m, *c, seeds_dev, monitor_every, include_start != 0, ctx->path_stats, ctx->stream));
+  return end_timing(ctx);
+}
+
+int hh_mc_path_stats(hh_ctx* ctx, const hh_model* m, const hh_config* c, uint32_t monitor_every, int32_t include_start,
+                     double* stats, int32_t stats_on_device, hh_result* out) {
+  if (!ctx) return HH_ERR_INVALID;
+  std::lock_guard<std::recursive_mutex> lock__(ctx->mu);
+  if (!m || !c || !stats) return fail(ctx, HH_ERR_INVALID, "hh_mc_path_stats: NULL argument");
+  const WallClock clock;
+  HH_HIP(ctx, hipSetDevice(ctx->device));
+  HH_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+  int rc = run_path_stats(ctx, "hh_mc_path_stats", m, c, monitor_every, include_start);
+  if (rc) return rc;
+  HH_HIP(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+  HH_HIP(ctx, hipMemcpyAsync(stats, ctx->path_stats, hh::PathStatsLayout(c->n_paths, c->antithetic != 0).total * sizeof(double),
+                             stats_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, ctx->stream));
+  HH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  if ((rc = release_host_operands(ctx))) return rc;
+  if (!out) return HH_OK;
+  std::memset(out, 0, sizeof(*out));
+  out->n_paths_done = c->n_paths;
+  return solve_times(ctx, clock, &out->kernel_ms, &out->total_ms);
+}
+
+int hh_mc_solve_path(hh_ctx* ctx, const hh_model* m, const hh_config* c, uint32_t monitor_every, int32_t include_start,
+                     const hh_path_payoff* payoffs, uint32_t n_payoffs, hh_result* out, double* path_values,
+                     double* stats) {
+  if (!ctx) return HH_ERR_INVALID;
+  std::lock_guard<std::recursive_mutex> lock__(ctx->mu);
+  if (!m || !c || !payoffs || !out) return fail(ctx, HH_ERR_INVALID, "hh_mc_solve_path: NULL argument");
+  if (n_payoffs == 0 || n_payoffs > HH_MAX_PATH_PAYOFFS)
+    return fail(ctx, HH_ERR_INVALID, "hh_mc_solve_path: 1 .. %d payoffs", HH_MAX_PATH_PAYOFFS);
+  for (uint32_t k = 0; k < n_payoffs; ++k) {
+    const hh_path_payoff& q = payoffs[k];
+    if (q.kind < HH_PAYOFF_VANILLA || q.kind > HH_PAYOFF_DIGITAL_ASSET)
+      return fail(ctx, HH_ERR_INVALID, "hh_mc_solve_path: payoff %u: unknown kind %d", k, q.kind);
+    if (q.kind == HH_PAYOFF_BARRIER && (q.barrier_type < HH_BARRIER_UP_OUT || q.barrier_type > HH_BARRIER_DOWN_IN))
+      return fail(ctx, HH_ERR_INVALID, "hh_mc_solve_path: payoff %u: unknown barrier type %d", k, q.barrier_type);
+    if (q.cp != 1.0 && q.cp != -1.0) return fail(ctx, HH_ERR_INVALID, "hh_mc_solve_path: payoff %u: cp must be +1 or -1", k);
+    if (!std::isfinite(q.strike) || !std::isfinite(q.rebate) || !std::isfinite(q.cash) || std::isnan(q.barrier))
+      return fail(ctx, HH_ERR_INVALID, "hh_mc_solve_path: payoff %u: strike, rebate, cash finite; barrier not NaN", k);
+  }
+  const WallClock clock;
+  HH_HIP(ctx, hipSetDevice(ctx->device));
+  HH_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+  int rc = run_path_stats(ctx, "hh_mc_solve_path", m, c, monitor_every, include_start);
+  if (rc) return rc;
+
+  const hh::PathStatsLayout at(c->n_paths, c->antithetic != 0);
+  hh::PathPayoffArgs b{};
+  b.stats = ctx->path_stats;
+  b.n_paths = c->n_paths;
+  b.n_chunks = hh::basket_chunks(c->n_paths);
+  b.antithetic = c->antithetic;
+  b.n_mon = (double)(c->n_steps / monitor_every + (include_start ? 1u : 0u));
+  if ((rc = stage_host(ctx, ctx->path_payoffs, (size_t)n_payoffs, payoffs, (size_t)n_payoffs, &b.payoffs))) return rc;
+  const size_t n_acc = (size_t)n_payoffs * HH_ACC_LEN;
+  if ((rc = ensure(ctx, ctx->basket_records, (size_t)n_payoffs * b.n_chunks * hh::kRecStride))) return rc;
+  if ((rc = ensure(ctx, ctx->basket_accum, n_acc))) return rc;
+  if (path_values && (rc = ensure(ctx, ctx->path_values, (size_t)n_payoffs * at.n_total))) return rc;
+  b.values = path_values ? ctx->path_values.p : nullptr;
+  b.records = ctx->basket_records;
+  if ((rc = begin_timing(ctx))) return rc;
+  HH_HIP(ctx, hh::launch_path_payoffs(b, n_payoffs, ctx->stream));
+  HH_HIP(ctx, hh::launch_reduce_records(ctx->basket_records, b.n_chunks, (double)c->n_paths, ctx->basket_accum,
+                                        ctx->stream, n_payoffs));
+  if ((rc = end_timing(ctx))) return rc;
+  HH_HIP(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+  std::vector<double> host(n_acc);
+  HH_HIP(ctx, hipMemcpyAsync(host.data(), ctx->basket_accum, n_acc * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  if (path_values)
+    HH_HIP(ctx, hipMemcpyAsync(path_values, ctx->path_values, (size_t)n_payoffs * at.n_total * sizeof(double),
+                               hipMemcpyDeviceToHost, ctx->stream));
+  if (stats)
+    HH_HIP(ctx, hipMemcpyAsync(stats, ctx->path_stats, at.total * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  HH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  if ((rc = release_host_operands(ctx))) return rc;
+  double kernel_ms, total_ms;
+  if ((rc = solve_times(ctx, clock, &kernel_ms, &total_ms))) return rc;
+  rc = finalize_results(m, 0, c, host.data(), n_payoffs, kernel_ms, total_ms, out);
+  return rc ? fail(ctx, rc, "finalize failed: the accumulator holds no trajectories") : HH_OK;
+}
+
 // ---- LSM on an ensemble sharded over several devices ------------------------------------------------
 
 size_t hh_lsm_shard_xchg_elems(uint32_t n_steps, int32_t degree) {

@@ -255,6 +255,23 @@ int launch_gbm_grid(const uint64_t* seeds_dev, uint64_t n_paths, uint32_t n_step
 // state into var_grid when it is not NULL (lognormal: ignored).
 int launch_euler_grid(const hh_model& m, const hh_config& c, const uint64_t* seeds_dev, bool log_state,
                       double* grid, double* var_grid, hipStream_t s);
+// Path-dependent payoffs (hh_path.hip).  The same trajectories as launch_euler_grid's (c: dynamics, em_split,
+// antithetic, n_paths, n_steps), reduced per trajectory to the HH_PATH_STATS numbers of PathStatsLayout over the
+// monitoring dates monitor_every, 2·monitor_every, …, n_steps (a divisor of n_steps) and, include_start, step 0.
+int launch_path_stats(const hh_model& m, const hh_config& c, const uint64_t* seeds_dev, uint32_t monitor_every,
+                      bool include_start, double* stats, hipStream_t s);
+// … and n_payoffs payoffs evaluated on them: one record per payoff and chunk, as launch_basket_payoffs leaves them
+struct PathPayoffArgs {
+  const double* stats;            // PathStatsLayout(n_paths, antithetic)
+  const hh_path_payoff* payoffs;  // device, [n_payoffs]
+  double* values;                 // device or nullptr: [n_payoffs][n_total], each member's payoff
+  double* records;                // [n_payoffs][n_chunks][kRecStride]
+  double n_mon;                   // monitoring dates of a trajectory
+  uint64_t n_paths;
+  uint32_t n_chunks;              // basket_chunks(n_paths)
+  int antithetic;
+};
+int launch_path_payoffs(const PathPayoffArgs& b, uint32_t n_payoffs, hipStream_t s);
 // form: kLsmFormPersistent = the whole backward induction in ONE launch when the ensemble fits the
 // chip (else it falls back by itself), kLsmFormPerDate = one launch per exercise date.  *form_used
 // says which was enqueued; after a persistent launch the caller synchronises and reads the word at

@@ -1,4 +1,5 @@
-// How the device scratch buffers are carved: the LSM induction's, the Broadie–Kaya chain's and the grid sort's.
+// How the device scratch buffers are carved: the LSM induction's, the path statistics', the Broadie–Kaya chain's and
+// the grid sort's.
 // Each layout is stated ONCE, as a struct of region offsets that one constructor fills by walking a cursor; the
 // allocation's size, the kernels' pointers and the host's read-backs all come from it (hh_lsm.hip, hh_bk.hip,
 // hh_api.hip).  A region is added here and nowhere else.  Plain size_t arithmetic, no HIP types: a host compiler
@@ -71,6 +72,18 @@ struct LsmScratch {
     stamps = c.take(kLsmStampSlots);
     total = c.at;
   }
+};
+
+// ---- path statistics (hh_path.hip) ----------------------------------------------------------------------------
+
+// What path_stats_kernel leaves of every trajectory and path_payoff_kernel reads: one row per statistic (enum
+// hh_path_stat), step-major like the path grids — stats[stat][column], column i = trajectory i, column n_paths + i
+// its antithetic mirror.  Offsets in doubles.  (constexpr: the two kernels index with it too)
+struct PathStatsLayout {
+  size_t n_total, total;
+  constexpr PathStatsLayout(uint64_t n_paths, bool antithetic)
+      : n_total((size_t)n_paths * (antithetic ? 2 : 1)), total((size_t)HH_PATH_STATS * n_total) {}
+  constexpr size_t row(int stat) const { return (size_t)stat * n_total; }
 };
 
 // ---- Broadie–Kaya (hh_bk.hip) ----------------------------------------------------------------------------------

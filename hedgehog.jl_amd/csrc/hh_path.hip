@@ -1,0 +1,239 @@
+// Path-dependent payoffs on Euler–Maruyama paths for gfx950: arithmetic / geometric Asian, discretely monitored
+// barrier, digital (include/hedgehog_mc.h, "Path-dependent payoffs").  Two kernels:
+//
+//   path_stats_kernel   simulates the trajectories of euler_kernel / euler_grid_kernel — the draws, the correlation
+//                       and the step are hh_sim.h's, so every state is theirs bit for bit — and keeps, instead of a
+//                       grid, HH_PATH_STATS running numbers per trajectory over the monitoring dates;
+//   path_payoff_kernel  evaluates any number of payoffs on those numbers, as basket_payoff_kernel evaluates strikes
+//                       on terminal samples, and leaves one record of sums per payoff and chunk.
+//
+// The 40 bytes per trajectory that go through memory between the two are about 1 % of the simulation's time at
+// 252 steps; in exchange one simulation serves every payoff of a call and the caller can have the statistics.
+#include "hh_sim.h"
+
+namespace hh {
+namespace {
+
+// v_max_f64 / v_min_f64 as ONE instruction each: written with fmax / fmin the compiler first canonicalises the
+// loop-carried operand (v_max_f64 v, v, v), as in HestonModel::step.  No operand is ever NaN here.
+__device__ __forceinline__ double vmax(double a, double b) {
+  double r;
+  asm("v_max_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+  return r;
+}
+__device__ __forceinline__ double vmin(double a, double b) {
+  double r;
+  asm("v_min_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+  return r;
+}
+
+// the running statistics of one trajectory (enum hh_path_stat)
+struct Running {
+  double sum_s = 0.0, sum_x = 0.0, max_s = 0.0, min_s = 0.0, s_t = 0.0;
+  __device__ __forceinline__ void first(double S, double x) {  // a sum starts with its first term
+    sum_s = S;
+    sum_x = x;
+    max_s = S;
+    min_s = S;
+    s_t = S;
+  }
+  __device__ __forceinline__ void next(double S, double x) {  // … and takes one rounded addition per later date
+    sum_s = sum_s + S;
+    sum_x = sum_x + x;
+    max_s = vmax(max_s, S);
+    min_s = vmin(min_s, S);
+    s_t = S;
+  }
+  __device__ __forceinline__ void store(double* __restrict__ stats, const PathStatsLayout& at, uint64_t col) const {
+    // plain stores, not the grids' nontemporal ones: path_payoff_kernel reads the rows straight back (measured:
+    // its 27 µs become 31 µs behind nontemporal stores, the statistics kernel does not change)
+    stats[at.row(HH_STAT_SUM_S) + col] = sum_s;
+    stats[at.row(HH_STAT_SUM_X) + col] = sum_x;
+    stats[at.row(HH_STAT_MAX_S) + col] = max_s;
+    stats[at.row(HH_STAT_MIN_S) + col] = min_s;
+    stats[at.row(HH_STAT_S_T) + col] = s_t;
+  }
+};
+
+// One trajectory per lane (and its mirror, -dW, in the same lane: column n_paths + i), GENERATE noise, after
+// euler_grid_kernel.  The monitoring dates are the steps monitor_every, 2·monitor_every, …, n_steps — monitor_every
+// divides n_steps, so the last step is one, and S = exp(x) is formed there only, as euler_grid_kernel's `put` forms
+// it — and step 0 (S0, log S0: the grid's row 0) when include_start.  The countdown to the next date and the
+// "a first term is in" flag depend on kernel arguments alone: uniform branches.  No LDS.
+template <class M, bool ANTI>
+__global__ __launch_bounds__(256) void path_stats_kernel(const SimArgs<0> a, const double S0,
+                                                         const uint32_t monitor_every, const int include_start,
+                                                         double* __restrict__ stats) {
+  using State = typename M::State;
+  constexpr int NC = M::NCOMP;
+  const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= a.n_paths) return;
+  const PathStatsLayout at(a.n_paths, ANTI);
+  const uint32_t n_steps = a.n_steps;
+  State st, sa;
+  M::init(st, a);
+  if constexpr (ANTI) M::init(sa, a);
+  Running r, ra;
+  bool started = include_start != 0;
+  if (started) {
+    r.first(S0, a.x0.v);
+    if constexpr (ANTI) ra.first(S0, a.x0.v);
+  }
+  uint32_t left = monitor_every;
+  auto date = [&]() {  // a step has been taken
+    if (--left != 0u) return;
+    left = monitor_every;
+    const double S = exp(st.x.v);
+    if (started) r.next(S, st.x.v);
+    else r.first(S, st.x.v);
+    if constexpr (ANTI) {
+      const double Sa = exp(sa.x.v);
+      if (started) ra.next(Sa, sa.x.v);
+      else ra.first(Sa, sa.x.v);
+    }
+    started = true;
+  };
+  const uint64_t key = a.seeds[i];  // montecarlo.jl:331
+  if constexpr (NC == 2) {
+    for (uint32_t s = 0; s < n_steps; ++s) {
+      double d1, d2;
+      euler_pair_increments(key, s, a, d1, d2);
+      M::step(st, a, d1, d2);
+      if constexpr (ANTI) M::step(sa, a, -d1, -d2);  // montecarlo.jl:258: -W
+      date();
+    }
+  } else {
+    // scalar noise: one Philox block feeds two consecutive steps
+    for (uint32_t s = 0; s < n_steps; s += 2) {
+      double z1, z2;
+      euler_scalar_normals(key, s >> 1, z1, z2);
+      const double d1 = a.sqrt_dt * z1;
+      M::step(st, a, d1, 0.0);
+      if constexpr (ANTI) M::step(sa, a, -d1, 0.0);
+      date();
+      if (s + 1 < n_steps) {
+        const double d2 = a.sqrt_dt * z2;
+        M::step(st, a, d2, 0.0);
+        if constexpr (ANTI) M::step(sa, a, -d2, 0.0);
+        date();
+      }
+    }
+  }
+  r.store(stats, at, i);
+  if constexpr (ANTI) ra.store(stats, at, a.n_paths + i);
+}
+
+// ------------------------------------------------------------------------------------------
+// payoffs on the statistics
+// ------------------------------------------------------------------------------------------
+
+constexpr int kPathKB = 4;  // payoffs a workgroup evaluates on each trajectory it loads
+
+// q is the same for every lane of the workgroup (scalar registers): the switch is a scalar branch
+__device__ __forceinline__ double path_payoff_of(const hh_path_payoff& q, const double (&t)[HH_PATH_STATS],
+                                                 double n_mon) {
+  const double S_T = t[HH_STAT_S_T];
+  const double mT = q.cp * (S_T - q.strike);
+  const double van = mT > 0.0 ? mT : 0.0;
+  switch (q.kind) {
+    case HH_PAYOFF_ASIAN_ARITH: {
+      const double m = q.cp * (t[HH_STAT_SUM_S] / n_mon - q.strike);
+      return m > 0.0 ? m : 0.0;
+    }
+    case HH_PAYOFF_ASIAN_GEOM: {
+      const double m = q.cp * (exp(t[HH_STAT_SUM_X] / n_mon) - q.strike);
+      return m > 0.0 ? m : 0.0;
+    }
+    case HH_PAYOFF_BARRIER: {
+      const bool up = q.barrier_type == HH_BARRIER_UP_OUT || q.barrier_type == HH_BARRIER_UP_IN;
+      const bool out = q.barrier_type == HH_BARRIER_UP_OUT || q.barrier_type == HH_BARRIER_DOWN_OUT;
+      const bool hit = up ? t[HH_STAT_MAX_S] >= q.barrier : t[HH_STAT_MIN_S] <= q.barrier;
+      return hit == out ? q.rebate : van;  // knock-out: hit ? rebate : van;  knock-in: hit ? van : rebate
+    }
+    case HH_PAYOFF_DIGITAL_CASH: return mT > 0.0 ? q.cash : 0.0;
+    case HH_PAYOFF_DIGITAL_ASSET: return mT > 0.0 ? S_T : 0.0;
+    default: return van;  // HH_PAYOFF_VANILLA (the entry point admits no other kind)
+  }
+}
+
+// After basket_payoff_kernel, with its block -> (chunk, payoff group) map (chunk c on XCD c mod 8 whatever the group,
+// so each XCD's L2 holds one eighth of the statistics for all payoffs): a workgroup loads the five statistics of a
+// trajectory (and of its mirror) once and evaluates every payoff of its group on them from registers.  Each payoff
+// keeps its own accumulators, lane order and record: its sums are those of a one-payoff launch bit for bit.
+__global__ __launch_bounds__(256) void path_payoff_kernel(const PathPayoffArgs b, const uint32_t n_payoffs) {
+  const uint32_t per_xcd = (b.n_chunks + 7u) / 8u;  // chunks an XCD owns
+  const uint32_t xcd = blockIdx.x & 7u, idx = blockIdx.x >> 3;
+  const uint32_t grp = idx / per_xcd, chunk = (idx % per_xcd) * 8u + xcd;
+  if (chunk >= b.n_chunks) return;  // padding of the last group of eight
+  const uint32_t k0 = grp * kPathKB;
+  hh_path_payoff q[kPathKB];
+#pragma unroll
+  for (int g = 0; g < kPathKB; ++g) q[g] = b.payoffs[min(k0 + g, n_payoffs - 1)];  // a short last group repeats its last payoff
+  const bool anti = b.antithetic != 0;
+  const PathStatsLayout at(b.n_paths, anti);
+  double acc[kPathKB][2];
+#pragma unroll
+  for (int g = 0; g < kPathKB; ++g) acc[g][0] = acc[g][1] = 0.0;
+  const uint64_t i0 = (uint64_t)chunk * kBasketChunk;
+  for (uint32_t j = threadIdx.x; j < (uint32_t)kBasketChunk; j += 256) {
+    const uint64_t i = i0 + j;
+    if (i >= b.n_paths) break;
+    double t[HH_PATH_STATS], ta[HH_PATH_STATS];
+#pragma unroll
+    for (int s = 0; s < HH_PATH_STATS; ++s) {
+      t[s] = b.stats[at.row(s) + i];
+      ta[s] = anti ? b.stats[at.row(s) + b.n_paths + i] : 0.0;
+    }
+#pragma unroll
+    for (int g = 0; g < kPathKB; ++g) {
+      const bool live = k0 + g < n_payoffs;  // uniform over the workgroup
+      double p = path_payoff_of(q[g], t, b.n_mon);
+      if (b.values && live) b.values[(size_t)(k0 + g) * at.n_total + i] = p;
+      if (anti) {
+        const double pa = path_payoff_of(q[g], ta, b.n_mon);
+        if (b.values && live) b.values[(size_t)(k0 + g) * at.n_total + b.n_paths + i] = pa;
+        p = (p + pa) / 2;  // montecarlo.jl:431
+      }
+      acc[g][0] += p;
+      acc[g][1] = fma(p, p, acc[g][1]);
+    }
+  }
+#pragma unroll
+  for (int g = 0; g < kPathKB; ++g) {
+    if (k0 + g >= n_payoffs) break;  // uniform over the workgroup
+    if (g) __syncthreads();          // the reduction's LDS staging is reused
+    block_reduce_store<2, 4, 0>(acc[g], b.records + ((size_t)(k0 + g) * b.n_chunks + chunk) * kRecStride);
+  }
+}
+
+}  // namespace
+
+int launch_path_stats(const hh_model& m, const hh_config& c, const uint64_t* seeds_dev, uint32_t monitor_every,
+                      bool include_start, double* stats, hipStream_t s) {
+  DevicePtrs p{};
+  p.seeds = seeds_dev;
+  const SimArgs<0> a = make_args0(m, c, p);
+  const dim3 g((unsigned)((c.n_paths + 255) / 256)), blk(256);
+  auto go = [&](auto model, auto anti) {
+    hipLaunchKernelGGL((path_stats_kernel<decltype(model), decltype(anti)::value>), g, blk, 0, s, a, m.S0,
+                       monitor_every, (int)include_start, stats);
+  };
+  auto with_anti = [&](auto model) {
+    if (c.antithetic) go(model, std::true_type{});
+    else go(model, std::false_type{});
+  };
+  if (c.dynamics == HH_LOGNORMAL) with_anti(GbmModel<0>{});
+  else if (c.em_split) with_anti(HestonModel<0, true>{});
+  else with_anti(HestonModel<0, false>{});
+  return (int)hipGetLastError();
+}
+
+int launch_path_payoffs(const PathPayoffArgs& b, uint32_t n_payoffs, hipStream_t s) {
+  const uint32_t n_groups = (n_payoffs + kPathKB - 1) / kPathKB;
+  if ((uint64_t)((b.n_chunks + 7u) / 8u) * 8u * n_groups > 0x7fffffffull) return (int)hipErrorInvalidConfiguration;
+  const dim3 grid(((b.n_chunks + 7u) / 8u) * 8u * n_groups), block(256);
+  hipLaunchKernelGGL(path_payoff_kernel, grid, block, 0, s, b, n_payoffs);
+  return (int)hipGetLastError();
+}
+
+}  // namespace hh

@@ -69,6 +69,107 @@ class VanillaOption:
         return np.maximum(self.call_put() * (np.asarray(spot) - self.strike), 0.0)
 
 
+# ---- path-dependent payoffs on Euler–Maruyama paths ----
+# The reference has none of these; the names follow its roadmap ("Structured Payoffs": arithmetic Asian, digitals,
+# discretely monitored barriers, `Monitoring` / `Averaging` modifiers of a payoff).  All are European, on the spot.
+class ArithmeticAverage: pass
+class GeometricAverage: pass
+class UpAndOut: pass
+class UpAndIn: pass
+class DownAndOut: pass
+class DownAndIn: pass
+class AssetOrNothing: pass
+
+
+for _c in (ArithmeticAverage, GeometricAverage, UpAndOut, UpAndIn, DownAndOut, DownAndIn, AssetOrNothing):
+    _tag_eq(_c)
+
+
+@dataclass(frozen=True)
+class CashOrNothing:
+    cash: Any = 1.0
+
+
+@dataclass(frozen=True)
+class Monitoring:
+    """The dates a path-dependent payoff looks at: the steps every, 2·every, …, steps of the simulation (`every` must
+    divide SimulationConfig.steps) and, include_start, step 0 (the spot itself)."""
+    every: int = 1
+    include_start: bool = False
+
+    def __post_init__(self):
+        if int(self.every) != self.every or self.every < 1:
+            raise ValueError(f"Monitoring.every must be a positive integer, got {self.every!r}")
+        object.__setattr__(self, "every", int(self.every))
+        object.__setattr__(self, "include_start", bool(self.include_start))
+
+
+def _of(value, kinds, what):
+    if not isinstance(value, kinds):
+        raise TypeError(f"{what} must be one of " + ", ".join(k.__name__ + "()" for k in kinds) + f", got {value!r}")
+    return value
+
+
+@dataclass(frozen=True)
+class AsianOption:
+    """max(cp·(A − strike), 0) with A the arithmetic or geometric average of the spot over the monitoring dates."""
+    strike: Any
+    expiry: int
+    call_put: Any
+    averaging: Any
+    monitoring: Monitoring
+
+    def __init__(self, strike, expiry_date, call_put, averaging=None, monitoring=None):
+        object.__setattr__(self, "strike", strike)
+        object.__setattr__(self, "expiry", to_ticks(expiry_date))
+        object.__setattr__(self, "call_put", _of(call_put, (Call, Put), "call_put"))
+        object.__setattr__(self, "averaging", _of(averaging or ArithmeticAverage(),
+                                                  (ArithmeticAverage, GeometricAverage), "averaging"))
+        object.__setattr__(self, "monitoring", _of(monitoring or Monitoring(), (Monitoring,), "monitoring"))
+
+
+@dataclass(frozen=True)
+class BarrierOption:
+    """A vanilla payoff knocked out or in when the spot touches the barrier on a monitoring date (a touch counts:
+    max S >= barrier for the up types, min S <= barrier for the down types); `rebate` is paid AT EXPIRY on the
+    paths that are knocked out (or never knocked in)."""
+    strike: Any
+    barrier: Any
+    expiry: int
+    call_put: Any
+    barrier_type: Any
+    rebate: Any
+    monitoring: Monitoring
+
+    def __init__(self, strike, barrier, expiry_date, call_put, barrier_type, rebate=0.0, monitoring=None):
+        object.__setattr__(self, "strike", strike)
+        object.__setattr__(self, "barrier", barrier)
+        object.__setattr__(self, "expiry", to_ticks(expiry_date))
+        object.__setattr__(self, "call_put", _of(call_put, (Call, Put), "call_put"))
+        object.__setattr__(self, "barrier_type", _of(barrier_type, (UpAndOut, UpAndIn, DownAndOut, DownAndIn),
+                                                     "barrier_type"))
+        object.__setattr__(self, "rebate", rebate)
+        object.__setattr__(self, "monitoring", _of(monitoring or Monitoring(), (Monitoring,), "monitoring"))
+
+
+@dataclass(frozen=True)
+class DigitalOption:
+    """cp·(S_T − strike) > 0 ? payout : 0, the payout a fixed cash amount or the asset itself."""
+    strike: Any
+    expiry: int
+    call_put: Any
+    payout: Any
+
+    def __init__(self, strike, expiry_date, call_put, payout=None):
+        object.__setattr__(self, "strike", strike)
+        object.__setattr__(self, "expiry", to_ticks(expiry_date))
+        object.__setattr__(self, "call_put", _of(call_put, (Call, Put), "call_put"))
+        object.__setattr__(self, "payout", _of(payout or CashOrNothing(), (CashOrNothing, AssetOrNothing), "payout"))
+
+
+PATH_PAYOFFS = (AsianOption, BarrierOption, DigitalOption)
+
+
 # ---- rate curve / vol surface (flat only) ----
 @dataclass(frozen=True)
 class FlatRateCurve:

@@ -14,8 +14,10 @@ import numpy as np
 from . import _ffi
 from .dates import yearfrac
 from .dual import Dual, n_partials, partials_of, value_of
-from .domain import (BlackScholesInputs, European, HestonInputs, MonteCarloSolution, PricingProblem,
-                    Spot, VanillaOption, _DeviceSamples, df, get_vol, zero_rate)
+from .domain import (PATH_PAYOFFS, ArithmeticAverage, AsianOption, BarrierOption, BlackScholesInputs, Call,
+                    CashOrNothing, DigitalOption, DownAndIn, DownAndOut, European, HestonInputs, Monitoring,
+                    MonteCarloSolution, PricingProblem, Spot, UpAndIn, UpAndOut, VanillaOption, _DeviceSamples, df,
+                    get_vol, zero_rate)
 
 
 # ---- montecarlo.jl:8-43 ----
@@ -223,6 +225,10 @@ def solve_montecarlo(prob: PricingProblem, method: MonteCarlo, ensemble: bool = 
 
     `replay` (optional, build extension): Wiener increments to consume instead of drawing them —
     numpy array [path][step][comp] (or tile-major), the noise-replay parity mode of DESIGN.md."""
+    if isinstance(prob.payoff, PATH_PAYOFFS):
+        if replay is not None:
+            raise MethodError("path-dependent payoffs draw their own noise: no replay")
+        return solve_path_payoffs([prob.payoff], prob.market_inputs, method, ensemble)[0]
     model, c, keep, P, discount = _model_and_config(prob, method)
     cfg = method.config
     if method.devices is not None:
@@ -264,6 +270,8 @@ def solve_montecarlo_many(probs, method: MonteCarlo, replay=None, replay_layout=
     problems): the caller then solves them one by one, as the reference does."""
     if not 1 < len(probs) <= _ffi.HH_MAX_MODELS:
         return None
+    if any(isinstance(p.payoff, PATH_PAYOFFS) for p in probs):  # one solve after the other (hh_mc_solve_path)
+        return None
     packed = [_model_and_config(p, method) for p in probs]
     if any(P for _, _, _, P, _ in packed):
         return None
@@ -288,6 +296,89 @@ def solve_montecarlo_many(probs, method: MonteCarlo, replay=None, replay_layout=
     ctx.check(ctx.lib.hh_mc_solve_multi(ctx.handle, models, len(probs), C.byref(c), res, None))
     return [MonteCarloSolution(p, method, res[k].price, None, std_error=res[k].std_error, result=res[k])
             for k, p in enumerate(probs)]
+
+
+# ---- path-dependent payoffs (hh_mc_solve_path) -------------------------------------------------------------------
+
+_BARRIER_TYPES = {UpAndOut: _ffi.HH_BARRIER_UP_OUT, UpAndIn: _ffi.HH_BARRIER_UP_IN,
+                  DownAndOut: _ffi.HH_BARRIER_DOWN_OUT, DownAndIn: _ffi.HH_BARRIER_DOWN_IN}
+
+
+def path_monitoring(payoff, steps):
+    """(monitor_every, include_start) of a payoff, or None for one that reads the state at expiry alone (a digital, a
+    European vanilla: it fits any monitoring).  ValueError when `every` does not divide the simulation's steps."""
+    mon = getattr(payoff, "monitoring", None)
+    if mon is None:
+        return None
+    if steps % mon.every != 0:
+        raise ValueError(f"Monitoring.every ({mon.every}) must divide SimulationConfig.steps ({steps})")
+    return mon.every, mon.include_start
+
+
+def pack_path_payoff(payoff) -> _ffi.hh_path_payoff:
+    """One payoff of hh_mc_solve_path.  A Dual in a field is refused: these solves carry no partials."""
+    q = _ffi.hh_path_payoff()
+    fields = [getattr(payoff, n, 0.0) for n in ("strike", "barrier", "rebate")] + [getattr(getattr(payoff, "payout", None), "cash", 0.0)]
+    if any(isinstance(v, Dual) for v in fields):
+        raise MethodError("path-dependent payoffs carry no dual partials: use FiniteDifference")
+    q.strike, q.cp = float(payoff.strike), payoff.call_put()
+    if isinstance(payoff, AsianOption):
+        arith = isinstance(payoff.averaging, ArithmeticAverage)
+        q.kind = _ffi.HH_PAYOFF_ASIAN_ARITH if arith else _ffi.HH_PAYOFF_ASIAN_GEOM
+    elif isinstance(payoff, BarrierOption):
+        q.kind, q.barrier_type = _ffi.HH_PAYOFF_BARRIER, _BARRIER_TYPES[type(payoff.barrier_type)]
+        q.barrier, q.rebate = float(payoff.barrier), float(payoff.rebate)
+    elif isinstance(payoff, DigitalOption):
+        cash = isinstance(payoff.payout, CashOrNothing)
+        q.kind = _ffi.HH_PAYOFF_DIGITAL_CASH if cash else _ffi.HH_PAYOFF_DIGITAL_ASSET
+        q.cash = float(payoff.payout.cash) if cash else 0.0
+    elif isinstance(payoff, VanillaOption) and isinstance(payoff.exercise_style, European) \
+            and isinstance(payoff.underlying, Spot):
+        q.kind = _ffi.HH_PAYOFF_VANILLA
+    else:
+        raise MethodError(f"no path payoff for {type(payoff).__name__}")
+    return q
+
+
+def _path_structs(payoffs, market_inputs, method: MonteCarlo):
+    """(hh_model, hh_config, monitor_every, include_start, discount) of payoffs that share an expiry and a monitoring.
+    The model and configuration are those of a European solve to that expiry (its strike and cp are not read)."""
+    if not isinstance(method.strategy, EulerMaruyama):
+        raise MethodError(f"path-dependent payoffs need EulerMaruyama paths, not {type(method.strategy).__name__}")
+    if method.devices is not None:
+        raise MethodError("path-dependent payoffs run on one device (MonteCarlo.devices is not supported)")
+    expiries = {p.expiry for p in payoffs}
+    if len(expiries) != 1:
+        raise ValueError("payoffs of one path solve share an expiry")
+    steps = method.config.steps
+    mons = {m for m in (path_monitoring(p, steps) for p in payoffs) if m is not None}
+    if len(mons) > 1:
+        raise ValueError("payoffs of one path solve share a monitoring")
+    every, start = mons.pop() if mons else (steps, False)
+    european = VanillaOption(1.0, expiries.pop(), European(), Call(), Spot())
+    model, c, keep, P, discount = _model_and_config(PricingProblem(european, market_inputs), method)
+    if P:  # the policy of every full-path entry point: never drop partials silently
+        raise MethodError("path-dependent payoffs carry no dual partials: use FiniteDifference")
+    del keep
+    return model, c, every, start, discount
+
+
+def solve_path_payoffs(payoffs, market_inputs, method: MonteCarlo, ensemble: bool = True):
+    """Payoffs that share an expiry and a monitoring on ONE simulation (hh_mc_solve_path): a MonteCarloSolution each,
+    in order.  `ensemble`: the (5, n_total) statistics of the trajectories (rows: enum hh_path_stat), shared by the
+    solutions; n_total counts the antithetic mirrors, columns trajectories + i."""
+    model, c, every, start, _ = _path_structs(payoffs, market_inputs, method)
+    packed = (_ffi.hh_path_payoff * len(payoffs))(*[pack_path_payoff(p) for p in payoffs])
+    cfg = method.config
+    ctx = _ffi.get_context(method.device)
+    c.seeds, c.seeds_on_device, c.seeds_len = cfg.device_seeds(ctx), 1, cfg.seeds.size
+    n_total = int(c.n_paths) * (2 if c.antithetic else 1)
+    stats = np.empty((_ffi.HH_PATH_STATS, n_total)) if ensemble else None
+    res = (_ffi.hh_result * len(payoffs))()
+    ctx.check(ctx.lib.hh_mc_solve_path(ctx.handle, C.byref(model), C.byref(c), every, int(start), packed, len(payoffs),
+                                       res, None, stats.ctypes.data if ensemble else None))
+    return [MonteCarloSolution(PricingProblem(p, market_inputs), method, res[k].price, stats,
+                               std_error=res[k].std_error, result=res[k]) for k, p in enumerate(payoffs)]
 
 
 def _solve_multi_gpu(prob, method, model, c, P, discount, ensemble, replay, replay_layout):

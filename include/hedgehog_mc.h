@@ -569,6 +569,64 @@ int hh_lsm_solve_euler(hh_ctx* ctx, const hh_model* model, const hh_config* cfg,
                        double* stop_value, double* spot_grid);
 
 /*
+ * Path-dependent payoffs on Euler–Maruyama paths: arithmetic / geometric Asian, discretely monitored barrier,
+ * cash-or-nothing / asset-or-nothing digital.  The reference has none of them (its roadmap lists them as "Structured
+ * Payoffs"); the conventions below are this library's.
+ *
+ * A solve is two kernels.  The first simulates the trajectories hh_euler_grid and hh_mc_solve simulate — the same
+ * draws, correlation and step, every state bit for bit — and keeps HH_PATH_STATS numbers of each instead of a grid
+ * (enum hh_path_stat), over the MONITORING DATES: the steps m, 2m, …, n_steps with m = monitor_every, which must
+ * divide n_steps, and step 0 (S0, log S0) as well when include_start:
+ *   HH_STAT_SUM_S  Σ S          HH_STAT_SUM_X  Σ log S          (the first date's term, then one rounded addition
+ *   HH_STAT_MAX_S  max S        HH_STAT_MIN_S  min S             per later date, in date order)
+ *   HH_STAT_S_T    S at step n_steps — hh_mc_solve's terminal sample
+ * with S = exp(log S) as hh_euler_grid's HH_PATH_SPOT rows hold it.  stats[stat][column], HH_PATH_STATS x n_total
+ * doubles, n_total = n_paths·(1 + antithetic): column i is trajectory i, column n_paths + i its mirror (-dW).
+ * The second kernel evaluates every payoff of the call on those numbers.  With n_mon the number of monitoring dates
+ * and van = max(cp·(S_T − strike), 0):
+ *   HH_PAYOFF_VANILLA        van
+ *   HH_PAYOFF_ASIAN_ARITH    max(cp·(SUM_S / n_mon − strike), 0)
+ *   HH_PAYOFF_ASIAN_GEOM     max(cp·(exp(SUM_X / n_mon) − strike), 0)
+ *   HH_PAYOFF_BARRIER        hit = MAX_S >= barrier (up) or MIN_S <= barrier (down), a touch counts;
+ *                            knock-out: hit ? rebate : van;   knock-in: hit ? van : rebate;   the rebate is paid at expiry
+ *   HH_PAYOFF_DIGITAL_CASH   cp·(S_T − strike) > 0 ? cash : 0
+ *   HH_PAYOFF_DIGITAL_ASSET  cp·(S_T − strike) > 0 ? S_T : 0
+ * Antithetic: a payoff's sample is the pair average (p + p̃)/2 (montecarlo.jl:431).  A payoff's sums do not depend
+ * on what else is in the call: result k is that of a call with payoff k alone, bit for bit.
+ *
+ * cfg: strategy = HH_EULER_MARUYAMA, dynamics = HH_LOGNORMAL or HH_HESTON, noise_mode = HH_NOISE_GENERATE,
+ * n_partials = 0; antithetic, em_split and the seeds (host, device, hh_seeds_cache) as for hh_euler_grid.
+ * model->strike and model->cp are not read; model->discount multiplies every mean.
+ *   hh_mc_path_stats  stats: host memory, or device memory when stats_on_device.  out (nullable): n_paths_done,
+ *                     kernel_ms, total_ms.
+ *   hh_mc_solve_path  out[k]: price, std_error, the sums, n_paths_done and the call's times of payoff k (dprice zero);
+ *                     path_values (nullable, host): row k = payoff k's sample on each of the n_total members, before
+ *                     the pair average; stats (nullable, host): as above.
+ * Synchronous.  hh_ctx_enable_timing: two slots per hh_mc_solve_path — the statistics kernel, then the payoff kernel
+ * with its record reduction — and one per hh_mc_path_stats.
+ * HH_ERR_UNSUPPORTED: REPLAY noise, dual partials, every other strategy.  HH_ERR_INVALID: monitor_every = 0 or not a
+ * divisor of n_steps, n_payoffs = 0 or above HH_MAX_PATH_PAYOFFS, an unknown kind or barrier type, a strike, rebate
+ * or cash that is not finite (a barrier may be ±inf: never / always hit), cp other than ±1, NULL arguments.
+ * Not provided: an accumulate (asynchronous) form and a multi-GPU form, REPLAY noise, dual partials (bump the inputs
+ * instead: the solves of a finite difference share their seeds), a Julia binding.
+ */
+enum hh_path_payoff_kind { HH_PAYOFF_VANILLA = 0, HH_PAYOFF_ASIAN_ARITH = 1, HH_PAYOFF_ASIAN_GEOM = 2,
+                           HH_PAYOFF_BARRIER = 3, HH_PAYOFF_DIGITAL_CASH = 4, HH_PAYOFF_DIGITAL_ASSET = 5 };
+enum hh_barrier_type { HH_BARRIER_UP_OUT = 0, HH_BARRIER_UP_IN = 1, HH_BARRIER_DOWN_OUT = 2, HH_BARRIER_DOWN_IN = 3 };
+enum hh_path_stat { HH_STAT_SUM_S = 0, HH_STAT_SUM_X = 1, HH_STAT_MAX_S = 2, HH_STAT_MIN_S = 3, HH_STAT_S_T = 4 };
+#define HH_PATH_STATS 5
+#define HH_MAX_PATH_PAYOFFS 1024
+typedef struct hh_path_payoff {
+  int32_t kind, barrier_type;  /* enum hh_path_payoff_kind; enum hh_barrier_type (HH_PAYOFF_BARRIER only) */
+  double strike, cp, barrier, rebate, cash;
+} hh_path_payoff;
+int hh_mc_path_stats(hh_ctx* ctx, const hh_model* model, const hh_config* cfg, uint32_t monitor_every,
+                     int32_t include_start, double* stats, int32_t stats_on_device, hh_result* out);
+int hh_mc_solve_path(hh_ctx* ctx, const hh_model* model, const hh_config* cfg, uint32_t monitor_every,
+                     int32_t include_start, const hh_path_payoff* payoffs, uint32_t n_payoffs, hh_result* out,
+                     double* path_values, double* stats);
+
+/*
  * The same solve for an ensemble SHARDED over several devices (one process and one hh_ctx per
  * device, trajectories split by contiguous ranges as for hh_mc_accumulate).  The backward induction
  * needs sums over ALL trajectories at three points — the in-the-money statistics of every row, the
