@@ -24,8 +24,9 @@ from .montecarlo import (AbstractPricingMethod, Antithetic, BlackScholesExact, E
                          solve_montecarlo, solve_montecarlo_many, solve_path_payoffs)
 from .distributed import rank_device, shard_range, solve_lsm_sharded, solve_sharded
 from .domain import (American, ArithmeticAverage, AsianOption, AssetOrNothing, BarrierOption, BlackScholesInputs,
-                    Call, CashOrNothing, DigitalOption, DownAndIn, DownAndOut, European, FlatRateCurve,
-                    FlatVolSurface, Forward, GeometricAverage, HestonInputs, Monitoring, MonteCarloSolution,
+                    Call, CashOrNothing, ContinuousMonitoring, DigitalOption, DownAndIn, DownAndOut, European,
+                    FlatRateCurve, FlatVolSurface, Forward, GeometricAverage, HestonInputs, LookbackOption, Monitoring,
+                    MonteCarloSolution,
                     PricingProblem, Put, RateCurve, Spot, UpAndIn, UpAndOut, VanillaOption, df, df_yf, get_vol,
                     spine_zeros, zero_rate, zero_rate_yf)
 
@@ -34,7 +35,8 @@ def solve(*args, **kw):
     """The reference's single verb (src/Hedgehog.jl:59-98), for the methods on the hot path:
 
         solve(prob::PricingProblem, method::MonteCarlo)                      montecarlo.jl:478
-        solve(prob::PricingProblem{AsianOption | BarrierOption | DigitalOption}, method::MonteCarlo)  (Euler paths)
+        solve(prob::PricingProblem{AsianOption | BarrierOption | DigitalOption | LookbackOption}, method::MonteCarlo)
+                                                  (Euler paths; barriers and lookbacks also ContinuousMonitoring())
         solve(gprob::GreekProblem, ::ForwardAD, method)                      greeks_problem.jl:249
         solve(gprob::GreekProblem, ::FiniteDifference, method)               greeks_problem.jl:318
         solve(gprob::SecondOrderGreekProblem, ::FiniteDifference, method)    greeks_problem.jl:396

@@ -24,7 +24,11 @@ HH_PAYOFF_VANILLA, HH_PAYOFF_ASIAN_ARITH, HH_PAYOFF_ASIAN_GEOM = 0, 1, 2
 HH_PAYOFF_BARRIER, HH_PAYOFF_DIGITAL_CASH, HH_PAYOFF_DIGITAL_ASSET = 3, 4, 5
 HH_BARRIER_UP_OUT, HH_BARRIER_UP_IN, HH_BARRIER_DOWN_OUT, HH_BARRIER_DOWN_IN = 0, 1, 2, 3
 HH_STAT_SUM_S, HH_STAT_SUM_X, HH_STAT_MAX_S, HH_STAT_MIN_S, HH_STAT_S_T = 0, 1, 2, 3, 4
+HH_PAYOFF_LOOKBACK_FLOAT, HH_PAYOFF_LOOKBACK_FIXED = 6, 7
+HH_STAT_CMAX_S, HH_STAT_CMIN_S = 5, 6
+HH_EXTREMES_MONITORED, HH_EXTREMES_BRIDGE = 0, 1
 HH_PATH_STATS = 5
+HH_PATH_STATS_BRIDGE = 7
 HH_MAX_PATH_PAYOFFS = 1024
 
 HH_OK, HH_ERR_INVALID, HH_ERR_UNSUPPORTED, HH_ERR_HIP, HH_ERR_NOMEM, HH_ERR_RCCL, HH_ERR_DEVICE_TIMEOUT = 0, -1, -2, -3, -4, -5, -6
@@ -147,6 +151,10 @@ SYMBOLS = [
                                    C.POINTER(hh_result)]),
     ("hh_mc_solve_path", C.c_int, [_vp, C.POINTER(hh_model), C.POINTER(hh_config), C.c_uint32, C.c_int32,
                                    C.POINTER(hh_path_payoff), C.c_uint32, C.POINTER(hh_result), _vp, _vp]),
+    ("hh_mc_path_stats_ex", C.c_int, [_vp, C.POINTER(hh_model), C.POINTER(hh_config), C.c_uint32, C.c_int32, C.c_int32, _vp,
+                                      C.c_int32, C.POINTER(hh_result)]),
+    ("hh_mc_solve_path_ex", C.c_int, [_vp, C.POINTER(hh_model), C.POINTER(hh_config), C.c_uint32, C.c_int32, C.c_int32,
+                                      C.POINTER(hh_path_payoff), C.c_uint32, C.POINTER(hh_result), _vp, _vp]),
     ("hh_lsm_shard_xchg_elems", C.c_size_t, [C.c_uint32, C.c_int32]),
     ("hh_lsm_shard_begin", C.c_int, [_vp, C.POINTER(hh_model), C.POINTER(hh_config), C.c_int32, C.c_double, _vp]),
     ("hh_lsm_shard_phase", C.c_int, [_vp, C.c_int32, C.c_uint32, _vp, _vp]),

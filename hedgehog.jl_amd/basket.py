@@ -17,7 +17,7 @@ import numpy as np
 from . import _ffi
 from .domain import PATH_PAYOFFS, European, MonteCarloSolution, PricingProblem, Spot, VanillaOption
 from .dual import Dual
-from .montecarlo import (MonteCarlo, _model_and_config, _price_from, path_monitoring, solve_montecarlo,
+from .montecarlo import (MonteCarlo, _model_and_config, _price_from, path_extremes, path_monitoring, solve_montecarlo,
                          solve_path_payoffs)
 
 
@@ -39,15 +39,23 @@ def path_groups(payoffs, steps):
     """The path solves of a basket: [((expiry, monitoring), [indices])], in order of first appearance.  Path-dependent
     payoffs are grouped by (expiry, monitoring).  A payoff that reads the state at expiry alone — a digital, a European
     vanilla on the spot — rides along with the first group of its expiry; digitals of an expiry without one form a
-    group of their own (monitored at expiry), vanillas of such an expiry are left to the terminal-sample basket."""
+    group of their own (monitored at expiry), vanillas of such an expiry are left to the terminal-sample basket.
+    A group also shares its extremes mode.  A continuously monitored barrier or lookback has no dates of its own: it
+    joins the first group of its expiry in which nothing reads the extremes of the dates (no discrete barrier or
+    lookback: a group of Asians, say), and otherwise the expiry's group without dates, with the digitals."""
     groups: dict = {}
     for i, p in enumerate(payoffs):
         if isinstance(p, PATH_PAYOFFS) and path_monitoring(p, steps) is not None:
             groups.setdefault((p.expiry, path_monitoring(p, steps)), []).append(i)
     for i, p in enumerate(payoffs):
+        if path_extremes(p) == _ffi.HH_EXTREMES_BRIDGE:
+            key = next((k for k, idx in groups.items() if k[0] == p.expiry and k[1] is not None and
+                        all(path_extremes(payoffs[j]) is None for j in idx)), (p.expiry, None))
+            groups.setdefault(key, []).append(i)
+    for i, p in enumerate(payoffs):
         vanilla = isinstance(p, VanillaOption) and isinstance(p.exercise_style, European) and \
             isinstance(p.underlying, Spot) and not isinstance(p.strike, Dual)
-        if not (vanilla or (isinstance(p, PATH_PAYOFFS) and path_monitoring(p, steps) is None)):
+        if not (vanilla or (isinstance(p, PATH_PAYOFFS) and path_monitoring(p, steps) is None and path_extremes(p) is None)):
             continue
         key = next((k for k in groups if k[0] == p.expiry and k[1] is not None), None)
         if key is None and not vanilla:

@@ -1280,15 +1280,20 @@ static int begin_timing(hh_ctx* ctx) {
   return HH_OK;
 }
 
-// The checks of both entry points, then the statistics of every trajectory into ctx->path_stats (one timing slot).
+// rows of the statistics under `extremes` (enum hh_path_extremes, validated)
+static int path_stat_rows(int32_t extremes) { return extremes == HH_EXTREMES_BRIDGE ? HH_PATH_STATS_BRIDGE : HH_PATH_STATS; }
+
+// The checks of every entry point, then the statistics of every trajectory into ctx->path_stats (one timing slot).
 static int run_path_stats(hh_ctx* ctx, const char* who, const hh_model* m, const hh_config* c, uint32_t monitor_every,
-                          int32_t include_start) {
+                          int32_t include_start, int32_t extremes) {
   const bool hest = c->dynamics == HH_HESTON;
   if (c->strategy != HH_EULER_MARUYAMA || (c->dynamics != HH_LOGNORMAL && !hest))
     return fail(ctx, HH_ERR_UNSUPPORTED, "%s needs LognormalDynamics or HestonDynamics + EulerMaruyama", who);
   if (c->noise_mode == HH_NOISE_REPLAY || c->n_partials != 0)
     return fail(ctx, HH_ERR_UNSUPPORTED, "%s: GENERATE noise, no dual partials", who);
   if (c->noise_mode != HH_NOISE_GENERATE) return fail(ctx, HH_ERR_INVALID, "unknown noise_mode %d", c->noise_mode);
+  if (extremes != HH_EXTREMES_MONITORED && extremes != HH_EXTREMES_BRIDGE)
+    return fail(ctx, HH_ERR_INVALID, "%s: unknown extremes %d", who, extremes);
   if (c->n_paths == 0 || c->n_steps == 0 || c->n_paths > kMaxPaths / 2 || c->n_steps > kMaxEulerSteps)
     return fail(ctx, HH_ERR_INVALID, "%s: 1 <= n_paths <= 2^31 - 128, 1 <= n_steps <= %u", who, kMaxEulerSteps);
   if (monitor_every == 0 || c->n_steps % monitor_every != 0)
@@ -1300,26 +1305,31 @@ static int run_path_stats(hh_ctx* ctx, const char* who, const hh_model* m, const
                 !std::isfinite(m->theta))))
     return fail(ctx, HH_ERR_INVALID, "%s: S0, T > 0, |rho| <= 1, model scalars finite", who);
   int rc;
-  if ((rc = ensure(ctx, ctx->path_stats, hh::PathStatsLayout(c->n_paths, c->antithetic != 0).total))) return rc;
+  const hh::PathStatsLayout at(c->n_paths, c->antithetic != 0, path_stat_rows(extremes));
+  if ((rc = ensure(ctx, ctx->path_stats, at.total))) return rc;
   const uint64_t* seeds_dev = nullptr;
   if ((rc = stage_path_seeds(ctx, c, &seeds_dev))) return rc;
   if ((rc = begin_timing(ctx))) return rc;
-  HH_HIP(ctx, hh::launch_path_stats(*m, *c, seeds_dev, monitor_every, include_start != 0, ctx->path_stats, ctx->stream));
+  HH_HIP(ctx, hh::launch_path_stats(*m, *c, seeds_dev, monitor_every, include_start != 0, extremes == HH_EXTREMES_BRIDGE,
+                                    ctx->path_stats, ctx->stream));
   return end_timing(ctx);
 }
 
-int hh_mc_path_stats(hh_ctx* ctx, const hh_model* m, const hh_config* c, uint32_t monitor_every, int32_t include_start,
-                     double* stats, int32_t stats_on_device, hh_result* out) {
+// hh_mc_path_stats and hh_mc_path_stats_ex
+static int path_stats_call(hh_ctx* ctx, const char* who, const hh_model* m, const hh_config* c, uint32_t monitor_every,
+                           int32_t include_start, int32_t extremes, double* stats, int32_t stats_on_device,
+                           hh_result* out) {
   if (!ctx) return HH_ERR_INVALID;
   std::lock_guard<std::recursive_mutex> lock__(ctx->mu);
-  if (!m || !c || !stats) return fail(ctx, HH_ERR_INVALID, "hh_mc_path_stats: NULL argument");
+  if (!m || !c || !stats) return fail(ctx, HH_ERR_INVALID, "%s: NULL argument", who);
   const WallClock clock;
   HH_HIP(ctx, hipSetDevice(ctx->device));
   HH_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-  int rc = run_path_stats(ctx, "hh_mc_path_stats", m, c, monitor_every, include_start);
+  int rc = run_path_stats(ctx, who, m, c, monitor_every, include_start, extremes);
   if (rc) return rc;
   HH_HIP(ctx, hipEventRecord(ctx->ev1, ctx->stream));
-  HH_HIP(ctx, hipMemcpyAsync(stats, ctx->path_stats, hh::PathStatsLayout(c->n_paths, c->antithetic != 0).total * sizeof(double),
+  const hh::PathStatsLayout at(c->n_paths, c->antithetic != 0, path_stat_rows(extremes));
+  HH_HIP(ctx, hipMemcpyAsync(stats, ctx->path_stats, at.total * sizeof(double),
                              stats_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, ctx->stream));
   HH_HIP(ctx, hipStreamSynchronize(ctx->stream));
   if ((rc = release_host_operands(ctx))) return rc;
@@ -1329,36 +1339,50 @@ int hh_mc_path_stats(hh_ctx* ctx, const hh_model* m, const hh_config* c, uint32_
   return solve_times(ctx, clock, &out->kernel_ms, &out->total_ms);
 }
 
-int hh_mc_solve_path(hh_ctx* ctx, const hh_model* m, const hh_config* c, uint32_t monitor_every, int32_t include_start,
-                     const hh_path_payoff* payoffs, uint32_t n_payoffs, hh_result* out, double* path_values,
-                     double* stats) {
+int hh_mc_path_stats(hh_ctx* ctx, const hh_model* m, const hh_config* c, uint32_t monitor_every, int32_t include_start,
+                     double* stats, int32_t stats_on_device, hh_result* out) {
+  return path_stats_call(ctx, "hh_mc_path_stats", m, c, monitor_every, include_start, HH_EXTREMES_MONITORED, stats,
+                         stats_on_device, out);
+}
+
+int hh_mc_path_stats_ex(hh_ctx* ctx, const hh_model* m, const hh_config* c, uint32_t monitor_every, int32_t include_start,
+                        int32_t extremes, double* stats, int32_t stats_on_device, hh_result* out) {
+  return path_stats_call(ctx, "hh_mc_path_stats_ex", m, c, monitor_every, include_start, extremes, stats, stats_on_device,
+                         out);
+}
+
+// hh_mc_solve_path (kinds up to HH_PAYOFF_DIGITAL_ASSET) and hh_mc_solve_path_ex (the lookbacks too)
+static int solve_path_call(hh_ctx* ctx, const char* who, int32_t last_kind, const hh_model* m, const hh_config* c,
+                           uint32_t monitor_every, int32_t include_start, int32_t extremes, const hh_path_payoff* payoffs,
+                           uint32_t n_payoffs, hh_result* out, double* path_values, double* stats) {
   if (!ctx) return HH_ERR_INVALID;
   std::lock_guard<std::recursive_mutex> lock__(ctx->mu);
-  if (!m || !c || !payoffs || !out) return fail(ctx, HH_ERR_INVALID, "hh_mc_solve_path: NULL argument");
+  if (!m || !c || !payoffs || !out) return fail(ctx, HH_ERR_INVALID, "%s: NULL argument", who);
   if (n_payoffs == 0 || n_payoffs > HH_MAX_PATH_PAYOFFS)
-    return fail(ctx, HH_ERR_INVALID, "hh_mc_solve_path: 1 .. %d payoffs", HH_MAX_PATH_PAYOFFS);
+    return fail(ctx, HH_ERR_INVALID, "%s: 1 .. %d payoffs", who, HH_MAX_PATH_PAYOFFS);
   for (uint32_t k = 0; k < n_payoffs; ++k) {
     const hh_path_payoff& q = payoffs[k];
-    if (q.kind < HH_PAYOFF_VANILLA || q.kind > HH_PAYOFF_DIGITAL_ASSET)
-      return fail(ctx, HH_ERR_INVALID, "hh_mc_solve_path: payoff %u: unknown kind %d", k, q.kind);
+    if (q.kind < HH_PAYOFF_VANILLA || q.kind > last_kind)
+      return fail(ctx, HH_ERR_INVALID, "%s: payoff %u: unknown kind %d", who, k, q.kind);
     if (q.kind == HH_PAYOFF_BARRIER && (q.barrier_type < HH_BARRIER_UP_OUT || q.barrier_type > HH_BARRIER_DOWN_IN))
-      return fail(ctx, HH_ERR_INVALID, "hh_mc_solve_path: payoff %u: unknown barrier type %d", k, q.barrier_type);
-    if (q.cp != 1.0 && q.cp != -1.0) return fail(ctx, HH_ERR_INVALID, "hh_mc_solve_path: payoff %u: cp must be +1 or -1", k);
+      return fail(ctx, HH_ERR_INVALID, "%s: payoff %u: unknown barrier type %d", who, k, q.barrier_type);
+    if (q.cp != 1.0 && q.cp != -1.0) return fail(ctx, HH_ERR_INVALID, "%s: payoff %u: cp must be +1 or -1", who, k);
     if (!std::isfinite(q.strike) || !std::isfinite(q.rebate) || !std::isfinite(q.cash) || std::isnan(q.barrier))
-      return fail(ctx, HH_ERR_INVALID, "hh_mc_solve_path: payoff %u: strike, rebate, cash finite; barrier not NaN", k);
+      return fail(ctx, HH_ERR_INVALID, "%s: payoff %u: strike, rebate, cash finite; barrier not NaN", who, k);
   }
   const WallClock clock;
   HH_HIP(ctx, hipSetDevice(ctx->device));
   HH_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-  int rc = run_path_stats(ctx, "hh_mc_solve_path", m, c, monitor_every, include_start);
+  int rc = run_path_stats(ctx, who, m, c, monitor_every, include_start, extremes);
   if (rc) return rc;
 
-  const hh::PathStatsLayout at(c->n_paths, c->antithetic != 0);
+  const hh::PathStatsLayout at(c->n_paths, c->antithetic != 0, path_stat_rows(extremes));
   hh::PathPayoffArgs b{};
   b.stats = ctx->path_stats;
   b.n_paths = c->n_paths;
   b.n_chunks = hh::basket_chunks(c->n_paths);
   b.antithetic = c->antithetic;
+  b.extremes = extremes;
   b.n_mon = (double)(c->n_steps / monitor_every + (include_start ? 1u : 0u));
   if ((rc = stage_host(ctx, ctx->path_payoffs, (size_t)n_payoffs, payoffs, (size_t)n_payoffs, &b.payoffs))) return rc;
   const size_t n_acc = (size_t)n_payoffs * HH_ACC_LEN;
@@ -1386,6 +1410,20 @@ int hh_mc_solve_path(hh_ctx* ctx, const hh_model* m, const hh_config* c, uint32_
   if ((rc = solve_times(ctx, clock, &kernel_ms, &total_ms))) return rc;
   rc = finalize_results(m, 0, c, host.data(), n_payoffs, kernel_ms, total_ms, out);
   return rc ? fail(ctx, rc, "finalize failed: the accumulator holds no trajectories") : HH_OK;
+}
+
+int hh_mc_solve_path(hh_ctx* ctx, const hh_model* m, const hh_config* c, uint32_t monitor_every, int32_t include_start,
+                     const hh_path_payoff* payoffs, uint32_t n_payoffs, hh_result* out, double* path_values,
+                     double* stats) {
+  return solve_path_call(ctx, "hh_mc_solve_path", HH_PAYOFF_DIGITAL_ASSET, m, c, monitor_every, include_start,
+                         HH_EXTREMES_MONITORED, payoffs, n_payoffs, out, path_values, stats);
+}
+
+int hh_mc_solve_path_ex(hh_ctx* ctx, const hh_model* m, const hh_config* c, uint32_t monitor_every, int32_t include_start,
+                        int32_t extremes, const hh_path_payoff* payoffs, uint32_t n_payoffs, hh_result* out,
+                        double* path_values, double* stats) {
+  return solve_path_call(ctx, "hh_mc_solve_path_ex", HH_PAYOFF_LOOKBACK_FIXED, m, c, monitor_every, include_start, extremes,
+                         payoffs, n_payoffs, out, path_values, stats);
 }
 
 // ---- LSM on an ensemble sharded over several devices ------------------------------------------------

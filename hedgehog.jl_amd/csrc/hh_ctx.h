@@ -44,7 +44,7 @@ struct hh_ctx {
   hh::BkTableKey bk_table_key{};  // Bessel tables resident in bk_scratch (dropped by ensure_bk_scratch)
   DevBuf<double> lsm_grid;    // [n_steps+1][ntot]
   DevBuf<double> heston_var;  // [n_steps+1][n_paths] variance rows of the exact Heston grid
-  DevBuf<double> path_stats;           // hh::PathStatsLayout: [HH_PATH_STATS][n_total]
+  DevBuf<double> path_stats;           // hh::PathStatsLayout: [5 or 7 rows][n_total]
   DevBuf<double> path_values;          // [n_payoffs][n_total] payoffs per member (hh_mc_solve_path, when asked for)
   DevBuf<hh_path_payoff> path_payoffs; // [n_payoffs]
   DevBuf<double> lsm_val;

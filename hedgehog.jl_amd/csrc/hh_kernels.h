@@ -258,11 +258,12 @@ int launch_euler_grid(const hh_model& m, const hh_config& c, const uint64_t* see
 // Path-dependent payoffs (hh_path.hip).  The same trajectories as launch_euler_grid's (c: dynamics, em_split,
 // antithetic, n_paths, n_steps), reduced per trajectory to the HH_PATH_STATS numbers of PathStatsLayout over the
 // monitoring dates monitor_every, 2·monitor_every, …, n_steps (a divisor of n_steps) and, include_start, step 0.
+// bridge: the HH_PATH_STATS_BRIDGE numbers — the five, bit for bit, then the continuous extremes over all steps.
 int launch_path_stats(const hh_model& m, const hh_config& c, const uint64_t* seeds_dev, uint32_t monitor_every,
-                      bool include_start, double* stats, hipStream_t s);
+                      bool include_start, bool bridge, double* stats, hipStream_t s);
 // … and n_payoffs payoffs evaluated on them: one record per payoff and chunk, as launch_basket_payoffs leaves them
 struct PathPayoffArgs {
-  const double* stats;            // PathStatsLayout(n_paths, antithetic)
+  const double* stats;            // PathStatsLayout(n_paths, antithetic, rows of `extremes`)
   const hh_path_payoff* payoffs;  // device, [n_payoffs]
   double* values;                 // device or nullptr: [n_payoffs][n_total], each member's payoff
   double* records;                // [n_payoffs][n_chunks][kRecStride]
@@ -270,6 +271,7 @@ struct PathPayoffArgs {
   uint64_t n_paths;
   uint32_t n_chunks;              // basket_chunks(n_paths)
   int antithetic;
+  int extremes;                   // enum hh_path_extremes: which rows a payoff's MAX / MIN are
 };
 int launch_path_payoffs(const PathPayoffArgs& b, uint32_t n_payoffs, hipStream_t s);
 // form: kLsmFormPersistent = the whole backward induction in ONE launch when the ensemble fits the

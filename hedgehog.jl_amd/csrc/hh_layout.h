@@ -78,11 +78,12 @@ struct LsmScratch {
 
 // What path_stats_kernel leaves of every trajectory and path_payoff_kernel reads: one row per statistic (enum
 // hh_path_stat), step-major like the path grids — stats[stat][column], column i = trajectory i, column n_paths + i
-// its antithetic mirror.  Offsets in doubles.  (constexpr: the two kernels index with it too)
+// its antithetic mirror.  `rows`: HH_PATH_STATS, or HH_PATH_STATS_BRIDGE when the two continuous extremes follow the
+// five.  Offsets in doubles.  (constexpr: the two kernels index with it too)
 struct PathStatsLayout {
   size_t n_total, total;
-  constexpr PathStatsLayout(uint64_t n_paths, bool antithetic)
-      : n_total((size_t)n_paths * (antithetic ? 2 : 1)), total((size_t)HH_PATH_STATS * n_total) {}
+  constexpr PathStatsLayout(uint64_t n_paths, bool antithetic, int rows = HH_PATH_STATS)
+      : n_total((size_t)n_paths * (antithetic ? 2 : 1)), total((size_t)rows * n_total) {}
   constexpr size_t row(int stat) const { return (size_t)stat * n_total; }
 };
 

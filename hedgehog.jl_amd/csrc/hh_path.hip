@@ -1,9 +1,11 @@
-// Path-dependent payoffs on Euler–Maruyama paths for gfx950: arithmetic / geometric Asian, discretely monitored
-// barrier, digital (include/hedgehog_mc.h, "Path-dependent payoffs").  Two kernels:
+// Path-dependent payoffs on Euler–Maruyama paths for gfx950: arithmetic / geometric Asian, barrier (on the simulation's
+// dates, or continuously monitored by Brownian bridge), lookback, digital (include/hedgehog_mc.h, "Path-dependent
+// payoffs").  Two kernels:
 //
 //   path_stats_kernel   simulates the trajectories of euler_kernel / euler_grid_kernel — the draws, the correlation
 //                       and the step are hh_sim.h's, so every state is theirs bit for bit — and keeps, instead of a
-//                       grid, HH_PATH_STATS running numbers per trajectory over the monitoring dates;
+//                       grid, HH_PATH_STATS running numbers per trajectory over the monitoring dates — and, in its
+//                       bridge form, the maximum and minimum of the scheme's continuous interpolation as well;
 //   path_payoff_kernel  evaluates any number of payoffs on those numbers, as basket_payoff_kernel evaluates strikes
 //                       on terminal samples, and leaves one record of sums per payoff and chunk.
 //
@@ -15,7 +17,8 @@ namespace hh {
 namespace {
 
 // v_max_f64 / v_min_f64 as ONE instruction each: written with fmax / fmin the compiler first canonicalises the
-// loop-carried operand (v_max_f64 v, v, v), as in HestonModel::step.  No operand is ever NaN here.
+// loop-carried operand (v_max_f64 v, v, v), as in HestonModel::step.  No operand is ever NaN here, but for the one
+// case Extremes names, where the instruction's own rule (the other operand) is what is wanted.
 __device__ __forceinline__ double vmax(double a, double b) {
   double r;
   asm("v_max_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
@@ -55,12 +58,38 @@ struct Running {
   }
 };
 
+// The running extremes of the scheme's CONTINUOUS interpolation, in log space (the bridge form).  Between x0 and x1 an
+// Euler step with frozen diffusion coefficient g is a Brownian bridge of variance q = g²·dt, whose maximum and minimum
+// have the laws that one uniform each inverts:  ½(x0 + x1 ± sqrt((x1 - x0)² + q·L)),  L = -2 ln U.
+// The endpoint x1 goes in by itself, so cmax >= every state exactly whatever the formula's rounding.  q = 0 (a clipped
+// variance) gives the endpoints' max / min from the same formula; should x1 == x0 as well, sqrt_pos(0) is NaN, which
+// v_max_f64 / v_min_f64 drop in favour of their other operand: the endpoint is all there is.
+struct Extremes {
+  double cmax = 0.0, cmin = 0.0;
+  __device__ __forceinline__ void first(double x) { cmax = cmin = x; }  // time 0 always counts
+  __device__ __forceinline__ void next(double x0, double x1, double q, double Lmax, double Lmin) {
+    const double d = x1 - x0, d2 = d * d, m = x0 + x1;
+    const double up = 0.5 * (m + sqrt_pos(fma(q, Lmax, d2)));
+    const double dn = 0.5 * (m - sqrt_pos(fma(q, Lmin, d2)));
+    cmax = vmax(vmax(cmax, up), x1);
+    cmin = vmin(vmin(cmin, dn), x1);
+  }
+  __device__ __forceinline__ void store(double* __restrict__ stats, const PathStatsLayout& at, uint64_t col) const {
+    stats[at.row(HH_STAT_CMAX_S) + col] = exp(cmax);
+    stats[at.row(HH_STAT_CMIN_S) + col] = exp(cmin);
+  }
+};
+
 // One trajectory per lane (and its mirror, -dW, in the same lane: column n_paths + i), GENERATE noise, after
 // euler_grid_kernel.  The monitoring dates are the steps monitor_every, 2·monitor_every, …, n_steps — monitor_every
 // divides n_steps, so the last step is one, and S = exp(x) is formed there only, as euler_grid_kernel's `put` forms
 // it — and step 0 (S0, log S0: the grid's row 0) when include_start.  The countdown to the next date and the
 // "a first term is in" flag depend on kernel arguments alone: uniform branches.  No LDS.
-template <class M, bool ANTI>
+// BRIDGE: rows HH_STAT_CMAX_S, HH_STAT_CMIN_S as well (Extremes), over ALL steps whatever monitor_every; one more Philox
+// block and two logarithms per step (euler_bridge_draws), shared with the mirror: -dW has the negated bridge, the
+// excess of its maximum is the excess of the original's minimum, so the mirror's maximum takes L2 and its minimum L1.
+// The trajectory and the five statistics are the other form's, operation for operation.
+template <class M, bool ANTI, bool BRIDGE>
 __global__ __launch_bounds__(256) void path_stats_kernel(const SimArgs<0> a, const double S0,
                                                          const uint32_t monitor_every, const int include_start,
                                                          double* __restrict__ stats) {
@@ -68,7 +97,7 @@ __global__ __launch_bounds__(256) void path_stats_kernel(const SimArgs<0> a, con
   constexpr int NC = M::NCOMP;
   const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= a.n_paths) return;
-  const PathStatsLayout at(a.n_paths, ANTI);
+  const PathStatsLayout at(a.n_paths, ANTI, BRIDGE ? HH_PATH_STATS_BRIDGE : HH_PATH_STATS);
   const uint32_t n_steps = a.n_steps;
   State st, sa;
   M::init(st, a);
@@ -78,6 +107,11 @@ __global__ __launch_bounds__(256) void path_stats_kernel(const SimArgs<0> a, con
   if (started) {
     r.first(S0, a.x0.v);
     if constexpr (ANTI) ra.first(S0, a.x0.v);
+  }
+  Extremes e, ea;
+  if constexpr (BRIDGE) {
+    e.first(a.x0.v);
+    if constexpr (ANTI) ea.first(a.x0.v);
   }
   uint32_t left = monitor_every;
   auto date = [&]() {  // a step has been taken
@@ -94,33 +128,45 @@ __global__ __launch_bounds__(256) void path_stats_kernel(const SimArgs<0> a, con
     started = true;
   };
   const uint64_t key = a.seeds[i];  // montecarlo.jl:331
+  // step k: the trajectory and its mirror (montecarlo.jl:258: -W), the extremes of bridge k, the date
+  auto advance = [&](uint32_t k, double d1, double d2) {
+    if constexpr (BRIDGE) {
+      const double x0 = st.x.v;
+      double xa0 = 0.0, g, ga = 0.0;
+      if constexpr (ANTI) xa0 = sa.x.v;
+      M::step(st, a, d1, d2, g);
+      if constexpr (ANTI) M::step(sa, a, -d1, -d2, ga);
+      double L1, L2;
+      euler_bridge_draws(key, k, L1, L2);
+      e.next(x0, st.x.v, (g * g) * a.dt, L1, L2);
+      if constexpr (ANTI) ea.next(xa0, sa.x.v, (ga * ga) * a.dt, L2, L1);
+    } else {
+      M::step(st, a, d1, d2);
+      if constexpr (ANTI) M::step(sa, a, -d1, -d2);
+    }
+    date();
+  };
   if constexpr (NC == 2) {
     for (uint32_t s = 0; s < n_steps; ++s) {
       double d1, d2;
       euler_pair_increments(key, s, a, d1, d2);
-      M::step(st, a, d1, d2);
-      if constexpr (ANTI) M::step(sa, a, -d1, -d2);  // montecarlo.jl:258: -W
-      date();
+      advance(s, d1, d2);
     }
   } else {
     // scalar noise: one Philox block feeds two consecutive steps
     for (uint32_t s = 0; s < n_steps; s += 2) {
       double z1, z2;
       euler_scalar_normals(key, s >> 1, z1, z2);
-      const double d1 = a.sqrt_dt * z1;
-      M::step(st, a, d1, 0.0);
-      if constexpr (ANTI) M::step(sa, a, -d1, 0.0);
-      date();
-      if (s + 1 < n_steps) {
-        const double d2 = a.sqrt_dt * z2;
-        M::step(st, a, d2, 0.0);
-        if constexpr (ANTI) M::step(sa, a, -d2, 0.0);
-        date();
-      }
+      advance(s, a.sqrt_dt * z1, 0.0);
+      if (s + 1 < n_steps) advance(s + 1, a.sqrt_dt * z2, 0.0);
     }
   }
   r.store(stats, at, i);
   if constexpr (ANTI) ra.store(stats, at, a.n_paths + i);
+  if constexpr (BRIDGE) {
+    e.store(stats, at, i);
+    if constexpr (ANTI) ea.store(stats, at, a.n_paths + i);
+  }
 }
 
 // ------------------------------------------------------------------------------------------
@@ -150,6 +196,11 @@ __device__ __forceinline__ double path_payoff_of(const hh_path_payoff& q, const 
       const bool hit = up ? t[HH_STAT_MAX_S] >= q.barrier : t[HH_STAT_MIN_S] <= q.barrier;
       return hit == out ? q.rebate : van;  // knock-out: hit ? rebate : van;  knock-in: hit ? van : rebate
     }
+    case HH_PAYOFF_LOOKBACK_FLOAT: return q.cp > 0.0 ? S_T - t[HH_STAT_MIN_S] : t[HH_STAT_MAX_S] - S_T;
+    case HH_PAYOFF_LOOKBACK_FIXED: {
+      const double m = q.cp > 0.0 ? t[HH_STAT_MAX_S] - q.strike : q.strike - t[HH_STAT_MIN_S];
+      return m > 0.0 ? m : 0.0;
+    }
     case HH_PAYOFF_DIGITAL_CASH: return mT > 0.0 ? q.cash : 0.0;
     case HH_PAYOFF_DIGITAL_ASSET: return mT > 0.0 ? S_T : 0.0;
     default: return van;  // HH_PAYOFF_VANILLA (the entry point admits no other kind)
@@ -160,6 +211,8 @@ __device__ __forceinline__ double path_payoff_of(const hh_path_payoff& q, const 
 // so each XCD's L2 holds one eighth of the statistics for all payoffs): a workgroup loads the five statistics of a
 // trajectory (and of its mirror) once and evaluates every payoff of its group on them from registers.  Each payoff
 // keeps its own accumulators, lane order and record: its sums are those of a one-payoff launch bit for bit.
+// b.extremes (uniform) says which rows a payoff's MAX / MIN are: the monitored ones, or — HH_EXTREMES_BRIDGE, a
+// seven-row buffer — the continuous ones, loaded into the same two slots; nothing else differs between the modes.
 __global__ __launch_bounds__(256) void path_payoff_kernel(const PathPayoffArgs b, const uint32_t n_payoffs) {
   const uint32_t per_xcd = (b.n_chunks + 7u) / 8u;  // chunks an XCD owns
   const uint32_t xcd = blockIdx.x & 7u, idx = blockIdx.x >> 3;
@@ -170,7 +223,9 @@ __global__ __launch_bounds__(256) void path_payoff_kernel(const PathPayoffArgs b
 #pragma unroll
   for (int g = 0; g < kPathKB; ++g) q[g] = b.payoffs[min(k0 + g, n_payoffs - 1)];  // a short last group repeats its last payoff
   const bool anti = b.antithetic != 0;
-  const PathStatsLayout at(b.n_paths, anti);
+  const bool cont = b.extremes == HH_EXTREMES_BRIDGE;
+  const PathStatsLayout at(b.n_paths, anti, cont ? HH_PATH_STATS_BRIDGE : HH_PATH_STATS);
+  const int row_max = cont ? HH_STAT_CMAX_S : HH_STAT_MAX_S, row_min = cont ? HH_STAT_CMIN_S : HH_STAT_MIN_S;
   double acc[kPathKB][2];
 #pragma unroll
   for (int g = 0; g < kPathKB; ++g) acc[g][0] = acc[g][1] = 0.0;
@@ -181,8 +236,9 @@ __global__ __launch_bounds__(256) void path_payoff_kernel(const PathPayoffArgs b
     double t[HH_PATH_STATS], ta[HH_PATH_STATS];
 #pragma unroll
     for (int s = 0; s < HH_PATH_STATS; ++s) {
-      t[s] = b.stats[at.row(s) + i];
-      ta[s] = anti ? b.stats[at.row(s) + b.n_paths + i] : 0.0;
+      const int row = s == HH_STAT_MAX_S ? row_max : s == HH_STAT_MIN_S ? row_min : s;
+      t[s] = b.stats[at.row(row) + i];
+      ta[s] = anti ? b.stats[at.row(row) + b.n_paths + i] : 0.0;
     }
 #pragma unroll
     for (int g = 0; g < kPathKB; ++g) {
@@ -209,18 +265,22 @@ __global__ __launch_bounds__(256) void path_payoff_kernel(const PathPayoffArgs b
 }  // namespace
 
 int launch_path_stats(const hh_model& m, const hh_config& c, const uint64_t* seeds_dev, uint32_t monitor_every,
-                      bool include_start, double* stats, hipStream_t s) {
+                      bool include_start, bool bridge, double* stats, hipStream_t s) {
   DevicePtrs p{};
   p.seeds = seeds_dev;
   const SimArgs<0> a = make_args0(m, c, p);
   const dim3 g((unsigned)((c.n_paths + 255) / 256)), blk(256);
-  auto go = [&](auto model, auto anti) {
-    hipLaunchKernelGGL((path_stats_kernel<decltype(model), decltype(anti)::value>), g, blk, 0, s, a, m.S0,
-                       monitor_every, (int)include_start, stats);
+  auto go = [&](auto model, auto anti, auto br) {
+    hipLaunchKernelGGL((path_stats_kernel<decltype(model), decltype(anti)::value, decltype(br)::value>), g, blk, 0, s, a,
+                       m.S0, monitor_every, (int)include_start, stats);
+  };
+  auto with_form = [&](auto model, auto anti) {
+    if (bridge) go(model, anti, std::true_type{});
+    else go(model, anti, std::false_type{});
   };
   auto with_anti = [&](auto model) {
-    if (c.antithetic) go(model, std::true_type{});
-    else go(model, std::false_type{});
+    if (c.antithetic) with_form(model, std::true_type{});
+    else with_form(model, std::false_type{});
   };
   if (c.dynamics == HH_LOGNORMAL) with_anti(GbmModel<0>{});
   else if (c.em_split) with_anti(HestonModel<0, true>{});

@@ -49,6 +49,12 @@ struct HestonModel {
   }
   __device__ static __forceinline__ void step(State& s, const SimArgs<P>& a, double dW1,
                                               double dW2) {
+    double g;
+    step(s, a, dW1, dW2, g);
+  }
+  // … handing out g, the diffusion coefficient the step puts on dW1: sqrt of the clipped variance at K (SPLIT) or at u.
+  // Frozen over the step, so between x and x' the scheme's own interpolation is a Brownian bridge of variance g²·dt.
+  __device__ static __forceinline__ void step(State& s, const SimArgs<P>& a, double dW1, double dW2, double& g) {
     const bool pos = s.v.v > 0.0;
     // v+ = max(v, 0) as ONE v_max_f64: written `pos ? v : 0` (or fmax) the compiler first canonicalises the
     // loop-carried v with v_max_f64 v, v, v — an instruction per path-step where the kernel issues one per cycle
@@ -98,6 +104,7 @@ struct HestonModel {
     }
     s.x.v = fma(sq, dW1, Kx);
     s.v.v = fma(a.sigma.v * sq, dW2, Kv);
+    g = sq;
   }
 };
 
@@ -116,6 +123,10 @@ struct GbmModel {
         s.x.d[k] = fma(a.sigma.d[k], dW, fma(a.dt, a.gdrift.d[k], s.x.d[k]));
     }
     s.x.v = fma(a.sigma.v, dW, fma(a.dt, a.gdrift.v, s.x.v));
+  }
+  __device__ static __forceinline__ void step(State& s, const SimArgs<P>& a, double dW, double, double& g) {
+    step(s, a, dW, 0.0);
+    g = a.sigma.v;
   }
 };
 
@@ -138,6 +149,15 @@ __device__ __forceinline__ void euler_pair_increments(uint64_t key, uint32_t s, 
 // one component (lognormal): one Philox pair per two steps — step 2h takes sqrt(dt)·z1, step 2h+1 sqrt(dt)·z2
 __device__ __forceinline__ void euler_scalar_normals(uint64_t key, uint32_t h, double& z1, double& z2) {
   normal_pair(key, h, 0u, 0u, kDomEuler, z1, z2);
+}
+
+// The two draws of step k's Brownian bridge (path_stats_kernel's bridge form): one more Philox block per step under
+// the trajectory's key — counter (k, 0, 0, kDomBridge) — as L1 = -2 ln U1, L2 = -2 ln U2 with U1 = u01(c0, c1),
+// U2 = u01(c2, c3).  Independent of every Euler increment (another domain) and of each other.
+__device__ __forceinline__ void euler_bridge_draws(uint64_t key, uint32_t k, double& L1, double& L2) {
+  const Philox4 b = philox4x32_10(k, 0u, 0u, kDomBridge, (uint32_t)key, (uint32_t)(key >> 32));
+  L1 = neg2_log_unit(u01_fast(b.c0, b.c1));
+  L2 = neg2_log_unit(u01_fast(b.c2, b.c3));
 }
 
 // ------------------------------------------------------------------------------------------

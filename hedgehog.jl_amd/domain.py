@@ -79,9 +79,14 @@ class UpAndIn: pass
 class DownAndOut: pass
 class DownAndIn: pass
 class AssetOrNothing: pass
+class ContinuousMonitoring:
+    """A barrier or a lookback watched at every instant of [0, expiry]: the maximum and minimum of the scheme's own
+    continuous interpolation, sampled by Brownian bridge between the simulation's steps (include/hedgehog_mc.h,
+    HH_EXTREMES_BRIDGE).  Takes no dates: it fits whatever `Monitoring` the averages of the same solve have."""
 
 
-for _c in (ArithmeticAverage, GeometricAverage, UpAndOut, UpAndIn, DownAndOut, DownAndIn, AssetOrNothing):
+for _c in (ArithmeticAverage, GeometricAverage, UpAndOut, UpAndIn, DownAndOut, DownAndIn, AssetOrNothing,
+           ContinuousMonitoring):
     _tag_eq(_c)
 
 
@@ -132,14 +137,15 @@ class AsianOption:
 class BarrierOption:
     """A vanilla payoff knocked out or in when the spot touches the barrier on a monitoring date (a touch counts:
     max S >= barrier for the up types, min S <= barrier for the down types); `rebate` is paid AT EXPIRY on the
-    paths that are knocked out (or never knocked in)."""
+    paths that are knocked out (or never knocked in).  monitoring: a `Monitoring` (dates of the simulation) or
+    `ContinuousMonitoring()`."""
     strike: Any
     barrier: Any
     expiry: int
     call_put: Any
     barrier_type: Any
     rebate: Any
-    monitoring: Monitoring
+    monitoring: Any
 
     def __init__(self, strike, barrier, expiry_date, call_put, barrier_type, rebate=0.0, monitoring=None):
         object.__setattr__(self, "strike", strike)
@@ -149,7 +155,8 @@ class BarrierOption:
         object.__setattr__(self, "barrier_type", _of(barrier_type, (UpAndOut, UpAndIn, DownAndOut, DownAndIn),
                                                      "barrier_type"))
         object.__setattr__(self, "rebate", rebate)
-        object.__setattr__(self, "monitoring", _of(monitoring or Monitoring(), (Monitoring,), "monitoring"))
+        object.__setattr__(self, "monitoring", _of(monitoring or Monitoring(), (Monitoring, ContinuousMonitoring),
+                                                   "monitoring"))
 
 
 @dataclass(frozen=True)
@@ -167,7 +174,25 @@ class DigitalOption:
         object.__setattr__(self, "payout", _of(payout or CashOrNothing(), (CashOrNothing, AssetOrNothing), "payout"))
 
 
-PATH_PAYOFFS = (AsianOption, BarrierOption, DigitalOption)
+@dataclass(frozen=True)
+class LookbackOption:
+    """strike=None, floating: a call pays S_T − min S, a put max S − S_T.  With a strike, fixed: a call pays
+    max(max S − strike, 0), a put max(strike − min S, 0).  The extremes run over the dates of a `Monitoring` or, with
+    `ContinuousMonitoring()`, over all of [0, expiry]."""
+    expiry: int
+    call_put: Any
+    strike: Any
+    monitoring: Any
+
+    def __init__(self, expiry_date, call_put, strike=None, monitoring=None):
+        object.__setattr__(self, "expiry", to_ticks(expiry_date))
+        object.__setattr__(self, "call_put", _of(call_put, (Call, Put), "call_put"))
+        object.__setattr__(self, "strike", strike)
+        object.__setattr__(self, "monitoring", _of(monitoring or Monitoring(), (Monitoring, ContinuousMonitoring),
+                                                   "monitoring"))
+
+
+PATH_PAYOFFS = (AsianOption, BarrierOption, DigitalOption, LookbackOption)
 
 
 # ---- rate curve / vol surface (flat only) ----

@@ -15,7 +15,8 @@ from . import _ffi
 from .dates import yearfrac
 from .dual import Dual, n_partials, partials_of, value_of
 from .domain import (PATH_PAYOFFS, ArithmeticAverage, AsianOption, BarrierOption, BlackScholesInputs, Call,
-                    CashOrNothing, DigitalOption, DownAndIn, DownAndOut, European, HestonInputs, Monitoring,
+                    CashOrNothing, ContinuousMonitoring, DigitalOption, DownAndIn, DownAndOut, European, HestonInputs,
+                    LookbackOption, Monitoring,
                     MonteCarloSolution, PricingProblem, Spot, UpAndIn, UpAndOut, VanillaOption, _DeviceSamples, df,
                     get_vol, zero_rate)
 
@@ -308,21 +309,34 @@ def path_monitoring(payoff, steps):
     """(monitor_every, include_start) of a payoff, or None for one that reads the state at expiry alone (a digital, a
     European vanilla: it fits any monitoring).  ValueError when `every` does not divide the simulation's steps."""
     mon = getattr(payoff, "monitoring", None)
-    if mon is None:
+    if mon is None or isinstance(mon, ContinuousMonitoring):  # continuous extremes run over every step
         return None
     if steps % mon.every != 0:
         raise ValueError(f"Monitoring.every ({mon.every}) must divide SimulationConfig.steps ({steps})")
     return mon.every, mon.include_start
 
 
+def path_extremes(payoff):
+    """enum hh_path_extremes of a payoff that reads the trajectory's maximum or minimum (a barrier, a lookback):
+    HH_EXTREMES_BRIDGE under ContinuousMonitoring, HH_EXTREMES_MONITORED on the dates of a Monitoring.  None for every
+    other payoff: it fits either."""
+    if not isinstance(payoff, (BarrierOption, LookbackOption)):
+        return None
+    cont = isinstance(payoff.monitoring, ContinuousMonitoring)
+    return _ffi.HH_EXTREMES_BRIDGE if cont else _ffi.HH_EXTREMES_MONITORED
+
+
 def pack_path_payoff(payoff) -> _ffi.hh_path_payoff:
-    """One payoff of hh_mc_solve_path.  A Dual in a field is refused: these solves carry no partials."""
+    """One payoff of hh_mc_solve_path / hh_mc_solve_path_ex.  A Dual in a field is refused: these solves carry no
+    partials."""
     q = _ffi.hh_path_payoff()
     fields = [getattr(payoff, n, 0.0) for n in ("strike", "barrier", "rebate")] + [getattr(getattr(payoff, "payout", None), "cash", 0.0)]
     if any(isinstance(v, Dual) for v in fields):
         raise MethodError("path-dependent payoffs carry no dual partials: use FiniteDifference")
-    q.strike, q.cp = float(payoff.strike), payoff.call_put()
-    if isinstance(payoff, AsianOption):
+    q.strike, q.cp = float(0.0 if payoff.strike is None else payoff.strike), payoff.call_put()
+    if isinstance(payoff, LookbackOption):  # strike=None: floating, the strike field is not read
+        q.kind = _ffi.HH_PAYOFF_LOOKBACK_FLOAT if payoff.strike is None else _ffi.HH_PAYOFF_LOOKBACK_FIXED
+    elif isinstance(payoff, AsianOption):
         arith = isinstance(payoff.averaging, ArithmeticAverage)
         q.kind = _ffi.HH_PAYOFF_ASIAN_ARITH if arith else _ffi.HH_PAYOFF_ASIAN_GEOM
     elif isinstance(payoff, BarrierOption):
@@ -364,19 +378,30 @@ def _path_structs(payoffs, market_inputs, method: MonteCarlo):
 
 
 def solve_path_payoffs(payoffs, market_inputs, method: MonteCarlo, ensemble: bool = True):
-    """Payoffs that share an expiry and a monitoring on ONE simulation (hh_mc_solve_path): a MonteCarloSolution each,
-    in order.  `ensemble`: the (5, n_total) statistics of the trajectories (rows: enum hh_path_stat), shared by the
-    solutions; n_total counts the antithetic mirrors, columns trajectories + i."""
+    """Payoffs that share an expiry, a monitoring and an extremes mode on ONE simulation: a MonteCarloSolution each, in
+    order.  hh_mc_solve_path as long as no payoff is a lookback or continuously monitored; hh_mc_solve_path_ex otherwise.
+    `ensemble`: the (5, n_total) statistics of the trajectories — (7, n_total) in bridge mode — (rows: enum
+    hh_path_stat), shared by the solutions; n_total counts the antithetic mirrors, columns trajectories + i."""
     model, c, every, start, _ = _path_structs(payoffs, market_inputs, method)
+    modes = {e for e in (path_extremes(p) for p in payoffs) if e is not None}
+    if len(modes) > 1:
+        raise ValueError("payoffs of one path solve share an extremes mode (Monitoring or ContinuousMonitoring)")
+    extremes = modes.pop() if modes else _ffi.HH_EXTREMES_MONITORED
+    bridge = extremes == _ffi.HH_EXTREMES_BRIDGE
+    extended = bridge or any(isinstance(p, LookbackOption) for p in payoffs)
     packed = (_ffi.hh_path_payoff * len(payoffs))(*[pack_path_payoff(p) for p in payoffs])
     cfg = method.config
     ctx = _ffi.get_context(method.device)
     c.seeds, c.seeds_on_device, c.seeds_len = cfg.device_seeds(ctx), 1, cfg.seeds.size
     n_total = int(c.n_paths) * (2 if c.antithetic else 1)
-    stats = np.empty((_ffi.HH_PATH_STATS, n_total)) if ensemble else None
+    stats = np.empty((_ffi.HH_PATH_STATS_BRIDGE if bridge else _ffi.HH_PATH_STATS, n_total)) if ensemble else None
     res = (_ffi.hh_result * len(payoffs))()
-    ctx.check(ctx.lib.hh_mc_solve_path(ctx.handle, C.byref(model), C.byref(c), every, int(start), packed, len(payoffs),
-                                       res, None, stats.ctypes.data if ensemble else None))
+    if extended:
+        ctx.check(ctx.lib.hh_mc_solve_path_ex(ctx.handle, C.byref(model), C.byref(c), every, int(start), extremes, packed,
+                                              len(payoffs), res, None, stats.ctypes.data if ensemble else None))
+    else:
+        ctx.check(ctx.lib.hh_mc_solve_path(ctx.handle, C.byref(model), C.byref(c), every, int(start), packed,
+                                           len(payoffs), res, None, stats.ctypes.data if ensemble else None))
     return [MonteCarloSolution(PricingProblem(p, market_inputs), method, res[k].price, stats,
                                std_error=res[k].std_error, result=res[k]) for k, p in enumerate(payoffs)]
 

@@ -609,12 +609,48 @@ int hh_lsm_solve_euler(hh_ctx* ctx, const hh_model* model, const hh_config* cfg,
  * or cash that is not finite (a barrier may be ±inf: never / always hit), cp other than ±1, NULL arguments.
  * Not provided: an accumulate (asynchronous) form and a multi-GPU form, REPLAY noise, dual partials (bump the inputs
  * instead: the solves of a finite difference share their seeds), a Julia binding.
+ *
+ * CONTINUOUS MONITORING AND LOOKBACKS: hh_mc_path_stats_ex, hh_mc_solve_path_ex.  The two calls above with one more
+ * argument, `extremes` (enum hh_path_extremes), which says what MAX and MIN of a trajectory are:
+ *   HH_EXTREMES_MONITORED  HH_STAT_MAX_S / HH_STAT_MIN_S: the spot on the monitoring dates, as above.  The same
+ *                          kernels, five rows: for kinds 0 .. 5 the call IS hh_mc_solve_path, bit for bit.
+ *   HH_EXTREMES_BRIDGE     HH_STAT_CMAX_S / HH_STAT_CMIN_S: the maximum and minimum over [0, T] of the scheme's own
+ *                          continuous interpolation.  The statistics are HH_PATH_STATS_BRIDGE = 7 rows of n_total: the
+ *                          five above, bit for bit, then these two.
+ * Both modes admit two more kinds, which read MAX / MIN of the mode as HH_PAYOFF_BARRIER does (a touch counts):
+ *   HH_PAYOFF_LOOKBACK_FLOAT  call: S_T − MIN;                   put: MAX − S_T;               strike is not read
+ *   HH_PAYOFF_LOOKBACK_FIXED  call: max(MAX − strike, 0);        put: max(strike − MIN, 0)
+ * Kinds 0 .. 2, 4 and 5 read neither: under HH_EXTREMES_BRIDGE they are what they are under HH_EXTREMES_MONITORED.
+ * The bridge.  An Euler–Maruyama step k takes log S from x_k to x_{k+1} with a diffusion coefficient g_k that is frozen
+ * over the step — sigma (lognormal); sqrt of the clipped variance at the drift-updated state (Heston, em_split) or at
+ * the step's initial state (em_split = 0) — so between the two states the scheme's interpolation is a Brownian bridge
+ * of variance q = g_k²·dt, and the maximum and the minimum of a bridge have closed-form laws that one uniform each
+ * inverts.  With Δ = x_{k+1} − x_k and L_i = −2 ln U_i:
+ *   M_k = ½·(x_k + x_{k+1} + sqrt(Δ² + q·L_1))          m_k = ½·(x_k + x_{k+1} − sqrt(Δ² + q·L_2))
+ * U_1, U_2: one more Philox4x32-10 block per step under the trajectory's seed as key, counter (k, 0, 0, 3) — the 3 is a
+ * domain of its own, no Euler increment shares a block with it — U_1 from output words 0, 1 and U_2 from words 2, 3,
+ * each ((w >> 12) + ½)·2⁻⁵² of the 64-bit word w = (hi << 32) | lo.  The mirror (−dW) of an antithetic pair has the
+ * negated bridge: its maximum takes L_2 and its minimum L_1, on its own states and its own g̃_k; nothing more is drawn.
+ * The running extremes start at log S0 — time 0 always counts, whatever include_start says about the sums — and take
+ * cmax = max(cmax, M_k, x_{k+1}), cmin = min(cmin, m_k, x_{k+1}) at EVERY step: monitor_every governs the sums and the
+ * discrete rows only.  HH_STAT_CMAX_S = exp(cmax), HH_STAT_CMIN_S = exp(cmin).  g_k = 0 (a clipped variance) gives the
+ * larger / smaller endpoint.  Under lognormal dynamics the extremes are exact in law (the step is); under Heston they
+ * are exact for the scheme's interpolation, not for the model.
+ * Each extreme has its exact marginal law, but U_1 and U_2 are independent: the JOINT law of a step's maximum and
+ * minimum is not reproduced, so nothing that needs both at once — a double barrier — is offered.
+ * Arguments, outputs, errors (with these functions' names in the texts) and timing slots are those of the pair above;
+ * an unknown `extremes` is HH_ERR_INVALID, an unknown kind is one outside 0 .. 7.  stats: 5 or 7 rows by the mode.
+ * No Julia binding, as for the pair above.
  */
 enum hh_path_payoff_kind { HH_PAYOFF_VANILLA = 0, HH_PAYOFF_ASIAN_ARITH = 1, HH_PAYOFF_ASIAN_GEOM = 2,
-                           HH_PAYOFF_BARRIER = 3, HH_PAYOFF_DIGITAL_CASH = 4, HH_PAYOFF_DIGITAL_ASSET = 5 };
+                           HH_PAYOFF_BARRIER = 3, HH_PAYOFF_DIGITAL_CASH = 4, HH_PAYOFF_DIGITAL_ASSET = 5,
+                           HH_PAYOFF_LOOKBACK_FLOAT = 6, HH_PAYOFF_LOOKBACK_FIXED = 7 /* the _ex entry points only */ };
 enum hh_barrier_type { HH_BARRIER_UP_OUT = 0, HH_BARRIER_UP_IN = 1, HH_BARRIER_DOWN_OUT = 2, HH_BARRIER_DOWN_IN = 3 };
-enum hh_path_stat { HH_STAT_SUM_S = 0, HH_STAT_SUM_X = 1, HH_STAT_MAX_S = 2, HH_STAT_MIN_S = 3, HH_STAT_S_T = 4 };
+enum hh_path_stat { HH_STAT_SUM_S = 0, HH_STAT_SUM_X = 1, HH_STAT_MAX_S = 2, HH_STAT_MIN_S = 3, HH_STAT_S_T = 4,
+                    HH_STAT_CMAX_S = 5, HH_STAT_CMIN_S = 6 /* HH_EXTREMES_BRIDGE only */ };
+enum hh_path_extremes { HH_EXTREMES_MONITORED = 0, HH_EXTREMES_BRIDGE = 1 };
 #define HH_PATH_STATS 5
+#define HH_PATH_STATS_BRIDGE 7 /* the five, then HH_STAT_CMAX_S = 5, HH_STAT_CMIN_S = 6 */
 #define HH_MAX_PATH_PAYOFFS 1024
 typedef struct hh_path_payoff {
   int32_t kind, barrier_type;  /* enum hh_path_payoff_kind; enum hh_barrier_type (HH_PAYOFF_BARRIER only) */
@@ -625,6 +661,12 @@ int hh_mc_path_stats(hh_ctx* ctx, const hh_model* model, const hh_config* cfg, u
 int hh_mc_solve_path(hh_ctx* ctx, const hh_model* model, const hh_config* cfg, uint32_t monitor_every,
                      int32_t include_start, const hh_path_payoff* payoffs, uint32_t n_payoffs, hh_result* out,
                      double* path_values, double* stats);
+int hh_mc_path_stats_ex(hh_ctx* ctx, const hh_model* model, const hh_config* cfg, uint32_t monitor_every,
+                        int32_t include_start, int32_t extremes, double* stats, int32_t stats_on_device,
+                        hh_result* out);
+int hh_mc_solve_path_ex(hh_ctx* ctx, const hh_model* model, const hh_config* cfg, uint32_t monitor_every,
+                        int32_t include_start, int32_t extremes, const hh_path_payoff* payoffs, uint32_t n_payoffs,
+                        hh_result* out, double* path_values, double* stats);
 
 /*
  * The same solve for an ensemble SHARDED over several devices (one process and one hh_ctx per
