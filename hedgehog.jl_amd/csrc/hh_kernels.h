@@ -126,11 +126,11 @@ inline uint32_t basket_chunks(uint64_t n_paths) {
 }
 
 // The exact-law kernels (one normal, one exp per trajectory — no time loop to amortise a workgroup's reduction
-// over) give a lane ONE pair of trajectories in a small ensemble and kExactPairs / kExactPairsHuge pairs in a
-// large / huge one: a workgroup of 256 lanes then leaves ONE record per 512 / 4096 / 32768 trajectories, the
-// chip always has >= 2048 workgroups to run and the reducer at most a few thousand records to add.  The form is
-// a function of the shard's n_paths alone, so a result is reproducible for a given (n_paths, sharding) as
-// everywhere else.
+// over) give a lane kExactPairsSmall (4) pairs of trajectories in a small ensemble and kExactPairs (8) /
+// kExactPairsHuge (64) pairs in a large / huge one: a workgroup of 256 lanes then leaves ONE record per 2048 / 4096 /
+// 32768 trajectories, a large ensemble always has >= 2048 workgroups to run and the reducer at most a few thousand
+// records to add.  The form is a function of the shard's n_paths alone, so a result is reproducible for a given
+// (n_paths, sharding) as everywhere else.
 constexpr int kExactPairs = 8, kExactPairsHuge = 64;
 constexpr int kExactPairsSmall = 4;  // below 2048·512·8 trajectories (profiles/r06_c_exact_pairs_ab.txt)
 int exact_pairs_per_lane(uint64_t n_paths);

@@ -516,8 +516,8 @@ static PartialMap classify_partials(const hh_model& m, const hh_config& c) {
   return pm;
 }
 
-// Pairs of trajectories per lane of the exact-law kernels: 1 / 2 / 4 in a small ensemble (kExactPairsSmall),
-// kExactPairs / kExactPairsHuge in a large / huge one.  A function of n_paths alone — every launcher and every
+// Pairs of trajectories per lane of the exact-law kernels: kExactPairsSmall (4) in a small ensemble,
+// kExactPairs (8) / kExactPairsHuge (64) in a large / huge one.  A function of n_paths alone — every launcher and every
 // record count in the library asks here.
 int exact_pairs_per_lane(uint64_t n_paths) {
   return n_paths >= (uint64_t)2048 * 512 * kExactPairsHuge ? kExactPairsHuge
@@ -619,9 +619,7 @@ static int launch_sim_p(const hh_model& m, const hh_config& c, const DevicePtrs&
       const int pairs = exact_pairs_per_lane(c.n_paths);
       return pairs == kExactPairsHuge ? exact_gbm_kernel<P, R, A, kExactPairsHuge>
              : pairs == kExactPairs   ? exact_gbm_kernel<P, R, A, kExactPairs>
-             : pairs == 4             ? exact_gbm_kernel<P, R, A, 4>
-             : pairs == 2             ? exact_gbm_kernel<P, R, A, 2>
-                                      : exact_gbm_kernel<P, R, A, 1>;
+                                      : exact_gbm_kernel<P, R, A, kExactPairsSmall>;
     };
     using T = std::true_type;
     using F = std::false_type;

@@ -249,9 +249,7 @@ static int launch_multi(const hh_model* models, const hh_config& c, const Device
       const int pairs = exact_pairs_per_lane(c.n_paths);
       return pairs == kExactPairsHuge ? exact_multi_kernel<R, A, K, kExactPairsHuge>
              : pairs == kExactPairs   ? exact_multi_kernel<R, A, K, kExactPairs>
-             : pairs == 4             ? exact_multi_kernel<R, A, K, 4>
-             : pairs == 2             ? exact_multi_kernel<R, A, K, 2>
-                                      : exact_multi_kernel<R, A, K, 1>;
+                                      : exact_multi_kernel<R, A, K, kExactPairsSmall>;
     };
     using T = std::true_type;
     using F = std::false_type;

@@ -215,8 +215,9 @@ def _e64(got, want):
     return float(abs(mp.mpf(got) - want))
 
 
-def reference(case, payoffs):
-    """Both runs of `case` and what the tests need of them.  ->
+def reference(case, payoffs, run=run):
+    """Both runs of `case` (by `run`: this module's scheme, or another law with the same output, as
+    oracle/lognormal_exact.py's) and what the tests need of them.  ->
       n, members         paths, members per path (2 when antithetic)
       S[m][i]            50-digit S_T of member m of path i;  S_e64, S_A: float arrays [m][i]
       clip_fraction      share of (member, step) pairs with v <= 0 (Heston)

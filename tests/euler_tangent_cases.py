@@ -99,6 +99,38 @@ def assembled(seeds, values, bars):
     return want, float(sum(abs(float(s)) * bars[1 + j] for j, s in enumerate(seeds)))
 
 
+def assert_bars_are_fp64_sized(ref, anti, limit, skip=()):
+    """The bars of a reference against the VALUES they guard: what tests/test_euler_tangent_exact_host.py::
+    test_bars_are_fp64_sized states, for any reference of euler_exact.reference's form.  `skip`: slots the caller
+    holds against another scale."""
+    ratios = []
+    for pj in ref["payoffs"]:
+        u = np.flatnonzero(pj["usable"])
+        bars = path_bar(pj["price_e64"], pj["price_A"])[u]
+        vals = np.array([[abs(float(t)) for t in row] for row in pj["price"]])[u]
+        if not vals[:, 0].any():  # out of the money on every path: exact zeros, to be reproduced exactly
+            assert not bars.any()
+            continue
+        sums, sbar = sum_of(pj["price"], pj["price_e64"], pj["price_A"], [int(i) for i in u], anti)
+        for s, slot in enumerate(("price",) + SLOTS):
+            if slot in skip:
+                continue
+            nz = vals[:, s] > 0
+            scale = np.median(vals[nz, s]) if nz.any() else np.median(vals[vals[:, 0] > 0, 0])
+            assert np.all(bars[:, s] <= limit * np.maximum(vals[:, s], scale)), slot
+            ratios.append(bars[nz, s] / vals[nz, s])
+            mag = vals[:, s].sum()
+            assert sbar[s] <= limit * max(mag, scale), slot
+            if abs(float(sums[s])) >= mag / 10:
+                assert sbar[s] <= limit * max(abs(float(sums[s])), scale), slot
+    ratios = np.concatenate(ratios)
+    assert np.median(ratios) <= 1e-11
+    assert np.mean(ratios <= 1e-9) >= 0.95
+    sbar = path_bar(ref["S_e64"], ref["S_A"])
+    S = np.array([[float(t) for t in row] for row in ref["S"]])
+    assert np.all(sbar <= 1e-10 * S)
+
+
 class Worst:
     """worst error/bar per kind of comparison, for the line a module prints at its end"""
 

@@ -99,32 +99,7 @@ def test_bars_are_fp64_sized(name):
     to 1.1e-9·Σ|terms|.  Every other case: at most 1.9e-10 and 8.5e-11.
     S_T: every bar below 1e-10·S_T (measured: at most 2.3e-11, at 50 steps)."""
     case = BY_ID[name]
-    ref = etc.reference(case)
-    limit = 1e-9 if case["n_steps"] <= 16 else 1e-8
-    ratios = []
-    for pj in ref["payoffs"]:
-        u = np.flatnonzero(pj["usable"])
-        bars = etc.path_bar(pj["price_e64"], pj["price_A"])[u]
-        vals = np.array([[abs(float(t)) for t in row] for row in pj["price"]])[u]
-        if not vals[:, 0].any():  # out of the money on every path: exact zeros, to be reproduced exactly
-            assert not bars.any()
-            continue
-        sums, sbar = etc.sum_of(pj["price"], pj["price_e64"], pj["price_A"], [int(i) for i in u], int(case["antithetic"]))
-        for s, slot in enumerate(("price",) + SLOTS):
-            nz = vals[:, s] > 0
-            scale = np.median(vals[nz, s]) if nz.any() else np.median(vals[vals[:, 0] > 0, 0])
-            assert np.all(bars[:, s] <= limit * np.maximum(vals[:, s], scale)), slot
-            ratios.append(bars[nz, s] / vals[nz, s])
-            mag = vals[:, s].sum()
-            assert sbar[s] <= limit * max(mag, scale), slot
-            if abs(float(sums[s])) >= mag / 10:
-                assert sbar[s] <= limit * max(abs(float(sums[s])), scale), slot
-    ratios = np.concatenate(ratios)
-    assert np.median(ratios) <= 1e-11
-    assert np.mean(ratios <= 1e-9) >= 0.95
-    sbar = etc.path_bar(ref["S_e64"], ref["S_A"])
-    S = np.array([[float(t) for t in row] for row in ref["S"]])
-    assert np.all(sbar <= 1e-10 * S)
+    etc.assert_bars_are_fp64_sized(etc.reference(case), int(case["antithetic"]), 1e-9 if case["n_steps"] <= 16 else 1e-8)
 
 
 @pytest.mark.parametrize("name", IDS)

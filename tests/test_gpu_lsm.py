@@ -38,6 +38,7 @@ def test_lsm_matches_oracle(hhlib, anti, cp, K, degree, n, steps):
     S0, r, sigma, T = (120.0 if cp > 0 else 100.0), (0.15 if cp > 0 else 0.05), 0.25, 0.75
     res, tau, val, grid, D = gpu_lsm(hhlib, S0, K, r, sigma, T, cp, seeds, steps, anti, degree)
     ref_grid = lsm_oracle.gbm_grid(seeds, steps, S0, r, sigma, T, anti)
+    # 1e-12 against the C oracle is a round figure; the grid's derived bar: test_gpu_lognormal_exact.py::test_lsm_path_grid
     np.testing.assert_allclose(grid, ref_grid, rtol=1e-12)
     ref = lsm_oracle.lsm_solve(ref_grid, K, cp, D, degree)
     assert res.n_paths_total == grid.shape[1]
@@ -209,6 +210,7 @@ if given is not None:
         seeds = np.random.default_rng(seed).integers(0, 2**63, n).astype(np.uint64)
         res, tau, val, grid, D = gpu_lsm(hhlib, S0, K, r, sigma, T, cp, seeds, steps, int(anti), degree)
         ref_grid = lsm_oracle.gbm_grid(seeds, steps, S0, r, sigma, T, int(anti))
+        # (a round figure; the derived bar is test_gpu_lognormal_exact.py::test_lsm_path_grid's)
         np.testing.assert_allclose(grid, ref_grid, rtol=1e-12)
         ref = lsm_oracle.lsm_solve(ref_grid, K, cp, D, degree)
         assert np.isfinite(res.price) and res.price >= 0.0

@@ -112,6 +112,23 @@ def test_multi_above_the_small_grid_and_with_a_ragged_tile(hhlib, oracle):
         assert all(same_bits(a[0], b[0]) for a, b in zip(solve_each(hhlib, models, c, False), solve_multi(hhlib, models, c, False)))
 
 
+@pytest.mark.parametrize("n_paths", [2048 * 512 * 8 + 700, 2048 * 512 * 64 + 513])
+@pytest.mark.parametrize("anti", [0, 1])
+@pytest.mark.parametrize("K", [2, 4])
+def test_exact_law_multi_in_the_large_lane_forms(hhlib, K, anti, n_paths):
+    """exact_multi_kernel gives a lane 4, 8 or 64 pairs of trajectories by the ensemble's size (exact_pairs_per_lane);
+    every other test here launches the 4-pair form.  The first sizes of the 8- and 64-pair forms, each with a ragged
+    last workgroup, GENERATE: every model's sums are those of its own hh_mc_solve, bit for bit.  No terminals."""
+    models = bumped_models(GBM, K, same_noise_law=False)
+    c = o.make_config(GBM, EXACT, n_paths, 1, antithetic=anti, seeds=np.array([77], dtype=np.uint64), path_offset=3)
+    each = solve_each(hhlib, models, c, False)
+    multi = solve_multi(hhlib, models, c, False)
+    for k, ((r1, _), (rk, _)) in enumerate(zip(each, multi)):
+        assert same_bits(r1, rk), k
+        assert rk.n_paths_done == n_paths
+    assert len({np.float64(r.price).tobytes() for r, _ in multi}) == K
+
+
 def test_multi_path_major_replay_and_device_buffers(hhlib, oracle):
     ctx = hhlib
     n_paths, n_steps = 256 * 12 + 3, 8
