@@ -6,8 +6,8 @@ Import as `hedgehog_jl_amd` (shim at the repository root; the directory name car
 """
 from . import _ffi
 from ._ffi import Context, HedgehogMCError, get_context, load_library
-from .analytic import (AnalyticSolution, BlackScholesAnalytic, CarrMadan, solve_black_scholes,
-                       solve_carr_madan)
+from .analytic import (AnalyticSolution, BlackScholesAnalytic, CarrMadan, MertonAnalytic, merton_series,
+                       solve_black_scholes, solve_carr_madan, solve_merton_analytic)
 from .basket import BasketPricingProblem, BasketPricingSolution, solve_basket
 from .trees import CoxRossRubinsteinMethod, CRRSolution, solve_crr, solve_crr_basket
 from .dates import Date, DateTime, add_years, to_ticks, yearfrac
@@ -19,13 +19,14 @@ from .greeks import (BatchGreekProblem, FDBackward, FDCentral, FDForward, Finite
 from .lsm import (LSM, EulerPaths, HestonExactPaths, LSMSolution, simulate_euler_paths,
                   simulate_heston_exact_paths, solve_lsm)
 from .montecarlo import (AbstractPricingMethod, Antithetic, BlackScholesExact, EulerMaruyama,
-                         HestonBroadieKaya, HestonDynamics, LognormalDynamics, MethodError,
+                         HestonBroadieKaya, HestonDynamics, LognormalDynamics, MertonDynamics, MertonExact, MethodError,
                          MonteCarlo, NoVarianceReduction, NormalLaw, SimulationConfig, marginal_law,
                          solve_montecarlo, solve_montecarlo_many, solve_path_payoffs)
 from .distributed import rank_device, shard_range, solve_lsm_sharded, solve_sharded
 from .domain import (American, ArithmeticAverage, AsianOption, AssetOrNothing, BarrierOption, BlackScholesInputs,
                     Call, CashOrNothing, ContinuousMonitoring, DigitalOption, DownAndIn, DownAndOut, European,
-                    FlatRateCurve, FlatVolSurface, Forward, GeometricAverage, HestonInputs, LookbackOption, Monitoring,
+                    FlatRateCurve, FlatVolSurface, Forward, GeometricAverage, HestonInputs, LookbackOption, MertonInputs,
+                    Monitoring,
                     MonteCarloSolution,
                     PricingProblem, Put, RateCurve, Spot, UpAndIn, UpAndOut, VanillaOption, df, df_yf, get_vol,
                     spine_zeros, zero_rate, zero_rate_yf)
@@ -43,6 +44,8 @@ def solve(*args, **kw):
         solve(gprob::BatchGreekProblem, ::GreekMethod, method)               greeks_problem.jl:559
         solve(prob::BasketPricingProblem, method::MonteCarlo | ::CarrMadan)  basket.jl:35
         solve(prob, ::CarrMadan) / solve(prob, ::BlackScholesAnalytic)       carr_madan.jl:47, black_scholes.jl:38
+        solve(prob::PricingProblem{…, MertonInputs}, ::MonteCarlo(MertonDynamics(), MertonExact() | EulerMaruyama(), …)
+              | ::CarrMadan(α, bound, MertonDynamics()) | ::MertonAnalytic)   Merton jump diffusion (no reference method)
         solve(prob::PricingProblem{<:VanillaOption{…,American,…}}, ::LSM)     least_squares_montecarlo.jl:99
         solve(prob::PricingProblem{<:VanillaOption}, ::CoxRossRubinsteinMethod) cox_ross_rubinstein.jl:99
         solve(prob::BasketPricingProblem, ::CoxRossRubinsteinMethod)         basket.jl:35
@@ -55,6 +58,8 @@ def solve(*args, **kw):
     if len(args) == 2 and isinstance(args[0], PricingProblem) and \
             isinstance(args[1], BlackScholesAnalytic):
         return solve_black_scholes(args[0], args[1])
+    if len(args) == 2 and isinstance(args[0], PricingProblem) and isinstance(args[1], MertonAnalytic):
+        return solve_merton_analytic(args[0], args[1])
     if len(args) == 2 and isinstance(args[0], PricingProblem) and isinstance(args[1], LSM):
         return solve_lsm(args[0], args[1], **kw)
     if len(args) == 2 and isinstance(args[0], PricingProblem) and isinstance(args[1], CoxRossRubinsteinMethod):

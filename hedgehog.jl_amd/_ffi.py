@@ -30,6 +30,8 @@ HH_EXTREMES_MONITORED, HH_EXTREMES_BRIDGE = 0, 1
 HH_PATH_STATS = 5
 HH_PATH_STATS_BRIDGE = 7
 HH_MAX_PATH_PAYOFFS = 1024
+HH_JUMP_MAX_MEAN = 64.0
+HH_JUMP_MAX_COUNT = 255
 
 HH_OK, HH_ERR_INVALID, HH_ERR_UNSUPPORTED, HH_ERR_HIP, HH_ERR_NOMEM, HH_ERR_RCCL, HH_ERR_DEVICE_TIMEOUT = 0, -1, -2, -3, -4, -5, -6
 HH_MGPU_AUTO, HH_MGPU_HOST_SUM, HH_MGPU_RCCL = 0, 1, 2
@@ -87,6 +89,11 @@ class hh_lsm_result(C.Structure):
 class hh_path_payoff(C.Structure):
     _fields_ = [("kind", C.c_int32), ("barrier_type", C.c_int32), ("strike", C.c_double), ("cp", C.c_double),
                 ("barrier", C.c_double), ("rebate", C.c_double), ("cash", C.c_double)]
+
+
+class hh_jump(C.Structure):
+    """The Merton jump parameters: intensity λ, mean μ_J and standard deviation σ_J of one jump in log S."""
+    _fields_ = [("lambda_", C.c_double), ("mu_j", C.c_double), ("sigma_j", C.c_double)]
 
 
 HH_BK_ROOT_SECANT, HH_BK_ROOT_ORDER2 = 0, 1
@@ -155,6 +162,12 @@ SYMBOLS = [
                                       C.c_int32, C.POINTER(hh_result)]),
     ("hh_mc_solve_path_ex", C.c_int, [_vp, C.POINTER(hh_model), C.POINTER(hh_config), C.c_uint32, C.c_int32, C.c_int32,
                                       C.POINTER(hh_path_payoff), C.c_uint32, C.POINTER(hh_result), _vp, _vp]),
+    ("hh_mc_solve_jump", C.c_int, [_vp, C.POINTER(hh_model), C.POINTER(hh_jump), C.POINTER(hh_config), C.POINTER(hh_result),
+                                   _vp]),
+    ("hh_mc_solve_path_jump", C.c_int, [_vp, C.POINTER(hh_model), C.POINTER(hh_jump), C.POINTER(hh_config), C.c_uint32,
+                                        C.c_int32, C.POINTER(hh_path_payoff), C.c_uint32, C.POINTER(hh_result), _vp, _vp]),
+    ("hh_carr_madan_jump", C.c_int, [_vp, C.POINTER(hh_model), C.POINTER(hh_jump), C.c_double, C.c_double,
+                                     _vp, _vp, _vp, _vp, _vp, C.c_uint32, _vp]),
     ("hh_lsm_shard_xchg_elems", C.c_size_t, [C.c_uint32, C.c_int32]),
     ("hh_lsm_shard_begin", C.c_int, [_vp, C.POINTER(hh_model), C.POINTER(hh_config), C.c_int32, C.c_double, _vp]),
     ("hh_lsm_shard_phase", C.c_int, [_vp, C.c_int32, C.c_uint32, _vp, _vp]),
@@ -514,6 +527,13 @@ def make_model(S0=100.0, V0=0.04, kappa=2.0, theta=0.04, sigma=0.3, rho=-0.7, r=
         setattr(m, "d" + name, C.cast(arr, C.POINTER(C.c_double)))
     m._keep = keep
     return m
+
+
+def make_jump(lam=0.0, mu_j=0.0, sigma_j=0.0):
+    """hh_jump from plain numbers (`lambda` is a Python keyword: the field is `lambda_`)."""
+    j = hh_jump()
+    j.lambda_, j.mu_j, j.sigma_j = lam, mu_j, sigma_j
+    return j
 
 
 def make_config(dynamics, strategy, n_paths, n_steps=1, antithetic=0, em_split=1, noise_mode=0,

@@ -6,6 +6,8 @@ so that such scripts run unchanged:
   CarrMadan(α, bound, dynamics)
                          /root/reference/src/pricing_methods/carr_madan.jl:15-92 — the Fourier
                          integral runs on the device (`hh_carr_madan`, csrc/hh_fourier.hip)
+  MertonAnalytic(n_terms) Merton's (1976) series for a European vanilla under jump diffusion (the reference has no
+                         jump model): a Poisson-weighted sum of Black prices, scalar code on the host
 """
 from __future__ import annotations
 
@@ -16,9 +18,9 @@ from typing import Any
 
 from . import _ffi
 from .dates import yearfrac
-from .domain import (BlackScholesInputs, European, HestonInputs, PricingProblem, VanillaOption, df,
+from .domain import (BlackScholesInputs, European, HestonInputs, MertonInputs, PricingProblem, VanillaOption, df,
                      get_vol, zero_rate)
-from .montecarlo import AbstractPricingMethod, HestonDynamics, LognormalDynamics, MethodError
+from .montecarlo import AbstractPricingMethod, HestonDynamics, LognormalDynamics, MertonDynamics, MethodError
 
 
 @dataclass(frozen=True)
@@ -70,6 +72,75 @@ def solve_black_scholes(prob: PricingProblem, method: BlackScholesAnalytic) -> A
     return AnalyticSolution(prob, method, price)
 
 
+@dataclass(frozen=True)
+class MertonAnalytic(AbstractPricingMethod):
+    """Merton's series, truncated after n_terms Poisson weights (the weight of term n is e^{−λT}(λT)ⁿ/n!)."""
+    n_terms: int = 200
+
+
+def merton_series(S0, K, cp, sigma, lam, mu_j, sigma_j, T, D, n_terms=200, term=None):
+    """Σ_n e^{−λT}(λT)ⁿ/n! · term(M_n, V_n): the jump count is Poisson(λT), and given n jumps log S_T is normal with
+    mean M_n = log S0 − log D + (−σ²/2 − λκ̄)T + n·μ_J and variance V_n = σ²T + n·σ_J², κ̄ = exp(μ_J + σ_J²/2) − 1.
+    term (default): the discounted Black price D·cp·(e^{M+V/2}·Φ(cp·d1) − K·Φ(cp·d2)), intrinsic where V = 0."""
+    def black(M, V):
+        F = math.exp(M + 0.5 * V)
+        if V <= 0.0:
+            return D * max(cp * (F - K), 0.0)
+        sd = math.sqrt(V)
+        d2 = (M - math.log(K)) / sd
+        return D * cp * (F * _ncdf(cp * (d2 + sd)) - K * _ncdf(cp * d2))
+    term = term or black
+    kbar = math.expm1(mu_j + 0.5 * sigma_j * sigma_j)
+    M0 = math.log(S0) - math.log(D) + (-0.5 * sigma * sigma - lam * kbar) * T
+    w, total = math.exp(-lam * T), 0.0
+    for n in range(int(n_terms)):
+        if n:
+            w = w * (lam * T) / n
+        total += w * term(M0 + n * mu_j, sigma * sigma * T + n * sigma_j * sigma_j)
+    return total
+
+
+def solve_merton_analytic(prob: PricingProblem, method: MertonAnalytic) -> AnalyticSolution:
+    payoff, m = prob.payoff, prob.market_inputs
+    if not (isinstance(payoff, VanillaOption) and isinstance(payoff.exercise_style, European)
+            and isinstance(m, MertonInputs)):
+        raise MethodError("MertonAnalytic: European VanillaOption on MertonInputs")
+    T = yearfrac(m.referenceDate, payoff.expiry)
+    price = merton_series(float(m.spot), float(payoff.strike), payoff.call_put(), float(get_vol(m.sigma, None, None)),
+                          float(m.jump_intensity), float(m.jump_mean), float(m.jump_std), T,
+                          float(df(m.rate, payoff.expiry)), method.n_terms)
+    return AnalyticSolution(prob, method, price)
+
+
+def _solve_carr_madan_merton(payoffs, m, method: CarrMadan):
+    """CarrMadan(α, bound, MertonDynamics()) on MertonInputs: every payoff's integral in one launch
+    (`hh_carr_madan_jump`).  No gradient form: a Dual anywhere is a MethodError."""
+    import numpy as np
+    from .dual import Dual
+    if not (isinstance(method.dynamics, MertonDynamics) and isinstance(m, MertonInputs)):
+        raise MethodError("no marginal_law for this dynamics / market-input pair")
+    vol = get_vol(m.sigma, None, None)
+    r_k = [zero_rate(m.rate, p.expiry) for p in payoffs]
+    D_k = [df(m.rate, p.expiry) for p in payoffs]
+    scal = [m.spot, vol, m.jump_intensity, m.jump_mean, m.jump_std, *r_k, *D_k, *(p.strike for p in payoffs)]
+    if any(isinstance(v, Dual) for v in scal):
+        raise MethodError("CarrMadan under MertonDynamics carries no dual partials: use FiniteDifference")
+    model = _ffi.hh_model()
+    model.S0, model.sigma = float(m.spot), float(vol)
+    jump = _ffi.make_jump(float(m.jump_intensity), float(m.jump_mean), float(m.jump_std))
+    K = len(payoffs)
+    strikes = np.array([float(p.strike) for p in payoffs])
+    cps = np.array([p.call_put() for p in payoffs], dtype=np.float64)
+    Ts = np.array([yearfrac(m.rate.reference_date, p.expiry) for p in payoffs])
+    rs, Ds = np.array([float(x) for x in r_k]), np.array([float(x) for x in D_k])
+    out = np.empty(K)
+    ctx = _ffi.get_context(method.device)
+    ctx.check(ctx.lib.hh_carr_madan_jump(ctx.handle, C.byref(model), C.byref(jump), float(method.α), float(method.bound),
+                                         strikes.ctypes.data, cps.ctypes.data, Ts.ctypes.data, rs.ctypes.data,
+                                         Ds.ctypes.data, K, out.ctypes.data))
+    return out
+
+
 def _carr_madan_model(m, method: CarrMadan):
     """The model scalars every payoff on these market inputs shares (marginal_law, montecarlo.jl:293-320)
     -> (hh_model of their VALUES, dynamics, the scalars themselves — possibly Dual — in the order of
@@ -103,6 +174,8 @@ def solve_carr_madan_basket(payoffs, market_inputs, method: CarrMadan):
         if not (isinstance(payoff, VanillaOption) and isinstance(payoff.exercise_style, European)):
             raise MethodError("CarrMadan: European VanillaOption")
     from .dual import Dual, n_partials, partials_of, value_of
+    if isinstance(method.dynamics, MertonDynamics) or isinstance(m, MertonInputs):
+        return _solve_carr_madan_merton(payoffs, m, method)
     model, dyn, scal = _carr_madan_model(m, method)
     K = len(payoffs)
     if any(isinstance(p.strike, Dual) for p in payoffs):
@@ -141,6 +214,8 @@ def solve_carr_madan(prob: PricingProblem, method: CarrMadan) -> AnalyticSolutio
     if not (isinstance(payoff, VanillaOption) and isinstance(payoff.exercise_style, European)):
         raise MethodError("CarrMadan: European VanillaOption")
     from .dual import n_partials
+    if isinstance(method.dynamics, MertonDynamics) or isinstance(m, MertonInputs):  # a basket of one
+        return AnalyticSolution(prob, method, float(_solve_carr_madan_merton([payoff], m, method)[0]))
     model, dyn, scal = _carr_madan_model(m, method)
     r_k, D_k = zero_rate(m.rate, payoff.expiry), df(m.rate, payoff.expiry)
     if n_partials(*scal, r_k, D_k) > 0:

@@ -1283,10 +1283,28 @@ static int begin_timing(hh_ctx* ctx) {
 // rows of the statistics under `extremes` (enum hh_path_extremes, validated)
 static int path_stat_rows(int32_t extremes) { return extremes == HH_EXTREMES_BRIDGE ? HH_PATH_STATS_BRIDGE : HH_PATH_STATS; }
 
+// The jump parameters of a Merton entry point (`who`); span: what one Poisson draw covers (T, or T/n_steps).
+static int check_jump(hh_ctx* ctx, const char* who, const hh_jump* jump, double span) {
+  if (!(jump->lambda >= 0.0) || !std::isfinite(jump->lambda))
+    return fail(ctx, HH_ERR_INVALID, "%s: jump lambda must be finite and >= 0", who);
+  if (!(jump->sigma_j >= 0.0) || !std::isfinite(jump->sigma_j))
+    return fail(ctx, HH_ERR_INVALID, "%s: jump sigma_j must be finite and >= 0", who);
+  if (!std::isfinite(jump->mu_j)) return fail(ctx, HH_ERR_INVALID, "%s: jump mu_j must be finite", who);
+  if (!std::isfinite(hh::merton_compensator(*jump)))
+    return fail(ctx, HH_ERR_INVALID, "%s: exp(mu_j + sigma_j^2/2) must be finite", who);
+  if (!(jump->lambda * span <= HH_JUMP_MAX_MEAN))
+    return fail(ctx, HH_ERR_INVALID, "%s: the Poisson mean of one draw, lambda * %g = %g, is above HH_JUMP_MAX_MEAN = %g", who,
+                span, jump->lambda * span, (double)HH_JUMP_MAX_MEAN);
+  return HH_OK;
+}
+
 // The checks of every entry point, then the statistics of every trajectory into ctx->path_stats (one timing slot).
+// jump (NULL: none): the Merton form — lognormal dynamics, the monitored rows.
 static int run_path_stats(hh_ctx* ctx, const char* who, const hh_model* m, const hh_config* c, uint32_t monitor_every,
-                          int32_t include_start, int32_t extremes) {
+                          int32_t include_start, int32_t extremes, const hh_jump* jump = nullptr) {
   const bool hest = c->dynamics == HH_HESTON;
+  if (jump && (hest || c->strategy != HH_EULER_MARUYAMA))
+    return fail(ctx, HH_ERR_UNSUPPORTED, "%s needs LognormalDynamics + EulerMaruyama", who);
   if (c->strategy != HH_EULER_MARUYAMA || (c->dynamics != HH_LOGNORMAL && !hest))
     return fail(ctx, HH_ERR_UNSUPPORTED, "%s needs LognormalDynamics or HestonDynamics + EulerMaruyama", who);
   if (c->noise_mode == HH_NOISE_REPLAY || c->n_partials != 0)
@@ -1305,13 +1323,17 @@ static int run_path_stats(hh_ctx* ctx, const char* who, const hh_model* m, const
                 !std::isfinite(m->theta))))
     return fail(ctx, HH_ERR_INVALID, "%s: S0, T > 0, |rho| <= 1, model scalars finite", who);
   int rc;
+  if (jump && (rc = check_jump(ctx, who, jump, m->T / (double)c->n_steps))) return rc;
   const hh::PathStatsLayout at(c->n_paths, c->antithetic != 0, path_stat_rows(extremes));
   if ((rc = ensure(ctx, ctx->path_stats, at.total))) return rc;
   const uint64_t* seeds_dev = nullptr;
   if ((rc = stage_path_seeds(ctx, c, &seeds_dev))) return rc;
   if ((rc = begin_timing(ctx))) return rc;
-  HH_HIP(ctx, hh::launch_path_stats(*m, *c, seeds_dev, monitor_every, include_start != 0, extremes == HH_EXTREMES_BRIDGE,
-                                    ctx->path_stats, ctx->stream));
+  if (jump)
+    HH_HIP(ctx, hh::launch_jump_stats(*m, *c, *jump, seeds_dev, monitor_every, include_start != 0, ctx->path_stats, ctx->stream));
+  else
+    HH_HIP(ctx, hh::launch_path_stats(*m, *c, seeds_dev, monitor_every, include_start != 0, extremes == HH_EXTREMES_BRIDGE,
+                                      ctx->path_stats, ctx->stream));
   return end_timing(ctx);
 }
 
@@ -1351,10 +1373,12 @@ int hh_mc_path_stats_ex(hh_ctx* ctx, const hh_model* m, const hh_config* c, uint
                          out);
 }
 
-// hh_mc_solve_path (kinds up to HH_PAYOFF_DIGITAL_ASSET) and hh_mc_solve_path_ex (the lookbacks too)
+// hh_mc_solve_path (kinds up to HH_PAYOFF_DIGITAL_ASSET), hh_mc_solve_path_ex (the lookbacks too) and, with `jump`,
+// hh_mc_solve_path_jump
 static int solve_path_call(hh_ctx* ctx, const char* who, int32_t last_kind, const hh_model* m, const hh_config* c,
                            uint32_t monitor_every, int32_t include_start, int32_t extremes, const hh_path_payoff* payoffs,
-                           uint32_t n_payoffs, hh_result* out, double* path_values, double* stats) {
+                           uint32_t n_payoffs, hh_result* out, double* path_values, double* stats,
+                           const hh_jump* jump = nullptr) {
   if (!ctx) return HH_ERR_INVALID;
   std::lock_guard<std::recursive_mutex> lock__(ctx->mu);
   if (!m || !c || !payoffs || !out) return fail(ctx, HH_ERR_INVALID, "%s: NULL argument", who);
@@ -1373,7 +1397,7 @@ static int solve_path_call(hh_ctx* ctx, const char* who, int32_t last_kind, cons
   const WallClock clock;
   HH_HIP(ctx, hipSetDevice(ctx->device));
   HH_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-  int rc = run_path_stats(ctx, who, m, c, monitor_every, include_start, extremes);
+  int rc = run_path_stats(ctx, who, m, c, monitor_every, include_start, extremes, jump);
   if (rc) return rc;
 
   const hh::PathStatsLayout at(c->n_paths, c->antithetic != 0, path_stat_rows(extremes));
@@ -1424,6 +1448,87 @@ int hh_mc_solve_path_ex(hh_ctx* ctx, const hh_model* m, const hh_config* c, uint
                         double* path_values, double* stats) {
   return solve_path_call(ctx, "hh_mc_solve_path_ex", HH_PAYOFF_LOOKBACK_FIXED, m, c, monitor_every, include_start, extremes,
                          payoffs, n_payoffs, out, path_values, stats);
+}
+
+// ---- Merton jump diffusion (hedgehog_mc.h, "Merton (1976) jump diffusion"; kernels: hh_jump.hip, hh_fourier.hip) ----
+
+int hh_mc_solve_path_jump(hh_ctx* ctx, const hh_model* m, const hh_jump* jump, const hh_config* c, uint32_t monitor_every,
+                          int32_t include_start, const hh_path_payoff* payoffs, uint32_t n_payoffs, hh_result* out,
+                          double* path_values, double* stats) {
+  if (!ctx) return HH_ERR_INVALID;
+  std::lock_guard<std::recursive_mutex> lock__(ctx->mu);
+  if (!jump) return fail(ctx, HH_ERR_INVALID, "hh_mc_solve_path_jump: NULL argument");
+  return solve_path_call(ctx, "hh_mc_solve_path_jump", HH_PAYOFF_LOOKBACK_FIXED, m, c, monitor_every, include_start,
+                         HH_EXTREMES_MONITORED, payoffs, n_payoffs, out, path_values, stats, jump);
+}
+
+int hh_mc_solve_jump(hh_ctx* ctx, const hh_model* m, const hh_jump* jump, const hh_config* c, hh_result* out,
+                     double* terminal) {
+  if (!ctx) return HH_ERR_INVALID;
+  std::lock_guard<std::recursive_mutex> lock__(ctx->mu);
+  const char* who = "hh_mc_solve_jump";
+  if (!m || !jump || !c || !out) return fail(ctx, HH_ERR_INVALID, "%s: NULL argument", who);
+  if (c->dynamics == HH_HESTON || c->strategy == HH_EULER_MARUYAMA || c->strategy == HH_BROADIE_KAYA)
+    return fail(ctx, HH_ERR_UNSUPPORTED, "%s needs LognormalDynamics + the exact law (HH_EXACT_LAW)", who);
+  if (c->noise_mode == HH_NOISE_REPLAY || c->n_partials != 0)
+    return fail(ctx, HH_ERR_UNSUPPORTED, "%s: GENERATE noise, no dual partials", who);
+  int rc = validate(ctx, m, c);
+  if (rc) return rc;
+  if ((rc = check_jump(ctx, who, jump, m->T))) return rc;
+  const WallClock clock;
+  std::memset(out, 0, sizeof(*out));
+  HH_HIP(ctx, hipSetDevice(ctx->device));
+  HH_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+  const uint32_t n_rec = hh::merton_records(c->n_paths);
+  if ((rc = ensure(ctx, ctx->records, (size_t)n_rec * hh::kRecStride))) return rc;
+  hh::DevicePtrs p{};
+  p.records = ctx->records;
+  if ((rc = stage_noise(ctx, c, p, false))) return rc;  // seeds[0]
+  if (terminal && c->terminal_on_device) {
+    p.terminal = terminal;
+  } else if (terminal) {
+    if ((rc = ensure(ctx, ctx->terminal, (size_t)c->n_paths * (c->antithetic ? 2 : 1)))) return rc;
+    p.terminal = ctx->terminal;
+  }
+  if ((rc = begin_timing(ctx))) return rc;
+  HH_HIP(ctx, hh::launch_merton_exact(*m, *c, *jump, p, ctx->stream));
+  HH_HIP(ctx, hh::launch_reduce_records(ctx->records, n_rec, (double)c->n_paths, ctx->accum, ctx->stream, 1, m, c));
+  if ((rc = end_timing(ctx))) return rc;
+  HH_HIP(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+  HH_HIP(ctx, hipMemcpyAsync(ctx->accum_host, ctx->accum, HH_ACC_LEN * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  HH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  if ((rc = release_host_operands(ctx))) return rc;
+  if ((rc = copy_back_terminal(ctx, c, terminal))) return rc;
+  rc = hh_mc_finalize(m, c, ctx->accum_host, out);
+  if (rc) return fail(ctx, rc, "finalize failed: the accumulator holds no trajectories");
+  return solve_times(ctx, clock, &out->kernel_ms, &out->total_ms);
+}
+
+int hh_carr_madan_jump(hh_ctx* ctx, const hh_model* m, const hh_jump* jump, double alpha, double bound,
+                       const double* strikes, const double* cps, const double* Ts, const double* r_drifts,
+                       const double* discounts, uint32_t n_payoffs, double* prices_out) {
+  if (!ctx) return HH_ERR_INVALID;
+  std::lock_guard<std::recursive_mutex> lock__(ctx->mu);
+  const char* who = "hh_carr_madan_jump";
+  if (!m || !jump || !strikes || !cps || !Ts || !r_drifts || !discounts || !prices_out)
+    return fail(ctx, HH_ERR_INVALID, "%s: NULL argument", who);
+  if (n_payoffs == 0 || n_payoffs > (1u << 20)) return fail(ctx, HH_ERR_INVALID, "%s: 1 .. 2^20 payoffs per call", who);
+  if (!(m->S0 > 0.0) || !std::isfinite(m->S0) || !std::isfinite(m->sigma) || !(alpha > 0.0) || !(bound > 0.0))
+    return fail(ctx, HH_ERR_INVALID, "%s: bad scalars", who);
+  int rc = check_jump(ctx, who, jump, 0.0);  // no draw here: the mean of one is not limited
+  if (rc) return rc;
+  if (!hh::carr_madan_subpanels(alpha, bound)) return fail(ctx, HH_ERR_INVALID, HH_CM_BOUND_MSG, who);
+  const size_t n = n_payoffs;
+  std::vector<double> host(5 * n);  // log K | T | r_drift | discount | (out)
+  if ((rc = cm_upload_payoffs(ctx, who, strikes, cps, Ts, r_drifts, discounts, n, n, host))) return rc;
+  HH_HIP(ctx, hh::launch_carr_madan_jump(*m, *jump, alpha, bound, ctx->payoffs, n_payoffs, ctx->payoffs + 4 * n, ctx->stream));
+  HH_HIP(ctx, hipMemcpyAsync(host.data() + 4 * n, ctx->payoffs + 4 * n, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  HH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  for (size_t k = 0; k < n; ++k) {  // parity_transform (payoffs.jl:172-193): put = call − S + K·D
+    const double call = host[4 * n + k];
+    prices_out[k] = cps[k] > 0.0 ? call : call - m->S0 + strikes[k] * discounts[k];
+  }
+  return HH_OK;
 }
 
 // ---- LSM on an ensemble sharded over several devices ------------------------------------------------

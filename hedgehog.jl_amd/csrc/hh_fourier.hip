@@ -72,7 +72,11 @@ struct FourierArgs {
   uint32_t n_payoffs, compat_sqrt_alpha;
   uint32_t m_sub;   // sub-panels per lane (carr_madan_subpanels)
   double sigma_ln;  // lognormal volatility (law_mu / law_sd are formed per payoff)
+  // Merton jumps (dynamics = kDynMerton, a code internal to this unit): the lognormal law above with the compensated
+  // drift, times exp(λT·(exp(iu·μ_J − σ_J²u²/2) − 1))
+  double lam, mu_j, sigma_j, lam_kbar;
 };
+constexpr int kDynMerton = 2;  // beside HH_LOGNORMAL = 0 and HH_HESTON = 1; never crosses the C-ABI
 
 // heston.jl:307-319, complex argument u
 __device__ cz heston_cf(const FourierArgs& a, cz u) {
@@ -96,10 +100,19 @@ __device__ cz normal_cf(const FourierArgs& a, cz t) {
   return zexp(a.law_mu * it - (0.5 * a.law_sd * a.law_sd) * (t * t));
 }
 
+// Merton (1976): log S_T = the lognormal law (law_mu carries the compensator −λκ̄T) + a compound Poisson sum of N(μ_J, σ_J²)
+__device__ cz merton_cf(const FourierArgs& a, cz t) {
+  const cz it = {-t.im, t.re};
+  const cz t2 = t * t;
+  const cz one = {1.0, 0.0};
+  const cz jump = zexp(a.mu_j * it - (0.5 * a.sigma_j * a.sigma_j) * t2) - one;
+  return zexp(a.law_mu * it - (0.5 * a.law_sd * a.law_sd) * t2 + (a.lam * a.T) * jump);
+}
+
 // carr_madan.jl:59-61, 88-92: damp · call_transform(v) · exp(−i v log K), real part
 __device__ double integrand(const FourierArgs& a, double v) {
   const cz u = {v, -(a.alpha + 1.0)};
-  const cz phi = a.dynamics == HH_HESTON ? heston_cf(a, u) : normal_cf(a, u);
+  const cz phi = a.dynamics == HH_HESTON ? heston_cf(a, u) : a.dynamics == kDynMerton ? merton_cf(a, u) : normal_cf(a, u);
   const cz den = {a.alpha * a.alpha + a.alpha - v * v, v * (2.0 * a.alpha + 1.0)};
   const cz val = zdiv(a.discount * phi, den) * zexp({0.0, -v * a.logK});
   return exp(-a.alpha * a.logK) / 6.28318530717958647692 * val.re;
@@ -317,6 +330,8 @@ __global__ __launch_bounds__(256) void carr_madan_kernel(const FourierArgs a0) {
     const double sqT = sqrt(a.T), tmul = a0.compat_sqrt_alpha ? sqT : a.T;
     a.law_mu = a.logS0 + (a.r - 0.5 * a0.sigma_ln * a0.sigma_ln) * tmul;  // montecarlo.jl:302
     a.law_sd = a0.sigma_ln * sqT;
+    if (a0.dynamics == kDynMerton)  // ((r − σ²/2) − λκ̄)·T, in that order: λ = 0 leaves the lognormal mean
+      a.law_mu = a.logS0 + ((a.r - 0.5 * a0.sigma_ln * a0.sigma_ln) - a0.lam_kbar) * a.T;
     a.out = a0.out + k;
   }
   const double w = 2.0 * a.bound / 256.0;  // panel width
@@ -367,6 +382,22 @@ int launch_carr_madan_basket(const hh_model& m, int dynamics, int compat_sqrt_al
   a.per_payoff = per_payoff_dev;
   a.n_payoffs = n_payoffs;
   a.compat_sqrt_alpha = (uint32_t)(compat_sqrt_alpha != 0);
+  if (const int rc = set_rule(a, alpha, bound)) return rc;
+  hipLaunchKernelGGL(carr_madan_kernel, dim3(n_payoffs), dim3(256), 0, s, a);
+  return (int)hipGetLastError();
+}
+
+int launch_carr_madan_jump(const hh_model& m, const hh_jump& jump, double alpha, double bound,
+                           const double* per_payoff_dev, uint32_t n_payoffs, double* out_dev, hipStream_t s) {
+  FourierArgs a{};
+  a.dynamics = kDynMerton;
+  a.logS0 = log(m.S0);
+  a.sigma_ln = m.sigma;
+  a.lam = jump.lambda; a.mu_j = jump.mu_j; a.sigma_j = jump.sigma_j;
+  a.lam_kbar = merton_compensator(jump);
+  a.out = out_dev;
+  a.per_payoff = per_payoff_dev;
+  a.n_payoffs = n_payoffs;
   if (const int rc = set_rule(a, alpha, bound)) return rc;
   hipLaunchKernelGGL(carr_madan_kernel, dim3(n_payoffs), dim3(256), 0, s, a);
   return (int)hipGetLastError();

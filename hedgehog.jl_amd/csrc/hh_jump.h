@@ -1,0 +1,40 @@
+// The jump count of the Merton model (include/hedgehog_mc.h, "Merton (1976) jump diffusion"): a Poisson variate by
+// inversion of one uniform, as a function the device kernels (hh_jump.hip) and a host program share — it includes
+// nothing of HIP, so that tests/c/jump_host_check.cpp can hold it to a 50-digit restatement and run it under the
+// host sanitizers.  Internal; the public surface is include/hedgehog_mc.h.
+#pragma once
+#include <stdint.h>
+
+#include "../../include/hedgehog_mc.h"
+
+#if defined(__HIPCC__)
+#define HH_JUMP_HD __host__ __device__
+#else
+#define HH_JUMP_HD
+#endif
+
+namespace hh {
+
+// The jump parameters of a launch, passed BY VALUE beside SimArgs (wave-uniform: scalar registers).
+struct JumpArgs {
+  double mean;     // Poisson mean of one draw: λ·T (terminal law), λ·dt (path form)
+  double p0;       // exp(-mean), formed on the host once per call
+  double mu_j;     // mean of one jump in log S
+  double sigma_j;  // standard deviation of one jump
+};
+
+// The smallest n with u <= c_n, c_0 = p0, p_k = p_{k-1}·m/k, c_k = c_{k-1} + p_k (one rounded operation each, in this
+// order); HH_JUMP_MAX_COUNT at the latest.  The cap is a condition of the loop, not a tuning knob: the cumulative sum
+// saturates in fp64 (m = 2.5: at 1 - 2^-52, below the largest uniform 1 - 2^-53), and a search bounded by the data alone
+// would then never end.  m = 0: p0 = 1, so n = 0 for every u.
+HH_JUMP_HD inline uint32_t poisson_inverse(double u, double m, double p0) {
+  double p = p0, c = p0;
+  for (uint32_t k = 1; k <= (uint32_t)HH_JUMP_MAX_COUNT; ++k) {
+    if (u <= c) return k - 1u;
+    p = p * m / (double)k;
+    c = c + p;
+  }
+  return (uint32_t)HH_JUMP_MAX_COUNT;
+}
+
+}  // namespace hh

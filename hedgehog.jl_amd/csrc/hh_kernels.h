@@ -274,6 +274,23 @@ struct PathPayoffArgs {
   int extremes;                   // enum hh_path_extremes: which rows a payoff's MAX / MIN are
 };
 int launch_path_payoffs(const PathPayoffArgs& b, uint32_t n_payoffs, hipStream_t s);
+// Merton jump diffusion (hh_jump.hip; include/hedgehog_mc.h, "Merton (1976) jump diffusion").  The scalars are checked
+// by the entry points.  λ·κ̄, the drift's compensator, as every launcher forms it:
+double merton_compensator(const hh_jump& jump);
+// the terminal law: a lane takes kMertonPerLane trajectories whatever the call, a workgroup leaves one record
+constexpr int kMertonPerLane = 8;
+inline uint32_t merton_records(uint64_t n_paths) {
+  const uint64_t per = (uint64_t)kTile * kMertonPerLane;
+  return (uint32_t)((n_paths + per - 1) / per);
+}
+// c: antithetic, n_paths, path_offset; p: seeds (seeds[0] is read), records [merton_records][kRecStride], terminal
+int launch_merton_exact(const hh_model& m, const hh_config& c, const hh_jump& jump, const DevicePtrs& p, hipStream_t s);
+// launch_path_stats' lognormal, monitored form under jumps: the same five rows
+int launch_jump_stats(const hh_model& m, const hh_config& c, const hh_jump& jump, const uint64_t* seeds_dev,
+                      uint32_t monitor_every, bool include_start, double* stats, hipStream_t s);
+// launch_carr_madan_basket (lognormal dynamics, compat_sqrt_alpha = 0) with the Merton characteristic function
+int launch_carr_madan_jump(const hh_model& m, const hh_jump& jump, double alpha, double bound,
+                           const double* per_payoff_dev, uint32_t n_payoffs, double* out_dev, hipStream_t s);
 // form: kLsmFormPersistent = the whole backward induction in ONE launch when the ensemble fits the
 // chip (else it falls back by itself), kLsmFormPerDate = one launch per exercise date.  *form_used
 // says which was enqueued; after a persistent launch the caller synchronises and reads the word at

@@ -328,6 +328,34 @@ class BlackScholesInputs:
 
 
 @dataclass(frozen=True)
+class MertonInputs:
+    """Merton (1976) jump diffusion (include/hedgehog_mc.h, "Merton (1976) jump diffusion"; the reference has no jump
+    model): BlackScholesInputs plus the intensity λ of the Poisson process and the mean μ_J and standard deviation σ_J
+    of one normal jump in log S.  The drift is compensated by λ·(exp(μ_J + σ_J²/2) − 1) inside the solvers."""
+    referenceDate: int
+    rate: FlatRateCurve
+    spot: Any
+    sigma: FlatVolSurface
+    jump_intensity: Any
+    jump_mean: Any
+    jump_std: Any
+
+    def __init__(self, reference_date, rate, spot, sigma, jump_intensity, jump_mean, jump_std):
+        ref = to_ticks(reference_date)
+        if not isinstance(rate, (FlatRateCurve, RateCurve)):
+            rate = FlatRateCurve(ref, rate)
+        if not isinstance(sigma, FlatVolSurface):
+            sigma = FlatVolSurface(ref, sigma)
+        for k, v in (("referenceDate", ref), ("rate", rate), ("spot", spot), ("sigma", sigma),
+                     ("jump_intensity", jump_intensity), ("jump_mean", jump_mean), ("jump_std", jump_std)):
+            object.__setattr__(self, k, v)
+
+    def black_scholes(self):
+        """the same market without jumps"""
+        return BlackScholesInputs(self.referenceDate, self.rate, self.spot, self.sigma)
+
+
+@dataclass(frozen=True)
 class HestonInputs:
     """market_inputs.jl:55-88; positional order (ref, rate, spot, V0, κ, θ, σ, ρ)."""
     referenceDate: int

@@ -16,7 +16,7 @@ from .dates import yearfrac
 from .dual import Dual, n_partials, partials_of, value_of
 from .domain import (PATH_PAYOFFS, ArithmeticAverage, AsianOption, BarrierOption, BlackScholesInputs, Call,
                     CashOrNothing, ContinuousMonitoring, DigitalOption, DownAndIn, DownAndOut, European, HestonInputs,
-                    LookbackOption, Monitoring,
+                    LookbackOption, MertonInputs, Monitoring,
                     MonteCarloSolution, PricingProblem, Spot, UpAndIn, UpAndOut, VanillaOption, _DeviceSamples, df,
                     get_vol, zero_rate)
 
@@ -34,9 +34,12 @@ class EulerMaruyama(SimulationStrategy): pass
 class ExactSimulation(SimulationStrategy): pass
 class HestonBroadieKaya(ExactSimulation): pass
 class BlackScholesExact(ExactSimulation): pass
+# ---- Merton jump diffusion (the reference has none; include/hedgehog_mc.h) ----
+class MertonDynamics(PriceDynamics): pass
+class MertonExact(ExactSimulation): pass
 
 for _c in (LognormalDynamics, HestonDynamics, NoVarianceReduction, Antithetic, EulerMaruyama,
-           HestonBroadieKaya, BlackScholesExact):
+           HestonBroadieKaya, BlackScholesExact, MertonDynamics, MertonExact):
     _c.__eq__ = lambda a, b: type(a) is type(b)
     _c.__hash__ = lambda a: hash(type(a).__name__)
     _c.__repr__ = lambda a: type(a).__name__ + "()"
@@ -178,6 +181,36 @@ def _model_and_config(prob: PricingProblem, method: MonteCarlo, n_paths=None, pa
     return model, c, keep, P, discount
 
 
+def is_merton(market_inputs, method) -> bool:
+    """Does anything of the pair name the Merton model?  Then only the Merton routes may take it."""
+    return isinstance(market_inputs, MertonInputs) or isinstance(getattr(method, "dynamics", None), MertonDynamics) or \
+        isinstance(getattr(method, "strategy", None), MertonExact)
+
+
+def _merton_structs(prob: PricingProblem, method: MonteCarlo):
+    """(hh_model, hh_config, hh_jump) of a Merton solve: the structs of the lognormal solve on the same market without
+    jumps — EulerMaruyama as it stands, MertonExact as the exact law with the correct ·T drift — and the jump
+    parameters beside them.  Every other mix of dynamics, strategy and inputs is a MethodError; so is a Dual anywhere:
+    these solves carry no partials."""
+    import dataclasses
+    m, dyn, strat = prob.market_inputs, method.dynamics, method.strategy
+    if not (isinstance(dyn, MertonDynamics) and isinstance(m, MertonInputs) and isinstance(strat, (EulerMaruyama, MertonExact))):
+        raise MethodError(f"no sde_problem / marginal_law for {type(dyn).__name__} + {type(strat).__name__} on "
+                          f"{type(m).__name__}")
+    if method.devices is not None:
+        raise MethodError("Merton solves run on one device (MonteCarlo.devices is not supported)")
+    jumps = (m.jump_intensity, m.jump_mean, m.jump_std)
+    if any(isinstance(v, Dual) for v in jumps):
+        raise MethodError("Merton solves carry no dual partials: use FiniteDifference")
+    plain = dataclasses.replace(method, dynamics=LognormalDynamics(), compat_sqrt_alpha=False,
+                                strategy=strat if isinstance(strat, EulerMaruyama) else BlackScholesExact())
+    model, c, keep, P, _ = _model_and_config(PricingProblem(prob.payoff, m.black_scholes()), plain)
+    if P:
+        raise MethodError("Merton solves carry no dual partials: use FiniteDifference")
+    del keep
+    return model, c, _ffi.make_jump(*(float(v) for v in jumps))
+
+
 @dataclass(frozen=True)
 class NormalLaw:
     """Distributions.Normal(μ, σ) as far as the reference's callers use it (mean, std, var)."""
@@ -226,6 +259,12 @@ def solve_montecarlo(prob: PricingProblem, method: MonteCarlo, ensemble: bool = 
 
     `replay` (optional, build extension): Wiener increments to consume instead of drawing them —
     numpy array [path][step][comp] (or tile-major), the noise-replay parity mode of DESIGN.md."""
+    if is_merton(prob.market_inputs, method):
+        if replay is not None:
+            raise MethodError("Merton solves draw their own noise: no replay")
+        if isinstance(method.strategy, EulerMaruyama):  # every payoff on the path statistics (hh_mc_solve_path_jump)
+            return solve_path_payoffs([prob.payoff], prob.market_inputs, method, ensemble)[0]
+        return _solve_merton_exact(prob, method, ensemble)
     if isinstance(prob.payoff, PATH_PAYOFFS):
         if replay is not None:
             raise MethodError("path-dependent payoffs draw their own noise: no replay")
@@ -263,6 +302,23 @@ def solve_montecarlo(prob: PricingProblem, method: MonteCarlo, ensemble: bool = 
                               std_error=res.std_error, result=res)
 
 
+def _solve_merton_exact(prob: PricingProblem, method: MonteCarlo, ensemble: bool = True) -> MonteCarloSolution:
+    """MonteCarlo(MertonDynamics(), MertonExact(), config) on a European vanilla: the terminal law (hh_mc_solve_jump)."""
+    if isinstance(method.strategy, MertonExact) and isinstance(prob.payoff, PATH_PAYOFFS):
+        raise MethodError("MertonExact samples the law at expiry: path-dependent payoffs need EulerMaruyama paths")
+    model, c, jump = _merton_structs(prob, method)
+    cfg = method.config
+    ctx = _ffi.get_context(method.device)
+    c.seeds, c.seeds_on_device, c.seeds_len = cfg.device_seeds(ctx), 1, cfg.seeds.size
+    n_paths, anti = int(c.n_paths), bool(c.antithetic)
+    term = np.empty(n_paths * (2 if anti else 1)) if ensemble else None
+    res = _ffi.hh_result()
+    ctx.check(ctx.lib.hh_mc_solve_jump(ctx.handle, C.byref(model), C.byref(jump), C.byref(c), C.byref(res),
+                                       term.ctypes.data if ensemble else None))
+    ens = None if term is None else ((term[:n_paths], term[n_paths:]) if anti else term)
+    return MonteCarloSolution(prob, method, res.price, ens, std_error=res.std_error, result=res)
+
+
 def solve_montecarlo_many(probs, method: MonteCarlo, replay=None, replay_layout=_ffi.HH_REPLAY_PATH_MAJOR):
     """Several problems under ONE method on the same draws — the solves a bumped Greek is made of
     (compute_fd_derivative, greeks_problem.jl:279-303; the second-order stencils :396-422) — in one pass of
@@ -272,6 +328,8 @@ def solve_montecarlo_many(probs, method: MonteCarlo, replay=None, replay_layout=
     if not 1 < len(probs) <= _ffi.HH_MAX_MODELS:
         return None
     if any(isinstance(p.payoff, PATH_PAYOFFS) for p in probs):  # one solve after the other (hh_mc_solve_path)
+        return None
+    if any(is_merton(p.market_inputs, method) for p in probs):  # no hh_mc_solve_multi form: one after the other
         return None
     packed = [_model_and_config(p, method) for p in probs]
     if any(P for _, _, _, P, _ in packed):
@@ -355,8 +413,9 @@ def pack_path_payoff(payoff) -> _ffi.hh_path_payoff:
 
 
 def _path_structs(payoffs, market_inputs, method: MonteCarlo):
-    """(hh_model, hh_config, monitor_every, include_start, discount) of payoffs that share an expiry and a monitoring.
-    The model and configuration are those of a European solve to that expiry (its strike and cp are not read)."""
+    """(hh_model, hh_config, monitor_every, include_start, hh_jump or None) of payoffs that share an expiry and a
+    monitoring.  The model and configuration are those of a European solve to that expiry (its strike and cp are not
+    read); Merton inputs bring their jump parameters."""
     if not isinstance(method.strategy, EulerMaruyama):
         raise MethodError(f"path-dependent payoffs need EulerMaruyama paths, not {type(method.strategy).__name__}")
     if method.devices is not None:
@@ -370,24 +429,31 @@ def _path_structs(payoffs, market_inputs, method: MonteCarlo):
         raise ValueError("payoffs of one path solve share a monitoring")
     every, start = mons.pop() if mons else (steps, False)
     european = VanillaOption(1.0, expiries.pop(), European(), Call(), Spot())
+    if is_merton(market_inputs, method):
+        model, c, jump = _merton_structs(PricingProblem(european, market_inputs), method)
+        return model, c, every, start, jump
     model, c, keep, P, discount = _model_and_config(PricingProblem(european, market_inputs), method)
     if P:  # the policy of every full-path entry point: never drop partials silently
         raise MethodError("path-dependent payoffs carry no dual partials: use FiniteDifference")
     del keep
-    return model, c, every, start, discount
+    return model, c, every, start, None
 
 
 def solve_path_payoffs(payoffs, market_inputs, method: MonteCarlo, ensemble: bool = True):
     """Payoffs that share an expiry, a monitoring and an extremes mode on ONE simulation: a MonteCarloSolution each, in
     order.  hh_mc_solve_path as long as no payoff is a lookback or continuously monitored; hh_mc_solve_path_ex otherwise.
     `ensemble`: the (5, n_total) statistics of the trajectories — (7, n_total) in bridge mode — (rows: enum
-    hh_path_stat), shared by the solutions; n_total counts the antithetic mirrors, columns trajectories + i."""
-    model, c, every, start, _ = _path_structs(payoffs, market_inputs, method)
+    hh_path_stat), shared by the solutions; n_total counts the antithetic mirrors, columns trajectories + i.
+    Merton inputs: hh_mc_solve_path_jump, the monitored rows only — ContinuousMonitoring is a MethodError, a bridge
+    between two states being wrong once a jump lies between them."""
+    model, c, every, start, jump = _path_structs(payoffs, market_inputs, method)
     modes = {e for e in (path_extremes(p) for p in payoffs) if e is not None}
     if len(modes) > 1:
         raise ValueError("payoffs of one path solve share an extremes mode (Monitoring or ContinuousMonitoring)")
     extremes = modes.pop() if modes else _ffi.HH_EXTREMES_MONITORED
     bridge = extremes == _ffi.HH_EXTREMES_BRIDGE
+    if jump is not None and bridge:
+        raise MethodError("ContinuousMonitoring is not offered under Merton jumps: monitor on the dates of a Monitoring")
     extended = bridge or any(isinstance(p, LookbackOption) for p in payoffs)
     packed = (_ffi.hh_path_payoff * len(payoffs))(*[pack_path_payoff(p) for p in payoffs])
     cfg = method.config
@@ -396,7 +462,10 @@ def solve_path_payoffs(payoffs, market_inputs, method: MonteCarlo, ensemble: boo
     n_total = int(c.n_paths) * (2 if c.antithetic else 1)
     stats = np.empty((_ffi.HH_PATH_STATS_BRIDGE if bridge else _ffi.HH_PATH_STATS, n_total)) if ensemble else None
     res = (_ffi.hh_result * len(payoffs))()
-    if extended:
+    if jump is not None:
+        ctx.check(ctx.lib.hh_mc_solve_path_jump(ctx.handle, C.byref(model), C.byref(jump), C.byref(c), every, int(start),
+                                                packed, len(payoffs), res, None, stats.ctypes.data if ensemble else None))
+    elif extended:
         ctx.check(ctx.lib.hh_mc_solve_path_ex(ctx.handle, C.byref(model), C.byref(c), every, int(start), extremes, packed,
                                               len(payoffs), res, None, stats.ctypes.data if ensemble else None))
     else:

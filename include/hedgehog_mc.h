@@ -669,6 +669,76 @@ int hh_mc_solve_path_ex(hh_ctx* ctx, const hh_model* model, const hh_config* cfg
                         hh_result* out, double* path_values, double* stats);
 
 /*
+ * Merton (1976) jump diffusion: lognormal dynamics plus a compound Poisson sum of normal jumps in log S, the drift
+ * compensated so that e^{-rt}·S stays a martingale.  The reference has no jump model (its roadmap lists "Merton model
+ * with Carr–Madan, Merton model with Monte Carlo" as open); the conventions below are this library's.
+ *   d log S = (r − σ²/2 − λ·κ̄) dt + σ dW + J dN        J ~ N(μ_J, σ_J²),  N Poisson of intensity λ
+ *   κ̄ = exp(μ_J + σ_J²/2) − 1
+ * Over a span τ, given n jumps in it, the jump sum is N(n·μ_J, n·σ_J²): one normal serves the whole sum.
+ *   ϕ(u) = E exp(iu·log S_T) = exp( iu·(log S0 + (r − σ²/2 − λκ̄)T) − σ²u²T/2 + λT·(exp(iu·μ_J − σ_J²u²/2) − 1) )
+ *   call = Σ_n e^{−λT}(λT)ⁿ/n! · (discounted Black call on a lognormal with log-mean log S0 + (r − σ²/2 − λκ̄)T + n·μ_J
+ *                                   and log-variance σ²T + n·σ_J²)
+ * hh_jump carries λ, μ_J, σ_J; σ = model->sigma, r = model->r_drift.  No existing struct changes.
+ *
+ * THE JUMP COUNT of a span with Poisson mean m (λ·T, or λ·T/n_steps) from one uniform U, by inversion
+ * (csrc/hh_jump.h, poisson_inverse — a host program can call it): with p_0 = exp(−m), formed on the host once per
+ * call, c_0 = p_0, p_k = p_{k−1}·m/k and c_k = c_{k−1} + p_k — one rounded fp64 operation each, in this order — N is
+ * the smallest n with U <= c_n, and the search stops at n = HH_JUMP_MAX_COUNT whatever U is: in fp64 the cumulative sum
+ * can saturate below the largest U = 1 − 2⁻⁵³ (m = 2.5 saturates at 1 − 2⁻⁵²), where a search without the cap would never end.
+ * m = 0 gives N = 0 for every U.  U = ((w >> 12) + ½)·2⁻⁵² of a 64-bit word w = (hi << 32) | lo, as everywhere.
+ * Every draw is a Philox4x32-10 block whose counter word 3 is 4, a domain no other draw of the library uses.
+ *
+ * hh_mc_solve_jump — the TERMINAL LAW, cfg->strategy = HH_EXACT_LAW.  Trajectory i of the call has the global index
+ * g = cfg->path_offset + i and is keyed by seeds[0], as the exact lognormal law is.
+ *   block A  counter (lo32 g, hi32 g, 0, 4): z1, z2 by Box–Muller, as every normal pair of the library
+ *   block B  counter (lo32 g, hi32 g, 1, 4): U from output words 0, 1;  N from U with m = λ·T
+ *   x_T = fma(σ√T, z1, m_T) + J        m_T = log S0 + ((r − σ²/2) − λκ̄)·T, formed on the host — ·T as it stands: there
+ *   J   = fma(σ_J·sqrt((double)N), z2, N·μ_J), added only when N > 0           is no compat_sqrt_alpha reading of it
+ * Antithetic: the mirror takes −z1, −z2 and the same N.  terminal (nullable; host, or device when
+ * cfg->terminal_on_device): exp(x_T) of the n_paths trajectories, then of their mirrors.  The payoff (model->strike,
+ * model->cp), the sums and hh_result are hh_mc_solve's.  1 .. 2^32 − 256 trajectories per call; a lane takes eight of
+ * them whatever the call, so a call's sums are reproducible, and [0, n) is [0, k) followed by [k, n) with
+ * path_offset = k, sample for sample.  Timing: one slot, as hh_mc_solve.
+ *
+ * hh_mc_solve_path_jump — the PATH FORM, cfg->strategy = HH_EULER_MARUYAMA: hh_mc_solve_path_ex under
+ * HH_EXTREMES_MONITORED with jumps.  Trajectory i is keyed by seeds[i]; its diffusion increments are exactly those of
+ * hh_mc_solve_path under lognormal dynamics, and so is the step, with the drift
+ * gdrift = (r − σ²/2) − λκ̄ formed on the host in that order: λ = 0 gives hh_mc_solve_path's bits.
+ *   block (h, 0, 0, 4) serves steps 2h and 2h+1: U of step 2h from output words 0, 1, U of step 2h+1 from words 2, 3;
+ *                      N_k from U with m = λ·dt, dt = T/n_steps
+ *   block (k, 1, 0, 4) is drawn only by a trajectory whose N_k > 0: z = the first normal of its pair
+ *   after step k:      x ← x + fma(σ_J·sqrt((double)N_k), z, N_k·μ_J), applied only when N_k > 0
+ * The mirror takes −dW, the same N_k and −z.  The statistics are the five rows of HH_EXTREMES_MONITORED over the same
+ * monitoring dates with the same arithmetic; payoff kinds 0 .. 7 are admitted, the lookbacks read the monitored rows.
+ * The log-Euler step is exact for this model, so the states on the dates are exact in law for any n_steps.
+ * Arguments, outputs and timing slots are hh_mc_solve_path's.
+ *
+ * hh_carr_madan_jump — hh_carr_madan_basket (lognormal dynamics, compat_sqrt_alpha = 0) with ϕ above: the same fixed
+ * quadrature rule, one workgroup per payoff, the same parity transform for puts.  λ = 0 is hh_carr_madan_basket.
+ *
+ * All three are synchronous.  Errors, checked on the host before any launch.  HH_ERR_INVALID: jump is NULL; λ or σ_J
+ * negative or not finite; μ_J not finite; exp(μ_J + σ_J²/2) not finite; the Poisson mean of one draw — λ·T (terminal
+ * law), λ·T/n_steps (path form) — above HH_JUMP_MAX_MEAN; everything hh_mc_solve / hh_mc_solve_path_ex /
+ * hh_carr_madan_basket reject.  HH_ERR_UNSUPPORTED: dynamics other than HH_LOGNORMAL, REPLAY noise, n_partials > 0,
+ * hh_mc_solve_jump with a strategy other than HH_EXACT_LAW, hh_mc_solve_path_jump with one other than
+ * HH_EULER_MARUYAMA.
+ * Not provided: multi-GPU and accumulate (asynchronous) forms, the hh_mc_solve_multi form, dual partials (bump the
+ * inputs: the solves of a finite difference share their seeds), a gradient of hh_carr_madan_jump, a Julia binding, and
+ * continuous (Brownian-bridge) extremes — a bridge between two states is wrong once a jump lies between them.
+ */
+#define HH_JUMP_MAX_MEAN  64.0   /* largest Poisson mean of one draw: λ·T (terminal law), λ·T/n_steps (path form) */
+#define HH_JUMP_MAX_COUNT 255    /* the inversion's search stops here at the latest */
+typedef struct hh_jump { double lambda, mu_j, sigma_j; } hh_jump;        /* 24 bytes */
+int hh_mc_solve_jump(hh_ctx* ctx, const hh_model* model, const hh_jump* jump, const hh_config* cfg, hh_result* out,
+                     double* terminal);
+int hh_mc_solve_path_jump(hh_ctx* ctx, const hh_model* model, const hh_jump* jump, const hh_config* cfg,
+                          uint32_t monitor_every, int32_t include_start, const hh_path_payoff* payoffs,
+                          uint32_t n_payoffs, hh_result* out, double* path_values, double* stats);
+int hh_carr_madan_jump(hh_ctx* ctx, const hh_model* model, const hh_jump* jump, double alpha, double bound,
+                       const double* strikes, const double* cps, const double* Ts, const double* r_drifts,
+                       const double* discounts, uint32_t n_payoffs, double* prices_out);
+
+/*
  * The same solve for an ensemble SHARDED over several devices (one process and one hh_ctx per
  * device, trajectories split by contiguous ranges as for hh_mc_accumulate).  The backward induction
  * needs sums over ALL trajectories at three points — the in-the-money statistics of every row, the

@@ -1,0 +1,485 @@
+"""Merton jump diffusion on the device (hh_jump.hip, hh_fourier.hip) — hh_mc_solve_jump, hh_mc_solve_path_jump,
+hh_carr_madan_jump and the Python routes above them.
+
+  * PATH BY PATH against the restatement of tests/merton_cases.py at 50 digits, on the draws the device makes itself: the
+    diffusion increments are read back (hh_wiener_fill), the jump uniforms come from the oracle's host Philox, the normals
+    of domain 4 are restated from its words by hh_rng.h's formulas.  Every state and statistic within
+    euler_tangent_cases.path_bar(e64, A) = 20·max(e64, ε·A); the jump count of every trajectory of the terminal law is
+    read off its sample (the candidates of different counts lie 1e-2 apart, the samples agree to 1e-14) and must be the
+    exact inversion's.  In the path form a wrong count at any step moves every later state by a whole jump: the bars
+    catch it.
+  * IDENTITIES, bit for bit: λ = 0 is the lognormal path form; jumps of size zero move no bit; the terminal law shards;
+    a payoff's result does not depend on its neighbours.
+  * THE LAW, fixed seeds: prices within 4 standard errors of Merton's series (an honest implementation misses one such
+    comparison with probability below 1e-4; a wrong compensator sign misses by tens).
+  * Carr–Madan against the exactly integrated truncated integral, at carr_madan_cases.price_bar's form.
+  * Errors: every HH_ERR_INVALID / HH_ERR_UNSUPPORTED case of the header, with its text, without a launch.
+The module prints its worst error/bar per kind of comparison at its end (`-s`)."""
+import ctypes as C
+import math
+
+import numpy as np
+import pytest
+
+mp = pytest.importorskip("mpmath")
+
+import hedgehog_jl_amd as hh  # noqa: E402
+from hedgehog_jl_amd import _ffi  # noqa: E402
+from tests import euler_tangent_cases as etc  # noqa: E402
+from tests import merton_cases as mc  # noqa: E402
+from tests import path_bridge_cases as bc  # noqa: E402
+from tests import path_payoff_cases as pc  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+DOC = mc.load_golden()
+GBM, HEST, EXACT, EULER = _ffi.HH_LOGNORMAL, _ffi.HH_HESTON, _ffi.HH_EXACT_LAW, _ffi.HH_EULER_MARUYAMA
+MONITORED = _ffi.HH_EXTREMES_MONITORED
+SEED = np.array([mc.TERMINAL_SEED], dtype=np.uint64)
+_cache = {}
+
+
+@pytest.fixture(scope="module")
+def worst():
+    w = etc.Worst("merton (device)")
+    yield w
+    w.report()
+
+
+def cached(key, make):
+    if key not in _cache:
+        _cache[key] = make()
+    return _cache[key]
+
+
+# ---- calls ---------------------------------------------------------------------------------------------------------------
+
+def n_total(c):
+    return int(c.n_paths) * (2 if c.antithetic else 1)
+
+
+def solve_jump(ctx, m, j, c, want_terminal=True):
+    res = _ffi.hh_result()
+    term = np.zeros(n_total(c)) if want_terminal else None
+    ctx.check(ctx.lib.hh_mc_solve_jump(ctx.handle, C.byref(m), C.byref(j), C.byref(c), C.byref(res),
+                                       term.ctypes.data if want_terminal else None))
+    assert res.n_paths_done == c.n_paths and res.kernel_ms > 0.0
+    return res, term
+
+
+def solve_path_jump(ctx, m, j, c, every, start, payoffs, want=True):
+    K = len(payoffs)
+    arr = (_ffi.hh_path_payoff * K)(*payoffs)
+    res = (_ffi.hh_result * K)()
+    values, stats = (np.empty((K, n_total(c))), np.empty((_ffi.HH_PATH_STATS, n_total(c)))) if want else (None, None)
+    ctx.check(ctx.lib.hh_mc_solve_path_jump(ctx.handle, C.byref(m), C.byref(j), C.byref(c), every, start, arr, K, res,
+                                            values.ctypes.data if want else None, stats.ctypes.data if want else None))
+    return list(res), values, stats
+
+
+def solve_path_lognormal(ctx, m, c, every, start, payoffs):
+    K = len(payoffs)
+    arr = (_ffi.hh_path_payoff * K)(*payoffs)
+    res = (_ffi.hh_result * K)()
+    values, stats = np.empty((K, n_total(c))), np.empty((_ffi.HH_PATH_STATS, n_total(c)))
+    ctx.check(ctx.lib.hh_mc_solve_path_ex(ctx.handle, C.byref(m), C.byref(c), every, start, MONITORED, arr, K, res,
+                                          values.ctypes.data, stats.ctypes.data))
+    return list(res), values, stats
+
+
+def same_result(a, b):
+    return (a.price, a.std_error, a.sum_payoff, a.sumsq_payoff, a.n_paths_done) == \
+        (b.price, b.std_error, b.sum_payoff, b.sumsq_payoff, b.n_paths_done)
+
+
+def device_increments(ctx, seeds, n_steps, T):
+    """dW[path][step]: the increments the path kernels draw for these seeds, filled on the device and copied out"""
+    n = len(seeds)
+    buf = _ffi.DeviceBuffer(ctx, 8 * ctx.lib.hh_replay_elems(n, n_steps, GBM))
+    try:
+        ctx.check(ctx.lib.hh_wiener_fill(ctx.handle, GBM, 0.0, T, n_steps, n, seeds.ctypes.data, 0, buf.ptr))
+        ctx.synchronize()
+        tiled = buf.download(np.empty(buf.nbytes // 8))
+    finally:
+        buf.free()
+    return np.ascontiguousarray(tiled.reshape(-1, n_steps, 256).transpose(0, 2, 1).reshape(-1, n_steps)[:n])
+
+
+def terminal_config(n, anti, offset=0, strategy=EXACT, **kw):
+    return _ffi.make_config(GBM, strategy, n, 1, antithetic=anti, seeds=SEED, path_offset=offset, **kw)
+
+
+# ---- (a) the terminal law, path by path ------------------------------------------------------------------------------------
+
+def terminal_counts(offset, mean):
+    if mean == 0.0:
+        return np.zeros(mc.TERMINAL_N, dtype=np.int64)
+    rec = next(r for r in DOC["counts"]["terminal"] if r["path_offset"] == offset and r["mean"] == mean)
+    return np.array(rec["N"], dtype=np.int64)
+
+
+def infer_counts(S, case, z, mirror):
+    """the jump count each sample was made with: the n whose x_T = m_T ± σ√T·z1 + n·μ_J ± σ_J√n·z2 is nearest log S"""
+    sgn = -1.0 if mirror else 1.0
+    kbar = math.expm1(case["mu_j"] + 0.5 * case["sigma_j"] ** 2)
+    mT = math.log(case["S0"]) + ((case["r_drift"] - 0.5 * case["sigma"] ** 2) - case["lam"] * kbar) * case["T"]
+    n = np.arange(64, dtype=np.float64)
+    out = []
+    for s, (z1, z2) in zip(S, z):
+        cand = mT + sgn * case["sigma"] * math.sqrt(case["T"]) * float(z1) + n * case["mu_j"] + sgn * case["sigma_j"] * np.sqrt(n) * float(z2)
+        d = np.abs(cand - math.log(s))
+        k = int(np.argmin(d))
+        assert d[k] < 1e-12 and np.partition(d, 1)[1] > 1e-6, (s, k, np.sort(d)[:2])
+        out.append(k)
+    return np.array(out)
+
+
+@pytest.mark.parametrize("mean", mc.TERMINAL_MEANS)
+@pytest.mark.parametrize("anti", [0, 1])
+@pytest.mark.parametrize("path_offset", mc.TERMINAL_OFFSETS)
+def test_terminal_law_path_by_path(hhlib, oracle, worst, path_offset, anti, mean):
+    """n_paths of 1, 3, 255, 256, 257 and 513 — below, at and above a workgroup's 256 lanes, into a lane's second
+    trajectory — at three offsets (2³³ − 1 carries into the counter's high word): every sample within its bar, every
+    jump count the exact inversion's, the mirrors at terminal[n + i]."""
+    case = mc.terminal_case(mean, anti)
+    z = cached(("tz", path_offset), lambda: mc.terminal_normals(oracle, mc.TERMINAL_SEED, path_offset, mc.TERMINAL_N))
+    N = terminal_counts(path_offset, mean)
+    assert mean == 0.0 or ((N > 0).any() and len(set(N)) >= 3)
+    ref = cached(("tref", path_offset, anti, mean), lambda: mc.terminal_reference(case, z, N))
+    bars = etc.path_bar(ref["e64"], ref["A"])
+    m, j = mc.model_of(case, 100.0, 1.0), mc.jump_of(case)
+    bad = []
+    for n in mc.TERMINAL_SIZES:
+        res, term = solve_jump(hhlib, m, j, terminal_config(n, anti, path_offset))
+        for mem in range(ref["members"]):
+            got = term[mem * n:(mem + 1) * n]
+            if mean > 0.0:
+                assert np.array_equal(infer_counts(got, case, z[:n], mem == 1), N[:n]), (n, mem)
+            for i in range(n):
+                bad.append(worst.check("terminal mirror" if mem else "terminal", got[i], ref["want"][mem][i], bars[mem][i],
+                                       f"offset {path_offset} mean {mean} n={n} path {i}"))
+        pay = np.maximum(term - 100.0, 0.0)
+        pay = (pay[:n] + pay[n:]) / 2 if anti else pay
+        assert res.sum_payoff == pytest.approx(math.fsum(pay), rel=1e-13, abs=1e-300)
+        assert res.price == pytest.approx(m.discount * math.fsum(pay) / n, rel=1e-13, abs=1e-300)
+    bad = [b for b in bad if b]
+    assert not bad, "\n".join(bad[:20])
+
+
+# ---- (b) the path form, path by path ---------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("anti", [0, 1])
+@pytest.mark.parametrize("include_start", [0, 1])
+@pytest.mark.parametrize("shape", mc.PATH_SHAPES, ids=lambda s: f"{s[0]}x{s[1]}")
+def test_path_form_path_by_path(hhlib, oracle, worst, shape, include_start, anti):
+    """All five rows of 257 trajectories (two workgroups) at λ·dt = 0.9 — N runs over 0 … 4 within a case — for n_steps
+    of 1, 5 (the odd tail of the two-step loop) and 6, monitored at every step or every third, with and without the
+    start; then every payoff kind on the device's own statistics."""
+    n_steps, every = shape
+    seeds, case = mc.path_seeds(), mc.path_case(n_steps, anti)
+    N = np.array(next(r for r in DOC["counts"]["path"] if r["n_steps"] == n_steps)["N"], dtype=np.int64)
+    assert (N == 0).any() and (N == 1).any() and (N >= 2).any()
+    dW = cached(("dW", n_steps), lambda: device_increments(hhlib, seeds, n_steps, case["T"]))
+    z = cached(("pz", n_steps), lambda: mc.path_normals(oracle, seeds, N))
+    ref = mc.path_reference(case, dW, N, z, every, include_start)
+    bars = etc.path_bar(ref["e64"], ref["A"])
+    m, j = mc.model_of(case), mc.jump_of(case)
+    c = _ffi.make_config(GBM, EULER, mc.PATH_N, n_steps, antithetic=anti, seeds=seeds)
+    payoffs = mc.payoff_list()
+    res, values, stats = solve_path_jump(hhlib, m, j, c, every, include_start, payoffs)
+    bad = []
+    for mem in range(ref["members"]):
+        for i in range(mc.PATH_N):
+            for row in range(5):
+                bad.append(worst.check(f"row {row}", stats[row][mem * mc.PATH_N + i], ref["want"][mem][i][row],
+                                       bars[mem][i][row], f"{n_steps}x{every} start={include_start} member {mem} path {i}"))
+    bad = [b for b in bad if b]
+    assert not bad, "\n".join(bad[:20])
+    n_mon = pc.n_mon(n_steps, every, include_start)
+    for k, q in enumerate(payoffs):
+        want = bc.payoff_from_stats(stats, q, n_mon, MONITORED)
+        if q.kind == pc.GEOM:  # numpy's exp against the device's
+            np.testing.assert_allclose(values[k], want, rtol=1e-14, atol=1e-13)
+        else:
+            assert np.array_equal(values[k], want), k
+        pair = (values[k][:mc.PATH_N] + values[k][mc.PATH_N:]) / 2 if anti else values[k]
+        assert res[k].sum_payoff == pytest.approx(math.fsum(pair), rel=1e-13, abs=1e-12)
+        assert res[k].n_paths_done == mc.PATH_N
+
+
+# ---- (c) identities, bit for bit ---------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("anti", [0, 1])
+def test_without_jumps_the_path_form_is_the_lognormal_one(hhlib, anti):
+    """λ = 0: rows and prices == those of hh_mc_path_stats / hh_mc_solve_path_ex on lognormal dynamics; λ > 0 with
+    μ_J = σ_J = 0: == again — κ̄ is exactly 0 and every jump adds 0.0, so the N > 0 branch and block (k, 1, 0, 4) run
+    without moving a bit."""
+    n, n_steps, every, start = 1000, 7, 1, 1
+    seeds = np.arange(1, n + 1, dtype=np.uint64) * np.uint64(0xD1B54A32D192ED03)
+    case = dict(mc.BASE, T=0.75)
+    m = mc.model_of(case)
+    c = _ffi.make_config(GBM, EULER, n, n_steps, antithetic=anti, seeds=seeds)
+    payoffs = mc.payoff_list()
+    res0, values0, stats0 = solve_path_lognormal(hhlib, m, c, every, start, payoffs)
+    plain = np.empty_like(stats0)
+    hhlib.check(hhlib.lib.hh_mc_path_stats(hhlib.handle, C.byref(m), C.byref(c), every, start, plain.ctypes.data, 0, None))
+    assert np.array_equal(plain, stats0)
+    for jump in (_ffi.make_jump(0.0, -0.1, 0.15), _ffi.make_jump(5.0, 0.0, 0.0), _ffi.make_jump(0.0, 0.0, 0.0)):
+        res, values, stats = solve_path_jump(hhlib, m, jump, c, every, start, payoffs)
+        assert np.array_equal(stats, stats0) and np.array_equal(values, values0)
+        assert all(same_result(a, b) for a, b in zip(res, res0))
+    # and jumps that are there do move the rows
+    _, _, moved = solve_path_jump(hhlib, m, _ffi.make_jump(5.0, -0.1, 0.15), c, every, start, payoffs)
+    assert not np.array_equal(moved[pc.S_T], stats0[pc.S_T])
+
+
+@pytest.mark.parametrize("anti", [0, 1])
+def test_terminal_law_identities(hhlib, anti):
+    """jumps of size zero leave the λ = 0 samples, bit for bit; [0, n) is [0, k) followed by [k, n) with
+    path_offset = k, sample for sample, at an offset that is no multiple of anything"""
+    n, k = 3001, 1234
+    case = dict(mc.BASE, lam=3.0)
+    m = mc.model_of(case, 105.0, 1.0)
+    _, t0 = solve_jump(hhlib, m, _ffi.make_jump(0.0, -0.1, 0.15), terminal_config(n, anti))
+    _, t1 = solve_jump(hhlib, m, _ffi.make_jump(3.0, 0.0, 0.0), terminal_config(n, anti))
+    assert np.array_equal(t0, t1)
+    j = mc.jump_of(case)
+    res, whole = solve_jump(hhlib, m, j, terminal_config(n, anti))
+    assert not np.array_equal(whole, t0)
+    ra, a = solve_jump(hhlib, m, j, terminal_config(k, anti))
+    rb, b = solve_jump(hhlib, m, j, terminal_config(n - k, anti, offset=k))
+    assert np.array_equal(whole[:n], np.concatenate([a[:k], b[:n - k]]))
+    if anti:
+        assert np.array_equal(whole[n:], np.concatenate([a[k:], b[n - k:]]))
+    assert res.sum_payoff == pytest.approx(ra.sum_payoff + rb.sum_payoff, rel=1e-13)
+    again, _ = solve_jump(hhlib, m, j, terminal_config(n, anti), want_terminal=False)  # the same call, the same bits
+    assert same_result(res, again)
+
+
+def test_a_payoffs_result_does_not_depend_on_its_neighbours(hhlib):
+    case = mc.path_case(6, 1)
+    m, j = mc.model_of(case), mc.jump_of(case)
+    c = _ffi.make_config(GBM, EULER, 5000, 6, antithetic=1, seeds=np.arange(7, 5007, dtype=np.uint64))
+    payoffs = mc.payoff_list()
+    together, _, _ = solve_path_jump(hhlib, m, j, c, 2, 0, payoffs, want=False)
+    for k, q in enumerate(payoffs):
+        alone, _, _ = solve_path_jump(hhlib, m, j, c, 2, 0, [q], want=False)
+        assert same_result(alone[0], together[k]), k
+
+
+# ---- (d) the law ---------------------------------------------------------------------------------------------------------------
+
+def within(res, want, what):
+    miss = abs(res.price - float(want)) / res.std_error
+    print(f"\n{what}: price {res.price:.6f}, series {float(want):.6f}, {miss:.2f} standard errors")
+    assert res.std_error > 0.0 and miss <= 4.0, (what, res.price, float(want), res.std_error)
+
+
+@pytest.mark.parametrize("anti", [0, 1])
+def test_terminal_law_prices_against_the_series(hhlib, anti):
+    """2¹⁸ trajectories at λ = 0.8, μ_J = −0.1, σ_J = 0.15: a call, a put, and the strike-0 call, which is the
+    martingale — the mean of discounted S_T against S0"""
+    case, n = dict(mc.BASE, discount=math.exp(-mc.BASE["r_drift"] * mc.BASE["T"])), 2 ** 18
+    j = mc.jump_of(case)
+    for K, cp in ((105.0, 1.0), (95.0, -1.0), (0.0, 1.0)):
+        res, _ = solve_jump(hhlib, mc.model_of(case, K, cp), j, terminal_config(n, anti), want_terminal=False)
+        want = mc.series(case, K, cp) if K > 0.0 else mp.mpf(case["S0"]) * mp.mpf(case["discount"]) * mp.exp(mp.mpf(case["r_drift"]) * mp.mpf(case["T"]))
+        within(res, want, f"terminal law K={K:g} cp={cp:+.0f} antithetic={anti}")
+
+
+def test_path_form_prices_against_the_series(hhlib):
+    """2¹⁷ trajectories: the vanilla kind and cash digitals at 16 steps, the same vanilla at 1 step — the log-Euler step
+    is exact for this model, so both are exact in law and each is held to 4 standard errors of the series"""
+    case, n = dict(mc.BASE, discount=math.exp(-mc.BASE["r_drift"] * mc.BASE["T"])), 2 ** 17
+    seeds = np.arange(1, n + 1, dtype=np.uint64) * np.uint64(0x9E3779B97F4A7C15) + np.uint64(3)
+    m, j = mc.model_of(case), mc.jump_of(case)
+    payoffs = [pc.payoff(pc.VANILLA, 105.0, 1.0), pc.payoff(pc.DCASH, 102.0, 1.0, cash=3.0), pc.payoff(pc.DCASH, 97.0, -1.0, cash=2.0)]
+    wants = [mc.series(case, 105.0, 1.0), mc.series(case, 102.0, 1.0, digital_cash=3.0), mc.series(case, 97.0, -1.0, digital_cash=2.0)]
+    res, _, _ = solve_path_jump(hhlib, m, j, _ffi.make_config(GBM, EULER, n, 16, seeds=seeds), 16, 0, payoffs, want=False)
+    for r, want, what in zip(res, wants, ("vanilla, 16 steps", "digital call", "digital put")):
+        within(r, want, "path form " + what)
+    res, _, _ = solve_path_jump(hhlib, m, j, _ffi.make_config(GBM, EULER, n, 1, seeds=seeds), 1, 0, payoffs[:1], want=False)
+    within(res[0], wants[0], "path form vanilla, 1 step")
+
+
+# ---- (e) Carr–Madan ------------------------------------------------------------------------------------------------------------
+
+def cm_arrays(rec):
+    model, rows = rec["model"], rec["payoffs"]
+    Ts = np.array([p["T"] for p in rows])
+    return (np.array([p["K"] for p in rows]), np.array([p["cp"] for p in rows]), Ts, np.full(len(rows), model["r_drift"]),
+            np.array([math.exp(-model["r_drift"] * T) for T in Ts]))
+
+
+@pytest.mark.parametrize("name", ["single", "basket33", "lambda0"])
+def test_carr_madan_against_the_exact_integral(hhlib, worst, name):
+    """a 1-payoff and a 33-payoff basket, calls and puts, two expiries: every price against the exactly integrated
+    truncated integral of the fixture, within max(1e-14·S0, 20·e64); λ = 0 also against the lognormal entry point"""
+    rec = next(b for b in DOC["carr_madan"] if b["id"] == name)
+    model = rec["model"]
+    arrs = cm_arrays(rec)
+    n = len(rec["payoffs"])
+    for p, D in zip(rec["payoffs"], arrs[4]):  # the fixture's discount factors are these doubles
+        assert D == mc.cm_case(dict(model, T=p["T"]), p["K"], rec["alpha"], rec["bound"])["discount"]
+    m, j, out = mc.model_of(model), mc.jump_of(model), np.empty(n)
+    hhlib.check(hhlib.lib.hh_carr_madan_jump(hhlib.handle, C.byref(m), C.byref(j), rec["alpha"], rec["bound"],
+                                             *[a.ctypes.data for a in arrs], n, out.ctypes.data))
+    bad = []
+    for k, p in enumerate(rec["payoffs"]):
+        bad.append(worst.check("carr-madan", out[k], mp.mpf(p["price"]), mc.cm_bar(model["S0"], p["e64"]), f"{name} payoff {k}"))
+    assert not [b for b in bad if b], bad
+    if name == "lambda0":
+        plain = np.empty(n)
+        hhlib.check(hhlib.lib.hh_carr_madan_basket(hhlib.handle, C.byref(m), GBM, 0, rec["alpha"], rec["bound"],
+                                                   *[a.ctypes.data for a in arrs], n, plain.ctypes.data))
+        for k, p in enumerate(rec["payoffs"]):
+            assert abs(out[k] - plain[k]) <= mc.cm_bar(model["S0"], p["e64"]), k
+    if name == "basket33":  # one workgroup per payoff: a payoff alone prices the same, bit for bit
+        one, alone = np.empty(1), [a[17:18].copy() for a in arrs]
+        hhlib.check(hhlib.lib.hh_carr_madan_jump(hhlib.handle, C.byref(m), C.byref(j), rec["alpha"], rec["bound"],
+                                                 *[a.ctypes.data for a in alone], 1, one.ctypes.data))
+        assert one[0] == out[17]
+
+
+# ---- (f) errors ------------------------------------------------------------------------------------------------------------------
+
+NAN, INF = float("nan"), float("inf")
+BAD_JUMPS = [  # (λ, μ_J, σ_J), text
+    ((-1.0, 0.0, 0.1), "jump lambda must be finite and >= 0"), ((NAN, 0.0, 0.1), "jump lambda must be finite and >= 0"),
+    ((INF, 0.0, 0.1), "jump lambda must be finite and >= 0"), ((1.0, 0.0, -0.1), "jump sigma_j must be finite and >= 0"),
+    ((1.0, 0.0, NAN), "jump sigma_j must be finite and >= 0"), ((1.0, 0.0, INF), "jump sigma_j must be finite and >= 0"),
+    ((1.0, NAN, 0.1), "jump mu_j must be finite"), ((1.0, INF, 0.1), "jump mu_j must be finite"),
+    ((1.0, -INF, 0.1), "jump mu_j must be finite"), ((1.0, 800.0, 0.1), "exp(mu_j + sigma_j^2/2) must be finite"),
+]
+
+
+def test_errors_come_back_without_a_launch(hhlib):
+    """every HH_ERR_INVALID and HH_ERR_UNSUPPORTED case of the header, hostile scalars included, with its text; no
+    timing slot is opened (nothing was launched) and the context solves afterwards"""
+    ctx = hhlib
+    case = dict(mc.BASE)
+    m, good = mc.model_of(case), mc.jump_of(case)
+    n, steps = 300, 4
+    seeds = np.arange(1, n + 1, dtype=np.uint64)
+    out, outs = _ffi.hh_result(), (_ffi.hh_result * 1)()
+    pay = (_ffi.hh_path_payoff * 1)(pc.payoff(pc.VANILLA, 100.0, 1.0))
+    exact = lambda **kw: terminal_config(n, 0, **kw)  # noqa: E731
+    euler = lambda **kw: _ffi.make_config(GBM, EULER, n, steps, seeds=seeds, **kw)  # noqa: E731
+
+    def term(mm, jj, cc):
+        return ctx.lib.hh_mc_solve_jump(ctx.handle, mm, jj, cc, C.byref(out), None)
+
+    def path(mm, jj, cc, every=1, arr=pay, k=1):
+        return ctx.lib.hh_mc_solve_path_jump(ctx.handle, mm, jj, cc, every, 0, arr, k, outs, None, None)
+
+    def expect(rc, code, text):
+        assert rc == code, (rc, code, text, ctx.lib.hh_last_error(ctx.handle))
+        assert text in ctx.lib.hh_last_error(ctx.handle).decode(), (text, ctx.lib.hh_last_error(ctx.handle))
+
+    ctx.enable_timing(True)
+    try:
+        ctx.read_timings()
+        INV, UNS = _ffi.HH_ERR_INVALID, _ffi.HH_ERR_UNSUPPORTED
+        for (lam, mu, sj), text in BAD_JUMPS:
+            bad = _ffi.make_jump(lam, mu, sj)
+            expect(term(C.byref(m), C.byref(bad), C.byref(exact())), INV, "hh_mc_solve_jump: " + text)
+            expect(path(C.byref(m), C.byref(bad), C.byref(euler())), INV, "hh_mc_solve_path_jump: " + text)
+        # the Poisson mean of one draw just above HH_JUMP_MAX_MEAN: λ·T, and λ·dt
+        over = _ffi.make_jump(math.nextafter(64.0, INF) / case["T"], 0.0, 0.1)
+        expect(term(C.byref(m), C.byref(over), C.byref(exact())), INV, "is above HH_JUMP_MAX_MEAN")
+        over = _ffi.make_jump(64.0 * steps / case["T"] * (1 + 1e-12), 0.0, 0.1)
+        expect(path(C.byref(m), C.byref(over), C.byref(euler())), INV, "is above HH_JUMP_MAX_MEAN")
+        # NULL arguments
+        expect(term(C.byref(m), None, C.byref(exact())), INV, "hh_mc_solve_jump: NULL argument")
+        expect(term(None, C.byref(good), C.byref(exact())), INV, "hh_mc_solve_jump: NULL argument")
+        expect(path(C.byref(m), None, C.byref(euler())), INV, "hh_mc_solve_path_jump: NULL argument")
+        expect(path(C.byref(m), C.byref(good), None), INV, "hh_mc_solve_path_jump: NULL argument")
+        # what the sibling entry points reject
+        expect(term(C.byref(mc.model_of(dict(case, S0=-1.0))), C.byref(good), C.byref(exact())), INV, "S0 must be > 0")
+        expect(term(C.byref(mc.model_of(dict(case, sigma=NAN))), C.byref(good), C.byref(exact())), INV, "model scalars must be finite")
+        expect(term(C.byref(m), C.byref(good), C.byref(_ffi.make_config(GBM, EXACT, 0, 1, seeds=SEED))), INV, "n_paths must be >= 1")
+        expect(term(C.byref(m), C.byref(good), C.byref(_ffi.make_config(GBM, EXACT, n, 1))), INV, "GENERATE needs seeds")
+        expect(path(C.byref(m), C.byref(good), C.byref(euler()), every=3), INV, "must be >= 1 and divide n_steps")
+        expect(path(C.byref(m), C.byref(good), C.byref(euler()), k=0), INV, "payoffs")
+        expect(path(C.byref(m), C.byref(good), C.byref(euler()), arr=(_ffi.hh_path_payoff * 1)(pc.payoff(8, 100.0, 1.0))), INV, "unknown kind 8")
+        expect(path(C.byref(mc.model_of(dict(case, T=INF))), C.byref(good), C.byref(euler())), INV, "model scalars finite")
+        # unsupported
+        expect(term(C.byref(m), C.byref(good), C.byref(_ffi.make_config(HEST, _ffi.HH_BROADIE_KAYA, n, 1, seeds=SEED))), UNS, "needs LognormalDynamics")
+        expect(term(C.byref(m), C.byref(good), C.byref(euler())), UNS, "needs LognormalDynamics + the exact law")
+        expect(term(C.byref(m), C.byref(good), C.byref(exact(noise_mode=_ffi.HH_NOISE_REPLAY, replay=np.zeros(n)))), UNS, "GENERATE noise, no dual partials")
+        expect(term(C.byref(m), C.byref(good), C.byref(exact(n_partials=1))), UNS, "GENERATE noise, no dual partials")
+        expect(path(C.byref(m), C.byref(good), C.byref(_ffi.make_config(HEST, EULER, n, steps, seeds=seeds))), UNS, "needs LognormalDynamics + EulerMaruyama")
+        expect(path(C.byref(m), C.byref(good), C.byref(_ffi.make_config(GBM, EXACT, n, steps, seeds=seeds))), UNS, "needs LognormalDynamics + EulerMaruyama")
+        expect(path(C.byref(m), C.byref(good), C.byref(euler(noise_mode=_ffi.HH_NOISE_REPLAY, replay=np.zeros(4)))), UNS, "GENERATE noise, no dual partials")
+        expect(path(C.byref(m), C.byref(good), C.byref(euler(n_partials=2))), UNS, "GENERATE noise, no dual partials")
+        assert ctx.read_timings() == []  # nothing was launched
+        # Carr–Madan
+        arrs = [np.array([x]) for x in (105.0, 1.0, 1.0, 0.03, math.exp(-0.03))]
+        price = np.empty(1)
+
+        def cm(jj, alpha=1.0, bound=32.0, k=1):
+            return ctx.lib.hh_carr_madan_jump(ctx.handle, C.byref(m), jj, alpha, bound, *[a.ctypes.data for a in arrs], k, price.ctypes.data)
+        expect(cm(None), INV, "hh_carr_madan_jump: NULL argument")
+        for (lam, mu, sj), text in BAD_JUMPS:
+            expect(cm(C.byref(_ffi.make_jump(lam, mu, sj))), INV, "hh_carr_madan_jump: " + text)
+        expect(cm(C.byref(good), alpha=0.0), INV, "hh_carr_madan_jump: bad scalars")
+        expect(cm(C.byref(good), alpha=1e-4, bound=32.0), INV, "bound/alpha must be <= 196608")
+        expect(cm(C.byref(good), k=0), INV, "1 .. 2^20 payoffs per call")
+        # the mean of exactly HH_JUMP_MAX_MEAN is admitted, and the context solves
+        edge = _ffi.make_jump(64.0 / case["T"], -0.01, 0.02)
+        res, t = solve_jump(ctx, m, edge, exact())
+        assert np.all(np.isfinite(t)) and np.all(t > 0.0)
+        res, _, stats = solve_path_jump(ctx, m, good, euler(), 2, 1, [pc.payoff(pc.VANILLA, 100.0, 1.0)])
+        assert np.all(np.isfinite(stats)) and res[0].price > 0.0
+        assert len(ctx.read_timings()) == 3  # one slot for the terminal law, two for the path form
+        assert cm(C.byref(good)) == _ffi.HH_OK and price[0] > 0.0
+    finally:
+        ctx.enable_timing(False)
+
+
+# ---- (g) the Python routes -------------------------------------------------------------------------------------------------
+
+def test_python_routes(hhlib):
+    """MertonExact and EulerMaruyama through hh.solve on MertonInputs, CarrMadan(α, bound, MertonDynamics()) against the
+    host series, a basket whose Euler group shares one simulation, and a finite-difference Greek through the lenses"""
+    ref, exp_ = hh.Date(2021, 1, 1), hh.Date(2022, 1, 1)
+    T = hh.yearfrac(ref, exp_)
+    mkt = hh.MertonInputs(ref, 0.03, 100.0, 0.2, 0.8, -0.1, 0.15)
+    call = hh.VanillaOption(105.0, exp_, hh.European(), hh.Call(), hh.Spot())
+    prob = hh.PricingProblem(call, mkt)
+    series = hh.solve(prob, hh.MertonAnalytic()).price
+    assert series == pytest.approx(float(mc.series(dict(mc.BASE, T=T), 105.0, 1.0)), abs=1e-12)
+    cm = hh.CarrMadan(1.0, 200.0, hh.MertonDynamics())
+    assert hh.solve(prob, cm).price == pytest.approx(series, abs=1e-11)
+    n = 2 ** 16
+    seeds = np.arange(1, n + 1, dtype=np.uint64) * np.uint64(0x9E3779B97F4A7C15)
+    exact = hh.MonteCarlo(hh.MertonDynamics(), hh.MertonExact(), hh.SimulationConfig(n, seeds=seeds, variance_reduction=hh.Antithetic()))
+    sol = hh.solve(prob, exact)
+    assert abs(sol.price - series) <= 4 * sol.std_error and len(sol.ensemble) == 2 and sol.ensemble[0].shape == (n,)
+    euler = hh.MonteCarlo(hh.MertonDynamics(), hh.EulerMaruyama(), hh.SimulationConfig(n, steps=12, seeds=seeds))
+    sol = hh.solve(prob, euler)
+    assert abs(sol.price - series) <= 4 * sol.std_error and sol.ensemble.shape == (5, n)
+    asian = hh.AsianOption(100.0, exp_, hh.Call(), monitoring=hh.Monitoring(1))
+    out = hh.BarrierOption(100.0, 80.0, exp_, hh.Call(), hh.DownAndOut(), monitoring=hh.Monitoring(1))
+    look = hh.LookbackOption(exp_, hh.Call(), monitoring=hh.Monitoring(1))
+    basket = hh.solve(hh.BasketPricingProblem([asian, call, out, look], mkt), euler)
+    prices = [s.price for s in basket.solutions]
+    assert prices[1] == sol.price                         # the vanilla rode along on the group's simulation: same seeds
+    assert 0.0 < prices[0] < prices[1] * 1.2 and 0.0 < prices[2] <= hh.solve(hh.PricingProblem(
+        hh.VanillaOption(100.0, exp_, hh.European(), hh.Call(), hh.Spot()), mkt), euler).price and prices[3] > prices[1]
+    for p, s in zip([asian, out, look], [basket.solutions[0], basket.solutions[2], basket.solutions[3]]):
+        assert hh.solve(hh.PricingProblem(p, mkt), euler).price == s.price
+    with pytest.raises(hh.MethodError):
+        hh.solve(hh.PricingProblem(hh.BarrierOption(100.0, 80.0, exp_, hh.Call(), hh.DownAndOut(),
+                                                    monitoring=hh.ContinuousMonitoring()), mkt), euler)
+    cmb = hh.solve(hh.BasketPricingProblem([call, hh.VanillaOption(95.0, exp_, hh.European(), hh.Put(), hh.Spot())], mkt), cm)
+    assert cmb.solutions[0].price == hh.solve(prob, cm).price
+    # Greeks by finite differences: common random numbers through the fixed seeds
+    # (a bumped intensity moves whole jumps in and out of a few trajectories: its difference is the noisy one)
+    for lens, rel in ((hh.SpotLens(), 0.05), (hh.VolLens(105.0, exp_), 0.05), (hh.optic("market_inputs.jump_intensity"), 0.3)):
+        fd = hh.FiniteDifference(1e-2)
+        want = hh.solve(hh.GreekProblem(prob, lens), fd, hh.MertonAnalytic()).greek
+        got = hh.solve(hh.GreekProblem(prob, lens), fd, exact).greek
+        assert got == pytest.approx(want, rel=rel), lens
+    with pytest.raises(hh.MethodError):
+        hh.solve(hh.GreekProblem(prob, hh.SpotLens()), hh.ForwardAD(), exact)
