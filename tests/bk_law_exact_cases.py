@@ -23,7 +23,26 @@ all x) is ADDED to the residual; where that remainder is more than a hundredth o
   ε·A     the recovery of ∫V from log S_T: with Z = 0, log S_T = log S0 + rT + (ρ/σ)(V_T − V0 − κθT) + (ρκ/σ − ½)·∫V;
           its terms carry an ulp each, A = f(x*)·(1 + Σ|terms|)/|ρκ/σ − ½| (the 1: the exp that makes S_T);
           0 for a sample that was never a spot
-Nothing in the bar comes from the code under test."""
+Nothing in the bar comes from the code under test.
+
+THE EIGHT READINGS of the reference's two `find_zero` calls (READINGS: hh_config.bk_root_form, bk_bracket_form, bk_caps;
+oracle/bk_oracle.py has the table) are held to the same bar.  E_alg, e64 and `reach` describe the series, which no
+reading touches; only `stop` belongs to the search, and it is read off the decision word's branch alike in all eight:
+  branch 0  the first search was accepted: bk_atol, in every reading.  The secant accepts on |f| <= atol.  Order2 also
+            accepts on |f| <= max(atol, 4ε|x|), and, when its iterates stall, on |f| <= ∛tol — but an accepted iterate
+            stands only if it passes the reference's own test once more: `if (ok && !(xb < 0.0 || fabs(fb) > p.atol))
+            break;` in tail_whole_trajectory (csrc/hh_bk.hip), `if ok and not (sol < 0 or abs(fsol) > atol)` in
+            bk_oracle.inverse_cdf.  (4ε|x| is far below either atol of CONTROLS.)
+  branch 1  the fall-back ladder, either bisection: f(x*)·bk_atol.  The midpoint form ends on `xb - xa <= p.atol`
+            (`stop = f == 0.0 || xb - xa <= p.atol || …`) and returns the middle.  The bit-pattern form ends at adjacent
+            floats (`!(xa < mid && mid < xb)`) and returns the end with the smaller residual, so its bracket is narrower
+            than atol by ten orders — and it still gets no tighter term.  One ulp, f(x*)·|x|·2⁻⁵², was tried: the fp64
+            oracle misses it by 6 % (short_T/q0.5, u = 0.999, tight, reading (1, 1, 1): 3.69e-11 against 3.47e-11),
+            because the sign of a residual at adjacent floats is decided by fp64 noise in the series, a little above
+            the 20·e64 taken at x*.  (No cap of CONTROLS ends a bisection early: the midpoint form needs a few dozen
+            halvings, the bit-pattern form ~62, against caps of 100 and 255.)
+  branch 2  max_guess was returned: nothing.
+The far cases (laws `<regime>/q0.5/far`: u = 10⁻⁶ — 10⁻⁵ in two — and 1 − 10⁻⁶) ride with their regime's cases."""
 import json
 import os
 
@@ -36,6 +55,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden", "bk_law_exact.json")
 EPS = 2.0 ** -53
 DEC_BRANCH_SHIFT, DEC_BISECT, DEC_MAXGUESS = 8, 1, 2
+DEC_ITERS_SHIFT = 16
+READINGS = [(rf, bf, cp) for rf in (0, 1) for bf in (0, 1) for cp in (0, 1)]  # (bk_root_form, bk_bracket_form, bk_caps)
 
 with open(GOLDEN) as _f:
     DOC = json.load(_f)
@@ -47,6 +68,21 @@ LAWS = {rec["id"]: rec for rec in DOC["laws"]}
 
 def cases_of(regime):
     return [c for c in CASES if c["regime"] == regime]
+
+
+def is_far(case):
+    return case["law"].endswith("/far")
+
+
+FAR_LOW = [c for c in CASES if is_far(c) and c["u"] < 0.5]   # u = 10⁻⁶ (10⁻⁵ where the maker moved it): the ladder, tight set
+
+
+def branch_of(decision):
+    return (int(decision) >> DEC_BRANCH_SHIFT) & 3
+
+
+def iterations_of(decision):
+    return (int(decision) >> DEC_ITERS_SHIFT) & 0xff
 
 
 def law_of(case):
@@ -94,18 +130,37 @@ def bar_of(case, control, decision, x, A=0.0):
     return stop + (c["E_alg"] if e_alg is None else e_alg) + 20.0 * max(c["e64"], EPS * A)
 
 
+_BUILT, _RESIDUALS = {}, {}
+
+
+def _built_law(case, x):
+    """the case's law with its table built up to x_max (kept: seconds each), or further for an x beyond it"""
+    x_max = mp.mpf(LAWS[case["law"]]["x_max"])
+    if x > x_max:
+        return law_of(case).build(mp.mpf(x))
+    if case["law"] not in _BUILT:
+        _BUILT[case["law"]] = law_of(case).build(x_max)
+    return _BUILT[case["law"]]
+
+
 def residual_of(case, x, bar):
-    """|F(x) − u| (and how it was formed) for a sample x given as an mpf"""
+    """|F(x) − u| (and how it was formed) for a sample x given as an mpf.  Kept per (case, x, how): readings of the
+    root search that walk the same path return the same bits."""
     with mp.workdps(bx.DPS):
-        d = mp.mpf(x) - mp.mpf(case["x"])
+        x = mp.mpf(x)
+        d = x - mp.mpf(case["x"])
         rem = mp.mpf(case["f5_bound"]) * d ** 6 / 720
-        if rem <= bar / 100:
-            taylor = mp.fsum(mp.mpf(case[k]) * d ** (n + 1) / mp.factorial(n + 1) for n, k in enumerate(("f", "f1", "f2", "f3", "f4")))
-            return float(abs(taylor) + rem), "taylor"
-        if not x > 0:
-            return float(mp.mpf(case["u"])), "outright"
-        law = law_of(case).build(max(mp.mpf(LAWS[case["law"]]["x_max"]), mp.mpf(x)))
-        return float(abs(law.F(x) - mp.mpf(case["u"]))), "outright"
+        how = "taylor" if rem <= bar / 100 else "outright"
+        key = (case["law"], case["u"], x, how)
+        if key not in _RESIDUALS:
+            if how == "taylor":
+                taylor = mp.fsum(mp.mpf(case[k]) * d ** (n + 1) / mp.factorial(n + 1) for n, k in enumerate(("f", "f1", "f2", "f3", "f4")))
+                _RESIDUALS[key] = float(abs(taylor) + rem)
+            elif not x > 0:
+                _RESIDUALS[key] = float(mp.mpf(case["u"]))
+            else:
+                _RESIDUALS[key] = float(abs(_built_law(case, x).F(x) - mp.mpf(case["u"])))
+        return _RESIDUALS[key], how
 
 
 class Worst:

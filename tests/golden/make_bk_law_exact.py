@@ -7,12 +7,19 @@ median V_T, {10⁻³, 0.9} at the low one, {0.5, 0.999} at the high one — nine
 variance: regime q2 (d = 0.13) at V_T = 2⁻¹⁰⁰⁰, the kernels' floor, u in {10⁻³, 0.5, 0.999}.  No case with a start
 variance other than the model's V0: no entry point that takes the caller's (V_T, u, Z) takes one.
 
-Per V_T ("laws"): the step and length of the table of Re ϕ(hj) behind F, the difference between F and F by half the
-step and twice the cut-off (asserted <= 10⁻²⁰ here), mean and variance from the cumulant function, a ladder of F.
-Per (V_T, u) ("cases"): x* = F⁻¹(u), f and its first four derivatives at x*, bounds on |f′| and |f⁗′| (the fifth) over
-ALL x (from ∫ aⁿ|Re ϕ|), and per control set E_alg = |F_alg(x*) − F(x*)|, E_alg_reach = |F_alg − F| on 33 or more equidistant points of the
-interval `reach`, the x a search on F_alg can stop at, e64 = |F_alg in doubles − F_alg at 50 digits| at x*, and the length of the
-sampler's series at 50 digits and in doubles.
+The far cases: regimes h252, intended and nu_one once more at their median V_T (laws `<regime>/q0.5/far`, listed behind
+the regime's own three), with x_max from the Chernoff bound at 10⁻⁸ instead of 10⁻⁴ and u in {10⁻⁶, 1 − 10⁻⁶} (FAR_US).
+Under the tight controls the low uniform sends every reading of the root search (bk_law_exact_cases.READINGS) to the
+fall-back ladder, and 1 − 10⁻⁶ is the flat upper tail, where Order2's Steffensen slope is worst conditioned.  Under the
+shipped controls these cases are nearly vacuous — E_alg there is hundreds of times u or 1 − u, so the bar admits nearly
+any x in `reach` — and are kept for the record format alone.
+The condition on a far case: in all eight readings and under both control sets the fp64 oracle's sample lies inside
+`reach` and the search does not leave by the max_guess exit (held by tests/test_bk_law_exact_host.py); a case that fails
+it has its u moved inward, 10⁻⁶ → 10⁻⁵ → 10⁻⁴.  Two did.  With u = 10⁻⁶ under the shipped controls, the midpoint
+bisection of readings (0, 0, ·) returned 0.00874 for `intended` and 0.0326 for `nu_one`, beyond `reach` (which ends at
+0.00810 and 0.0303: E_alg is a wave in x, and |F − u| there is 5.4e-4 and 1.0e-3, more than the twice
+(stop + E_alg(x*)) that `reach` allows for).  At 10⁻⁵ all eight readings stay inside under both sets, and under the tight
+set all eight still take the ladder.  h252 holds at 10⁻⁶, and every law holds at 1 − 10⁻⁶.
 """
 import json
 import math
@@ -35,6 +42,9 @@ CONTROLS = {
 }
 US = {0.001: (1e-3, 0.9), 0.5: (1e-3, 0.3, 0.5, 0.9, 0.999), 0.999: (0.5, 0.999)}
 ABSORBED_US = (1e-3, 0.5, 0.999)
+FAR_REGIMES = ("h252", "intended", "nu_one")
+FAR_US = {"h252": (1e-6, 1 - 1e-6), "intended": (1e-5, 1 - 1e-6), "nu_one": (1e-5, 1 - 1e-6)}   # (chosen as the docstring says)
+FAR_TAIL = 8        # x_max of a far law: P(∫V > x_max) <= 10⁻⁸
 DIGITS = 34
 REACH_POINTS = 33   # at least; more where the series' error turns by more than REACH_PHASE between two of them
 REACH_PHASE = 0.2
@@ -58,6 +68,8 @@ def tasks():
     for name, p in regimes().items():
         for q, us in US.items():
             out.append(dict(regime=name, law=f"{name}/q{q:g}", VT=variance_quantile(p, q), us=us))
+        if name in FAR_REGIMES:
+            out.append(dict(regime=name, law=f"{name}/q0.5/far", VT=variance_quantile(p, 0.5), us=FAR_US[name], tail=FAR_TAIL))
     out.append(dict(regime="q2", law="q2/absorbed", VT=bx.VT_FLOOR, us=ABSORBED_US))
     return out
 
@@ -73,12 +85,13 @@ def run(task):
         one, sym = law.phi(mp.mpf(0)), law.phi(mp.mpf(1)) - mp.conj(law.phi(mp.mpf(-1)))
         assert abs(one - 1) < mp.mpf(10) ** -35 and abs(sym) < mp.mpf(10) ** -35, (task, one, sym)
         mean, var = law.moments()
-        # x_max: P(∫V > x_max) <= 10⁻⁴ by Chernoff, so the 0.999 quantile lies below it
+        # x_max: P(∫V > x_max) <= 10⁻⁴ (a far law: 10⁻⁸) by Chernoff, so the 0.999 (1 − 10⁻⁶) quantile lies below it
+        tail = task.get("tail", 4)
         k, T, s2, *_ = law._consts()
         pole = (k * k + 4 * mp.pi ** 2 / (T * T)) / (2 * s2)
-        x_max = min((mp.log(law.mgf(q * pole)) + mp.log(10 ** 4)) / (q * pole) for q in (0.3, 0.5, 0.7, 0.85, 0.95))
+        x_max = min((mp.log(law.mgf(q * pole)) + mp.log(10 ** tail)) / (q * pole) for q in (0.3, 0.5, 0.7, 0.85, 0.95))
         law.build(x_max)
-        assert law.F(x_max) > 1 - mp.mpf(10) ** -4
+        assert law.F(x_max) > 1 - mp.mpf(10) ** -tail
         cases, xs = [], []
         for u in task["us"]:
             x = law.quantile(u, bx.start_of(law, u, 0.0, float(x_max)))

@@ -1,7 +1,9 @@
 """The exact conditional law of ∫V (oracle/bk_law_exact.py, tests/golden/bk_law_exact.json) checked against itself, and
-the fp64 Broadie–Kaya oracle's samples held to it at the bars of tests/bk_law_exact_cases.py — the bars the device test
-uses, shown here to be within reach of a correct implementation in doubles.  No GPU.  Prints its worst residual/bar per
-regime and control set (`-s`)."""
+the fp64 Broadie–Kaya oracle's samples held to it at the bars of tests/bk_law_exact_cases.py — the bars the device tests
+use, shown here to be within reach of a correct implementation in doubles, in every one of the eight readings of the
+root search (bk_law_exact_cases.READINGS).  No GPU.  Prints its worst residual/bar per reading, regime and control set
+(`-s`)."""
+import functools
 import math
 
 import numpy as np
@@ -27,7 +29,7 @@ def test_the_fixture_holds_the_cases_asked_for():
     from tests.test_gpu_bk import PARAMS
     assert bc.REGIMES == PARAMS and len(PARAMS) == 9
     for name in PARAMS:
-        cs = [c for c in bc.cases_of(name) if c["VT"] != bx.VT_FLOOR]
+        cs = [c for c in bc.cases_of(name) if c["VT"] != bx.VT_FLOOR and not bc.is_far(c)]
         assert len(cs) >= 6 and len({c["VT"] for c in cs}) == 3
         assert {c["u"] for c in cs} == {1e-3, 0.3, 0.5, 0.9, 0.999}
         assert abs(PARAMS[name]["rho"] * PARAMS[name]["kappa"] / PARAMS[name]["sigma"] - 0.5) >= 0.5
@@ -39,6 +41,16 @@ def test_the_fixture_holds_the_cases_asked_for():
     t = bc.CONTROLS["tight"]
     assert (t["bk_atol"], t["bk_cf_tol"], t["bk_n_sigma"]) == (1e-10, 1e-10, 12.0)
     assert all(set(c["controls"]) == set(bc.CONTROLS) for c in bc.CASES)
+    assert sum(not bc.is_far(c) for c in bc.CASES) == 84
+    far = [c for c in bc.CASES if bc.is_far(c)]
+    # (10⁻⁵ where the maker had to move a 10⁻⁶ inward: its docstring)
+    assert sorted((c["regime"], c["u"]) for c in far) == sorted(
+        (r, u) for r, low in (("h252", 1e-6), ("intended", 1e-5), ("nu_one", 1e-5)) for u in (low, 1 - 1e-6))
+    assert [c for c in far if c["u"] < 0.5] == bc.FAR_LOW and len(bc.FAR_LOW) == 3
+    for c in far:  # the regime's median V_T, the law's own x_max from the Chernoff bound at 10⁻⁸
+        near = bc.LAWS[c["law"][:-len("/far")]]
+        assert c["VT"] == near["VT"] and mp.mpf(bc.LAWS[c["law"]]["x_max"]) > mp.mpf(near["x_max"])
+        assert mp.mpf(bc.LAWS[c["law"]]["ladder"][-1][1]) > 1 - mp.mpf(10) ** -8
 
 
 @pytest.mark.parametrize("law_id", list(bc.LAWS))
@@ -166,32 +178,71 @@ def test_half_the_step_and_twice_the_cut_off(law_id):
         assert law.verify(xs) < TEN ** -20
 
 
-def oracle_sample(case, control):
+@functools.lru_cache(maxsize=None)
+def _oracle_sample(law_id, u, control, reading):
+    case = next(c for c in bc.CASES if c["law"] == law_id and c["u"] == u)
     p, ctl = bc.REGIMES[case["regime"]], bc.CONTROLS[control]
     dist = bk_oracle.LogHestonDistribution(p["S0"], p["V0"], p["kappa"], p["theta"], p["sigma"], p["rho"], p["r"], p["T"])
     trace = []
     x = bk_oracle.sample_from_cf(case["u"], bk_oracle.HestonCFIterator(case["VT"], dist), n=ctl["bk_n_sigma"],
                                  cf_tol=ctl["bk_cf_tol"], atol=ctl["bk_atol"], moment_h=ctl["bk_moment_h"],
                                  maxiter_newton=ctl["bk_newton_maxiter"], maxiter_bisection=ctl["bk_bisect_maxiter"],
-                                 trace=trace)
+                                 trace=trace, root_form=reading[0], bracket_form=reading[1], caps=reading[2])
     return x, trace[0]
+
+
+def oracle_sample(case, control, reading=(0, 0, 0)):
+    """(sample, decision word) of the fp64 oracle; kept, for the tests that ask what the search did"""
+    return _oracle_sample(case["law"], case["u"], control, tuple(reading))
+
+
+def reading_id(reading):
+    return "root%d-bracket%d-caps%d" % tuple(reading)
 
 
 @pytest.fixture(scope="module")
 def worst():
-    w = bc.Worst("bk_law_exact (fp64 oracle)")
-    yield w
-    w.report()
+    ws = {r: bc.Worst("bk_law_exact (fp64 oracle)" + ("" if r == (0, 0, 0) else ", " + reading_id(r))) for r in bc.READINGS}
+    yield ws
+    for w in ws.values():
+        w.report()
 
 
-@pytest.mark.parametrize("control", list(bc.CONTROLS))
-@pytest.mark.parametrize("regime", list(bc.REGIMES))
-def test_the_fp64_oracle_meets_the_bars(worst, regime, control):
-    """oracle/bk_oracle.py's sample for every case's (V_T, u) under the case's controls, held to the exact law at the
-    device test's bar (the recovery term left out: the oracle hands over ∫V itself)."""
+# (reading (0, 0, 0) under the ids it has always had: regime-control)
+ORACLE_RUNS = [(regime, control, reading) for reading in bc.READINGS for control in bc.CONTROLS for regime in bc.REGIMES]
+
+
+@pytest.mark.parametrize("regime,control,reading", ORACLE_RUNS,
+                         ids=[f"{g}-{c}" + ("" if r == (0, 0, 0) else "-" + reading_id(r)) for g, c, r in ORACLE_RUNS])
+def test_the_fp64_oracle_meets_the_bars(worst, regime, control, reading):
+    """oracle/bk_oracle.py's sample for every case's (V_T, u) under the case's controls, in every reading of the root
+    search, held to the exact law at the device test's bar (the recovery term left out: the oracle hands over ∫V
+    itself).  A far case's sample must besides lie inside `reach` (Worst.check fails it otherwise) and must not be
+    max_guess: the condition the fixture's maker chose their uniforms under."""
     bad = []
     for case in bc.cases_of(regime):
-        x, decision = oracle_sample(case, control)
-        bad.append(worst.check(case, control, mp.mpf(x), decision, "oracle"))
+        x, decision = oracle_sample(case, control, reading)
+        bad.append(worst[reading].check(case, control, mp.mpf(x), decision, "oracle"))
+        if bc.is_far(case) and bc.branch_of(decision) == bc.DEC_MAXGUESS:
+            bad.append(f"{control} {case['law']} u={case['u']:g}: left by the max_guess exit")
     bad = [b for b in bad if b]
     assert not bad, "\n".join(bad)
+
+
+@pytest.mark.parametrize("reading", bc.READINGS, ids=reading_id)
+@pytest.mark.parametrize("control", list(bc.CONTROLS))
+def test_every_reading_reaches_the_ladder(control, reading):
+    """Conditions on the INPUTS, not measurements: the fixture sends the oracle down the fall-back ladder (branch 1) in
+    every reading, under either control set, on at least 5 of the 84 original cases, and under the tight set on every
+    far case with the low uniform (10⁻⁶, or the 10⁻⁵ it was moved to); the bit-pattern bisection (bracket_form 1) then runs to adjacent floats, 40 halvings at the
+    very least.  If a change of the fixture breaks one of these, the fixture is what has to change."""
+    ladders = {}
+    for case in bc.CASES:
+        decision = oracle_sample(case, control, reading)[1]
+        if bc.branch_of(decision) == bc.DEC_BISECT:
+            ladders[(case["law"], case["u"])] = bc.iterations_of(decision)
+    assert sum(not law.endswith("/far") for law, _ in ladders) >= 5, ladders
+    if control == "tight":
+        assert all((c["law"], c["u"]) in ladders for c in bc.FAR_LOW), ladders
+    if reading[1] == 1:
+        assert min(ladders.values()) >= 40, ladders

@@ -42,11 +42,13 @@ def ctx():
     c.close()
 
 
-def config_of(control, draws):
+def config_of(control, draws, reading=(0, 0, 0)):
+    """`reading`: (bk_root_form, bk_bracket_form, bk_caps) — tests/test_gpu_bk_law_exact_forms.py runs the other seven"""
     n = draws.shape[1]
     c = _ffi.make_config(_ffi.HH_HESTON, _ffi.HH_BROADIE_KAYA, n, noise_mode=_ffi.HH_NOISE_REPLAY, replay=draws.ravel())
     for k, v in bc.CONTROLS[control].items():
         setattr(c, k, type(getattr(c, k))(v))
+    c.bk_root_form, c.bk_bracket_form, c.bk_caps = reading
     return c
 
 
@@ -61,12 +63,12 @@ def draws_of(cases, n, positions, seed):
     return np.ascontiguousarray(d)
 
 
-def solve(ctx, regime, control, draws, S0=None):
+def solve(ctx, regime, control, draws, S0=None, reading=(0, 0, 0)):
     p = dict(bc.REGIMES[regime])
     if S0 is not None:
         p["S0"] = S0
     m = _ffi.make_model(**p)
-    c = config_of(control, draws)
+    c = config_of(control, draws, reading)
     n = draws.shape[1]
     res, term = _ffi.hh_result(), np.zeros(n)
     ctx.check(ctx.lib.hh_mc_solve(ctx.handle, C.byref(m), C.byref(c), C.byref(res), term.ctypes.data))

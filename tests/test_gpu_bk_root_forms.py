@@ -15,7 +15,12 @@ Two of the readings are worse conditioned than the shipped one, and the bars say
   that is rounding noise, so the ITERATION COUNT differs (by at most 8 of ~62) between two implementations on up to
   29 % of the ladders
   (the value then by what their CDFs differ by, over the density).  The count is left out of the comparison of the
-  decision words for those; the branch, the evaluations of the first search and the series length are not."""
+  decision words for those; the branch, the evaluations of the first search and the series length are not.
+
+The VALUES of these readings are held to the exact conditional law of ∫V in tests/test_gpu_bk_law_exact_forms.py, at a
+bar that depends on no decision matching anything (tests/bk_law_exact_cases.py; ~10⁻¹⁰ of the CDF under its tight
+controls).  This file now answers one question only: does the kernel take the restatement's path?  Its value bars are
+no guard on the samples and are not meant as one."""
 import ctypes as C
 import math
 
