@@ -10,6 +10,7 @@ from .analytic import (AnalyticSolution, BlackScholesAnalytic, CarrMadan, Merton
                        solve_black_scholes, solve_carr_madan, solve_merton_analytic)
 from .basket import BasketPricingProblem, BasketPricingSolution, solve_basket
 from .trees import CoxRossRubinsteinMethod, CRRSolution, solve_crr, solve_crr_basket
+from .pde import CrankNicolsonMethod, PDESolution, fd_inputs, solve_pde, solve_pde_basket
 from .dates import Date, DateTime, add_years, to_ticks, yearfrac
 from .dual import Dual, partials_of, value_of
 from .greeks import (BatchGreekProblem, FDBackward, FDCentral, FDForward, FiniteDifference,
@@ -49,6 +50,8 @@ def solve(*args, **kw):
         solve(prob::PricingProblem{<:VanillaOption{…,American,…}}, ::LSM)     least_squares_montecarlo.jl:99
         solve(prob::PricingProblem{<:VanillaOption}, ::CoxRossRubinsteinMethod) cox_ross_rubinstein.jl:99
         solve(prob::BasketPricingProblem, ::CoxRossRubinsteinMethod)         basket.jl:35
+        solve(prob::PricingProblem{<:VanillaOption} | ::BasketPricingProblem, ::CrankNicolsonMethod)
+                                                  (a Crank–Nicolson grid per option; no reference method)
     """
     from . import greeks as _g
     if len(args) == 2 and isinstance(args[0], PricingProblem) and isinstance(args[1], MonteCarlo):
@@ -64,8 +67,10 @@ def solve(*args, **kw):
         return solve_lsm(args[0], args[1], **kw)
     if len(args) == 2 and isinstance(args[0], PricingProblem) and isinstance(args[1], CoxRossRubinsteinMethod):
         return solve_crr(args[0], args[1])
+    if len(args) == 2 and isinstance(args[0], PricingProblem) and isinstance(args[1], CrankNicolsonMethod):
+        return solve_pde(args[0], args[1])
     if len(args) == 2 and isinstance(args[0], BasketPricingProblem) and \
-            isinstance(args[1], (MonteCarlo, CarrMadan, CoxRossRubinsteinMethod)):
+            isinstance(args[1], (MonteCarlo, CarrMadan, CoxRossRubinsteinMethod, CrankNicolsonMethod)):
         return solve_basket(args[0], args[1], **kw)
     if len(args) == 3 and isinstance(args[0], GreekProblem):
         if isinstance(args[1], ForwardAD):

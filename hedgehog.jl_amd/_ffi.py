@@ -112,6 +112,8 @@ HH_CM_GRAD_LEN = 8  # enum hh_cm_grad: S0, V0, kappa, theta, sigma, rho, r_drift
 HH_LSM_FORM_PER_DATE, HH_LSM_FORM_PERSISTENT, HH_LSM_FORM_AUTO = 0, 1, 2
 HH_CRR_MAX_STEPS, HH_CRR_FORM_A_MAX_STEPS = 32768, 2047
 HH_CRR_EUROPEAN, HH_CRR_AMERICAN_FORWARD, HH_CRR_AMERICAN_SPOT = 0, 1, 2
+HH_FD_MAX_SPACE, HH_FD_MAX_TIME, HH_FD_FORM_A_MAX_SPACE = 4096, 65536, 1024
+HH_FD_EUROPEAN, HH_FD_AMERICAN = 0, 1
 
 
 class HedgehogMCError(RuntimeError):
@@ -147,6 +149,7 @@ SYMBOLS = [
     ("hh_carr_madan_basket_grad", C.c_int, [_vp, C.POINTER(hh_model), C.c_int32, C.c_int32, C.c_double,
                                             C.c_double, _vp, _vp, _vp, _vp, _vp, C.c_uint32, _vp, _vp]),
     ("hh_crr_solve", C.c_int, [_vp, C.c_int32, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_uint32, _vp, _vp]),
+    ("hh_fd_solve", C.c_int, [_vp, C.c_int32, C.c_int32, C.c_int32, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("hh_lsm_grid_elems", C.c_size_t, [C.c_uint64, C.c_uint32, C.c_int32]),
     ("hh_lsm_solve", C.c_int, [_vp, C.POINTER(hh_model), C.POINTER(hh_config), C.c_int32, C.c_double, C.POINTER(hh_lsm_result), _vp, _vp, _vp]),
     ("hh_lsm_solve_grid", C.c_int, [_vp, C.POINTER(hh_model), _vp, C.c_uint64, C.c_uint32, C.c_int32, C.c_double, C.POINTER(hh_lsm_result), _vp, _vp]),

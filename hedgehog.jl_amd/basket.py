@@ -67,13 +67,17 @@ def path_groups(payoffs, steps):
 
 def solve_basket(prob: BasketPricingProblem, method, ensemble: bool = False):
     """basket.jl:35-38 for a MonteCarlo method (one simulation per expiry group), CarrMadan (every
-    Fourier integral in one launch) or CoxRossRubinsteinMethod (every tree in one launch)."""
+    Fourier integral in one launch), CoxRossRubinsteinMethod (every tree in one launch) or CrankNicolsonMethod
+    (every grid in one launch)."""
     from .analytic import AnalyticSolution, CarrMadan, solve_carr_madan_basket
     from .trees import CoxRossRubinsteinMethod, CRRSolution, solve_crr_basket
+    from .pde import CrankNicolsonMethod, solve_pde_basket
     if isinstance(method, CoxRossRubinsteinMethod):
         prices = solve_crr_basket(prob.payoffs, prob.market_inputs, method)
         return BasketPricingSolution(prob, [CRRSolution(PricingProblem(p, prob.market_inputs), method, float(x))
                                             for p, x in zip(prob.payoffs, prices)])
+    if isinstance(method, CrankNicolsonMethod):
+        return BasketPricingSolution(prob, solve_pde_basket(prob.payoffs, prob.market_inputs, method))
     if isinstance(method, CarrMadan):
         prices = solve_carr_madan_basket(prob.payoffs, prob.market_inputs, method)
         return BasketPricingSolution(prob, [AnalyticSolution(PricingProblem(p, prob.market_inputs), method,

@@ -235,6 +235,17 @@ struct CrrTree {
 // one workgroup per tree; spot_factors_dev: rows of `steps` doubles (NULL when no tree reads one)
 int launch_crr(const CrrTree* trees_dev, const double* spot_factors_dev, int steps, uint32_t n_trees,
                double* out_dev, hipStream_t s);
+// Crank–Nicolson grids (hh_fd.hip): one option's scalars as hh_fd_solve stages them (11 doubles)
+struct FdOption {
+  double S0, K, cp, r, T;  // spot, strike, ±1, zero rate, years to expiry
+  double h, x0;            // node spacing in log-spot, ln S0 (node M/2)
+  double lo, di, up;       // the operator's coefficients (hh_fd.h: fd_coef), checked positive on the host
+  int32_t style;           // enum hh_fd_style
+  int32_t pad_;
+};
+// one workgroup per option; out_dev[3][n_options]: prices, deltas, gammas
+int launch_fd(const FdOption* opts_dev, int space_steps, int time_steps, int rannacher_steps, uint32_t n_options,
+              double* out_dev, hipStream_t s);
 // LSM (hh_lsm.hip)
 uint32_t lsm_chunks(uint64_t ntot);
 size_t lsm_scratch_doubles(uint64_t ntot, uint32_t n_steps, int degree);

@@ -503,6 +503,42 @@ int hh_crr_solve(hh_ctx* ctx, int32_t steps, uint32_t n_trees, const double* for
                  double* prices_out);
 
 /*
+ * Crank–Nicolson finite differences — the Black–Scholes equation in x = ln S on a uniform grid, for a European or
+ * American VanillaOption on BlackScholesInputs, and a basket of them in ONE launch, one grid per option, all with the
+ * same (space_steps M, time_steps N, rannacher_steps R).  The reference has no such method (its roadmap names it).
+ * Per option k:
+ *   spots[k], strikes[k], cps[k] (+1 call / -1 put)
+ *   sigmas[k]      = get_vol(sigma, expiry, strike),  rates[k] = zero_rate(rate, expiry)
+ *   expiries[k]    = T = yearfrac(referenceDate, expiry)
+ *   half_widths[k] = W, half the grid's width in log-spot (the Python layer: n_std·σ√T + |ln(K/S0)| + |r − σ²/2|·T)
+ *   styles[k]      = enum hh_fd_style
+ * Grid: h = W / (M/2), x_j = ln S0 + (j − M/2)·h for j = 0 … M (the spot is node M/2), S_j = exp(x_j), payoff
+ * g_j = max(cp·(S_j − K), 0).  Operator, a = σ²/2, b = r − σ²/2:  lo = a/h² − b/(2h),  di = −2a/h² − r,
+ * up = a/h² + b/(2h).  Backwards from expiry, Δt = T/N: each of the first R steps is two implicit-Euler half steps
+ * (k = Δt/2, θ = 1), every other step one Crank–Nicolson step (k = Δt, θ = ½); a step solves
+ *   (1 − θk·di)·V_j − θk·lo·V_{j−1} − θk·up·V_{j+1} = V_j + (1 − θ)k·(lo·V_{j−1} + di·V_j + up·V_{j+1}),  j = 1 … M − 1,
+ * with the Dirichlet ends at the new τ (τ accumulated by adding k): call V_0 = 0, V_M = S_M − K·e^{−rτ} in both
+ * styles; put V_M = 0 and V_0 = K·e^{−rτ} − S_0 (European) or K − S_0 (American).  American exercise is
+ * Brennan–Schwartz, a direct solve: a put eliminates the super-diagonal from the top row downwards and substitutes
+ * upwards with V_j = max(·, g_j); a call mirrors it; European is the same solve without the max.  Outputs, c = M/2,
+ * d1 = (V_{c+1} − V_{c−1})/(2h), d2 = (V_{c+1} − 2V_c + V_{c−1})/h²:  price V_c, delta d1/S0, gamma (d2 − d1)/S0².
+ * M even, 4 <= M <= HH_FD_MAX_SPACE; 1 <= N <= HH_FD_MAX_TIME; 0 <= R <= N; 1 .. 2^20 options per call.
+ * prices_out[n_options]; deltas_out and gammas_out may be NULL.  Synchronous.  HH_ERR_INVALID — nothing is written —
+ * for a NULL required pointer, M / N / R / n_options out of range, an unknown style, or an option whose operator
+ * fails `lo > 0 && up > 0` (too coarse a grid for its drift, or a NaN).  Other scalars are not checked: every loop
+ * is bounded by M or N.  The kernel form depends on M alone (csrc/hh_fd.hip): an option prices to the same bits
+ * alone, in a basket, and at any position in one.
+ */
+#define HH_FD_MAX_SPACE 4096          /* most space intervals M                                      */
+#define HH_FD_MAX_TIME 65536          /* most time steps N                                           */
+#define HH_FD_FORM_A_MAX_SPACE 1024   /* up to here one wave prices an option, beyond it four waves  */
+enum hh_fd_style { HH_FD_EUROPEAN = 0, HH_FD_AMERICAN = 1 };
+int hh_fd_solve(hh_ctx* ctx, int32_t space_steps, int32_t time_steps, int32_t rannacher_steps, uint32_t n_options,
+                const double* spots, const double* strikes, const double* cps, const double* sigmas,
+                const double* rates, const double* expiries, const double* half_widths, const int32_t* styles,
+                double* prices_out, double* deltas_out, double* gammas_out);
+
+/*
  * Longstaff–Schwartz American pricing on the full path grid:
  *   solve(::PricingProblem{VanillaOption{…,American,…}}, ::LSM)
  *                              (src/pricing_methods/least_squares_montecarlo.jl:99-165)
@@ -851,7 +887,7 @@ int hh_wiener_fill(hh_ctx* ctx, int32_t dynamics, double rho, double T, uint32_t
  * enabled, every hh_mc_accumulate / hh_mc_solve brackets EVERYTHING IT ENQUEUES — the simulation
  * kernels and, where it is a kernel of its own, the record reduction; not the staging copies in front —
  * with HIP events on the ctx stream (one slot per call; hh_mc_accumulate_multi on Broadie–Kaya: one per
- * model — a chain's, then each finish pass's); hh_crr_solve brackets its one tree kernel (one slot per
+ * model — a chain's, then each finish pass's); hh_crr_solve and hh_fd_solve bracket their one kernel (one slot per
  * call, neither the upload nor the copy back); hh_ctx_read_timings
  * synchronizes the stream and returns the elapsed ms of the slots recorded since the last read
  * (at most 256 are kept).
