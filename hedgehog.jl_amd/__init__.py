@@ -20,7 +20,7 @@ from .greeks import (BatchGreekProblem, FDBackward, FDCentral, FDForward, Finite
 from .lsm import (LSM, EulerPaths, HestonExactPaths, LSMSolution, simulate_euler_paths,
                   simulate_heston_exact_paths, solve_lsm)
 from .montecarlo import (AbstractPricingMethod, Antithetic, BlackScholesExact, EulerMaruyama,
-                         HestonBroadieKaya, HestonDynamics, LognormalDynamics, MertonDynamics, MertonExact, MethodError,
+                         HestonBroadieKaya, HestonDynamics, HestonQE, LognormalDynamics, MertonDynamics, MertonExact, MethodError,
                          MonteCarlo, NoVarianceReduction, NormalLaw, SimulationConfig, marginal_law,
                          solve_montecarlo, solve_montecarlo_many, solve_path_payoffs)
 from .distributed import rank_device, shard_range, solve_lsm_sharded, solve_sharded
@@ -47,6 +47,8 @@ def solve(*args, **kw):
         solve(prob, ::CarrMadan) / solve(prob, ::BlackScholesAnalytic)       carr_madan.jl:47, black_scholes.jl:38
         solve(prob::PricingProblem{…, MertonInputs}, ::MonteCarlo(MertonDynamics(), MertonExact() | EulerMaruyama(), …)
               | ::CarrMadan(α, bound, MertonDynamics()) | ::MertonAnalytic)   Merton jump diffusion (no reference method)
+        solve(prob::PricingProblem{…, HestonInputs}, ::MonteCarlo(HestonDynamics(), HestonQE(psi_c, martingale), …))
+                                                                              Andersen's QE scheme (no reference method)
         solve(prob::PricingProblem{<:VanillaOption{…,American,…}}, ::LSM)     least_squares_montecarlo.jl:99
         solve(prob::PricingProblem{<:VanillaOption}, ::CoxRossRubinsteinMethod) cox_ross_rubinstein.jl:99
         solve(prob::BasketPricingProblem, ::CoxRossRubinsteinMethod)         basket.jl:35

@@ -16,7 +16,7 @@ HH_MAX_MODELS = 16
 HH_ACC_SUM, HH_ACC_SUMSQ, HH_ACC_DSUM, HH_ACC_NPATHS = 0, 1, 2, 10
 
 HH_LOGNORMAL, HH_HESTON = 0, 1
-HH_EULER_MARUYAMA, HH_EXACT_LAW, HH_BROADIE_KAYA = 0, 1, 2
+HH_EULER_MARUYAMA, HH_EXACT_LAW, HH_BROADIE_KAYA, HH_QE = 0, 1, 2, 3
 HH_NOISE_GENERATE, HH_NOISE_REPLAY = 0, 1
 HH_REPLAY_TILE_MAJOR, HH_REPLAY_PATH_MAJOR = 0, 1
 HH_PATH_SPOT, HH_PATH_LOG = 0, 1
@@ -32,6 +32,7 @@ HH_PATH_STATS_BRIDGE = 7
 HH_MAX_PATH_PAYOFFS = 1024
 HH_JUMP_MAX_MEAN = 64.0
 HH_JUMP_MAX_COUNT = 255
+HH_QE_MAX_PSI = 1e9
 
 HH_OK, HH_ERR_INVALID, HH_ERR_UNSUPPORTED, HH_ERR_HIP, HH_ERR_NOMEM, HH_ERR_RCCL, HH_ERR_DEVICE_TIMEOUT = 0, -1, -2, -3, -4, -5, -6
 HH_MGPU_AUTO, HH_MGPU_HOST_SUM, HH_MGPU_RCCL = 0, 1, 2
@@ -94,6 +95,11 @@ class hh_path_payoff(C.Structure):
 class hh_jump(C.Structure):
     """The Merton jump parameters: intensity λ, mean μ_J and standard deviation σ_J of one jump in log S."""
     _fields_ = [("lambda_", C.c_double), ("mu_j", C.c_double), ("sigma_j", C.c_double)]
+
+
+class hh_qe(C.Structure):
+    """The quadratic-exponential step's options: the branch threshold ψ_c (0: the default 1.5) and the martingale switch."""
+    _fields_ = [("psi_c", C.c_double), ("martingale", C.c_int32), ("reserved", C.c_int32)]
 
 
 HH_BK_ROOT_SECANT, HH_BK_ROOT_ORDER2 = 0, 1
@@ -171,6 +177,10 @@ SYMBOLS = [
                                         C.c_int32, C.POINTER(hh_path_payoff), C.c_uint32, C.POINTER(hh_result), _vp, _vp]),
     ("hh_carr_madan_jump", C.c_int, [_vp, C.POINTER(hh_model), C.POINTER(hh_jump), C.c_double, C.c_double,
                                      _vp, _vp, _vp, _vp, _vp, C.c_uint32, _vp]),
+    ("hh_mc_path_stats_qe", C.c_int, [_vp, C.POINTER(hh_model), C.POINTER(hh_qe), C.POINTER(hh_config), C.c_uint32,
+                                      C.c_int32, _vp, C.c_int32, _vp, C.POINTER(hh_result)]),
+    ("hh_mc_solve_path_qe", C.c_int, [_vp, C.POINTER(hh_model), C.POINTER(hh_qe), C.POINTER(hh_config), C.c_uint32,
+                                      C.c_int32, C.POINTER(hh_path_payoff), C.c_uint32, C.POINTER(hh_result), _vp, _vp, _vp]),
     ("hh_lsm_shard_xchg_elems", C.c_size_t, [C.c_uint32, C.c_int32]),
     ("hh_lsm_shard_begin", C.c_int, [_vp, C.POINTER(hh_model), C.POINTER(hh_config), C.c_int32, C.c_double, _vp]),
     ("hh_lsm_shard_phase", C.c_int, [_vp, C.c_int32, C.c_uint32, _vp, _vp]),
@@ -537,6 +547,13 @@ def make_jump(lam=0.0, mu_j=0.0, sigma_j=0.0):
     j = hh_jump()
     j.lambda_, j.mu_j, j.sigma_j = lam, mu_j, sigma_j
     return j
+
+
+def make_qe(psi_c=0.0, martingale=False):
+    """hh_qe from plain numbers (psi_c = 0: the library's default 1.5)"""
+    q = hh_qe()
+    q.psi_c, q.martingale, q.reserved = psi_c, int(bool(martingale)), 0
+    return q
 
 
 def make_config(dynamics, strategy, n_paths, n_steps=1, antithetic=0, em_split=1, noise_mode=0,

@@ -17,7 +17,7 @@ import numpy as np
 from . import _ffi
 from .domain import PATH_PAYOFFS, European, MonteCarloSolution, PricingProblem, Spot, VanillaOption
 from .dual import Dual
-from .montecarlo import (EulerMaruyama, MonteCarlo, _model_and_config, _price_from, is_merton, path_extremes,
+from .montecarlo import (EulerMaruyama, HestonQE, MonteCarlo, _model_and_config, _price_from, is_merton, is_qe, path_extremes,
                          path_monitoring, solve_montecarlo, solve_path_payoffs)
 
 
@@ -90,16 +90,17 @@ def solve_basket(prob: BasketPricingProblem, method, ensemble: bool = False):
         for _, idx in path_groups(payoffs, method.config.steps):
             for i, sol in zip(idx, solve_path_payoffs([payoffs[i] for i in idx], prob.market_inputs, method, ensemble)):
                 sols[i] = sol
-    if is_merton(prob.market_inputs, method):
-        # Merton jumps have no terminal-sample basket: what is left rides on one path simulation per expiry
-        # (EulerMaruyama: hh_mc_solve_path_jump, the vanilla kind), or is solved one by one (MertonExact: the same seed
-        # gives the same trajectories)
+    if is_merton(prob.market_inputs, method) or is_qe(method):
+        # Merton jumps and HestonQE paths have no terminal-sample basket: what is left rides on one path simulation per
+        # expiry (EulerMaruyama: hh_mc_solve_path_jump, HestonQE: hh_mc_solve_path_qe, the vanilla kind), or is solved
+        # one by one (MertonExact: the same seed gives the same trajectories)
+        on_paths = isinstance(method.strategy, (EulerMaruyama, HestonQE))
         rest: dict = {}
         for i, p in enumerate(payoffs):
             if sols[i] is None:
-                rest.setdefault(getattr(p, "expiry", None) if isinstance(method.strategy, EulerMaruyama) else i, []).append(i)
+                rest.setdefault(getattr(p, "expiry", None) if on_paths else i, []).append(i)
         for idx in rest.values():
-            if isinstance(method.strategy, EulerMaruyama):
+            if on_paths:
                 for i, sol in zip(idx, solve_path_payoffs([payoffs[i] for i in idx], prob.market_inputs, method, ensemble)):
                     sols[i] = sol
             else:

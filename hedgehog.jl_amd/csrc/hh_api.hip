@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "hh_kernels.h"
+#include "hh_qe.h"
 
 #include "hh_ctx.h"
 
@@ -1298,14 +1299,42 @@ static int check_jump(hh_ctx* ctx, const char* who, const hh_jump* jump, double 
   return HH_OK;
 }
 
+// The scalars of a quadratic-exponential entry point (`who`), after the checks every path entry point makes.
+static int check_qe(hh_ctx* ctx, const char* who, const hh_model* m, const hh_config* c, const hh_qe* qe) {
+  if (!(m->kappa > 0.0) || !(m->theta > 0.0) || !(m->sigma > 0.0) || !(m->V0 >= 0.0))
+    return fail(ctx, HH_ERR_INVALID, "%s: kappa, theta, sigma must be > 0 and V0 >= 0", who);
+  // ψ <= σ²/(2κθ) in every state (its maximum over v >= 0): bounded, 1 − p = 2/(ψ + 1) stays far from rounding to 0
+  if (!((m->sigma * m->sigma) / (2.0 * m->kappa * m->theta) <= HH_QE_MAX_PSI))
+    return fail(ctx, HH_ERR_INVALID, "%s: sigma^2 / (2 kappa theta) = %g is above HH_QE_MAX_PSI = %g", who,
+                (m->sigma * m->sigma) / (2.0 * m->kappa * m->theta), (double)HH_QE_MAX_PSI);
+  if (!(qe->psi_c == 0.0 || (qe->psi_c >= 1.0 && qe->psi_c <= 2.0)))
+    return fail(ctx, HH_ERR_INVALID, "%s: psi_c must be 0 (the default 1.5) or lie in [1, 2]", who);
+  const hh::QeArgs q = hh::qe_launch_args(*m, *c, *qe);
+  const double all[] = {q.E, q.c1, q.c2, q.th_ome, q.rdt, q.K0, q.K1, q.K2, q.K3, q.A, q.k13};
+  for (double t : all)
+    if (!std::isfinite(t)) return fail(ctx, HH_ERR_INVALID, "%s: the step's constants are not finite", who);
+  if (!(q.th_ome > 0.0) || !(q.c2 > 0.0))
+    return fail(ctx, HH_ERR_INVALID, "%s: kappa * dt is so small that 1 - exp(-kappa * dt) or the step's variance rounds to 0", who);
+  if (qe->martingale && q.A > 0.0)
+    return fail(ctx, HH_ERR_UNSUPPORTED,
+                "%s: the martingale correction needs A = K2 + K4/2 <= 0 (every rho <= 0 gives that), A = %g: run without it",
+                who, q.A);
+  return HH_OK;
+}
+
 // The checks of every entry point, then the statistics of every trajectory into ctx->path_stats (one timing slot).
 // jump (NULL: none): the Merton form — lognormal dynamics, the monitored rows.
+// qe (NULL: none): the quadratic-exponential Heston step — the monitored rows, and the variance at expiry of every
+// member into ctx->heston_var when want_var.
 static int run_path_stats(hh_ctx* ctx, const char* who, const hh_model* m, const hh_config* c, uint32_t monitor_every,
-                          int32_t include_start, int32_t extremes, const hh_jump* jump = nullptr) {
+                          int32_t include_start, int32_t extremes, const hh_jump* jump = nullptr,
+                          const hh_qe* qe = nullptr, bool want_var = false) {
   const bool hest = c->dynamics == HH_HESTON;
+  if (qe && (!hest || c->strategy != HH_QE))
+    return fail(ctx, HH_ERR_UNSUPPORTED, "%s needs HestonDynamics + the quadratic-exponential strategy (HH_QE)", who);
   if (jump && (hest || c->strategy != HH_EULER_MARUYAMA))
     return fail(ctx, HH_ERR_UNSUPPORTED, "%s needs LognormalDynamics + EulerMaruyama", who);
-  if (c->strategy != HH_EULER_MARUYAMA || (c->dynamics != HH_LOGNORMAL && !hest))
+  if (!qe && (c->strategy != HH_EULER_MARUYAMA || (c->dynamics != HH_LOGNORMAL && !hest)))
     return fail(ctx, HH_ERR_UNSUPPORTED, "%s needs LognormalDynamics or HestonDynamics + EulerMaruyama", who);
   if (c->noise_mode == HH_NOISE_REPLAY || c->n_partials != 0)
     return fail(ctx, HH_ERR_UNSUPPORTED, "%s: GENERATE noise, no dual partials", who);
@@ -1324,12 +1353,17 @@ static int run_path_stats(hh_ctx* ctx, const char* who, const hh_model* m, const
     return fail(ctx, HH_ERR_INVALID, "%s: S0, T > 0, |rho| <= 1, model scalars finite", who);
   int rc;
   if (jump && (rc = check_jump(ctx, who, jump, m->T / (double)c->n_steps))) return rc;
+  if (qe && (rc = check_qe(ctx, who, m, c, qe))) return rc;
   const hh::PathStatsLayout at(c->n_paths, c->antithetic != 0, path_stat_rows(extremes));
   if ((rc = ensure(ctx, ctx->path_stats, at.total))) return rc;
+  if (qe && want_var && (rc = ensure(ctx, ctx->heston_var, (size_t)at.n_total))) return rc;
   const uint64_t* seeds_dev = nullptr;
   if ((rc = stage_path_seeds(ctx, c, &seeds_dev))) return rc;
   if ((rc = begin_timing(ctx))) return rc;
-  if (jump)
+  if (qe)
+    HH_HIP(ctx, hh::launch_qe_stats(*m, *c, *qe, seeds_dev, monitor_every, include_start != 0, ctx->path_stats,
+                                    want_var ? ctx->heston_var.p : nullptr, ctx->stream));
+  else if (jump)
     HH_HIP(ctx, hh::launch_jump_stats(*m, *c, *jump, seeds_dev, monitor_every, include_start != 0, ctx->path_stats, ctx->stream));
   else
     HH_HIP(ctx, hh::launch_path_stats(*m, *c, seeds_dev, monitor_every, include_start != 0, extremes == HH_EXTREMES_BRIDGE,
@@ -1340,19 +1374,21 @@ static int run_path_stats(hh_ctx* ctx, const char* who, const hh_model* m, const
 // hh_mc_path_stats and hh_mc_path_stats_ex
 static int path_stats_call(hh_ctx* ctx, const char* who, const hh_model* m, const hh_config* c, uint32_t monitor_every,
                            int32_t include_start, int32_t extremes, double* stats, int32_t stats_on_device,
-                           hh_result* out) {
+                           hh_result* out, const hh_qe* qe = nullptr, double* var_T = nullptr) {
   if (!ctx) return HH_ERR_INVALID;
   std::lock_guard<std::recursive_mutex> lock__(ctx->mu);
   if (!m || !c || !stats) return fail(ctx, HH_ERR_INVALID, "%s: NULL argument", who);
   const WallClock clock;
   HH_HIP(ctx, hipSetDevice(ctx->device));
   HH_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-  int rc = run_path_stats(ctx, who, m, c, monitor_every, include_start, extremes);
+  int rc = run_path_stats(ctx, who, m, c, monitor_every, include_start, extremes, nullptr, qe, var_T != nullptr);
   if (rc) return rc;
   HH_HIP(ctx, hipEventRecord(ctx->ev1, ctx->stream));
   const hh::PathStatsLayout at(c->n_paths, c->antithetic != 0, path_stat_rows(extremes));
   HH_HIP(ctx, hipMemcpyAsync(stats, ctx->path_stats, at.total * sizeof(double),
                              stats_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, ctx->stream));
+  if (var_T)
+    HH_HIP(ctx, hipMemcpyAsync(var_T, ctx->heston_var, at.n_total * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   HH_HIP(ctx, hipStreamSynchronize(ctx->stream));
   if ((rc = release_host_operands(ctx))) return rc;
   if (!out) return HH_OK;
@@ -1378,7 +1414,7 @@ int hh_mc_path_stats_ex(hh_ctx* ctx, const hh_model* m, const hh_config* c, uint
 static int solve_path_call(hh_ctx* ctx, const char* who, int32_t last_kind, const hh_model* m, const hh_config* c,
                            uint32_t monitor_every, int32_t include_start, int32_t extremes, const hh_path_payoff* payoffs,
                            uint32_t n_payoffs, hh_result* out, double* path_values, double* stats,
-                           const hh_jump* jump = nullptr) {
+                           const hh_jump* jump = nullptr, const hh_qe* qe = nullptr, double* var_T = nullptr) {
   if (!ctx) return HH_ERR_INVALID;
   std::lock_guard<std::recursive_mutex> lock__(ctx->mu);
   if (!m || !c || !payoffs || !out) return fail(ctx, HH_ERR_INVALID, "%s: NULL argument", who);
@@ -1397,7 +1433,7 @@ static int solve_path_call(hh_ctx* ctx, const char* who, int32_t last_kind, cons
   const WallClock clock;
   HH_HIP(ctx, hipSetDevice(ctx->device));
   HH_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-  int rc = run_path_stats(ctx, who, m, c, monitor_every, include_start, extremes, jump);
+  int rc = run_path_stats(ctx, who, m, c, monitor_every, include_start, extremes, jump, qe, var_T != nullptr);
   if (rc) return rc;
 
   const hh::PathStatsLayout at(c->n_paths, c->antithetic != 0, path_stat_rows(extremes));
@@ -1428,6 +1464,8 @@ static int solve_path_call(hh_ctx* ctx, const char* who, int32_t last_kind, cons
                                hipMemcpyDeviceToHost, ctx->stream));
   if (stats)
     HH_HIP(ctx, hipMemcpyAsync(stats, ctx->path_stats, at.total * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  if (var_T)
+    HH_HIP(ctx, hipMemcpyAsync(var_T, ctx->heston_var, at.n_total * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   HH_HIP(ctx, hipStreamSynchronize(ctx->stream));
   if ((rc = release_host_operands(ctx))) return rc;
   double kernel_ms, total_ms;
@@ -1529,6 +1567,27 @@ int hh_carr_madan_jump(hh_ctx* ctx, const hh_model* m, const hh_jump* jump, doub
     prices_out[k] = cps[k] > 0.0 ? call : call - m->S0 + strikes[k] * discounts[k];
   }
   return HH_OK;
+}
+
+// ---- Heston paths by the quadratic-exponential scheme (hedgehog_mc.h; kernel: hh_qe.hip) ----------------------
+
+int hh_mc_path_stats_qe(hh_ctx* ctx, const hh_model* m, const hh_qe* qe, const hh_config* c, uint32_t monitor_every,
+                        int32_t include_start, double* stats, int32_t stats_on_device, double* var_T, hh_result* out) {
+  if (!ctx) return HH_ERR_INVALID;
+  std::lock_guard<std::recursive_mutex> lock__(ctx->mu);
+  if (!qe) return fail(ctx, HH_ERR_INVALID, "hh_mc_path_stats_qe: NULL argument");
+  return path_stats_call(ctx, "hh_mc_path_stats_qe", m, c, monitor_every, include_start, HH_EXTREMES_MONITORED, stats,
+                         stats_on_device, out, qe, var_T);
+}
+
+int hh_mc_solve_path_qe(hh_ctx* ctx, const hh_model* m, const hh_qe* qe, const hh_config* c, uint32_t monitor_every,
+                        int32_t include_start, const hh_path_payoff* payoffs, uint32_t n_payoffs, hh_result* out,
+                        double* path_values, double* stats, double* var_T) {
+  if (!ctx) return HH_ERR_INVALID;
+  std::lock_guard<std::recursive_mutex> lock__(ctx->mu);
+  if (!qe) return fail(ctx, HH_ERR_INVALID, "hh_mc_solve_path_qe: NULL argument");
+  return solve_path_call(ctx, "hh_mc_solve_path_qe", HH_PAYOFF_LOOKBACK_FIXED, m, c, monitor_every, include_start,
+                         HH_EXTREMES_MONITORED, payoffs, n_payoffs, out, path_values, stats, nullptr, qe, var_T);
 }
 
 // ---- LSM on an ensemble sharded over several devices ------------------------------------------------

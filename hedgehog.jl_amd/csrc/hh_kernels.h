@@ -302,6 +302,14 @@ int launch_jump_stats(const hh_model& m, const hh_config& c, const hh_jump& jump
 // launch_carr_madan_basket (lognormal dynamics, compat_sqrt_alpha = 0) with the Merton characteristic function
 int launch_carr_madan_jump(const hh_model& m, const hh_jump& jump, double alpha, double bound,
                            const double* per_payoff_dev, uint32_t n_payoffs, double* out_dev, hipStream_t s);
+// Heston paths by the quadratic-exponential scheme (hh_qe.hip; include/hedgehog_mc.h, "Heston paths by the
+// quadratic-exponential scheme").  The scalars are checked by the entry points, which ask qe_launch_args for the
+// host-formed constants (A decides whether the martingale correction is admitted).
+struct QeArgs;
+QeArgs qe_launch_args(const hh_model& m, const hh_config& c, const hh_qe& qe);
+// launch_path_stats' monitored form with the QE step: the same five rows; var_T (nullable): n_total doubles
+int launch_qe_stats(const hh_model& m, const hh_config& c, const hh_qe& qe, const uint64_t* seeds_dev,
+                    uint32_t monitor_every, bool include_start, double* stats, double* var_T, hipStream_t s);
 // form: kLsmFormPersistent = the whole backward induction in ONE launch when the ensemble fits the
 // chip (else it falls back by itself), kLsmFormPerDate = one launch per exercise date.  *form_used
 // says which was enqueued; after a persistent launch the caller synchronises and reads the word at

@@ -14,7 +14,7 @@ import numpy as np
 from . import _ffi
 from .dates import yearfrac
 from .dual import Dual, n_partials, partials_of, value_of
-from .domain import (PATH_PAYOFFS, ArithmeticAverage, AsianOption, BarrierOption, BlackScholesInputs, Call,
+from .domain import (PATH_PAYOFFS, American, ArithmeticAverage, AsianOption, BarrierOption, BlackScholesInputs, Call,
                     CashOrNothing, ContinuousMonitoring, DigitalOption, DownAndIn, DownAndOut, European, HestonInputs,
                     LookbackOption, MertonInputs, Monitoring,
                     MonteCarloSolution, PricingProblem, Spot, UpAndIn, UpAndOut, VanillaOption, _DeviceSamples, df,
@@ -43,6 +43,23 @@ for _c in (LognormalDynamics, HestonDynamics, NoVarianceReduction, Antithetic, E
     _c.__eq__ = lambda a, b: type(a) is type(b)
     _c.__hash__ = lambda a: hash(type(a).__name__)
     _c.__repr__ = lambda a: type(a).__name__ + "()"
+
+
+
+
+# ---- Heston paths by Andersen's quadratic-exponential scheme (the reference has none; include/hedgehog_mc.h) ----
+@dataclass(frozen=True)
+class HestonQE(SimulationStrategy):
+    """MonteCarlo(HestonDynamics(), HestonQE(psi_c, martingale), config) on HestonInputs: every payoff on the path
+    statistics of hh_mc_solve_path_qe.  psi_c in [1, 2] separates the quadratic from the exponential branch;
+    martingale=True corrects the log-spot drift per step so that the discounted spot is a martingale of the scheme
+    (admitted by the library for A = K2 + K4/2 <= 0, which every ρ <= 0 gives)."""
+    psi_c: float = 1.5
+    martingale: bool = False
+
+    def __post_init__(self):
+        if not 1.0 <= float(self.psi_c) <= 2.0:
+            raise ValueError(f"HestonQE: psi_c must lie in [1, 2] (both branches exist exactly there), not {self.psi_c}")
 
 
 class AbstractPricingMethod: pass
@@ -181,6 +198,30 @@ def _model_and_config(prob: PricingProblem, method: MonteCarlo, n_paths=None, pa
     return model, c, keep, P, discount
 
 
+def is_qe(method) -> bool:
+    return isinstance(getattr(method, "strategy", None), HestonQE)
+
+
+def _qe_structs(prob: PricingProblem, method: MonteCarlo):
+    """(hh_model, hh_config, hh_qe) of a quadratic-exponential solve: the structs of the Euler–Maruyama Heston solve on
+    the same market (its dates and drift rate) under strategy HH_QE, and the scheme's options beside them.  Anything
+    but HestonDynamics on HestonInputs is a MethodError; so is a Dual anywhere: these solves carry no partials."""
+    import dataclasses
+    m, dyn, strat = prob.market_inputs, method.dynamics, method.strategy
+    if not (isinstance(dyn, HestonDynamics) and isinstance(m, HestonInputs)):
+        raise MethodError(f"HestonQE simulates HestonDynamics() on HestonInputs, not {type(dyn).__name__} on "
+                          f"{type(m).__name__}: use EulerMaruyama or the model's exact strategy there")
+    if method.devices is not None:
+        raise MethodError("HestonQE solves run on one device (MonteCarlo.devices is not supported)")
+    model, c, keep, P, _ = _model_and_config(prob, dataclasses.replace(method, strategy=EulerMaruyama()))
+    if P:
+        raise MethodError("HestonQE solves carry no dual partials (ForwardAD): use FiniteDifference — its solves share "
+                          "their seeds")
+    del keep
+    c.strategy = _ffi.HH_QE
+    return model, c, _ffi.make_qe(float(strat.psi_c), bool(strat.martingale))
+
+
 def is_merton(market_inputs, method) -> bool:
     """Does anything of the pair name the Merton model?  Then only the Merton routes may take it."""
     return isinstance(market_inputs, MertonInputs) or isinstance(getattr(method, "dynamics", None), MertonDynamics) or \
@@ -259,6 +300,10 @@ def solve_montecarlo(prob: PricingProblem, method: MonteCarlo, ensemble: bool = 
 
     `replay` (optional, build extension): Wiener increments to consume instead of drawing them —
     numpy array [path][step][comp] (or tile-major), the noise-replay parity mode of DESIGN.md."""
+    if is_qe(method):  # every payoff on the path statistics (hh_mc_solve_path_qe)
+        if replay is not None:
+            raise MethodError("HestonQE solves draw their own noise: no replay (EulerMaruyama takes one)")
+        return solve_path_payoffs([prob.payoff], prob.market_inputs, method, ensemble)[0]
     if is_merton(prob.market_inputs, method):
         if replay is not None:
             raise MethodError("Merton solves draw their own noise: no replay")
@@ -329,7 +374,7 @@ def solve_montecarlo_many(probs, method: MonteCarlo, replay=None, replay_layout=
         return None
     if any(isinstance(p.payoff, PATH_PAYOFFS) for p in probs):  # one solve after the other (hh_mc_solve_path)
         return None
-    if any(is_merton(p.market_inputs, method) for p in probs):  # no hh_mc_solve_multi form: one after the other
+    if is_qe(method) or any(is_merton(p.market_inputs, method) for p in probs):  # no hh_mc_solve_multi form: one after the other
         return None
     packed = [_model_and_config(p, method) for p in probs]
     if any(P for _, _, _, P, _ in packed):
@@ -415,8 +460,16 @@ def pack_path_payoff(payoff) -> _ffi.hh_path_payoff:
 def _path_structs(payoffs, market_inputs, method: MonteCarlo):
     """(hh_model, hh_config, monitor_every, include_start, hh_jump or None) of payoffs that share an expiry and a
     monitoring.  The model and configuration are those of a European solve to that expiry (its strike and cp are not
-    read); Merton inputs bring their jump parameters."""
-    if not isinstance(method.strategy, EulerMaruyama):
+    read); Merton inputs bring their jump parameters, a HestonQE strategy its hh_qe in the same place."""
+    if is_qe(method):
+        for p in payoffs:
+            if isinstance(getattr(p, "exercise_style", None), American):
+                raise MethodError("American exercise is not offered on HestonQE paths: use LSM(HestonDynamics(), "
+                                  "EulerMaruyama() | HestonBroadieKaya(), …)")
+            if isinstance(getattr(p, "monitoring", None), ContinuousMonitoring):
+                raise MethodError("ContinuousMonitoring() is not offered on HestonQE paths (the step's interpolation is "
+                                  "no frozen-coefficient bridge): monitor on the dates of a Monitoring, or use EulerMaruyama()")
+    elif not isinstance(method.strategy, EulerMaruyama):
         raise MethodError(f"path-dependent payoffs need EulerMaruyama paths, not {type(method.strategy).__name__}")
     if method.devices is not None:
         raise MethodError("path-dependent payoffs run on one device (MonteCarlo.devices is not supported)")
@@ -429,6 +482,9 @@ def _path_structs(payoffs, market_inputs, method: MonteCarlo):
         raise ValueError("payoffs of one path solve share a monitoring")
     every, start = mons.pop() if mons else (steps, False)
     european = VanillaOption(1.0, expiries.pop(), European(), Call(), Spot())
+    if is_qe(method):
+        model, c, qe = _qe_structs(PricingProblem(european, market_inputs), method)
+        return model, c, every, start, qe
     if is_merton(market_inputs, method):
         model, c, jump = _merton_structs(PricingProblem(european, market_inputs), method)
         return model, c, every, start, jump
@@ -444,9 +500,11 @@ def solve_path_payoffs(payoffs, market_inputs, method: MonteCarlo, ensemble: boo
     order.  hh_mc_solve_path as long as no payoff is a lookback or continuously monitored; hh_mc_solve_path_ex otherwise.
     `ensemble`: the (5, n_total) statistics of the trajectories — (7, n_total) in bridge mode — (rows: enum
     hh_path_stat), shared by the solutions; n_total counts the antithetic mirrors, columns trajectories + i.
+    A HestonQE strategy: hh_mc_solve_path_qe, the monitored rows only.
     Merton inputs: hh_mc_solve_path_jump, the monitored rows only — ContinuousMonitoring is a MethodError, a bridge
     between two states being wrong once a jump lies between them."""
     model, c, every, start, jump = _path_structs(payoffs, market_inputs, method)
+    qe, jump = (jump, None) if isinstance(jump, _ffi.hh_qe) else (None, jump)
     modes = {e for e in (path_extremes(p) for p in payoffs) if e is not None}
     if len(modes) > 1:
         raise ValueError("payoffs of one path solve share an extremes mode (Monitoring or ContinuousMonitoring)")
@@ -462,7 +520,10 @@ def solve_path_payoffs(payoffs, market_inputs, method: MonteCarlo, ensemble: boo
     n_total = int(c.n_paths) * (2 if c.antithetic else 1)
     stats = np.empty((_ffi.HH_PATH_STATS_BRIDGE if bridge else _ffi.HH_PATH_STATS, n_total)) if ensemble else None
     res = (_ffi.hh_result * len(payoffs))()
-    if jump is not None:
+    if qe is not None:
+        ctx.check(ctx.lib.hh_mc_solve_path_qe(ctx.handle, C.byref(model), C.byref(qe), C.byref(c), every, int(start), packed,
+                                              len(payoffs), res, None, stats.ctypes.data if ensemble else None, None))
+    elif jump is not None:
         ctx.check(ctx.lib.hh_mc_solve_path_jump(ctx.handle, C.byref(model), C.byref(jump), C.byref(c), every, int(start),
                                                 packed, len(payoffs), res, None, stats.ctypes.data if ensemble else None))
     elif extended:

@@ -76,7 +76,8 @@ enum hh_status {
 /* montecarlo.jl:8-22 */
 enum hh_dynamics { HH_LOGNORMAL = 0, HH_HESTON = 1 };
 /* montecarlo.jl:86-115: EulerMaruyama / BlackScholesExact / HestonBroadieKaya */
-enum hh_strategy { HH_EULER_MARUYAMA = 0, HH_EXACT_LAW = 1, HH_BROADIE_KAYA = 2 };
+enum hh_strategy { HH_EULER_MARUYAMA = 0, HH_EXACT_LAW = 1, HH_BROADIE_KAYA = 2,
+                   HH_QE = 3 /* the quadratic-exponential Heston step: hh_mc_path_stats_qe, hh_mc_solve_path_qe only */ };
 enum hh_noise_mode { HH_NOISE_GENERATE = 0, HH_NOISE_REPLAY = 1 };
 enum hh_replay_layout { HH_REPLAY_TILE_MAJOR = 0, HH_REPLAY_PATH_MAJOR = 1 };
 
@@ -773,6 +774,70 @@ int hh_mc_solve_path_jump(hh_ctx* ctx, const hh_model* model, const hh_jump* jum
 int hh_carr_madan_jump(hh_ctx* ctx, const hh_model* model, const hh_jump* jump, double alpha, double bound,
                        const double* strikes, const double* cps, const double* Ts, const double* r_drifts,
                        const double* discounts, uint32_t n_payoffs, double* prices_out);
+
+/*
+ * Heston paths by the quadratic-exponential scheme (Andersen 2008, "Simple and efficient simulation of the Heston
+ * stochastic volatility model", the QE scheme with central weights γ1 = γ2 = ½).  The Euler step with a clipped
+ * variance is badly biased where 2κθ < σ²; this step matches the conditional mean and variance of the variance process
+ * exactly and costs about what an Euler step costs.  The reference has no such scheme; the conventions are this
+ * library's.  cfg->strategy = HH_QE, cfg->dynamics = HH_HESTON; hh_qe carries ψ_c and the martingale switch.
+ *
+ * ON THE HOST, once per call, each a single rounded fp64 operation in this order (csrc/hh_qe.h, qe_args), with
+ * κ, θ, σ, ρ of the model, r = model->r_drift and dt = T/n_steps:
+ *   E   = exp(−(κ·dt))             ome = 1 − E              s2 = σ·σ
+ *   c1  = ((s2·E)·ome)/κ           c2  = ((θ·s2)·(ome·ome))/(2·κ)           th_ome = θ·ome        rdt = r·dt
+ *   K0  = −((((ρ·κ)·θ)·dt)/σ)      h   = (½·dt)·((κ·ρ)/σ − ½)
+ *   K1  = h − ρ/σ                  K2  = h + ρ/σ            K3 = K4 = (½·dt)·(1 − ρ·ρ)
+ *   A   = K2 + ½·K4                k13 = K1 + ½·K3          ψ_c = qe->psi_c, 1.5 when that is 0
+ * They travel by value beside the model block (QeArgs); no existing struct changes.
+ *
+ * ONE STEP k takes (x, v) = (log S, variance) to (x′, v′), operation by operation (csrc/hh_qe.h):
+ *   m  = th_ome + v·E              s² = v·c1 + c2           ψ = s²/(m·m)
+ *   quadratic branch, ψ <= ψ_c:    t = 2/ψ     b² = (t − 1) + sqrt(t)·sqrt(t − 1)      a = m/(1 + b²)
+ *                                  v′ = a·((sqrt(b²) + Z_v)·(sqrt(b²) + Z_v))
+ *   exponential branch, otherwise: p = (ψ − 1)/(ψ + 1)     q = 1 − p     β = q/m
+ *                                  v′ = 0 if U <= p, else log(q/(1 − U))/β
+ *   x′ = (x + (((rdt + K0) + K1·v) + K2·v′)) + sqrt(K3·v + K4·v′)·Z_x
+ * MARTINGALE CORRECTION (qe->martingale != 0): K0 is replaced, per step and member, by K0* = −ln M − k13·v with
+ *   quadratic branch:    d = 1 − (2·A)·a       ln M = ((A·b²)·a)/d − ½·log(d)
+ *   exponential branch:  ln M = log(p + (β·q)/(β − A))
+ * so that E[exp(x′ − rdt) | x, v] = exp(x) exactly.  It is admitted only when A <= 0 — every ρ <= 0 gives that — where
+ * d >= 1 and β − A >= β > 0 in every state; A > 0 with the correction requested is HH_ERR_UNSUPPORTED.
+ * Degenerate states: the checks below give th_ome > 0 and c2 > 0, and v >= 0 always (v′ is a square times a > 0, zero,
+ * or a logarithm of a number >= 1 over β > 0), so m > 0 and ψ > 0 in every state: no division meets a zero.
+ * ψ <= ψ_c <= 2 gives t >= 1, ψ > ψ_c >= 1 gives 0 < p < 1; K3·v + K4·v′ >= 0.  Every device loop is bounded by n_steps.
+ *
+ * DRAWS: Philox4x32-10 blocks under the trajectory's seed (seeds[i]) as key, counter word 3 = 5, a domain no other draw
+ * of the library uses.
+ *   block (k, 0, 0, 5)  the Box–Muller pair of step k: (Z_v, Z_x), independent — the correlation lives in the K's
+ *   block (k, 1, 0, 5)  U = ((w >> 12) + ½)·2⁻⁵² from output words 0, 1; drawn only by a trajectory that is in the
+ *                       exponential branch at step k
+ * The mirror of an antithetic pair takes −Z_v, −Z_x and 1 − U (exact: the uniforms are symmetric about ½) on its own
+ * states, and reads U when it is itself in the exponential branch.
+ *
+ * hh_mc_path_stats_qe / hh_mc_solve_path_qe: hh_mc_path_stats / hh_mc_solve_path_ex under HH_EXTREMES_MONITORED with this
+ * step in place of the Euler step — the same monitoring dates, the same statistics arithmetic, the same five rows, the
+ * same payoff kernel; kinds 0 .. 7 are admitted, the lookbacks read the monitored rows.  var_T (nullable, host):
+ * n_total doubles, the variance at expiry of each member, mirrors at n_paths + i.  Synchronous; timing slots as the
+ * Euler pair's.  Errors, checked on the host before any launch.  HH_ERR_INVALID: qe is NULL; κ, θ or σ not > 0,
+ * V0 < 0, |ρ| > 1, anything not finite; ψ_c outside {0} ∪ [1, 2]; κ·dt so small that 1 − E rounds to 0;
+ * σ²/(2κθ) — the maximum of ψ over v >= 0, whatever dt — above HH_QE_MAX_PSI, so that 1 − p = 2/(ψ + 1) and β stay
+ * far from rounding to 0; everything
+ * hh_mc_solve_path_ex rejects.  HH_ERR_UNSUPPORTED: dynamics other than HH_HESTON, a strategy other than HH_QE, REPLAY
+ * noise, n_partials > 0, the correction with A > 0 (run without it).
+ * Not provided: bridge extremes (the QE step's interpolation is not a frozen-coefficient bridge), REPLAY noise, dual
+ * partials (bump the inputs: the solves share their seeds), accumulate and multi-GPU forms, the hh_mc_solve_multi form,
+ * LSM on these paths, a spot / variance grid, weights other than ½, the TG scheme, the correction for A > 0, a Julia
+ * binding.
+ */
+#define HH_QE_MAX_PSI 1e9   /* largest σ²/(2κθ), the maximum of ψ over v >= 0, these entry points admit */
+typedef struct hh_qe { double psi_c; int32_t martingale; int32_t reserved; } hh_qe;   /* 16 bytes */
+int hh_mc_path_stats_qe(hh_ctx* ctx, const hh_model* model, const hh_qe* qe, const hh_config* cfg,
+                        uint32_t monitor_every, int32_t include_start, double* stats, int32_t stats_on_device,
+                        double* var_T, hh_result* out);
+int hh_mc_solve_path_qe(hh_ctx* ctx, const hh_model* model, const hh_qe* qe, const hh_config* cfg,
+                        uint32_t monitor_every, int32_t include_start, const hh_path_payoff* payoffs,
+                        uint32_t n_payoffs, hh_result* out, double* path_values, double* stats, double* var_T);
 
 /*
  * The same solve for an ensemble SHARDED over several devices (one process and one hh_ctx per

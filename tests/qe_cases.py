@@ -1,0 +1,363 @@
+"""Heston paths by the quadratic-exponential scheme (include/hedgehog_mc.h, "Heston paths by the quadratic-exponential
+scheme"): what the host and the device tests share.
+
+  * the step restated generically in the number type, as tests/merton_cases.py's walk is: mpmath at 50 digits is the
+    reference, Python floats in the header's operation order are "the same formulas in fp64", whose distance from the
+    50-digit run is e64.  The host-formed constants are formed by the same walk, so the float run forms them as
+    csrc/hh_qe.h's qe_args does;
+  * the draws of domain 5 from the oracle's host Philox: the normals restated at 50 digits by hh_rng.h's formulas
+    (tests/lognormal_exact_cases.box_muller), U by path_bridge_cases.u01;
+  * the conditional moments of v′ and the martingale identity by exact integration over Z_v and U.
+
+The bar of a statistic is euler_tangent_cases.path_bar(e64, A) = 20·max(e64, ε·A), imported.  Two magnitudes are
+carried beside every value and A is the SMALLER of them:
+  a  oracle/euler_exact.py's rules: |x| + |y| for a sum, A_x·A_y for a product, max(|f|, |f′|·A_w) through a function —
+     a quotient x/y is x·(1/y) with 1/y such a function.  Through this step's chain of quotients (ψ = s²/m², t = 2/ψ,
+     a = m/(1 + b²), β = (1 − p)/m) the product rule multiplies the ratios A/|value| of its operands at every
+     operation, and they start at 10 (1 − E cancels a digit): a reaches 1e9 after one step, 1e198 after two and
+     overflows on the third.  Bars made of it alone are infinite and hold nothing;
+  b  the first-order running error bound in units of ε: b_x + b_y + |r| for a sum, |x|·b_y + |y|·b_x + |r| for a
+     product, b_x/|y| + |x|·b_y/y² + |r| for a quotient, |f′|·b_w + |f| through a function (r, f: the result, whose own
+     rounding is the last term).  It stays within a few hundred times the value over six steps.
+So no bar is wider than the rules of oracle/euler_exact.py make it, and every bar is finite.  A normal enters with its
+own magnitude |z|.  The BRANCH a state takes
+(ψ <= ψ_c; U <= p) is no rounding matter: tests/golden/make_qe_exact.py asserts for every trajectory of the device
+tests' fixed seeds that the fp64 walk and the 50-digit walk take the same branches and that |ψ − ψ_c| and |U − p|
+exceed MARGIN at every step.
+
+MUTATIONS of the restatement (tests/test_qe_host.py holds each to the golden values): `mut` names one of
+  swap_K   K1 and K2 exchanged            b_not_b2  a = m/(1 + b)             p_over_psi  p = (ψ − 1)/ψ
+  keep_U   the mirror keeps U             K3_full   the correction with K3 for K3/2
+"""
+import json
+import os
+
+import mpmath as mp
+import numpy as np
+
+from hedgehog_jl_amd import _ffi
+from oracle import euler_exact as ex
+from tests.lognormal_exact_cases import box_muller
+from tests.path_bridge_cases import u01
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "qe_exact.json")
+DOM_QE = 5
+MARGIN = 1e-9
+DPS = ex.DPS
+MUTATIONS = ("swap_K", "b_not_b2", "p_over_psi", "keep_U", "K3_full")
+
+# the model of the issue's first section (2κθ = 0.024 against σ² = 0.81: far inside the region Euler is biased in)
+LAW = dict(S0=100.0, V0=0.04, kappa=0.3, theta=0.04, sigma=0.9, rho=-0.5, r_drift=0.0, T=5.0)
+# the correction's model
+DRIFTY = dict(S0=100.0, V0=0.04, kappa=0.5, theta=0.04, sigma=1.0, rho=-0.9, r_drift=0.0, T=10.0)
+MODELS = {
+    # near the Feller boundary (2κθ = 0.16, σ² = 0.25: ψ at v = 0 is 1.5625, just above ψ_c): ψ mostly below 1.5
+    "feller": dict(S0=100.0, V0=0.04, kappa=2.0, theta=0.04, sigma=0.5, rho=-0.7, r_drift=0.03, T=0.5),
+    # the first section's model started at a small variance: ψ mostly far above 1.5
+    "low_v0": dict(LAW, V0=0.001),
+}
+PATH_N = 257
+PATH_SHAPES = ((1, 1), (5, 1), (6, 3))  # (n_steps, monitor_every)
+GOLDEN_N, GOLDEN_SHAPE = 64, (5, 1)     # the trajectories whose 50-digit rows the fixture records
+
+
+def load_golden():
+    return json.load(open(GOLDEN)) if os.path.exists(GOLDEN) else None
+
+
+def path_seeds():
+    return np.arange(1, PATH_N + 1, dtype=np.uint64) * np.uint64(0xD1B54A32D192ED03) + np.uint64(5)
+
+
+# ---- the draws of domain 5 ----------------------------------------------------------------------------------------------
+
+def _key(seed):
+    return [int(seed) & 0xFFFFFFFF, int(seed) >> 32]
+
+
+def step_normals(oracle, seeds, n_steps):
+    """Z[i][k] = (Z_v, Z_x) at 50 digits: the Box–Muller pair of block (k, 0, 0, 5) under seeds[i]"""
+    with mp.workdps(DPS):
+        return [[box_muller(oracle.philox([k, 0, 0, DOM_QE], _key(s))) for k in range(n_steps)] for s in seeds]
+
+
+def step_uniforms(oracle, seeds, n_steps):
+    """U[i][k]: words 0, 1 of block (k, 1, 0, 5) — whether the device draws it or not"""
+    U = np.empty((len(seeds), n_steps))
+    for i, s in enumerate(seeds):
+        for k in range(n_steps):
+            w = oracle.philox([k, 1, 0, DOM_QE], _key(s))
+            U[i, k] = u01(w[0], w[1])
+    return U
+
+
+# ---- the restatement ----------------------------------------------------------------------------------------------------
+
+class VA:
+    """a value and its two running magnitudes (the module's docstring): a by oracle/euler_exact.py's rules, b the
+    first-order error bound in units of ε; A = min(a, b)"""
+    __slots__ = ("v", "a", "b")
+
+    def __init__(self, v, a=None, b=None):
+        self.v = v
+        self.a = abs(v) if a is None else a
+        self.b = abs(v) if b is None else b
+
+    @property
+    def A(self):
+        return min(self.a, self.b)
+
+    def __neg__(self):
+        return VA(-self.v, self.a, self.b)
+
+    def __add__(self, o):
+        r = self.v + o.v
+        return VA(r, self.a + o.a, self.b + o.b + abs(r))
+
+    def __sub__(self, o):
+        r = self.v - o.v
+        return VA(r, self.a + o.a, self.b + o.b + abs(r))
+
+    def __mul__(self, o):
+        r = self.v * o.v
+        return VA(r, self.a * o.a, abs(self.v) * o.b + abs(o.v) * self.b + abs(r))
+
+
+def _div(x, y):
+    inv = 1 / y.v
+    r = x.v / y.v
+    return VA(r, x.a * max(abs(inv), y.a * inv * inv), x.b * abs(inv) + abs(x.v) * y.b * inv * inv + abs(r))
+
+
+def _sqrt(w):
+    if not w.v > 0:
+        return VA(w.v - w.v, ex._sqrt(w.a), ex._sqrt(w.b))
+    s = ex._sqrt(w.v)
+    return VA(s, max(s, w.a / (2 * s)), w.b / (2 * s) + s)
+
+
+def _log(w):
+    l = ex._log(w.v)
+    return VA(l, max(abs(l), w.a / abs(w.v)), w.b / abs(w.v) + abs(l))
+
+
+def _expo(t):
+    e = ex._exp(t.v)
+    return VA(e, e * max(t.a, 1), e * t.b + e)
+
+
+def _pick(x, y, larger):
+    first = (x.v >= y.v) if larger else (x.v <= y.v)
+    return VA(x.v if first else y.v, max(x.a, y.a), max(x.b, y.b))
+
+
+def _log_input(num, S0):
+    """log of a positive input, as euler_exact.dlog carries it"""
+    lx = ex._log(num(S0))
+    return VA(lx, max(abs(lx), 1), max(abs(lx), 1))
+
+
+def constants(case, n_steps, num, psi_c=0.0):
+    """qe_args in the header's order, as values with magnitudes"""
+    c = {k: VA(num(case[k])) for k in ("kappa", "theta", "sigma", "rho", "r_drift")}
+    one, half, two = VA(num(1.0)), VA(num(0.5)), VA(num(2.0))
+    dt = VA(num(case["T"]) / n_steps)
+    q = dict(one=one, half=half, two=two)
+    q["E"] = _expo(-(c["kappa"] * dt))
+    ome, s2 = one - q["E"], c["sigma"] * c["sigma"]
+    q["c1"] = _div((s2 * q["E"]) * ome, c["kappa"])
+    q["c2"] = _div((c["theta"] * s2) * (ome * ome), two * c["kappa"])
+    q["th_ome"] = c["theta"] * ome
+    q["rdt"] = c["r_drift"] * dt
+    kr, ros = _div(c["kappa"] * c["rho"], c["sigma"]), _div(c["rho"], c["sigma"])
+    q["K0"] = -_div(((c["rho"] * c["kappa"]) * c["theta"]) * dt, c["sigma"])
+    h = (half * dt) * (kr - half)
+    q["K1"], q["K2"] = h - ros, h + ros
+    q["K3"] = q["K4"] = (half * dt) * (one - c["rho"] * c["rho"])
+    q["A"] = q["K2"] + half * q["K4"]
+    q["k13"] = q["K1"] + half * q["K3"]
+    q["psi_c"] = 1.5 if psi_c == 0.0 else psi_c
+    return q
+
+
+def moments(q, v):
+    m = q["th_ome"] + v * q["E"]
+    s2 = v * q["c1"] + q["c2"]
+    return m, _div(s2, m * m)
+
+
+def quad_terms(q, m, psi, mut=None):
+    t = _div(q["two"], psi)
+    b2 = (t - q["one"]) + _sqrt(t) * _sqrt(t - q["one"])
+    a = _div(m, q["one"] + (_sqrt(b2) if mut == "b_not_b2" else b2))
+    return a, b2
+
+
+def quad_lnM(q, a, b2):
+    d = q["one"] - (q["two"] * q["A"]) * a
+    return _div((q["A"] * b2) * a, d) - q["half"] * _log(d)
+
+
+def exp_terms(q, m, psi, mut=None):
+    p = _div(psi - q["one"], psi if mut == "p_over_psi" else psi + q["one"])
+    omp = q["one"] - p
+    return p, omp, _div(omp, m)
+
+
+def exp_lnM(q, p, omp, beta):
+    return _log(p + _div(beta * omp, beta - q["A"]))
+
+
+def step(q, x, v, zv, zx, U, mart, num, record=None, mut=None):
+    """(x, v) -> (x′, v′) of one member on its own draws; the branch goes on `record` as (ψ, quadratic?, U <= p or None,
+    U − p or None)"""
+    m, psi = moments(q, v)
+    quad = psi.v <= q["psi_c"]
+    K1, K2 = (q["K2"], q["K1"]) if mut == "swap_K" else (q["K1"], q["K2"])
+    if quad:
+        a, b2 = quad_terms(q, m, psi, mut)
+        bz = _sqrt(b2) + zv
+        vn = a * (bz * bz)
+        lnM = quad_lnM(q, a, b2) if mart else None
+        if record is not None:
+            record.append((psi.v, True, None, None))
+    else:
+        p, omp, beta = exp_terms(q, m, psi, mut)
+        zero = U.v <= p.v
+        vn = VA(num(0.0)) if zero else _div(_log(_div(omp, q["one"] - U)), beta)
+        lnM = exp_lnM(q, p, omp, beta) if mart else None
+        if record is not None:
+            record.append((psi.v, False, zero, U.v - p.v))
+    k0 = q["K0"]
+    if mart:
+        k13 = q["K1"] + q["K3"] if mut == "K3_full" else q["k13"]
+        k0 = -lnM - k13 * v
+    drift = ((q["rdt"] + k0) + K1 * v) + K2 * vn
+    xn = (x + drift) + _sqrt(q["K3"] * v + q["K4"] * vn) * zx
+    return xn, vn
+
+
+def walk(case, n_steps, num, Z, U, mirror, mart, record=None, mut=None, psi_c=0.0):
+    """one member of one trajectory: -> (xs, v_T): the log spot after every step and the variance at expiry, as VAs"""
+    q = constants(case, n_steps, num, psi_c)
+    x, v = _log_input(num, case["S0"]), VA(num(case["V0"]))
+    xs = []
+    for k in range(n_steps):
+        zv, zx = VA(num(Z[k][0])), VA(num(Z[k][1]))
+        u = VA(num(float(U[k])))
+        if mirror:
+            zv, zx = -zv, -zx
+            if mut != "keep_U":
+                u = q["one"] - u
+        x, v = step(q, x, v, zv, zx, u, mart, num, record, mut)
+        xs.append(x)
+    return xs, v
+
+
+def rows_of(case, xs, num, monitor_every, include_start):
+    """the five statistics (rows of enum hh_path_stat) over the monitoring dates: a sum starts with its first term"""
+    rows = None
+
+    def take(S, x):
+        nonlocal rows
+        rows = [S, x, S, S, S] if rows is None else \
+            [rows[0] + S, rows[1] + x, _pick(rows[2], S, True), _pick(rows[3], S, False), S]
+
+    if include_start:
+        take(VA(num(case["S0"])), _log_input(num, case["S0"]))
+    for k, x in enumerate(xs):
+        if (k + 1) % monitor_every == 0:
+            take(_expo(x), x)
+    return rows
+
+
+def walks(case, n_steps, Z, U, anti, mart, n=None, mut=None, check=True):
+    """both runs of every member of the first n trajectories -> list [member][path] of (xs_mp, vT_mp, xs_64, vT_64) and
+    the branch counts; `check`: the two runs take the same branches with MARGIN to spare (asserted)"""
+    n = len(Z) if n is None else n
+    members = 2 if anti else 1
+    out = [[None] * n for _ in range(members)]
+    counts = dict(quadratic=0, exponential=0, zero=0)
+    with mp.workdps(DPS):
+        for i in range(n):
+            Z64 = [(float(a), float(b)) for a, b in Z[i]]
+            for m in range(members):
+                rm, r6 = [], []
+                xs_mp, v_mp = walk(case, n_steps, mp.mpf, Z[i], U[i], m == 1, mart, rm, mut)
+                xs_64, v_64 = walk(case, n_steps, float, Z64, U[i], m == 1, mart, r6, mut)
+                if check:
+                    for (psi, quad, zero, du), (_, quad6, zero6, _) in zip(rm, r6):
+                        assert quad == quad6 and zero == zero6, (i, m)
+                        assert abs(psi - mp.mpf(1.5)) > MARGIN and (du is None or abs(du) > MARGIN), (i, m, psi, du)
+                for _, quad, zero, _ in rm:
+                    counts["quadratic" if quad else "exponential"] += 1
+                    counts["zero"] += bool(zero)
+                out[m][i] = (xs_mp, v_mp, xs_64, v_64)
+    return out, counts
+
+
+def reference(case, runs, monitor_every, include_start):
+    """-> want [member][path][row] (mpf; row 5 is var_T), e64 and A (float arrays [member][path][6])"""
+    members, n = len(runs), len(runs[0])
+    want = [[None] * n for _ in range(members)]
+    e64, A = np.zeros((members, n, 6)), np.zeros((members, n, 6))
+    with mp.workdps(DPS):
+        for m in range(members):
+            for i, (xs_mp, v_mp, xs_64, v_64) in enumerate(runs[m]):
+                ref = rows_of(case, xs_mp, mp.mpf, monitor_every, include_start) + [v_mp]
+                f64 = rows_of(case, xs_64, float, monitor_every, include_start) + [v_64]
+                want[m][i] = [t.v for t in ref]
+                A[m, i] = [float(t.A) for t in ref]
+                e64[m, i] = [float(abs(mp.mpf(b.v) - a.v)) for a, b in zip(ref, f64)]
+    return dict(want=want, e64=e64, A=A, members=members)
+
+
+# ---- exact integration of one step ---------------------------------------------------------------------------------------
+
+def _phi(z):
+    return mp.exp(-z * z / 2) / mp.sqrt(2 * mp.pi)
+
+
+def step_expectation(case, n_steps, v, f, mart=False, mut=None, psi_c=0.0):
+    """E f(v′, drift′) of one step from the state v (a double, taken exactly) in the restatement's own arithmetic at the
+    working precision: over Z_v in the quadratic branch, over U in the exponential one (the atom U <= p, then the
+    inverse's range).  drift′ = x′ − x − sqrt(·)·Z_x − rdt, the log-spot step's deterministic part without the rate."""
+    q = constants(case, n_steps, mp.mpf, psi_c)
+    V = VA(mp.mpf(v))
+    m, psi = moments(q, V)
+
+    def after(vn, lnM):
+        k0 = q["K0"] if not mart else -lnM - (q["K1"] + q["K3"] if mut == "K3_full" else q["k13"]) * V
+        drift = (k0 + q["K1"] * V) + q["K2"] * vn
+        return f(vn.v, drift.v, (q["K3"] * V + q["K4"] * vn).v)
+
+    if psi.v <= q["psi_c"]:
+        a, b2 = quad_terms(q, m, psi, mut)
+        lnM = quad_lnM(q, a, b2) if mart else None
+        b = _sqrt(b2)
+
+        def g(z):
+            bz = b + VA(z)
+            return after(a * (bz * bz), lnM) * _phi(z)
+        return mp.quad(g, [-40, -8, -2, 0, 2, 8, 40]), "quadratic", m.v, psi.v
+    p, omp, beta = exp_terms(q, m, psi, mut)
+    lnM = exp_lnM(q, p, omp, beta) if mart else None
+
+    def h(w):  # v′ = w, density β(1 − p)e^{−βw} on w > 0
+        return after(VA(w), lnM) * beta.v * omp.v * mp.exp(-beta.v * w)
+    top = 200 / beta.v
+    return p.v * after(VA(mp.mpf(0)), lnM) + mp.quad(h, mp.linspace(0, top, 41)), "exponential", m.v, psi.v
+
+
+# ---- the C structs of a case ---------------------------------------------------------------------------------------------
+
+HES, QE, EULER = _ffi.HH_HESTON, _ffi.HH_QE, _ffi.HH_EULER_MARUYAMA
+
+
+def model_of(case, strike=100.0, cp=1.0):
+    return _ffi.make_model(S0=case["S0"], V0=case["V0"], kappa=case["kappa"], theta=case["theta"], sigma=case["sigma"],
+                           rho=case["rho"], r=case["r_drift"], T=case["T"], strike=strike, cp=cp, discount=case.get("discount"))
+
+
+def config_of(n, n_steps, seeds, anti=0, **kw):
+    return _ffi.make_config(HES, QE, n, n_steps, antithetic=anti, seeds=seeds, **kw)
