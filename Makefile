@@ -11,12 +11,15 @@ test-cpu: build
 # the pool): the oracle (oracle/_asan/libhh_oracle.so, loaded into a python that has libasan preloaded) driven by its
 # own pin and property tests, and the host builds of the device headers — hh_math.h, hh_bessel.h (g++), hh_rng.h
 # (hipcc, host side only) — each under AddressSanitizer + UBSan.  detect_leaks=0: the interpreter's own allocations.
+# Then the Bates step composed from hh_qe.h and hh_jump.h (tests/c/bates_host_check.cpp): a program of its own, built
+# with -fsanitize=address,undefined by its test and run as a program — nothing preloaded, nothing loaded into python.
 ASAN_RT := $(shell gcc -print-file-name=libasan.so)
 test-cpu-asan:
 	$(MAKE) -C oracle -s asan
 	HH_SANITIZE=1 LD_PRELOAD=$(ASAN_RT) ASAN_OPTIONS=detect_leaks=0:abort_on_error=1 UBSAN_OPTIONS=halt_on_error=1:print_stacktrace=1 \
 	  python -m pytest tests/test_oracle_pins.py tests/test_properties.py tests/test_math_host.py tests/test_bessel_host.py \
 	  tests/test_rng_host.py tests/test_scratch_layout_host.py -q -m "not gpu" -p no:cacheprovider
+	python -m pytest tests/test_bates_host.py -q -p no:cacheprovider -k step_host_program
 
 test-gpu: build
 	python -m pytest tests -q -m gpu

@@ -19,12 +19,12 @@ from .greeks import (BatchGreekProblem, FDBackward, FDCentral, FDForward, Finite
                      ZeroRateSpineLens, optic, set)
 from .lsm import (LSM, EulerPaths, HestonExactPaths, LSMSolution, simulate_euler_paths,
                   simulate_heston_exact_paths, solve_lsm)
-from .montecarlo import (AbstractPricingMethod, Antithetic, BlackScholesExact, EulerMaruyama,
+from .montecarlo import (AbstractPricingMethod, Antithetic, BatesDynamics, BlackScholesExact, EulerMaruyama,
                          HestonBroadieKaya, HestonDynamics, HestonQE, LognormalDynamics, MertonDynamics, MertonExact, MethodError,
                          MonteCarlo, NoVarianceReduction, NormalLaw, SimulationConfig, marginal_law,
                          solve_montecarlo, solve_montecarlo_many, solve_path_payoffs)
 from .distributed import rank_device, shard_range, solve_lsm_sharded, solve_sharded
-from .domain import (American, ArithmeticAverage, AsianOption, AssetOrNothing, BarrierOption, BlackScholesInputs,
+from .domain import (American, ArithmeticAverage, AsianOption, AssetOrNothing, BarrierOption, BatesInputs, BlackScholesInputs,
                     Call, CashOrNothing, ContinuousMonitoring, DigitalOption, DownAndIn, DownAndOut, European,
                     FlatRateCurve, FlatVolSurface, Forward, GeometricAverage, HestonInputs, LookbackOption, MertonInputs,
                     Monitoring,
@@ -49,6 +49,8 @@ def solve(*args, **kw):
               | ::CarrMadan(α, bound, MertonDynamics()) | ::MertonAnalytic)   Merton jump diffusion (no reference method)
         solve(prob::PricingProblem{…, HestonInputs}, ::MonteCarlo(HestonDynamics(), HestonQE(psi_c, martingale), …))
                                                                               Andersen's QE scheme (no reference method)
+        solve(prob::PricingProblem{…, BatesInputs}, ::MonteCarlo(BatesDynamics(), HestonQE(psi_c, martingale), …)
+              | ::CarrMadan(α, bound, BatesDynamics()))   Bates: Heston QE paths with Merton jumps (no reference method)
         solve(prob::PricingProblem{<:VanillaOption{…,American,…}}, ::LSM)     least_squares_montecarlo.jl:99
         solve(prob::PricingProblem{<:VanillaOption}, ::CoxRossRubinsteinMethod) cox_ross_rubinstein.jl:99
         solve(prob::BasketPricingProblem, ::CoxRossRubinsteinMethod)         basket.jl:35
@@ -56,6 +58,10 @@ def solve(*args, **kw):
                                                   (a Crank–Nicolson grid per option; no reference method)
     """
     from . import greeks as _g
+    from .montecarlo import BATES_ROUTES, is_bates
+    if len(args) == 2 and isinstance(args[0], (PricingProblem, BasketPricingProblem)) and \
+            not isinstance(args[1], (MonteCarlo, CarrMadan)) and is_bates(args[0].market_inputs, args[1]):
+        raise MethodError(f"{type(args[1]).__name__} does not price the Bates model: use {BATES_ROUTES}")
     if len(args) == 2 and isinstance(args[0], PricingProblem) and isinstance(args[1], MonteCarlo):
         return solve_montecarlo(args[0], args[1], **kw)
     if len(args) == 2 and isinstance(args[0], PricingProblem) and isinstance(args[1], CarrMadan):

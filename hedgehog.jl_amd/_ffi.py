@@ -181,6 +181,13 @@ SYMBOLS = [
                                       C.c_int32, _vp, C.c_int32, _vp, C.POINTER(hh_result)]),
     ("hh_mc_solve_path_qe", C.c_int, [_vp, C.POINTER(hh_model), C.POINTER(hh_qe), C.POINTER(hh_config), C.c_uint32,
                                       C.c_int32, C.POINTER(hh_path_payoff), C.c_uint32, C.POINTER(hh_result), _vp, _vp, _vp]),
+    ("hh_mc_path_stats_bates", C.c_int, [_vp, C.POINTER(hh_model), C.POINTER(hh_qe), C.POINTER(hh_jump), C.POINTER(hh_config),
+                                         C.c_uint32, C.c_int32, _vp, C.c_int32, _vp, C.POINTER(hh_result)]),
+    ("hh_mc_solve_path_bates", C.c_int, [_vp, C.POINTER(hh_model), C.POINTER(hh_qe), C.POINTER(hh_jump), C.POINTER(hh_config),
+                                         C.c_uint32, C.c_int32, C.POINTER(hh_path_payoff), C.c_uint32, C.POINTER(hh_result),
+                                         _vp, _vp, _vp]),
+    ("hh_carr_madan_bates", C.c_int, [_vp, C.POINTER(hh_model), C.POINTER(hh_jump), C.c_double, C.c_double,
+                                      _vp, _vp, _vp, _vp, _vp, C.c_uint32, _vp]),
     ("hh_lsm_shard_xchg_elems", C.c_size_t, [C.c_uint32, C.c_int32]),
     ("hh_lsm_shard_begin", C.c_int, [_vp, C.POINTER(hh_model), C.POINTER(hh_config), C.c_int32, C.c_double, _vp]),
     ("hh_lsm_shard_phase", C.c_int, [_vp, C.c_int32, C.c_uint32, _vp, _vp]),

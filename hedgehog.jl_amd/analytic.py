@@ -20,7 +20,8 @@ from . import _ffi
 from .dates import yearfrac
 from .domain import (BlackScholesInputs, European, HestonInputs, MertonInputs, PricingProblem, VanillaOption, df,
                      get_vol, zero_rate)
-from .montecarlo import AbstractPricingMethod, HestonDynamics, LognormalDynamics, MertonDynamics, MethodError
+from .montecarlo import (BATES_ROUTES, AbstractPricingMethod, BatesDynamics, HestonDynamics, LognormalDynamics, MertonDynamics,
+                         MethodError, is_bates)
 
 
 @dataclass(frozen=True)
@@ -141,6 +142,38 @@ def _solve_carr_madan_merton(payoffs, m, method: CarrMadan):
     return out
 
 
+def _solve_carr_madan_bates(payoffs, m, method: CarrMadan):
+    """CarrMadan(α, bound, BatesDynamics()) on BatesInputs: every payoff's integral in one launch
+    (`hh_carr_madan_bates`).  No gradient form: a Dual anywhere is a MethodError."""
+    import numpy as np
+    from .dual import Dual
+    from .domain import BatesInputs
+    if not (isinstance(method.dynamics, BatesDynamics) and isinstance(m, BatesInputs)):
+        raise MethodError(f"no Bates characteristic function for {type(method.dynamics).__name__} on {type(m).__name__}: "
+                          f"use {BATES_ROUTES}")
+    r_k = [zero_rate(m.rate, p.expiry) for p in payoffs]
+    D_k = [df(m.rate, p.expiry) for p in payoffs]
+    scal = [m.spot, m.V0, m.κ, m.θ, m.σ, m.ρ, m.jump_intensity, m.jump_mean, m.jump_std, *r_k, *D_k,
+            *(p.strike for p in payoffs)]
+    if any(isinstance(v, Dual) for v in scal):
+        raise MethodError("CarrMadan under BatesDynamics carries no dual partials (ForwardAD): use FiniteDifference")
+    model = _ffi.hh_model()
+    model.S0, model.V0, model.kappa, model.theta = float(m.spot), float(m.V0), float(m.κ), float(m.θ)
+    model.sigma, model.rho = float(m.σ), float(m.ρ)
+    jump = _ffi.make_jump(float(m.jump_intensity), float(m.jump_mean), float(m.jump_std))
+    K = len(payoffs)
+    strikes = np.array([float(p.strike) for p in payoffs])
+    cps = np.array([p.call_put() for p in payoffs], dtype=np.float64)
+    Ts = np.array([yearfrac(m.rate.reference_date, p.expiry) for p in payoffs])
+    rs, Ds = np.array([float(x) for x in r_k]), np.array([float(x) for x in D_k])
+    out = np.empty(K)
+    ctx = _ffi.get_context(method.device)
+    ctx.check(ctx.lib.hh_carr_madan_bates(ctx.handle, C.byref(model), C.byref(jump), float(method.α), float(method.bound),
+                                          strikes.ctypes.data, cps.ctypes.data, Ts.ctypes.data, rs.ctypes.data,
+                                          Ds.ctypes.data, K, out.ctypes.data))
+    return out
+
+
 def _carr_madan_model(m, method: CarrMadan):
     """The model scalars every payoff on these market inputs shares (marginal_law, montecarlo.jl:293-320)
     -> (hh_model of their VALUES, dynamics, the scalars themselves — possibly Dual — in the order of
@@ -174,6 +207,8 @@ def solve_carr_madan_basket(payoffs, market_inputs, method: CarrMadan):
         if not (isinstance(payoff, VanillaOption) and isinstance(payoff.exercise_style, European)):
             raise MethodError("CarrMadan: European VanillaOption")
     from .dual import Dual, n_partials, partials_of, value_of
+    if is_bates(m, method):
+        return _solve_carr_madan_bates(payoffs, m, method)
     if isinstance(method.dynamics, MertonDynamics) or isinstance(m, MertonInputs):
         return _solve_carr_madan_merton(payoffs, m, method)
     model, dyn, scal = _carr_madan_model(m, method)
@@ -214,6 +249,8 @@ def solve_carr_madan(prob: PricingProblem, method: CarrMadan) -> AnalyticSolutio
     if not (isinstance(payoff, VanillaOption) and isinstance(payoff.exercise_style, European)):
         raise MethodError("CarrMadan: European VanillaOption")
     from .dual import n_partials
+    if is_bates(m, method):  # a basket of one
+        return AnalyticSolution(prob, method, float(_solve_carr_madan_bates([payoff], m, method)[0]))
     if isinstance(method.dynamics, MertonDynamics) or isinstance(m, MertonInputs):  # a basket of one
         return AnalyticSolution(prob, method, float(_solve_carr_madan_merton([payoff], m, method)[0]))
     model, dyn, scal = _carr_madan_model(m, method)

@@ -17,7 +17,7 @@ import numpy as np
 from . import _ffi
 from .domain import PATH_PAYOFFS, European, MonteCarloSolution, PricingProblem, Spot, VanillaOption
 from .dual import Dual
-from .montecarlo import (EulerMaruyama, HestonQE, MonteCarlo, _model_and_config, _price_from, is_merton, is_qe, path_extremes,
+from .montecarlo import (EulerMaruyama, HestonQE, MonteCarlo, _model_and_config, _price_from, is_bates, is_merton, is_qe, path_extremes,
                          path_monitoring, solve_montecarlo, solve_path_payoffs)
 
 
@@ -90,10 +90,11 @@ def solve_basket(prob: BasketPricingProblem, method, ensemble: bool = False):
         for _, idx in path_groups(payoffs, method.config.steps):
             for i, sol in zip(idx, solve_path_payoffs([payoffs[i] for i in idx], prob.market_inputs, method, ensemble)):
                 sols[i] = sol
-    if is_merton(prob.market_inputs, method) or is_qe(method):
-        # Merton jumps and HestonQE paths have no terminal-sample basket: what is left rides on one path simulation per
-        # expiry (EulerMaruyama: hh_mc_solve_path_jump, HestonQE: hh_mc_solve_path_qe, the vanilla kind), or is solved
-        # one by one (MertonExact: the same seed gives the same trajectories)
+    if is_merton(prob.market_inputs, method) or is_qe(method) or is_bates(prob.market_inputs, method):
+        # Merton jumps, HestonQE and Bates paths have no terminal-sample basket: what is left rides on one path simulation
+        # per expiry (EulerMaruyama: hh_mc_solve_path_jump, HestonQE: hh_mc_solve_path_qe or, under BatesDynamics,
+        # hh_mc_solve_path_bates; the vanilla kind), or is solved one by one (MertonExact: the same seed gives the same
+        # trajectories; a Bates mix no route serves: its MethodError)
         on_paths = isinstance(method.strategy, (EulerMaruyama, HestonQE))
         rest: dict = {}
         for i, p in enumerate(payoffs):

@@ -1326,13 +1326,15 @@ static int check_qe(hh_ctx* ctx, const char* who, const hh_model* m, const hh_co
 // jump (NULL: none): the Merton form — lognormal dynamics, the monitored rows.
 // qe (NULL: none): the quadratic-exponential Heston step — the monitored rows, and the variance at expiry of every
 // member into ctx->heston_var when want_var.
+// jump and qe together (the Bates entry points alone pass both): that step with jumps, its constants formed on
+// r_c = r_drift − λκ̄.
 static int run_path_stats(hh_ctx* ctx, const char* who, const hh_model* m, const hh_config* c, uint32_t monitor_every,
                           int32_t include_start, int32_t extremes, const hh_jump* jump = nullptr,
                           const hh_qe* qe = nullptr, bool want_var = false) {
   const bool hest = c->dynamics == HH_HESTON;
   if (qe && (!hest || c->strategy != HH_QE))
     return fail(ctx, HH_ERR_UNSUPPORTED, "%s needs HestonDynamics + the quadratic-exponential strategy (HH_QE)", who);
-  if (jump && (hest || c->strategy != HH_EULER_MARUYAMA))
+  if (jump && !qe && (hest || c->strategy != HH_EULER_MARUYAMA))
     return fail(ctx, HH_ERR_UNSUPPORTED, "%s needs LognormalDynamics + EulerMaruyama", who);
   if (!qe && (c->strategy != HH_EULER_MARUYAMA || (c->dynamics != HH_LOGNORMAL && !hest)))
     return fail(ctx, HH_ERR_UNSUPPORTED, "%s needs LognormalDynamics or HestonDynamics + EulerMaruyama", who);
@@ -1353,14 +1355,19 @@ static int run_path_stats(hh_ctx* ctx, const char* who, const hh_model* m, const
     return fail(ctx, HH_ERR_INVALID, "%s: S0, T > 0, |rho| <= 1, model scalars finite", who);
   int rc;
   if (jump && (rc = check_jump(ctx, who, jump, m->T / (double)c->n_steps))) return rc;
-  if (qe && (rc = check_qe(ctx, who, m, c, qe))) return rc;
+  hh_model m_c = *m;  // Bates: the step's constants, and their checks, on the compensated rate
+  if (jump && qe) m_c.r_drift = m->r_drift - hh::merton_compensator(*jump);
+  if (qe && (rc = check_qe(ctx, who, &m_c, c, qe))) return rc;
   const hh::PathStatsLayout at(c->n_paths, c->antithetic != 0, path_stat_rows(extremes));
   if ((rc = ensure(ctx, ctx->path_stats, at.total))) return rc;
   if (qe && want_var && (rc = ensure(ctx, ctx->heston_var, (size_t)at.n_total))) return rc;
   const uint64_t* seeds_dev = nullptr;
   if ((rc = stage_path_seeds(ctx, c, &seeds_dev))) return rc;
   if ((rc = begin_timing(ctx))) return rc;
-  if (qe)
+  if (qe && jump)
+    HH_HIP(ctx, hh::launch_bates_stats(*m, *c, *qe, *jump, seeds_dev, monitor_every, include_start != 0, ctx->path_stats,
+                                       want_var ? ctx->heston_var.p : nullptr, ctx->stream));
+  else if (qe)
     HH_HIP(ctx, hh::launch_qe_stats(*m, *c, *qe, seeds_dev, monitor_every, include_start != 0, ctx->path_stats,
                                     want_var ? ctx->heston_var.p : nullptr, ctx->stream));
   else if (jump)
@@ -1374,14 +1381,15 @@ static int run_path_stats(hh_ctx* ctx, const char* who, const hh_model* m, const
 // hh_mc_path_stats and hh_mc_path_stats_ex
 static int path_stats_call(hh_ctx* ctx, const char* who, const hh_model* m, const hh_config* c, uint32_t monitor_every,
                            int32_t include_start, int32_t extremes, double* stats, int32_t stats_on_device,
-                           hh_result* out, const hh_qe* qe = nullptr, double* var_T = nullptr) {
+                           hh_result* out, const hh_qe* qe = nullptr, double* var_T = nullptr,
+                           const hh_jump* jump = nullptr) {
   if (!ctx) return HH_ERR_INVALID;
   std::lock_guard<std::recursive_mutex> lock__(ctx->mu);
   if (!m || !c || !stats) return fail(ctx, HH_ERR_INVALID, "%s: NULL argument", who);
   const WallClock clock;
   HH_HIP(ctx, hipSetDevice(ctx->device));
   HH_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-  int rc = run_path_stats(ctx, who, m, c, monitor_every, include_start, extremes, nullptr, qe, var_T != nullptr);
+  int rc = run_path_stats(ctx, who, m, c, monitor_every, include_start, extremes, jump, qe, var_T != nullptr);
   if (rc) return rc;
   HH_HIP(ctx, hipEventRecord(ctx->ev1, ctx->stream));
   const hh::PathStatsLayout at(c->n_paths, c->antithetic != 0, path_stat_rows(extremes));
@@ -1588,6 +1596,55 @@ int hh_mc_solve_path_qe(hh_ctx* ctx, const hh_model* m, const hh_qe* qe, const h
   if (!qe) return fail(ctx, HH_ERR_INVALID, "hh_mc_solve_path_qe: NULL argument");
   return solve_path_call(ctx, "hh_mc_solve_path_qe", HH_PAYOFF_LOOKBACK_FIXED, m, c, monitor_every, include_start,
                          HH_EXTREMES_MONITORED, payoffs, n_payoffs, out, path_values, stats, nullptr, qe, var_T);
+}
+
+// ---- Bates: the quadratic-exponential step with Merton jumps (hedgehog_mc.h; kernels: hh_bates.hip, hh_fourier.hip) ----
+
+int hh_mc_path_stats_bates(hh_ctx* ctx, const hh_model* m, const hh_qe* qe, const hh_jump* jump, const hh_config* c,
+                           uint32_t monitor_every, int32_t include_start, double* stats, int32_t stats_on_device,
+                           double* var_T, hh_result* out) {
+  if (!ctx) return HH_ERR_INVALID;
+  std::lock_guard<std::recursive_mutex> lock__(ctx->mu);
+  if (!qe || !jump) return fail(ctx, HH_ERR_INVALID, "hh_mc_path_stats_bates: NULL argument");
+  return path_stats_call(ctx, "hh_mc_path_stats_bates", m, c, monitor_every, include_start, HH_EXTREMES_MONITORED, stats,
+                         stats_on_device, out, qe, var_T, jump);
+}
+
+int hh_mc_solve_path_bates(hh_ctx* ctx, const hh_model* m, const hh_qe* qe, const hh_jump* jump, const hh_config* c,
+                           uint32_t monitor_every, int32_t include_start, const hh_path_payoff* payoffs,
+                           uint32_t n_payoffs, hh_result* out, double* path_values, double* stats, double* var_T) {
+  if (!ctx) return HH_ERR_INVALID;
+  std::lock_guard<std::recursive_mutex> lock__(ctx->mu);
+  if (!qe || !jump) return fail(ctx, HH_ERR_INVALID, "hh_mc_solve_path_bates: NULL argument");
+  return solve_path_call(ctx, "hh_mc_solve_path_bates", HH_PAYOFF_LOOKBACK_FIXED, m, c, monitor_every, include_start,
+                         HH_EXTREMES_MONITORED, payoffs, n_payoffs, out, path_values, stats, jump, qe, var_T);
+}
+
+int hh_carr_madan_bates(hh_ctx* ctx, const hh_model* m, const hh_jump* jump, double alpha, double bound,
+                        const double* strikes, const double* cps, const double* Ts, const double* r_drifts,
+                        const double* discounts, uint32_t n_payoffs, double* prices_out) {
+  if (!ctx) return HH_ERR_INVALID;
+  std::lock_guard<std::recursive_mutex> lock__(ctx->mu);
+  const char* who = "hh_carr_madan_bates";
+  if (!m || !jump || !strikes || !cps || !Ts || !r_drifts || !discounts || !prices_out)
+    return fail(ctx, HH_ERR_INVALID, "%s: NULL argument", who);
+  if (n_payoffs == 0 || n_payoffs > (1u << 20)) return fail(ctx, HH_ERR_INVALID, "%s: 1 .. 2^20 payoffs per call", who);
+  if (!(m->S0 > 0.0) || !(alpha > 0.0) || !(bound > 0.0) || m->sigma == 0.0)  // hh_carr_madan_basket's, under HH_HESTON
+    return fail(ctx, HH_ERR_INVALID, "%s: bad scalars", who);
+  int rc = check_jump(ctx, who, jump, 0.0);  // no draw here: the mean of one is not limited
+  if (rc) return rc;
+  if (!hh::carr_madan_subpanels(alpha, bound)) return fail(ctx, HH_ERR_INVALID, HH_CM_BOUND_MSG, who);
+  const size_t n = n_payoffs;
+  std::vector<double> host(5 * n);  // log K | T | r_drift | discount | (out)
+  if ((rc = cm_upload_payoffs(ctx, who, strikes, cps, Ts, r_drifts, discounts, n, n, host))) return rc;
+  HH_HIP(ctx, hh::launch_carr_madan_bates(*m, *jump, alpha, bound, ctx->payoffs, n_payoffs, ctx->payoffs + 4 * n, ctx->stream));
+  HH_HIP(ctx, hipMemcpyAsync(host.data() + 4 * n, ctx->payoffs + 4 * n, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  HH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  for (size_t k = 0; k < n; ++k) {  // parity_transform (payoffs.jl:172-193): put = call − S + K·D
+    const double call = host[4 * n + k];
+    prices_out[k] = cps[k] > 0.0 ? call : call - m->S0 + strikes[k] * discounts[k];
+  }
+  return HH_OK;
 }
 
 // ---- LSM on an ensemble sharded over several devices ------------------------------------------------

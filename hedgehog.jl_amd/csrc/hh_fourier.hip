@@ -73,13 +73,15 @@ struct FourierArgs {
   uint32_t m_sub;   // sub-panels per lane (carr_madan_subpanels)
   double sigma_ln;  // lognormal volatility (law_mu / law_sd are formed per payoff)
   // Merton jumps (dynamics = kDynMerton, a code internal to this unit): the lognormal law above with the compensated
-  // drift, times exp(λT·(exp(iu·μ_J − σ_J²u²/2) − 1))
+  // drift, times exp(λT·(exp(iu·μ_J − σ_J²u²/2) − 1)); Bates (carr_madan_bates_kernel): the Heston law with them
   double lam, mu_j, sigma_j, lam_kbar;
 };
 constexpr int kDynMerton = 2;  // beside HH_LOGNORMAL = 0 and HH_HESTON = 1; never crosses the C-ABI
 
-// heston.jl:307-319, complex argument u
-__device__ cz heston_cf(const FourierArgs& a, cz u) {
+// heston.jl:307-319, complex argument u.  JUMP (Bates 1996): a.r carries r − λκ̄ and the jump term
+// (λ·T)·(exp(μ_J·iu − (½σ_J²)·u²) − 1) is added to the exponent last.
+template <bool JUMP>
+__device__ __forceinline__ cz heston_cf_law(const FourierArgs& a, cz u) {
   const cz iu = {-u.im, u.re};
   const cz kri = {a.kappa - a.rho * a.sigma * iu.re, -a.rho * a.sigma * iu.im};  // κ − ρσ·iu
   const cz u2 = u * u;
@@ -91,8 +93,11 @@ __device__ cz heston_cf(const FourierArgs& a, cz u) {
   const cz C = (a.kappa * a.theta / (a.sigma * a.sigma)) *
                (a.T * (kri - d1) - 2.0 * zlog(zdiv(one_m_ged, one - g)));
   const cz Dv = (1.0 / (a.sigma * a.sigma)) * ((kri - d1) * zdiv(one - ed, one_m_ged));
-  return zexp(C + a.V0 * Dv + a.logS0 * iu + (a.r * a.T) * iu);
+  cz e = C + a.V0 * Dv + a.logS0 * iu + (a.r * a.T) * iu;
+  if constexpr (JUMP) e = e + (a.lam * a.T) * (zexp(a.mu_j * iu - (0.5 * a.sigma_j * a.sigma_j) * u2) - one);
+  return zexp(e);
 }
+__device__ cz heston_cf(const FourierArgs& a, cz u) { return heston_cf_law<false>(a, u); }
 
 // sample_from_cf.jl:14-16: cf(Normal(μ, σ), t) = exp(i t μ − σ² t²/2)
 __device__ cz normal_cf(const FourierArgs& a, cz t) {
@@ -109,14 +114,19 @@ __device__ cz merton_cf(const FourierArgs& a, cz t) {
   return zexp(a.law_mu * it - (0.5 * a.law_sd * a.law_sd) * t2 + (a.lam * a.T) * jump);
 }
 
-// carr_madan.jl:59-61, 88-92: damp · call_transform(v) · exp(−i v log K), real part
-__device__ double integrand(const FourierArgs& a, double v) {
+// carr_madan.jl:59-61, 88-92: damp · call_transform(v) · exp(−i v log K), real part.  BATES: the Heston law with jumps,
+// whatever a.dynamics says
+template <bool BATES>
+__device__ __forceinline__ double integrand_law(const FourierArgs& a, double v) {
   const cz u = {v, -(a.alpha + 1.0)};
-  const cz phi = a.dynamics == HH_HESTON ? heston_cf(a, u) : a.dynamics == kDynMerton ? merton_cf(a, u) : normal_cf(a, u);
+  cz phi;
+  if constexpr (BATES) phi = heston_cf_law<true>(a, u);
+  else phi = a.dynamics == HH_HESTON ? heston_cf(a, u) : a.dynamics == kDynMerton ? merton_cf(a, u) : normal_cf(a, u);
   const cz den = {a.alpha * a.alpha + a.alpha - v * v, v * (2.0 * a.alpha + 1.0)};
   const cz val = zdiv(a.discount * phi, den) * zexp({0.0, -v * a.logK});
   return exp(-a.alpha * a.logK) / 6.28318530717958647692 * val.re;
 }
+__device__ double integrand(const FourierArgs& a, double v) { return integrand_law<false>(a, v); }
 
 // 16-point Gauss–Legendre on [-1, 1] (positive half; symmetric)
 __constant__ double kGLx[8] = {0.0950125098376374401853193, 0.2816035507792589132304605,
@@ -354,6 +364,37 @@ __global__ __launch_bounds__(256) void carr_madan_kernel(const FourierArgs a0) {
   if (threadIdx.x == 0) a.out[0] = ((sm[0] + sm[1]) + sm[2]) + sm[3];
 }
 
+// hh_carr_madan_bates: carr_madan_kernel's basket form (per_payoff is never NULL) under the Bates law — the same panels,
+// nodes and sums with integrand_law<true>; a sibling, so that the kernel above compiles to what it compiled to
+__device__ double integrand_bates(const FourierArgs& a, double v) { return integrand_law<true>(a, v); }
+__global__ __launch_bounds__(256) void carr_madan_bates_kernel(const FourierArgs a0) {
+  FourierArgs a = a0;
+  const uint32_t kp = blockIdx.x, n = a0.n_payoffs;
+  a.logK = a0.per_payoff[kp];
+  a.T = a0.per_payoff[n + kp];
+  a.r = a0.per_payoff[2 * n + kp] - a0.lam_kbar;  // r_c = r_k − λκ̄: λ = 0 leaves the Heston drift
+  a.discount = a0.per_payoff[3 * n + kp];
+  a.out = a0.out + kp;
+  const double w = 2.0 * a.bound / 256.0;  // panel width
+  const double mid = -a.bound + (threadIdx.x + 0.5) * w, half = 0.5 * w;
+  const double hsub = half / (double)a.m_sub;
+  double s = 0.0;
+#pragma unroll 1
+  for (uint32_t j = 0; j < a.m_sub; ++j) {
+    const double msub = subpanel_centre(mid, hsub, a.m_sub, j);
+    double sj = 0.0;
+#pragma unroll 1
+    for (int k = 0; k < 8; ++k)
+      sj += kGLw[k] * (integrand_bates(a, msub - hsub * kGLx[k]) + integrand_bates(a, msub + hsub * kGLx[k]));
+    s += sj * hsub;
+  }
+  for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
+  __shared__ double sm[4];
+  if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) a.out[0] = ((sm[0] + sm[1]) + sm[2]) + sm[3];
+}
+
 }  // namespace
 
 uint32_t carr_madan_subpanels(double alpha, double bound) {
@@ -400,6 +441,23 @@ int launch_carr_madan_jump(const hh_model& m, const hh_jump& jump, double alpha,
   a.n_payoffs = n_payoffs;
   if (const int rc = set_rule(a, alpha, bound)) return rc;
   hipLaunchKernelGGL(carr_madan_kernel, dim3(n_payoffs), dim3(256), 0, s, a);
+  return (int)hipGetLastError();
+}
+
+int launch_carr_madan_bates(const hh_model& m, const hh_jump& jump, double alpha, double bound,
+                            const double* per_payoff_dev, uint32_t n_payoffs, double* out_dev, hipStream_t s) {
+  FourierArgs a{};
+  a.dynamics = HH_HESTON;
+  a.logS0 = log(m.S0); a.V0 = m.V0; a.kappa = m.kappa; a.theta = m.theta; a.sigma = m.sigma;
+  a.rho = m.rho;
+  a.sigma_ln = m.sigma;
+  a.lam = jump.lambda; a.mu_j = jump.mu_j; a.sigma_j = jump.sigma_j;
+  a.lam_kbar = merton_compensator(jump);
+  a.out = out_dev;
+  a.per_payoff = per_payoff_dev;
+  a.n_payoffs = n_payoffs;
+  if (const int rc = set_rule(a, alpha, bound)) return rc;
+  hipLaunchKernelGGL(carr_madan_bates_kernel, dim3(n_payoffs), dim3(256), 0, s, a);
   return (int)hipGetLastError();
 }
 

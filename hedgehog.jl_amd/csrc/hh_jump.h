@@ -1,8 +1,10 @@
-// The jump count of the Merton model (include/hedgehog_mc.h, "Merton (1976) jump diffusion"): a Poisson variate by
-// inversion of one uniform, as a function the device kernels (hh_jump.hip) and a host program share — it includes
+// The jump count and the jump sum of the Merton model (include/hedgehog_mc.h, "Merton (1976) jump diffusion"): a Poisson
+// variate by inversion of one uniform and the sum of its jumps from one normal, as functions the device kernels
+// (hh_jump.hip, hh_bates.hip) and a host program share — it includes
 // nothing of HIP, so that tests/c/jump_host_check.cpp can hold it to a 50-digit restatement and run it under the
 // host sanitizers.  Internal; the public surface is include/hedgehog_mc.h.
 #pragma once
+#include <math.h>
 #include <stdint.h>
 
 #include "../../include/hedgehog_mc.h"
@@ -35,6 +37,27 @@ HH_JUMP_HD inline uint32_t poisson_inverse(double u, double m, double p0) {
     c = c + p;
   }
   return (uint32_t)HH_JUMP_MAX_COUNT;
+}
+
+// the jump sum of N > 0 jumps from one standard normal: N(N·μ_J, N·σ_J²)
+HH_JUMP_HD inline __attribute__((always_inline)) double jump_sum(const JumpArgs& j, uint32_t N, double z) {
+  const double n = (double)N;
+  return fma(j.sigma_j * sqrt(n), z, n * j.mu_j);
+}
+
+// The host's part.  exp(μ_J + σ_J²/2) − 1 (expm1: exact 0 for μ_J = σ_J = 0, no cancellation for small jumps) …
+inline double kappa_bar(const hh_jump& jump) { return expm1(jump.mu_j + 0.5 * jump.sigma_j * jump.sigma_j); }
+// … λ·κ̄, the drift's compensator, as every launcher forms it
+inline double merton_compensator(const hh_jump& jump) { return jump.lambda * kappa_bar(jump); }
+
+// the parameters of a launch whose one Poisson draw covers `span` (T, or T/n_steps)
+inline JumpArgs jump_args(const hh_jump& jump, double span) {
+  JumpArgs j{};
+  j.mean = jump.lambda * span;
+  j.p0 = exp(-j.mean);
+  j.mu_j = jump.mu_j;
+  j.sigma_j = jump.sigma_j;
+  return j;
 }
 
 }  // namespace hh

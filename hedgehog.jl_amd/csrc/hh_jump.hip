@@ -21,12 +21,6 @@
 namespace hh {
 namespace {
 
-// the jump sum of N > 0 jumps from one standard normal: N(N·μ_J, N·σ_J²)
-__device__ __forceinline__ double jump_sum(const JumpArgs& j, uint32_t N, double z) {
-  const double n = (double)N;
-  return fma(j.sigma_j * sqrt(n), z, n * j.mu_j);
-}
-
 // ------------------------------------------------------------------------------------------
 // terminal law
 // ------------------------------------------------------------------------------------------
@@ -128,21 +122,7 @@ __global__ __launch_bounds__(256) void jump_stats_kernel(const SimArgs<0> a, con
   if constexpr (ANTI) ra.store(stats, at, a.n_paths + i);
 }
 
-// exp(μ_J + σ_J²/2) − 1 (expm1: exact 0 for μ_J = σ_J = 0, no cancellation for small jumps)
-double kappa_bar(const hh_jump& jump) { return std::expm1(jump.mu_j + 0.5 * jump.sigma_j * jump.sigma_j); }
-
-JumpArgs jump_args(const hh_jump& jump, double span) {
-  JumpArgs j{};
-  j.mean = jump.lambda * span;
-  j.p0 = std::exp(-j.mean);
-  j.mu_j = jump.mu_j;
-  j.sigma_j = jump.sigma_j;
-  return j;
-}
-
 }  // namespace
-
-double merton_compensator(const hh_jump& jump) { return jump.lambda * kappa_bar(jump); }
 
 int launch_merton_exact(const hh_model& m, const hh_config& c, const hh_jump& jump, const DevicePtrs& p, hipStream_t s) {
   SimArgs<0> a = make_args0(m, c, p);

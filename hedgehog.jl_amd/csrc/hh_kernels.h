@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "../../include/hedgehog_mc.h"
+#include "hh_jump.h"
 #include "hh_layout.h"
 
 namespace hh {
@@ -286,8 +287,7 @@ struct PathPayoffArgs {
 };
 int launch_path_payoffs(const PathPayoffArgs& b, uint32_t n_payoffs, hipStream_t s);
 // Merton jump diffusion (hh_jump.hip; include/hedgehog_mc.h, "Merton (1976) jump diffusion").  The scalars are checked
-// by the entry points.  λ·κ̄, the drift's compensator, as every launcher forms it:
-double merton_compensator(const hh_jump& jump);
+// by the entry points.  λ·κ̄, the drift's compensator, as every launcher forms it: hh_jump.h's merton_compensator.
 // the terminal law: a lane takes kMertonPerLane trajectories whatever the call, a workgroup leaves one record
 constexpr int kMertonPerLane = 8;
 inline uint32_t merton_records(uint64_t n_paths) {
@@ -310,6 +310,16 @@ QeArgs qe_launch_args(const hh_model& m, const hh_config& c, const hh_qe& qe);
 // launch_path_stats' monitored form with the QE step: the same five rows; var_T (nullable): n_total doubles
 int launch_qe_stats(const hh_model& m, const hh_config& c, const hh_qe& qe, const uint64_t* seeds_dev,
                     uint32_t monitor_every, bool include_start, double* stats, double* var_T, hipStream_t s);
+// Bates (hh_bates.hip, hh_fourier.hip; include/hedgehog_mc.h, "Bates (1996): Heston variance with Merton jumps").  The
+// scalars are checked by the entry points.  qe_launch_args with r_c = r_drift − merton_compensator(jump) for r:
+QeArgs bates_launch_args(const hh_model& m, const hh_config& c, const hh_qe& qe, const hh_jump& jump);
+// launch_qe_stats with a jump count per step and, on the lane that has one, a jump: the same five rows and var_T
+int launch_bates_stats(const hh_model& m, const hh_config& c, const hh_qe& qe, const hh_jump& jump,
+                       const uint64_t* seeds_dev, uint32_t monitor_every, bool include_start, double* stats,
+                       double* var_T, hipStream_t s);
+// launch_carr_madan_basket (HH_HESTON, compat_sqrt_alpha = 0) with the Bates characteristic function
+int launch_carr_madan_bates(const hh_model& m, const hh_jump& jump, double alpha, double bound,
+                            const double* per_payoff_dev, uint32_t n_payoffs, double* out_dev, hipStream_t s);
 // form: kLsmFormPersistent = the whole backward induction in ONE launch when the ensemble fits the
 // chip (else it falls back by itself), kLsmFormPerDate = one launch per exercise date.  *form_used
 // says which was enqueued; after a persistent launch the caller synchronises and reads the word at

@@ -383,6 +383,43 @@ class HestonInputs:
 
 
 @dataclass(frozen=True)
+class BatesInputs:
+    """Bates (1996) — Heston variance with Merton jumps (include/hedgehog_mc.h, "Bates (1996): Heston variance with Merton
+    jumps"; the reference has no such model): HestonInputs' scalars and MertonInputs' jump parameters in a class of its
+    own, a subclass of neither, so that no route of either takes it silently.  The drift is compensated by
+    λ·(exp(μ_J + σ_J²/2) − 1) inside the solvers."""
+    referenceDate: int
+    rate: FlatRateCurve
+    spot: Any
+    V0: Any
+    κ: Any
+    θ: Any
+    σ: Any
+    ρ: Any
+    jump_intensity: Any
+    jump_mean: Any
+    jump_std: Any
+
+    def __init__(self, reference_date, rate, spot, V0, κ, θ, σ, ρ, jump_intensity, jump_mean, jump_std):
+        ref = to_ticks(reference_date)
+        if not isinstance(rate, (FlatRateCurve, RateCurve)):
+            rate = FlatRateCurve(ref, rate)
+        for k, v in (("referenceDate", ref), ("rate", rate), ("spot", spot), ("V0", V0), ("κ", κ), ("θ", θ), ("σ", σ),
+                     ("ρ", ρ), ("jump_intensity", jump_intensity), ("jump_mean", jump_mean), ("jump_std", jump_std)):
+            object.__setattr__(self, k, v)
+
+    # ASCII aliases
+    kappa = property(lambda s: s.κ)
+    theta = property(lambda s: s.θ)
+    sigma = property(lambda s: s.σ)
+    rho = property(lambda s: s.ρ)
+
+    def heston(self):
+        """the same market without jumps"""
+        return HestonInputs(self.referenceDate, self.rate, self.spot, self.V0, self.κ, self.θ, self.σ, self.ρ)
+
+
+@dataclass(frozen=True)
 class PricingProblem:
     """pricing_methods.jl:19-22."""
     payoff: Any

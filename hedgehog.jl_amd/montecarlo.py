@@ -16,7 +16,7 @@ from .dates import yearfrac
 from .dual import Dual, n_partials, partials_of, value_of
 from .domain import (PATH_PAYOFFS, American, ArithmeticAverage, AsianOption, BarrierOption, BlackScholesInputs, Call,
                     CashOrNothing, ContinuousMonitoring, DigitalOption, DownAndIn, DownAndOut, European, HestonInputs,
-                    LookbackOption, MertonInputs, Monitoring,
+                    LookbackOption, MertonInputs, BatesInputs, Monitoring,
                     MonteCarloSolution, PricingProblem, Spot, UpAndIn, UpAndOut, VanillaOption, _DeviceSamples, df,
                     get_vol, zero_rate)
 
@@ -37,6 +37,8 @@ class BlackScholesExact(ExactSimulation): pass
 # ---- Merton jump diffusion (the reference has none; include/hedgehog_mc.h) ----
 class MertonDynamics(PriceDynamics): pass
 class MertonExact(ExactSimulation): pass
+# ---- Bates: Heston variance with Merton jumps (the reference has none; include/hedgehog_mc.h) ----
+class BatesDynamics(PriceDynamics): pass
 
 for _c in (LognormalDynamics, HestonDynamics, NoVarianceReduction, Antithetic, EulerMaruyama,
            HestonBroadieKaya, BlackScholesExact, MertonDynamics, MertonExact):
@@ -222,6 +224,43 @@ def _qe_structs(prob: PricingProblem, method: MonteCarlo):
     return model, c, _ffi.make_qe(float(strat.psi_c), bool(strat.martingale))
 
 
+BATES_ROUTES = ("MonteCarlo(BatesDynamics(), HestonQE(psi_c, martingale), config) or "
+                "CarrMadan(alpha, bound, BatesDynamics()) on BatesInputs")
+
+
+def is_bates(market_inputs, method) -> bool:
+    """Does anything of the pair name the Bates model?  Then only the Bates routes may take it."""
+    return isinstance(market_inputs, BatesInputs) or isinstance(getattr(method, "dynamics", None), BatesDynamics)
+
+
+def _require_bates_route(market_inputs, method):
+    """the one Monte Carlo route of the model, or a MethodError that names it"""
+    dyn, strat = method.dynamics, method.strategy
+    if not (isinstance(dyn, BatesDynamics) and isinstance(market_inputs, BatesInputs) and isinstance(strat, HestonQE)):
+        raise MethodError(f"no Bates solve for {type(dyn).__name__} + {type(strat).__name__} on "
+                          f"{type(market_inputs).__name__}: use {BATES_ROUTES}")
+
+
+def _bates_structs(prob: PricingProblem, method: MonteCarlo):
+    """(hh_model, hh_config, hh_qe, hh_jump) of a Bates solve: the structs of the HestonQE solve on the same market
+    without jumps (its dates and drift rate, strategy HH_QE) and the jump parameters beside them.  Every other mix of
+    dynamics, strategy and inputs is a MethodError that names the route; so is a Dual anywhere."""
+    import dataclasses
+    m = prob.market_inputs
+    _require_bates_route(m, method)
+    if method.devices is not None:
+        raise MethodError("Bates solves run on one device (MonteCarlo.devices is not supported)")
+    jumps = (m.jump_intensity, m.jump_mean, m.jump_std)
+    if any(isinstance(v, Dual) for v in jumps):
+        raise MethodError("Bates solves carry no dual partials (ForwardAD): use FiniteDifference — its solves share "
+                          "their seeds")
+    try:
+        model, c, qe = _qe_structs(PricingProblem(prob.payoff, m.heston()), dataclasses.replace(method, dynamics=HestonDynamics()))
+    except MethodError as e:
+        raise MethodError(str(e).replace("HestonQE solves", "Bates solves")) from None
+    return model, c, qe, _ffi.make_jump(*(float(v) for v in jumps))
+
+
 def is_merton(market_inputs, method) -> bool:
     """Does anything of the pair name the Merton model?  Then only the Merton routes may take it."""
     return isinstance(market_inputs, MertonInputs) or isinstance(getattr(method, "dynamics", None), MertonDynamics) or \
@@ -300,6 +339,10 @@ def solve_montecarlo(prob: PricingProblem, method: MonteCarlo, ensemble: bool = 
 
     `replay` (optional, build extension): Wiener increments to consume instead of drawing them —
     numpy array [path][step][comp] (or tile-major), the noise-replay parity mode of DESIGN.md."""
+    if is_bates(prob.market_inputs, method):  # every payoff on the path statistics (hh_mc_solve_path_bates)
+        if replay is not None:
+            raise MethodError("Bates solves draw their own noise: no replay")
+        return solve_path_payoffs([prob.payoff], prob.market_inputs, method, ensemble)[0]
     if is_qe(method):  # every payoff on the path statistics (hh_mc_solve_path_qe)
         if replay is not None:
             raise MethodError("HestonQE solves draw their own noise: no replay (EulerMaruyama takes one)")
@@ -374,7 +417,8 @@ def solve_montecarlo_many(probs, method: MonteCarlo, replay=None, replay_layout=
         return None
     if any(isinstance(p.payoff, PATH_PAYOFFS) for p in probs):  # one solve after the other (hh_mc_solve_path)
         return None
-    if is_qe(method) or any(is_merton(p.market_inputs, method) for p in probs):  # no hh_mc_solve_multi form: one after the other
+    if is_qe(method) or any(is_merton(p.market_inputs, method) or is_bates(p.market_inputs, method) for p in probs):
+        # no hh_mc_solve_multi form: one after the other
         return None
     packed = [_model_and_config(p, method) for p in probs]
     if any(P for _, _, _, P, _ in packed):
@@ -460,8 +504,19 @@ def pack_path_payoff(payoff) -> _ffi.hh_path_payoff:
 def _path_structs(payoffs, market_inputs, method: MonteCarlo):
     """(hh_model, hh_config, monitor_every, include_start, hh_jump or None) of payoffs that share an expiry and a
     monitoring.  The model and configuration are those of a European solve to that expiry (its strike and cp are not
-    read); Merton inputs bring their jump parameters, a HestonQE strategy its hh_qe in the same place."""
-    if is_qe(method):
+    read); Merton inputs bring their jump parameters, a HestonQE strategy its hh_qe in the same place, a Bates solve the
+    pair (hh_qe, hh_jump)."""
+    bates = is_bates(market_inputs, method)
+    if bates:
+        _require_bates_route(market_inputs, method)
+        for p in payoffs:
+            if isinstance(getattr(p, "exercise_style", None), American):
+                raise MethodError("American exercise is not offered on Bates paths (no LSM on them): European payoffs on "
+                                  + BATES_ROUTES)
+            if isinstance(getattr(p, "monitoring", None), ContinuousMonitoring):
+                raise MethodError("ContinuousMonitoring() is not offered on Bates paths (a bridge between two states is "
+                                  "wrong once a jump lies between them): monitor on the dates of a Monitoring")
+    elif is_qe(method):
         for p in payoffs:
             if isinstance(getattr(p, "exercise_style", None), American):
                 raise MethodError("American exercise is not offered on HestonQE paths: use LSM(HestonDynamics(), "
@@ -482,6 +537,9 @@ def _path_structs(payoffs, market_inputs, method: MonteCarlo):
         raise ValueError("payoffs of one path solve share a monitoring")
     every, start = mons.pop() if mons else (steps, False)
     european = VanillaOption(1.0, expiries.pop(), European(), Call(), Spot())
+    if bates:
+        model, c, qe, jump = _bates_structs(PricingProblem(european, market_inputs), method)
+        return model, c, every, start, (qe, jump)
     if is_qe(method):
         model, c, qe = _qe_structs(PricingProblem(european, market_inputs), method)
         return model, c, every, start, qe
@@ -501,16 +559,20 @@ def solve_path_payoffs(payoffs, market_inputs, method: MonteCarlo, ensemble: boo
     `ensemble`: the (5, n_total) statistics of the trajectories — (7, n_total) in bridge mode — (rows: enum
     hh_path_stat), shared by the solutions; n_total counts the antithetic mirrors, columns trajectories + i.
     A HestonQE strategy: hh_mc_solve_path_qe, the monitored rows only.
+    BatesDynamics on BatesInputs under a HestonQE strategy: hh_mc_solve_path_bates, the monitored rows only.
     Merton inputs: hh_mc_solve_path_jump, the monitored rows only — ContinuousMonitoring is a MethodError, a bridge
     between two states being wrong once a jump lies between them."""
     model, c, every, start, jump = _path_structs(payoffs, market_inputs, method)
-    qe, jump = (jump, None) if isinstance(jump, _ffi.hh_qe) else (None, jump)
+    if isinstance(jump, tuple):  # Bates: both
+        qe, jump = jump
+    else:
+        qe, jump = (jump, None) if isinstance(jump, _ffi.hh_qe) else (None, jump)
     modes = {e for e in (path_extremes(p) for p in payoffs) if e is not None}
     if len(modes) > 1:
         raise ValueError("payoffs of one path solve share an extremes mode (Monitoring or ContinuousMonitoring)")
     extremes = modes.pop() if modes else _ffi.HH_EXTREMES_MONITORED
     bridge = extremes == _ffi.HH_EXTREMES_BRIDGE
-    if jump is not None and bridge:
+    if jump is not None and qe is None and bridge:
         raise MethodError("ContinuousMonitoring is not offered under Merton jumps: monitor on the dates of a Monitoring")
     extended = bridge or any(isinstance(p, LookbackOption) for p in payoffs)
     packed = (_ffi.hh_path_payoff * len(payoffs))(*[pack_path_payoff(p) for p in payoffs])
@@ -520,7 +582,11 @@ def solve_path_payoffs(payoffs, market_inputs, method: MonteCarlo, ensemble: boo
     n_total = int(c.n_paths) * (2 if c.antithetic else 1)
     stats = np.empty((_ffi.HH_PATH_STATS_BRIDGE if bridge else _ffi.HH_PATH_STATS, n_total)) if ensemble else None
     res = (_ffi.hh_result * len(payoffs))()
-    if qe is not None:
+    if qe is not None and jump is not None:
+        ctx.check(ctx.lib.hh_mc_solve_path_bates(ctx.handle, C.byref(model), C.byref(qe), C.byref(jump), C.byref(c), every,
+                                                 int(start), packed, len(payoffs), res, None,
+                                                 stats.ctypes.data if ensemble else None, None))
+    elif qe is not None:
         ctx.check(ctx.lib.hh_mc_solve_path_qe(ctx.handle, C.byref(model), C.byref(qe), C.byref(c), every, int(start), packed,
                                               len(payoffs), res, None, stats.ctypes.data if ensemble else None, None))
     elif jump is not None:

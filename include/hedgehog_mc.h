@@ -840,6 +840,71 @@ int hh_mc_solve_path_qe(hh_ctx* ctx, const hh_model* model, const hh_qe* qe, con
                         uint32_t n_payoffs, hh_result* out, double* path_values, double* stats, double* var_T);
 
 /*
+ * Bates (1996): Heston variance with Merton jumps — the model often called SVJ: the stochastic variance of the section
+ * above and the compound Poisson jumps of the Merton section in one log spot.
+ *   d log S = (r − λκ̄ − v/2) dt + √v dW_S + J dN        J ~ N(μ_J, σ_J²),  N Poisson of intensity λ
+ *   dv      = κ(θ − v) dt + σ√v dW_v                     corr(dW_S, dW_v) = ρ
+ *   κ̄ = exp(μ_J + σ_J²/2) − 1
+ * The jumps are independent of both Brownian motions.  The parameters travel in the existing hh_model, hh_qe and
+ * hh_jump, with cfg->dynamics = HH_HESTON and cfg->strategy = HH_QE: no struct changes, no enum gains a value.
+ *
+ * ON THE HOST, once per call:
+ *   lam_kbar = λ·expm1(μ_J + ½σ_J²)       the compensator, the same function the Merton entry points use
+ *   r_c      = model->r_drift − lam_kbar
+ *   the QE constants of the section above (csrc/hh_qe.h, qe_args) with r_c in place of r: rdt = r_c·dt, dt = T/n_steps,
+ *   every other constant as there;  mean = λ·dt and p_0 = exp(−mean) of the jump count (csrc/hh_jump.h, jump_args).
+ * λ = 0 gives r_c == r and mean == 0.
+ *
+ * ONE STEP k, operation by operation:
+ *   1. the QE step of the section above on (x, v), on its own draws of domain 5, unchanged: block (k, 0, 0, 5) gives
+ *      (Z_v, Z_x), block (k, 1, 0, 5) gives U under the same branch condition;
+ *   2. N_k = the jump count (csrc/hh_jump.h, poisson_inverse) of U_J with mean and p_0; U_J from block (k >> 1, 0, 0, 4):
+ *      output words 0, 1 for an even k, words 2, 3 for an odd one — one block serves two consecutive steps;
+ *   3. only where N_k > 0: z = the first normal of block (k, 1, 0, 4);
+ *   4. x ← x + fma(σ_J·sqrt((double)N_k), z, N_k·μ_J), only where N_k > 0 — after the QE step and before the monitoring
+ *      date.
+ * These are the jump draws of hh_mc_solve_path_jump under the same seed and counters; domains 4 and 5 are disjoint, so
+ * the two streams are independent.  The mirror of an antithetic pair takes −Z_v, −Z_x and 1 − U on its own states, the
+ * same N_k and −z.  The MARTINGALE CORRECTION is QE's, unchanged: the jumps are compensated through r_c alone, so that
+ * with it E[exp(x′ − r·dt) | x, v] = exp(x) exactly (E exp(J·) = exp(λκ̄·dt) exactly, whatever dt).
+ * Two identities follow and are tested:
+ *   λ = 0 gives hh_mc_solve_path_qe's bits in every output;
+ *   a trajectory of these entry points and one of hh_mc_solve_path_jump with the same seed and the same λ·dt have the
+ *   same N_k and z at every step.
+ * Every device loop is bounded by n_steps, the count search by HH_JUMP_MAX_COUNT.
+ *
+ * hh_mc_path_stats_bates / hh_mc_solve_path_bates: hh_mc_path_stats_qe / hh_mc_solve_path_qe with `jump` after `qe` —
+ * the same dates, the same statistics arithmetic, the same five rows and var_T, payoff kinds 0 .. 7, the same timing
+ * slots.  Synchronous.
+ *
+ * hh_carr_madan_bates — hh_carr_madan_basket under HH_HESTON (compat_sqrt_alpha = 0) with
+ *   ϕ_B(u) = ϕ_H(u; r → r_c) · exp(λT·(exp(iu·μ_J − σ_J²u²/2) − 1))
+ * Per payoff r_c = r_k − lam_kbar, in that order; the Heston exponent as hh_carr_madan_basket forms it, with r_c in it;
+ * (λ·T)·(exp(μ_J·iu − (½σ_J²)·u²) − 1) added to the exponent last.  The same quadrature rule, one workgroup per payoff,
+ * the same parity transform for puts.  λ = 0 returns hh_carr_madan_basket's bits (HH_HESTON, compat_sqrt_alpha = 0).
+ * Synchronous.
+ *
+ * Errors, checked on the host before any launch.  HH_ERR_INVALID: qe or jump is NULL; everything the Merton entry points
+ * reject in hh_jump, the Poisson mean of one draw being λ·T/n_steps (hh_carr_madan_bates draws nothing: no limit on
+ * it); everything the QE entry points reject, the step's constants being formed on r_c; everything hh_mc_solve_path_ex
+ * or hh_carr_madan_basket reject.  HH_ERR_UNSUPPORTED: dynamics other than HH_HESTON, a strategy other than HH_QE,
+ * REPLAY noise, n_partials > 0, the martingale correction with A > 0.
+ * Not provided: a terminal-law form on Broadie–Kaya, bridge extremes, a gradient of hh_carr_madan_bates, LSM on these
+ * paths, multi-GPU and accumulate forms, the hh_mc_solve_multi form, dual partials (bump the inputs: the solves share
+ * their seeds), a Julia binding.
+ */
+int hh_mc_path_stats_bates(hh_ctx* ctx, const hh_model* model, const hh_qe* qe, const hh_jump* jump,
+                           const hh_config* cfg, uint32_t monitor_every, int32_t include_start, double* stats,
+                           int32_t stats_on_device, double* var_T, hh_result* out);
+int hh_mc_solve_path_bates(hh_ctx* ctx, const hh_model* model, const hh_qe* qe, const hh_jump* jump,
+                           const hh_config* cfg, uint32_t monitor_every, int32_t include_start,
+                           const hh_path_payoff* payoffs, uint32_t n_payoffs, hh_result* out, double* path_values,
+                           double* stats, double* var_T);
+int hh_carr_madan_bates(hh_ctx* ctx, const hh_model* model, const hh_jump* jump, double alpha, double bound,
+                        const double* strikes, const double* cps, const double* Ts, const double* r_drifts,
+                        const double* discounts, uint32_t n_payoffs, double* prices_out);
+
+/*
  * The same solve for an ensemble SHARDED over several devices (one process and one hh_ctx per
  * device, trajectories split by contiguous ranges as for hh_mc_accumulate).  The backward induction
  * needs sums over ALL trajectories at three points — the in-the-money statistics of every row, the
