@@ -33,6 +33,8 @@ HH_MAX_PATH_PAYOFFS = 1024
 HH_JUMP_MAX_MEAN = 64.0
 HH_JUMP_MAX_COUNT = 255
 HH_QE_MAX_PSI = 1e9
+HH_MAX_ASSETS = 8
+HH_INDEX_WEIGHTED_SUM, HH_INDEX_GEOMETRIC, HH_INDEX_BEST_OF, HH_INDEX_WORST_OF = 0, 1, 2, 3
 
 HH_OK, HH_ERR_INVALID, HH_ERR_UNSUPPORTED, HH_ERR_HIP, HH_ERR_NOMEM, HH_ERR_RCCL, HH_ERR_DEVICE_TIMEOUT = 0, -1, -2, -3, -4, -5, -6
 HH_MGPU_AUTO, HH_MGPU_HOST_SUM, HH_MGPU_RCCL = 0, 1, 2
@@ -100,6 +102,14 @@ class hh_jump(C.Structure):
 class hh_qe(C.Structure):
     """The quadratic-exponential step's options: the branch threshold ψ_c (0: the default 1.5) and the martingale switch."""
     _fields_ = [("psi_c", C.c_double), ("martingale", C.c_int32), ("reserved", C.c_int32)]
+
+
+class hh_assets(C.Structure):
+    """Several correlated lognormal assets and the index kind: spots, volatilities, weights and the row-major
+    correlation matrix with row stride HH_MAX_ASSETS."""
+    _fields_ = [("n_assets", C.c_uint32), ("index_kind", C.c_int32),
+                ("spots", C.c_double * HH_MAX_ASSETS), ("sigmas", C.c_double * HH_MAX_ASSETS),
+                ("weights", C.c_double * HH_MAX_ASSETS), ("corr", C.c_double * (HH_MAX_ASSETS * HH_MAX_ASSETS))]
 
 
 HH_BK_ROOT_SECANT, HH_BK_ROOT_ORDER2 = 0, 1
@@ -188,6 +198,10 @@ SYMBOLS = [
                                          _vp, _vp, _vp]),
     ("hh_carr_madan_bates", C.c_int, [_vp, C.POINTER(hh_model), C.POINTER(hh_jump), C.c_double, C.c_double,
                                       _vp, _vp, _vp, _vp, _vp, C.c_uint32, _vp]),
+    ("hh_mc_path_stats_assets", C.c_int, [_vp, C.POINTER(hh_model), C.POINTER(hh_assets), C.POINTER(hh_config), C.c_uint32,
+                                          C.c_int32, _vp, C.c_int32, C.POINTER(hh_result)]),
+    ("hh_mc_solve_path_assets", C.c_int, [_vp, C.POINTER(hh_model), C.POINTER(hh_assets), C.POINTER(hh_config), C.c_uint32,
+                                          C.c_int32, C.POINTER(hh_path_payoff), C.c_uint32, C.POINTER(hh_result), _vp, _vp]),
     ("hh_lsm_shard_xchg_elems", C.c_size_t, [C.c_uint32, C.c_int32]),
     ("hh_lsm_shard_begin", C.c_int, [_vp, C.POINTER(hh_model), C.POINTER(hh_config), C.c_int32, C.c_double, _vp]),
     ("hh_lsm_shard_phase", C.c_int, [_vp, C.c_int32, C.c_uint32, _vp, _vp]),
@@ -554,6 +568,22 @@ def make_jump(lam=0.0, mu_j=0.0, sigma_j=0.0):
     j = hh_jump()
     j.lambda_, j.mu_j, j.sigma_j = lam, mu_j, sigma_j
     return j
+
+
+def make_assets(spots, sigmas, weights, corr, index_kind=HH_INDEX_WEIGHTED_SUM):
+    """hh_assets from plain numbers; corr is the d × d correlation matrix (nested sequences or an array)"""
+    a = hh_assets()
+    d = len(spots)
+    if not 1 <= d <= HH_MAX_ASSETS or len(sigmas) != d or len(weights) != d or len(corr) != d:
+        raise ValueError(f"1 .. {HH_MAX_ASSETS} assets, with as many sigmas, weights and correlation rows")
+    a.n_assets, a.index_kind = d, int(index_kind)
+    for i in range(d):
+        a.spots[i], a.sigmas[i], a.weights[i] = float(spots[i]), float(sigmas[i]), float(weights[i])
+        if len(corr[i]) != d:
+            raise ValueError("the correlation matrix must be square")
+        for j in range(d):
+            a.corr[i * HH_MAX_ASSETS + j] = float(corr[i][j])
+    return a
 
 
 def make_qe(psi_c=0.0, martingale=False):

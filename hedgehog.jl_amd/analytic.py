@@ -6,6 +6,8 @@ so that such scripts run unchanged:
   CarrMadan(α, bound, dynamics)
                          /root/reference/src/pricing_methods/carr_madan.jl:15-92 — the Fourier
                          integral runs on the device (`hh_carr_madan`, csrc/hh_fourier.hip)
+  MultiAssetAnalytic()   a European vanilla on a geometric index of several correlated lognormal assets, and Margrabe's
+                         exchange option (the reference prices one underlying only): scalar code on the host
   MertonAnalytic(n_terms) Merton's (1976) series for a European vanilla under jump diffusion (the reference has no
                          jump model): a Poisson-weighted sum of Black prices, scalar code on the host
 """
@@ -22,6 +24,8 @@ from .domain import (BlackScholesInputs, European, HestonInputs, MertonInputs, P
                      get_vol, zero_rate)
 from .montecarlo import (BATES_ROUTES, AbstractPricingMethod, BatesDynamics, HestonDynamics, LognormalDynamics, MertonDynamics,
                          MethodError, is_bates)
+from .multiasset import GeometricMean, IndexOption, MultiAssetInputs, WeightedSum, index_weights
+from .domain import Spot
 
 
 @dataclass(frozen=True)
@@ -268,3 +272,51 @@ def solve_carr_madan(prob: PricingProblem, method: CarrMadan) -> AnalyticSolutio
     ctx.check(ctx.lib.hh_carr_madan(ctx.handle, C.byref(model), dyn, int(method.compat_sqrt_alpha),
                                     float(method.α), float(method.bound), C.byref(out)))
     return AnalyticSolution(prob, method, out.value)
+
+
+# ---- several correlated lognormal assets (multiasset.py) ------------------------------------------------------------
+
+@dataclass(frozen=True)
+class MultiAssetAnalytic(AbstractPricingMethod):
+    """The two closed forms that need no special function beyond Φ: a European vanilla on a GeometricMean index (which is
+    lognormal), and Margrabe's exchange option — a call struck at 0 on WeightedSum((a, −b)), a, b > 0."""
+
+
+def solve_multiasset_analytic(prob: PricingProblem, method: MultiAssetAnalytic):
+    o, m = prob.payoff, prob.market_inputs
+    q = getattr(o, "payoff", None)
+    if not (isinstance(o, IndexOption) and isinstance(m, MultiAssetInputs) and isinstance(q, VanillaOption)
+            and isinstance(q.exercise_style, European) and isinstance(q.underlying, Spot)):
+        raise MethodError("MultiAssetAnalytic: an IndexOption of a European VanillaOption on MultiAssetInputs")
+    d = m.n_assets
+    w = index_weights(o.index, d)
+    S, sg = [float(t) for t in m.spots], [float(t) for t in m.sigmas]
+    Cm = [[float(t) for t in row] for row in m.correlation]
+    T = float(yearfrac(m.referenceDate, q.expiry))
+    r, D = float(zero_rate(m.rate, q.expiry)), float(df(m.rate, q.expiry))
+    K, cp = float(q.strike), q.call_put()
+    if isinstance(o.index, GeometricMean):
+        mean = math.fsum(w[i] * (math.log(S[i]) + (r - 0.5 * sg[i] * sg[i]) * T) for i in range(d))
+        var = T * math.fsum(w[i] * w[j] * sg[i] * sg[j] * Cm[i][j] for i in range(d) for j in range(d))
+        if not K > 0.0:
+            raise MethodError("MultiAssetAnalytic: a geometric-index vanilla needs a strike > 0")
+        if var <= 0.0:
+            price = D * max(cp * (math.exp(mean) - K), 0.0)
+        else:
+            sd = math.sqrt(var)
+            d2 = (mean - math.log(K)) / sd
+            price = D * cp * (math.exp(mean + 0.5 * var) * _ncdf(cp * (d2 + sd)) - K * _ncdf(cp * d2))
+        return AnalyticSolution(prob, method, price)
+    if isinstance(o.index, WeightedSum) and d == 2 and K == 0.0 and cp > 0.0 and w[0] > 0.0 and w[1] < 0.0:
+        a, b = w[0] * S[0], -w[1] * S[1]
+        var = (sg[0] * sg[0] + sg[1] * sg[1] - 2.0 * Cm[0][1] * sg[0] * sg[1]) * T
+        if var <= 0.0:
+            price = max(a - b, 0.0)
+        else:
+            sd = math.sqrt(var)
+            d1 = (math.log(a / b) + 0.5 * var) / sd
+            price = a * _ncdf(d1) - b * _ncdf(d1 - sd)
+        return AnalyticSolution(prob, method, (D * math.exp(r * T)) * price)
+    raise MethodError("MultiAssetAnalytic prices a European vanilla on a GeometricMean index and Margrabe's exchange option "
+                      "(a call struck at 0 on WeightedSum((a, -b)) of two assets): use MonteCarlo(MultiAssetDynamics(), "
+                      "EulerMaruyama(), config) for everything else")

@@ -72,6 +72,9 @@ def solve_basket(prob: BasketPricingProblem, method, ensemble: bool = False):
     from .analytic import AnalyticSolution, CarrMadan, solve_carr_madan_basket
     from .trees import CoxRossRubinsteinMethod, CRRSolution, solve_crr_basket
     from .pde import CrankNicolsonMethod, solve_pde_basket
+    from .multiasset import is_multiasset, solve_index_options
+    if is_multiasset(prob.payoffs, prob.market_inputs, method):  # IndexOptions: one statistics pass per distinct index
+        return BasketPricingSolution(prob, solve_index_options(prob.payoffs, prob.market_inputs, method, ensemble))
     if isinstance(method, CoxRossRubinsteinMethod):
         prices = solve_crr_basket(prob.payoffs, prob.market_inputs, method)
         return BasketPricingSolution(prob, [CRRSolution(PricingProblem(p, prob.market_inputs), method, float(x))

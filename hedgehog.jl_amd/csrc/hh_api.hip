@@ -8,6 +8,7 @@
 #include <mutex>
 #include <vector>
 
+#include "hh_assets.h"
 #include "hh_kernels.h"
 #include "hh_qe.h"
 
@@ -1299,6 +1300,34 @@ static int check_jump(hh_ctx* ctx, const char* who, const hh_jump* jump, double 
   return HH_OK;
 }
 
+// The assets and the index of a multi-asset entry point (`who`): everything that does not depend on the model or the
+// configuration, the positive definiteness of the correlation matrix included.
+static int check_assets(hh_ctx* ctx, const char* who, const hh_assets* as) {
+  if (as->n_assets < 1u || as->n_assets > (uint32_t)HH_MAX_ASSETS)
+    return fail(ctx, HH_ERR_INVALID, "%s: n_assets (%u) must lie in 1 .. %d", who, as->n_assets, HH_MAX_ASSETS);
+  if (as->index_kind < HH_INDEX_WEIGHTED_SUM || as->index_kind > HH_INDEX_WORST_OF)
+    return fail(ctx, HH_ERR_INVALID, "%s: unknown index_kind %d", who, as->index_kind);
+  const bool extreme = as->index_kind == HH_INDEX_BEST_OF || as->index_kind == HH_INDEX_WORST_OF;
+  bool any_weight = false;
+  for (uint32_t i = 0; i < as->n_assets; ++i) {
+    if (!(as->spots[i] > 0.0) || !std::isfinite(as->spots[i]))
+      return fail(ctx, HH_ERR_INVALID, "%s: asset %u: the spot must be finite and > 0", who, i);
+    if (!(as->sigmas[i] >= 0.0) || !std::isfinite(as->sigmas[i]))
+      return fail(ctx, HH_ERR_INVALID, "%s: asset %u: sigma must be finite and >= 0", who, i);
+    if (!std::isfinite(as->weights[i])) return fail(ctx, HH_ERR_INVALID, "%s: asset %u: the weight must be finite", who, i);
+    if (extreme && !(as->weights[i] > 0.0))
+      return fail(ctx, HH_ERR_INVALID, "%s: asset %u: a best-of / worst-of weight must be > 0", who, i);
+    any_weight = any_weight || as->weights[i] != 0.0;
+  }
+  if (as->index_kind == HH_INDEX_WEIGHTED_SUM && !any_weight)
+    return fail(ctx, HH_ERR_INVALID, "%s: every weight of the weighted sum is zero", who);
+  if (const char* defect = hh::corr_defect(*as)) return fail(ctx, HH_ERR_INVALID, "%s: %s", who, defect);
+  double L[hh::kAssetsTri];
+  if (!hh::cholesky(as->corr, as->n_assets, L))
+    return fail(ctx, HH_ERR_INVALID, "%s: the correlation matrix is not positive definite", who);
+  return HH_OK;
+}
+
 // The scalars of a quadratic-exponential entry point (`who`), after the checks every path entry point makes.
 static int check_qe(hh_ctx* ctx, const char* who, const hh_model* m, const hh_config* c, const hh_qe* qe) {
   if (!(m->kappa > 0.0) || !(m->theta > 0.0) || !(m->sigma > 0.0) || !(m->V0 >= 0.0))
@@ -1328,10 +1357,14 @@ static int check_qe(hh_ctx* ctx, const char* who, const hh_model* m, const hh_co
 // member into ctx->heston_var when want_var.
 // jump and qe together (the Bates entry points alone pass both): that step with jumps, its constants formed on
 // r_c = r_drift − λκ̄.
+// assets (NULL: none; never with jump or qe): the index of several correlated lognormal assets — the monitored rows;
+// of the model only T, r_drift and discount are read.
 static int run_path_stats(hh_ctx* ctx, const char* who, const hh_model* m, const hh_config* c, uint32_t monitor_every,
                           int32_t include_start, int32_t extremes, const hh_jump* jump = nullptr,
-                          const hh_qe* qe = nullptr, bool want_var = false) {
+                          const hh_qe* qe = nullptr, bool want_var = false, const hh_assets* assets = nullptr) {
   const bool hest = c->dynamics == HH_HESTON;
+  if (assets && (hest || c->dynamics != HH_LOGNORMAL || c->strategy != HH_EULER_MARUYAMA))
+    return fail(ctx, HH_ERR_UNSUPPORTED, "%s needs LognormalDynamics + EulerMaruyama", who);
   if (qe && (!hest || c->strategy != HH_QE))
     return fail(ctx, HH_ERR_UNSUPPORTED, "%s needs HestonDynamics + the quadratic-exponential strategy (HH_QE)", who);
   if (jump && !qe && (hest || c->strategy != HH_EULER_MARUYAMA))
@@ -1348,12 +1381,16 @@ static int run_path_stats(hh_ctx* ctx, const char* who, const hh_model* m, const
   if (monitor_every == 0 || c->n_steps % monitor_every != 0)
     return fail(ctx, HH_ERR_INVALID, "%s: monitor_every (%u) must be >= 1 and divide n_steps (%u)", who, monitor_every,
                 c->n_steps);
-  if (!(m->S0 > 0.0) || !(m->T > 0.0) || !std::isfinite(m->S0) || !std::isfinite(m->T) ||
-      !std::isfinite(m->sigma) || !std::isfinite(m->r_drift) || !std::isfinite(m->discount) ||
-      (hest && (!(std::fabs(m->rho) <= 1.0) || !std::isfinite(m->V0) || !std::isfinite(m->kappa) ||
-                !std::isfinite(m->theta))))
+  if (assets) {
+    if (!(m->T > 0.0) || !std::isfinite(m->T) || !std::isfinite(m->r_drift) || !std::isfinite(m->discount))
+      return fail(ctx, HH_ERR_INVALID, "%s: T > 0, r_drift and discount finite", who);
+  } else if (!(m->S0 > 0.0) || !(m->T > 0.0) || !std::isfinite(m->S0) || !std::isfinite(m->T) ||
+             !std::isfinite(m->sigma) || !std::isfinite(m->r_drift) || !std::isfinite(m->discount) ||
+             (hest && (!(std::fabs(m->rho) <= 1.0) || !std::isfinite(m->V0) || !std::isfinite(m->kappa) ||
+                       !std::isfinite(m->theta))))
     return fail(ctx, HH_ERR_INVALID, "%s: S0, T > 0, |rho| <= 1, model scalars finite", who);
   int rc;
+  if (assets && (rc = check_assets(ctx, who, assets))) return rc;
   if (jump && (rc = check_jump(ctx, who, jump, m->T / (double)c->n_steps))) return rc;
   hh_model m_c = *m;  // Bates: the step's constants, and their checks, on the compensated rate
   if (jump && qe) m_c.r_drift = m->r_drift - hh::merton_compensator(*jump);
@@ -1364,7 +1401,10 @@ static int run_path_stats(hh_ctx* ctx, const char* who, const hh_model* m, const
   const uint64_t* seeds_dev = nullptr;
   if ((rc = stage_path_seeds(ctx, c, &seeds_dev))) return rc;
   if ((rc = begin_timing(ctx))) return rc;
-  if (qe && jump)
+  if (assets)
+    HH_HIP(ctx, hh::launch_assets_stats(*m, *c, *assets, seeds_dev, monitor_every, include_start != 0, ctx->path_stats,
+                                        ctx->stream));
+  else if (qe && jump)
     HH_HIP(ctx, hh::launch_bates_stats(*m, *c, *qe, *jump, seeds_dev, monitor_every, include_start != 0, ctx->path_stats,
                                        want_var ? ctx->heston_var.p : nullptr, ctx->stream));
   else if (qe)
@@ -1382,14 +1422,14 @@ static int run_path_stats(hh_ctx* ctx, const char* who, const hh_model* m, const
 static int path_stats_call(hh_ctx* ctx, const char* who, const hh_model* m, const hh_config* c, uint32_t monitor_every,
                            int32_t include_start, int32_t extremes, double* stats, int32_t stats_on_device,
                            hh_result* out, const hh_qe* qe = nullptr, double* var_T = nullptr,
-                           const hh_jump* jump = nullptr) {
+                           const hh_jump* jump = nullptr, const hh_assets* assets = nullptr) {
   if (!ctx) return HH_ERR_INVALID;
   std::lock_guard<std::recursive_mutex> lock__(ctx->mu);
   if (!m || !c || !stats) return fail(ctx, HH_ERR_INVALID, "%s: NULL argument", who);
   const WallClock clock;
   HH_HIP(ctx, hipSetDevice(ctx->device));
   HH_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-  int rc = run_path_stats(ctx, who, m, c, monitor_every, include_start, extremes, jump, qe, var_T != nullptr);
+  int rc = run_path_stats(ctx, who, m, c, monitor_every, include_start, extremes, jump, qe, var_T != nullptr, assets);
   if (rc) return rc;
   HH_HIP(ctx, hipEventRecord(ctx->ev1, ctx->stream));
   const hh::PathStatsLayout at(c->n_paths, c->antithetic != 0, path_stat_rows(extremes));
@@ -1418,11 +1458,12 @@ int hh_mc_path_stats_ex(hh_ctx* ctx, const hh_model* m, const hh_config* c, uint
 }
 
 // hh_mc_solve_path (kinds up to HH_PAYOFF_DIGITAL_ASSET), hh_mc_solve_path_ex (the lookbacks too) and, with `jump`,
-// hh_mc_solve_path_jump
+// hh_mc_solve_path_jump; with `assets`, hh_mc_solve_path_assets: the payoffs on the statistics of the index
 static int solve_path_call(hh_ctx* ctx, const char* who, int32_t last_kind, const hh_model* m, const hh_config* c,
                            uint32_t monitor_every, int32_t include_start, int32_t extremes, const hh_path_payoff* payoffs,
                            uint32_t n_payoffs, hh_result* out, double* path_values, double* stats,
-                           const hh_jump* jump = nullptr, const hh_qe* qe = nullptr, double* var_T = nullptr) {
+                           const hh_jump* jump = nullptr, const hh_qe* qe = nullptr, double* var_T = nullptr,
+                           const hh_assets* assets = nullptr) {
   if (!ctx) return HH_ERR_INVALID;
   std::lock_guard<std::recursive_mutex> lock__(ctx->mu);
   if (!m || !c || !payoffs || !out) return fail(ctx, HH_ERR_INVALID, "%s: NULL argument", who);
@@ -1437,11 +1478,17 @@ static int solve_path_call(hh_ctx* ctx, const char* who, int32_t last_kind, cons
     if (q.cp != 1.0 && q.cp != -1.0) return fail(ctx, HH_ERR_INVALID, "%s: payoff %u: cp must be +1 or -1", who, k);
     if (!std::isfinite(q.strike) || !std::isfinite(q.rebate) || !std::isfinite(q.cash) || std::isnan(q.barrier))
       return fail(ctx, HH_ERR_INVALID, "%s: payoff %u: strike, rebate, cash finite; barrier not NaN", who, k);
+    if (assets && q.kind == HH_PAYOFF_ASIAN_GEOM && assets->index_kind == HH_INDEX_WEIGHTED_SUM)
+      for (uint32_t i = 0; i < assets->n_assets && i < (uint32_t)HH_MAX_ASSETS; ++i)  // n_assets is checked further down
+        if (assets->weights[i] < 0.0)
+          return fail(ctx, HH_ERR_INVALID,
+                      "%s: payoff %u: a geometric Asian on a weighted sum with a negative weight: the sum of logarithms "
+                      "is not defined where the index is <= 0", who, k);
   }
   const WallClock clock;
   HH_HIP(ctx, hipSetDevice(ctx->device));
   HH_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-  int rc = run_path_stats(ctx, who, m, c, monitor_every, include_start, extremes, jump, qe, var_T != nullptr);
+  int rc = run_path_stats(ctx, who, m, c, monitor_every, include_start, extremes, jump, qe, var_T != nullptr, assets);
   if (rc) return rc;
 
   const hh::PathStatsLayout at(c->n_paths, c->antithetic != 0, path_stat_rows(extremes));
@@ -1596,6 +1643,29 @@ int hh_mc_solve_path_qe(hh_ctx* ctx, const hh_model* m, const hh_qe* qe, const h
   if (!qe) return fail(ctx, HH_ERR_INVALID, "hh_mc_solve_path_qe: NULL argument");
   return solve_path_call(ctx, "hh_mc_solve_path_qe", HH_PAYOFF_LOOKBACK_FIXED, m, c, monitor_every, include_start,
                          HH_EXTREMES_MONITORED, payoffs, n_payoffs, out, path_values, stats, nullptr, qe, var_T);
+}
+
+// ---- several correlated lognormal assets (hedgehog_mc.h; kernel: hh_assets.hip) --------------------------------------
+
+int hh_mc_path_stats_assets(hh_ctx* ctx, const hh_model* m, const hh_assets* assets, const hh_config* c,
+                            uint32_t monitor_every, int32_t include_start, double* stats, int32_t stats_on_device,
+                            hh_result* out) {
+  if (!ctx) return HH_ERR_INVALID;
+  std::lock_guard<std::recursive_mutex> lock__(ctx->mu);
+  if (!assets) return fail(ctx, HH_ERR_INVALID, "hh_mc_path_stats_assets: NULL argument");
+  return path_stats_call(ctx, "hh_mc_path_stats_assets", m, c, monitor_every, include_start, HH_EXTREMES_MONITORED, stats,
+                         stats_on_device, out, nullptr, nullptr, nullptr, assets);
+}
+
+int hh_mc_solve_path_assets(hh_ctx* ctx, const hh_model* m, const hh_assets* assets, const hh_config* c,
+                            uint32_t monitor_every, int32_t include_start, const hh_path_payoff* payoffs,
+                            uint32_t n_payoffs, hh_result* out, double* path_values, double* stats) {
+  if (!ctx) return HH_ERR_INVALID;
+  std::lock_guard<std::recursive_mutex> lock__(ctx->mu);
+  if (!assets) return fail(ctx, HH_ERR_INVALID, "hh_mc_solve_path_assets: NULL argument");
+  return solve_path_call(ctx, "hh_mc_solve_path_assets", HH_PAYOFF_LOOKBACK_FIXED, m, c, monitor_every, include_start,
+                         HH_EXTREMES_MONITORED, payoffs, n_payoffs, out, path_values, stats, nullptr, nullptr, nullptr,
+                         assets);
 }
 
 // ---- Bates: the quadratic-exponential step with Merton jumps (hedgehog_mc.h; kernels: hh_bates.hip, hh_fourier.hip) ----

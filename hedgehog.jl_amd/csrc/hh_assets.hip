@@ -1,0 +1,144 @@
+// Several correlated lognormal assets for gfx950 (wave64, fp64 VALU): the five monitored statistics of
+// path_stats_kernel (hh_path_stats.h: Running) for a scalar INDEX of d assets — a weighted sum, a geometric mean, the
+// best or the worst of them (include/hedgehog_mc.h, "Several correlated lognormal assets" — the draws, the step and the
+// index are stated there in full).  Its output goes through path_payoff_kernel untouched: every payoff kind prices on
+// the index.
+//
+// One trajectory per lane, and its mirror in the same lane.  d, the index kind and the mirror are template
+// parameters and every loop over assets is unrolled in full: the d log-states (2d with the mirror) and the d normals
+// of a step are named registers — a per-thread array indexed at run time would go to scratch.  The Cholesky factor and
+// the step's constants are formed on the host (hh_assets.h) and arrive by value: wave-uniform.  No LDS, no barriers;
+// every loop is bounded by n_steps or by d.
+#include <cmath>
+
+#include "hh_assets.h"
+#include "hh_path_stats.h"
+#include "hh_sim.h"
+
+namespace hh {
+namespace {
+
+// the pair (I, x) of the index on a date — what Running::first / next take as (S, log S)
+template <int D, int KIND>
+__device__ __forceinline__ void index_of(const AssetArgs& c, const double (&x)[D], double& I, double& xi) {
+  if constexpr (KIND == HH_INDEX_WEIGHTED_SUM) {
+    I = c.w[0] * exp(x[0]);
+#pragma unroll
+    for (int i = 1; i < D; ++i) I = fma(c.w[i], exp(x[i]), I);
+    xi = log(I);
+  } else if constexpr (KIND == HH_INDEX_GEOMETRIC) {
+    xi = c.w[0] * x[0];
+#pragma unroll
+    for (int i = 1; i < D; ++i) xi = fma(c.w[i], x[i], xi);
+    I = exp(xi);
+  } else {  // best-of, worst-of: log w_i is in the initial state
+    xi = x[0];
+#pragma unroll
+    for (int i = 1; i < D; ++i) xi = KIND == HH_INDEX_BEST_OF ? vmax(xi, x[i]) : vmin(xi, x[i]);
+    I = exp(xi);
+  }
+}
+
+// x_i += drift_i + Σ_{j<=i} A_ij·(±z_j), the sum as a chain of fma in j
+template <int D, bool MIRROR>
+__device__ __forceinline__ void step_assets(const AssetArgs& c, double (&x)[D], const double (&z)[2 * ((D + 1) / 2)]) {
+#pragma unroll
+  for (int i = 0; i < D; ++i) {
+    double acc = c.drift[i];
+#pragma unroll
+    for (int j = 0; j <= i; ++j) acc = fma(c.A[tri(i, j)], MIRROR ? -z[j] : z[j], acc);
+    x[i] = x[i] + acc;
+  }
+}
+
+template <int D, int KIND, bool ANTI>
+__global__ __launch_bounds__(256) void assets_stats_kernel(const AssetArgs c, const uint64_t* __restrict__ seeds,
+                                                           const uint64_t n_paths, const uint32_t n_steps,
+                                                           const uint32_t monitor_every, const int include_start,
+                                                           double* __restrict__ stats) {
+  constexpr int H = (D + 1) / 2;  // Philox blocks, and Box–Muller pairs, of a step
+  const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n_paths) return;
+  const PathStatsLayout at(n_paths, ANTI, HH_PATH_STATS);
+  double x[D], xa[D];
+#pragma unroll
+  for (int k = 0; k < D; ++k) x[k] = xa[k] = c.x0[k];
+  Running r, ra;
+  bool started = include_start != 0;
+  if (started) {
+    double I, xi;
+    index_of<D, KIND>(c, x, I, xi);
+    r.first(I, xi);
+    if constexpr (ANTI) ra.first(I, xi);  // the mirror starts from the same states
+  }
+  const uint64_t key = seeds[i];
+  uint32_t left = monitor_every;
+  for (uint32_t s = 0; s < n_steps; ++s) {
+    double z[2 * H];
+#pragma unroll
+    for (int h = 0; h < H; ++h) normal_pair(key, s, (uint32_t)h, 0u, kDomAssets, z[2 * h], z[2 * h + 1]);
+    step_assets<D, false>(c, x, z);
+    if constexpr (ANTI) step_assets<D, true>(c, xa, z);
+    if (--left != 0u) continue;
+    left = monitor_every;
+    double I, xi;
+    index_of<D, KIND>(c, x, I, xi);
+    if (started) r.next(I, xi);
+    else r.first(I, xi);
+    if constexpr (ANTI) {
+      index_of<D, KIND>(c, xa, I, xi);
+      if (started) ra.next(I, xi);
+      else ra.first(I, xi);
+    }
+    started = true;
+  }
+  r.store(stats, at, i);
+  if constexpr (ANTI) ra.store(stats, at, n_paths + i);
+}
+
+using AssetsKernel = void (*)(const AssetArgs, const uint64_t*, const uint64_t, const uint32_t, const uint32_t, const int,
+                              double*);
+
+template <int D, int KIND>
+AssetsKernel pick_member(bool anti) {
+  return anti ? assets_stats_kernel<D, KIND, true> : assets_stats_kernel<D, KIND, false>;
+}
+template <int D>
+AssetsKernel pick_kind(int kind, bool anti) {
+  switch (kind) {
+    case HH_INDEX_WEIGHTED_SUM: return pick_member<D, HH_INDEX_WEIGHTED_SUM>(anti);
+    case HH_INDEX_GEOMETRIC: return pick_member<D, HH_INDEX_GEOMETRIC>(anti);
+    case HH_INDEX_BEST_OF: return pick_member<D, HH_INDEX_BEST_OF>(anti);
+    case HH_INDEX_WORST_OF: return pick_member<D, HH_INDEX_WORST_OF>(anti);
+    default: return nullptr;
+  }
+}
+AssetsKernel pick_kernel(uint32_t d, int kind, bool anti) {
+  switch (d) {
+    case 1: return pick_kind<1>(kind, anti);
+    case 2: return pick_kind<2>(kind, anti);
+    case 3: return pick_kind<3>(kind, anti);
+    case 4: return pick_kind<4>(kind, anti);
+    case 5: return pick_kind<5>(kind, anti);
+    case 6: return pick_kind<6>(kind, anti);
+    case 7: return pick_kind<7>(kind, anti);
+    case 8: return pick_kind<8>(kind, anti);
+    default: return nullptr;
+  }
+}
+
+}  // namespace
+
+int launch_assets_stats(const hh_model& m, const hh_config& c, const hh_assets& assets, const uint64_t* seeds_dev,
+                        uint32_t monitor_every, bool include_start, double* stats, hipStream_t s) {
+  double L[kAssetsTri] = {};
+  const AssetsKernel kernel = pick_kernel(assets.n_assets, assets.index_kind, c.antithetic != 0);
+  if (!kernel || !cholesky(assets.corr, assets.n_assets, L)) return (int)hipErrorInvalidValue;  // the entry points check both
+  const AssetArgs a = asset_args(assets, m.r_drift, m.T, c.n_steps, L);
+  const dim3 g((unsigned)((c.n_paths + 255) / 256)), blk(256);
+  hipLaunchKernelGGL(kernel, g, blk, 0, s, a, seeds_dev, (uint64_t)c.n_paths, (uint32_t)c.n_steps, monitor_every,
+                     (int)include_start, stats);
+  return (int)hipGetLastError();
+}
+
+}  // namespace hh

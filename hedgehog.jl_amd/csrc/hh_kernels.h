@@ -320,6 +320,11 @@ int launch_bates_stats(const hh_model& m, const hh_config& c, const hh_qe& qe, c
 // launch_carr_madan_basket (HH_HESTON, compat_sqrt_alpha = 0) with the Bates characteristic function
 int launch_carr_madan_bates(const hh_model& m, const hh_jump& jump, double alpha, double bound,
                             const double* per_payoff_dev, uint32_t n_payoffs, double* out_dev, hipStream_t s);
+// Several correlated lognormal assets (hh_assets.hip; include/hedgehog_mc.h, "Several correlated lognormal assets"):
+// launch_path_stats' five monitored rows for the index of `assets`.  m: T, r_drift; c: antithetic, n_paths, n_steps.
+// The entry points have checked the assets (hh_assets.h: corr_defect, cholesky); the factor is formed again here.
+int launch_assets_stats(const hh_model& m, const hh_config& c, const hh_assets& assets, const uint64_t* seeds_dev,
+                        uint32_t monitor_every, bool include_start, double* stats, hipStream_t s);
 // form: kLsmFormPersistent = the whole backward induction in ONE launch when the ensemble fits the
 // chip (else it falls back by itself), kLsmFormPerDate = one launch per exercise date.  *form_used
 // says which was enqueued; after a persistent launch the caller synchronises and reads the word at

@@ -82,7 +82,61 @@ class ZeroRateSpineLens(GreekLens):
         return m.rate.rate
 
 
+def _assets(prob, lens):
+    from .multiasset import MultiAssetInputs
+    m = prob.market_inputs
+    if not isinstance(m, MultiAssetInputs):
+        raise TypeError(f"{type(lens).__name__} needs market_inputs::MultiAssetInputs")
+    return m
+
+
+@dataclass(frozen=True)
+class AssetSpotLens(GreekLens):
+    """the spot of asset i (0-based) of MultiAssetInputs"""
+    i: int
+
+    def __call__(self, prob): return _assets(prob, self).spots[self.i]
+
+
+@dataclass(frozen=True)
+class AssetVolLens(GreekLens):
+    """the flat volatility of asset i (0-based) of MultiAssetInputs"""
+    i: int
+
+    def __call__(self, prob): return _assets(prob, self).sigmas[self.i]
+
+
+@dataclass(frozen=True)
+class CorrelationLens(GreekLens):
+    """the correlation of assets i and j (0-based, i != j) of MultiAssetInputs; `set` writes both symmetric entries"""
+    i: int
+    j: int
+
+    def __post_init__(self):
+        if self.i == self.j:
+            raise ValueError("CorrelationLens: the diagonal of a correlation matrix is 1")
+
+    def __call__(self, prob): return _assets(prob, self).correlation[self.i][self.j]
+
+
+def _with(seq, i, val):
+    out = list(seq)
+    out[i] = val
+    return tuple(out)
+
+
 def set(prob, lens, val):  # noqa: A001 - the reference's name (Accessors.set)
+    if isinstance(lens, AssetSpotLens):
+        m = _assets(prob, lens)
+        return _replace(prob, "market_inputs", m.replace(spots=_with(m.spots, lens.i, val)))
+    if isinstance(lens, AssetVolLens):
+        m = _assets(prob, lens)
+        return _replace(prob, "market_inputs", m.replace(sigmas=_with(m.sigmas, lens.i, val)))
+    if isinstance(lens, CorrelationLens):
+        m = _assets(prob, lens)
+        rows = [list(r) for r in m.correlation]
+        rows[lens.i][lens.j] = rows[lens.j][lens.i] = val
+        return _replace(prob, "market_inputs", m.replace(correlation=rows))
     if isinstance(lens, PropertyLens):
         return _set_path(prob, lens.path, val)
     if isinstance(lens, SpotLens):

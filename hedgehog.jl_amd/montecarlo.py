@@ -339,6 +339,9 @@ def solve_montecarlo(prob: PricingProblem, method: MonteCarlo, ensemble: bool = 
 
     `replay` (optional, build extension): Wiener increments to consume instead of drawing them —
     numpy array [path][step][comp] (or tile-major), the noise-replay parity mode of DESIGN.md."""
+    from .multiasset import is_multiasset, solve_multiasset
+    if is_multiasset([prob.payoff], prob.market_inputs, method):  # an index of several assets (hh_mc_solve_path_assets)
+        return solve_multiasset(prob, method, ensemble, replay)
     if is_bates(prob.market_inputs, method):  # every payoff on the path statistics (hh_mc_solve_path_bates)
         if replay is not None:
             raise MethodError("Bates solves draw their own noise: no replay")
@@ -414,6 +417,9 @@ def solve_montecarlo_many(probs, method: MonteCarlo, replay=None, replay_layout=
     Returns None when the problems cannot share a pass (dual numbers in one of them, more than HH_MAX_MODELS
     problems): the caller then solves them one by one, as the reference does."""
     if not 1 < len(probs) <= _ffi.HH_MAX_MODELS:
+        return None
+    from .multiasset import is_multiasset
+    if any(is_multiasset([p.payoff], p.market_inputs, method) for p in probs):  # one solve after the other, on shared seeds
         return None
     if any(isinstance(p.payoff, PATH_PAYOFFS) for p in probs):  # one solve after the other (hh_mc_solve_path)
         return None

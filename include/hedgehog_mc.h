@@ -905,6 +905,75 @@ int hh_carr_madan_bates(hh_ctx* ctx, const hh_model* model, const hh_jump* jump,
                         const double* discounts, uint32_t n_payoffs, double* prices_out);
 
 /*
+ * Several correlated lognormal assets and a scalar INDEX of them: baskets, spreads, geometric baskets, best-of and
+ * worst-of (rainbow) options.  The reference prices options on one underlying only; the conventions are this library's.
+ *   d log S_i = (r − σ_i²/2) dt + σ_i dW_i          corr(dW_i, dW_j) = C_ij          i, j < d = n_assets <= HH_MAX_ASSETS
+ * The statistics kernel keeps the five running numbers of hh_mc_path_stats (enum hh_path_stat) for the index instead
+ * of for a spot, so every payoff kind of hh_mc_solve_path_ex prices on the index through the same payoff kernel.  The
+ * log-Euler step below is exact in law for this model: the states on the dates are exact for any n_steps.
+ * Of hh_model only T, r_drift and discount are read; hh_assets carries the rest.  cfg->dynamics = HH_LOGNORMAL,
+ * cfg->strategy = HH_EULER_MARUYAMA.  No existing struct changes, no enum gains a value.
+ *
+ * ON THE HOST, once per call (csrc/hh_assets.h — a host program can include it), every operation one rounded fp64
+ * operation in the order written:
+ *   CHOLESKY, Cholesky–Banachiewicz, row by row: for i = 0 .. d−1, for j = 0 .. i:
+ *       s = C_ij;  for k = 0 .. j−1 in this order:  s = s − L_ik·L_jk   (a product, then a subtraction)
+ *       j < i:  L_ij = s / L_jj          j == i:  L_ii = sqrt(s); s not > 0 or not finite: not positive definite
+ *   dt = T/n_steps          sqrt_dt = sqrt(dt)
+ *   drift_i = (r_drift − (0.5·σ_i)·σ_i)·dt
+ *   A_ij    = (σ_i·L_ij)·sqrt_dt                       j <= i
+ *   x0_i    = log(spot_i)                              best-of, worst-of: log(spot_i) + log(w_i)
+ * They travel by value in the kernel's argument block.
+ *
+ * DRAWS: trajectory i is keyed by seeds[i].  At step k (0-based) the asset pair h = 0 .. ⌈d/2⌉−1 takes the Philox4x32-10
+ * block of counter (k, h, 0, 6) — word 3 = 6, a domain no other draw of the library uses — whose Box–Muller pair, as every
+ * normal pair of the library, is (z_2h, z_2h+1); for odd d the last block's second normal is dropped.
+ *
+ * ONE STEP, per asset i = 0 .. d−1 in order:
+ *   acc = drift_i;   for j = 0 .. i:  acc = fma(A_ij, z_j, acc);   x_i = x_i + acc
+ * The mirror of an antithetic pair lives in the same lane and takes −z_j in the same chain; nothing more is drawn.
+ *
+ * THE INDEX on a monitoring date — the dates are hh_mc_path_stats': steps monitor_every, 2·monitor_every, …, n_steps,
+ * and step 0 when include_start — is the pair (I, x) the statistics take as (S, log S):
+ *   HH_INDEX_WEIGHTED_SUM   I = w_0·exp(x_0), then I = fma(w_i, exp(x_i), I) in asset order;   x = log(I)
+ *   HH_INDEX_GEOMETRIC      x = w_0·x_0, then x = fma(w_i, x_i, x);                            I = exp(x)
+ *   HH_INDEX_BEST_OF        x = max_i x_i   (log w_i is in the initial state);                 I = exp(x)
+ *   HH_INDEX_WORST_OF       x = min_i x_i                                                      I = exp(x)
+ * so the index is Σ w_i S_i, Π S_i^{w_i}, max_i w_i S_i, min_i w_i S_i.  A weighted sum with negative weights (a spread)
+ * may be <= 0: its row HH_STAT_SUM_X is then NaN or −inf and no admitted payoff reads it.  The date-0 term comes from the
+ * same function on the initial states: with every σ_i = 0 and r_drift = 0 all dates of a trajectory agree bit for bit.
+ *
+ * hh_mc_path_stats_assets / hh_mc_solve_path_assets: hh_mc_path_stats / hh_mc_solve_path_ex under
+ * HH_EXTREMES_MONITORED on the index — the same five rows, the same layout (mirrors at n_paths + i), the same payoff
+ * kernel, payoff kinds 0 .. 7, the lookbacks on the monitored rows.  Arguments, outputs and timing slots are
+ * hh_mc_solve_path's.  Synchronous.
+ *
+ * Errors, checked on the host before any launch.  HH_ERR_INVALID: assets is NULL; n_assets outside 1 .. HH_MAX_ASSETS;
+ * an unknown index_kind; a spot not finite or not > 0; a sigma not finite or < 0; C_ii != 1; C_ij != C_ji; C_ij not
+ * finite or |C_ij| > 1; C not positive definite (above); a weight not finite; all weights zero (weighted sum); a weight
+ * <= 0 (best-of, worst-of); HH_PAYOFF_ASIAN_GEOM on a weighted sum with a negative weight; T not > 0, r_drift or
+ * discount not finite; everything else hh_mc_solve_path_ex rejects.  HH_ERR_UNSUPPORTED: dynamics other than
+ * HH_LOGNORMAL, a strategy other than HH_EULER_MARUYAMA, REPLAY noise, n_partials > 0.
+ * Not provided: barriers on single assets, payoffs that read more than one index (one call per index, on the same
+ * seeds), dividends and quantos, stochastic volatility per asset, American exercise, continuous (bridge) monitoring,
+ * REPLAY noise, dual partials (bump the inputs: the solves share their seeds), accumulate, hh_mc_solve_multi and
+ * multi-GPU forms, more than HH_MAX_ASSETS assets, a Julia binding.
+ */
+#define HH_MAX_ASSETS 8
+enum hh_index_kind { HH_INDEX_WEIGHTED_SUM = 0, HH_INDEX_GEOMETRIC = 1, HH_INDEX_BEST_OF = 2, HH_INDEX_WORST_OF = 3 };
+typedef struct hh_assets {
+  uint32_t n_assets; int32_t index_kind;
+  double spots[HH_MAX_ASSETS], sigmas[HH_MAX_ASSETS], weights[HH_MAX_ASSETS];
+  double corr[HH_MAX_ASSETS * HH_MAX_ASSETS];   /* corr[i*HH_MAX_ASSETS + j], i, j < n_assets */
+} hh_assets;                                    /* 8 + 3·64 + 512 = 712 bytes */
+int hh_mc_path_stats_assets(hh_ctx* ctx, const hh_model* model, const hh_assets* assets, const hh_config* cfg,
+                            uint32_t monitor_every, int32_t include_start, double* stats, int32_t stats_on_device,
+                            hh_result* out);
+int hh_mc_solve_path_assets(hh_ctx* ctx, const hh_model* model, const hh_assets* assets, const hh_config* cfg,
+                            uint32_t monitor_every, int32_t include_start, const hh_path_payoff* payoffs,
+                            uint32_t n_payoffs, hh_result* out, double* path_values, double* stats);
+
+/*
  * The same solve for an ensemble SHARDED over several devices (one process and one hh_ctx per
  * device, trajectories split by contiguous ranges as for hh_mc_accumulate).  The backward induction
  * needs sums over ALL trajectories at three points — the in-the-money statistics of every row, the
