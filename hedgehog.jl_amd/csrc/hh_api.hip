@@ -1351,37 +1351,70 @@ static int check_qe(hh_ctx* ctx, const char* who, const hh_model* m, const hh_co
   return HH_OK;
 }
 
-// The checks of every entry point, then the statistics of every trajectory into ctx->path_stats (one timing slot).
-// jump (NULL: none): the Merton form — lognormal dynamics, the monitored rows.
-// qe (NULL: none): the quadratic-exponential Heston step — the monitored rows, and the variance at expiry of every
-// member into ctx->heston_var when want_var.
-// jump and qe together (the Bates entry points alone pass both): that step with jumps, its constants formed on
-// r_c = r_drift − λκ̄.
-// assets (NULL: none; never with jump or qe): the index of several correlated lognormal assets — the monitored rows;
-// of the model only T, r_drift and discount are read.
-static int run_path_stats(hh_ctx* ctx, const char* who, const hh_model* m, const hh_config* c, uint32_t monitor_every,
-                          int32_t include_start, int32_t extremes, const hh_jump* jump = nullptr,
-                          const hh_qe* qe = nullptr, bool want_var = false, const hh_assets* assets = nullptr) {
-  const bool hest = c->dynamics == HH_HESTON;
-  if (assets && (hest || c->dynamics != HH_LOGNORMAL || c->strategy != HH_EULER_MARUYAMA))
-    return fail(ctx, HH_ERR_UNSUPPORTED, "%s needs LognormalDynamics + EulerMaruyama", who);
-  if (qe && (!hest || c->strategy != HH_QE))
-    return fail(ctx, HH_ERR_UNSUPPORTED, "%s needs HestonDynamics + the quadratic-exponential strategy (HH_QE)", who);
-  if (jump && !qe && (hest || c->strategy != HH_EULER_MARUYAMA))
-    return fail(ctx, HH_ERR_UNSUPPORTED, "%s needs LognormalDynamics + EulerMaruyama", who);
-  if (!qe && (c->strategy != HH_EULER_MARUYAMA || (c->dynamics != HH_LOGNORMAL && !hest)))
-    return fail(ctx, HH_ERR_UNSUPPORTED, "%s needs LognormalDynamics or HestonDynamics + EulerMaruyama", who);
+// The path-statistics family: which kernel an entry point runs and what travels with it — one constructor per kernel.
+struct PathFamily {
+  enum Kernel { kEuler, kJump, kQe, kBates, kAssets } kernel;
+  const char* who;                           // the entry point, as its messages name it
+  int32_t last_kind;                         // the last payoff kind it admits (the solve forms)
+  int32_t extremes = HH_EXTREMES_MONITORED;  // enum hh_path_extremes: the bridge form is path_stats_kernel's alone
+  const hh_jump* jump = nullptr;
+  const hh_qe* qe = nullptr;
+  const hh_assets* assets = nullptr;
+  double* var_T = nullptr;  // host, nullable: the variance at expiry of every member (the QE step)
+  bool missing = false;     // a struct the kernel needs came as NULL: the entry point's "NULL argument"
+  // path_stats_kernel: lognormal or Heston dynamics by Euler–Maruyama
+  PathFamily(const char* w, int32_t last, int32_t ext) : kernel(kEuler), who(w), last_kind(last), extremes(ext) {}
+  // jump_stats_kernel, the Merton form: lognormal dynamics
+  PathFamily(const char* w, int32_t last, const hh_jump* j) : kernel(kJump), who(w), last_kind(last), jump(j), missing(!j) {}
+  // qe_stats_kernel: the quadratic-exponential Heston step
+  PathFamily(const char* w, int32_t last, const hh_qe* q, double* v)
+      : kernel(kQe), who(w), last_kind(last), qe(q), var_T(v), missing(!q) {}
+  // bates_stats_kernel: that step with jumps, its constants formed on r_c = r_drift − λκ̄
+  PathFamily(const char* w, int32_t last, const hh_qe* q, const hh_jump* j, double* v)
+      : kernel(kBates), who(w), last_kind(last), jump(j), qe(q), var_T(v), missing(!q || !j) {}
+  // assets_stats_kernel: the index of several correlated lognormal assets; of the model only T, r_drift, discount are read
+  PathFamily(const char* w, int32_t last, const hh_assets* a) : kernel(kAssets), who(w), last_kind(last), assets(a), missing(!a) {}
+};
+
+// The checks of every entry point, then the statistics of every trajectory into ctx->path_stats (one timing slot) and,
+// where f.var_T, the variances at expiry into ctx->heston_var.
+static int run_path_stats(hh_ctx* ctx, const PathFamily& f, const hh_model* m, const hh_config* c, uint32_t monitor_every,
+                          int32_t include_start) {
+  const char* who = f.who;
+  const bool hest = c->dynamics == HH_HESTON, logn = c->dynamics == HH_LOGNORMAL, em = c->strategy == HH_EULER_MARUYAMA;
+  // the dynamics and strategy a kernel simulates, and how its entry points say so
+  static const char kLognEm[] = "LognormalDynamics + EulerMaruyama";
+  static const char kAnyEm[] = "LognormalDynamics or HestonDynamics + EulerMaruyama";
+  bool ok = false;
+  const char* needs = kAnyEm;
+  switch (f.kernel) {
+    case PathFamily::kEuler: ok = em && (logn || hest); break;
+    case PathFamily::kJump:  // dynamics that are neither are told what the plain entry points tell them
+      ok = em && logn;
+      if (hest || !em) needs = kLognEm;
+      break;
+    case PathFamily::kAssets:
+      ok = em && logn;
+      needs = kLognEm;
+      break;
+    case PathFamily::kQe:
+    case PathFamily::kBates:
+      ok = hest && c->strategy == HH_QE;
+      needs = "HestonDynamics + the quadratic-exponential strategy (HH_QE)";
+      break;
+  }
+  if (!ok) return fail(ctx, HH_ERR_UNSUPPORTED, "%s needs %s", who, needs);
   if (c->noise_mode == HH_NOISE_REPLAY || c->n_partials != 0)
     return fail(ctx, HH_ERR_UNSUPPORTED, "%s: GENERATE noise, no dual partials", who);
   if (c->noise_mode != HH_NOISE_GENERATE) return fail(ctx, HH_ERR_INVALID, "unknown noise_mode %d", c->noise_mode);
-  if (extremes != HH_EXTREMES_MONITORED && extremes != HH_EXTREMES_BRIDGE)
-    return fail(ctx, HH_ERR_INVALID, "%s: unknown extremes %d", who, extremes);
+  if (f.extremes != HH_EXTREMES_MONITORED && f.extremes != HH_EXTREMES_BRIDGE)
+    return fail(ctx, HH_ERR_INVALID, "%s: unknown extremes %d", who, f.extremes);
   if (c->n_paths == 0 || c->n_steps == 0 || c->n_paths > kMaxPaths / 2 || c->n_steps > kMaxEulerSteps)
     return fail(ctx, HH_ERR_INVALID, "%s: 1 <= n_paths <= 2^31 - 128, 1 <= n_steps <= %u", who, kMaxEulerSteps);
   if (monitor_every == 0 || c->n_steps % monitor_every != 0)
     return fail(ctx, HH_ERR_INVALID, "%s: monitor_every (%u) must be >= 1 and divide n_steps (%u)", who, monitor_every,
                 c->n_steps);
-  if (assets) {
+  if (f.assets) {
     if (!(m->T > 0.0) || !std::isfinite(m->T) || !std::isfinite(m->r_drift) || !std::isfinite(m->discount))
       return fail(ctx, HH_ERR_INVALID, "%s: T > 0, r_drift and discount finite", who);
   } else if (!(m->S0 > 0.0) || !(m->T > 0.0) || !std::isfinite(m->S0) || !std::isfinite(m->T) ||
@@ -1390,53 +1423,58 @@ static int run_path_stats(hh_ctx* ctx, const char* who, const hh_model* m, const
                        !std::isfinite(m->theta))))
     return fail(ctx, HH_ERR_INVALID, "%s: S0, T > 0, |rho| <= 1, model scalars finite", who);
   int rc;
-  if (assets && (rc = check_assets(ctx, who, assets))) return rc;
-  if (jump && (rc = check_jump(ctx, who, jump, m->T / (double)c->n_steps))) return rc;
+  if (f.assets && (rc = check_assets(ctx, who, f.assets))) return rc;
+  if (f.jump && (rc = check_jump(ctx, who, f.jump, m->T / (double)c->n_steps))) return rc;
   hh_model m_c = *m;  // Bates: the step's constants, and their checks, on the compensated rate
-  if (jump && qe) m_c.r_drift = m->r_drift - hh::merton_compensator(*jump);
-  if (qe && (rc = check_qe(ctx, who, &m_c, c, qe))) return rc;
-  const hh::PathStatsLayout at(c->n_paths, c->antithetic != 0, path_stat_rows(extremes));
+  if (f.jump && f.qe) m_c.r_drift = m->r_drift - hh::merton_compensator(*f.jump);
+  if (f.qe && (rc = check_qe(ctx, who, &m_c, c, f.qe))) return rc;
+  const hh::PathStatsLayout at(c->n_paths, c->antithetic != 0, path_stat_rows(f.extremes));
   if ((rc = ensure(ctx, ctx->path_stats, at.total))) return rc;
-  if (qe && want_var && (rc = ensure(ctx, ctx->heston_var, (size_t)at.n_total))) return rc;
+  if (f.qe && f.var_T && (rc = ensure(ctx, ctx->heston_var, (size_t)at.n_total))) return rc;
   const uint64_t* seeds_dev = nullptr;
   if ((rc = stage_path_seeds(ctx, c, &seeds_dev))) return rc;
   if ((rc = begin_timing(ctx))) return rc;
-  if (assets)
-    HH_HIP(ctx, hh::launch_assets_stats(*m, *c, *assets, seeds_dev, monitor_every, include_start != 0, ctx->path_stats,
-                                        ctx->stream));
-  else if (qe && jump)
-    HH_HIP(ctx, hh::launch_bates_stats(*m, *c, *qe, *jump, seeds_dev, monitor_every, include_start != 0, ctx->path_stats,
-                                       want_var ? ctx->heston_var.p : nullptr, ctx->stream));
-  else if (qe)
-    HH_HIP(ctx, hh::launch_qe_stats(*m, *c, *qe, seeds_dev, monitor_every, include_start != 0, ctx->path_stats,
-                                    want_var ? ctx->heston_var.p : nullptr, ctx->stream));
-  else if (jump)
-    HH_HIP(ctx, hh::launch_jump_stats(*m, *c, *jump, seeds_dev, monitor_every, include_start != 0, ctx->path_stats, ctx->stream));
-  else
-    HH_HIP(ctx, hh::launch_path_stats(*m, *c, seeds_dev, monitor_every, include_start != 0, extremes == HH_EXTREMES_BRIDGE,
-                                      ctx->path_stats, ctx->stream));
+  const bool start = include_start != 0;
+  double* const var_dev = f.var_T ? ctx->heston_var.p : nullptr;
+  switch (f.kernel) {
+    case PathFamily::kEuler:
+      HH_HIP(ctx, hh::launch_path_stats(*m, *c, seeds_dev, monitor_every, start, f.extremes == HH_EXTREMES_BRIDGE,
+                                        ctx->path_stats, ctx->stream));
+      break;
+    case PathFamily::kJump:
+      HH_HIP(ctx, hh::launch_jump_stats(*m, *c, *f.jump, seeds_dev, monitor_every, start, ctx->path_stats, ctx->stream));
+      break;
+    case PathFamily::kQe:
+      HH_HIP(ctx, hh::launch_qe_stats(*m, *c, *f.qe, seeds_dev, monitor_every, start, ctx->path_stats, var_dev, ctx->stream));
+      break;
+    case PathFamily::kBates:
+      HH_HIP(ctx, hh::launch_bates_stats(*m, *c, *f.qe, *f.jump, seeds_dev, monitor_every, start, ctx->path_stats, var_dev,
+                                         ctx->stream));
+      break;
+    case PathFamily::kAssets:
+      HH_HIP(ctx, hh::launch_assets_stats(*m, *c, *f.assets, seeds_dev, monitor_every, start, ctx->path_stats, ctx->stream));
+      break;
+  }
   return end_timing(ctx);
 }
 
-// hh_mc_path_stats and hh_mc_path_stats_ex
-static int path_stats_call(hh_ctx* ctx, const char* who, const hh_model* m, const hh_config* c, uint32_t monitor_every,
-                           int32_t include_start, int32_t extremes, double* stats, int32_t stats_on_device,
-                           hh_result* out, const hh_qe* qe = nullptr, double* var_T = nullptr,
-                           const hh_jump* jump = nullptr, const hh_assets* assets = nullptr) {
+// the statistics-only entry points: hh_mc_path_stats and its _ex, _qe, _bates and _assets forms
+static int path_stats_call(hh_ctx* ctx, const PathFamily& f, const hh_model* m, const hh_config* c, uint32_t monitor_every,
+                           int32_t include_start, double* stats, int32_t stats_on_device, hh_result* out) {
   if (!ctx) return HH_ERR_INVALID;
   std::lock_guard<std::recursive_mutex> lock__(ctx->mu);
-  if (!m || !c || !stats) return fail(ctx, HH_ERR_INVALID, "%s: NULL argument", who);
+  if (!m || !c || !stats || f.missing) return fail(ctx, HH_ERR_INVALID, "%s: NULL argument", f.who);
   const WallClock clock;
   HH_HIP(ctx, hipSetDevice(ctx->device));
   HH_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-  int rc = run_path_stats(ctx, who, m, c, monitor_every, include_start, extremes, jump, qe, var_T != nullptr, assets);
+  int rc = run_path_stats(ctx, f, m, c, monitor_every, include_start);
   if (rc) return rc;
   HH_HIP(ctx, hipEventRecord(ctx->ev1, ctx->stream));
-  const hh::PathStatsLayout at(c->n_paths, c->antithetic != 0, path_stat_rows(extremes));
+  const hh::PathStatsLayout at(c->n_paths, c->antithetic != 0, path_stat_rows(f.extremes));
   HH_HIP(ctx, hipMemcpyAsync(stats, ctx->path_stats, at.total * sizeof(double),
                              stats_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, ctx->stream));
-  if (var_T)
-    HH_HIP(ctx, hipMemcpyAsync(var_T, ctx->heston_var, at.n_total * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  if (f.var_T)
+    HH_HIP(ctx, hipMemcpyAsync(f.var_T, ctx->heston_var, at.n_total * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   HH_HIP(ctx, hipStreamSynchronize(ctx->stream));
   if ((rc = release_host_operands(ctx))) return rc;
   if (!out) return HH_OK;
@@ -1447,31 +1485,31 @@ static int path_stats_call(hh_ctx* ctx, const char* who, const hh_model* m, cons
 
 int hh_mc_path_stats(hh_ctx* ctx, const hh_model* m, const hh_config* c, uint32_t monitor_every, int32_t include_start,
                      double* stats, int32_t stats_on_device, hh_result* out) {
-  return path_stats_call(ctx, "hh_mc_path_stats", m, c, monitor_every, include_start, HH_EXTREMES_MONITORED, stats,
-                         stats_on_device, out);
+  return path_stats_call(ctx, {"hh_mc_path_stats", 0, HH_EXTREMES_MONITORED}, m, c, monitor_every, include_start,
+                         stats, stats_on_device, out);
 }
 
 int hh_mc_path_stats_ex(hh_ctx* ctx, const hh_model* m, const hh_config* c, uint32_t monitor_every, int32_t include_start,
                         int32_t extremes, double* stats, int32_t stats_on_device, hh_result* out) {
-  return path_stats_call(ctx, "hh_mc_path_stats_ex", m, c, monitor_every, include_start, extremes, stats, stats_on_device,
-                         out);
+  return path_stats_call(ctx, {"hh_mc_path_stats_ex", 0, extremes}, m, c, monitor_every, include_start, stats,
+                         stats_on_device, out);
 }
 
-// hh_mc_solve_path (kinds up to HH_PAYOFF_DIGITAL_ASSET), hh_mc_solve_path_ex (the lookbacks too) and, with `jump`,
-// hh_mc_solve_path_jump; with `assets`, hh_mc_solve_path_assets: the payoffs on the statistics of the index
-static int solve_path_call(hh_ctx* ctx, const char* who, int32_t last_kind, const hh_model* m, const hh_config* c,
-                           uint32_t monitor_every, int32_t include_start, int32_t extremes, const hh_path_payoff* payoffs,
-                           uint32_t n_payoffs, hh_result* out, double* path_values, double* stats,
-                           const hh_jump* jump = nullptr, const hh_qe* qe = nullptr, double* var_T = nullptr,
-                           const hh_assets* assets = nullptr) {
+// the solve entry points: hh_mc_solve_path (kinds up to HH_PAYOFF_DIGITAL_ASSET) and its _ex, _jump, _qe, _bates and
+// _assets forms (the lookbacks too) — the payoffs on the statistics, under kPathAssets those of the index
+static int solve_path_call(hh_ctx* ctx, const PathFamily& f, const hh_model* m, const hh_config* c, uint32_t monitor_every,
+                           int32_t include_start, const hh_path_payoff* payoffs, uint32_t n_payoffs, hh_result* out,
+                           double* path_values, double* stats) {
   if (!ctx) return HH_ERR_INVALID;
   std::lock_guard<std::recursive_mutex> lock__(ctx->mu);
-  if (!m || !c || !payoffs || !out) return fail(ctx, HH_ERR_INVALID, "%s: NULL argument", who);
+  const char* who = f.who;
+  const hh_assets* assets = f.assets;
+  if (!m || !c || !payoffs || !out || f.missing) return fail(ctx, HH_ERR_INVALID, "%s: NULL argument", who);
   if (n_payoffs == 0 || n_payoffs > HH_MAX_PATH_PAYOFFS)
     return fail(ctx, HH_ERR_INVALID, "%s: 1 .. %d payoffs", who, HH_MAX_PATH_PAYOFFS);
   for (uint32_t k = 0; k < n_payoffs; ++k) {
     const hh_path_payoff& q = payoffs[k];
-    if (q.kind < HH_PAYOFF_VANILLA || q.kind > last_kind)
+    if (q.kind < HH_PAYOFF_VANILLA || q.kind > f.last_kind)
       return fail(ctx, HH_ERR_INVALID, "%s: payoff %u: unknown kind %d", who, k, q.kind);
     if (q.kind == HH_PAYOFF_BARRIER && (q.barrier_type < HH_BARRIER_UP_OUT || q.barrier_type > HH_BARRIER_DOWN_IN))
       return fail(ctx, HH_ERR_INVALID, "%s: payoff %u: unknown barrier type %d", who, k, q.barrier_type);
@@ -1488,16 +1526,16 @@ static int solve_path_call(hh_ctx* ctx, const char* who, int32_t last_kind, cons
   const WallClock clock;
   HH_HIP(ctx, hipSetDevice(ctx->device));
   HH_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-  int rc = run_path_stats(ctx, who, m, c, monitor_every, include_start, extremes, jump, qe, var_T != nullptr, assets);
+  int rc = run_path_stats(ctx, f, m, c, monitor_every, include_start);
   if (rc) return rc;
 
-  const hh::PathStatsLayout at(c->n_paths, c->antithetic != 0, path_stat_rows(extremes));
+  const hh::PathStatsLayout at(c->n_paths, c->antithetic != 0, path_stat_rows(f.extremes));
   hh::PathPayoffArgs b{};
   b.stats = ctx->path_stats;
   b.n_paths = c->n_paths;
   b.n_chunks = hh::basket_chunks(c->n_paths);
   b.antithetic = c->antithetic;
-  b.extremes = extremes;
+  b.extremes = f.extremes;
   b.n_mon = (double)(c->n_steps / monitor_every + (include_start ? 1u : 0u));
   if ((rc = stage_host(ctx, ctx->path_payoffs, (size_t)n_payoffs, payoffs, (size_t)n_payoffs, &b.payoffs))) return rc;
   const size_t n_acc = (size_t)n_payoffs * HH_ACC_LEN;
@@ -1519,8 +1557,8 @@ static int solve_path_call(hh_ctx* ctx, const char* who, int32_t last_kind, cons
                                hipMemcpyDeviceToHost, ctx->stream));
   if (stats)
     HH_HIP(ctx, hipMemcpyAsync(stats, ctx->path_stats, at.total * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  if (var_T)
-    HH_HIP(ctx, hipMemcpyAsync(var_T, ctx->heston_var, at.n_total * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  if (f.var_T)
+    HH_HIP(ctx, hipMemcpyAsync(f.var_T, ctx->heston_var, at.n_total * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   HH_HIP(ctx, hipStreamSynchronize(ctx->stream));
   if ((rc = release_host_operands(ctx))) return rc;
   double kernel_ms, total_ms;
@@ -1532,15 +1570,15 @@ static int solve_path_call(hh_ctx* ctx, const char* who, int32_t last_kind, cons
 int hh_mc_solve_path(hh_ctx* ctx, const hh_model* m, const hh_config* c, uint32_t monitor_every, int32_t include_start,
                      const hh_path_payoff* payoffs, uint32_t n_payoffs, hh_result* out, double* path_values,
                      double* stats) {
-  return solve_path_call(ctx, "hh_mc_solve_path", HH_PAYOFF_DIGITAL_ASSET, m, c, monitor_every, include_start,
-                         HH_EXTREMES_MONITORED, payoffs, n_payoffs, out, path_values, stats);
+  return solve_path_call(ctx, {"hh_mc_solve_path", HH_PAYOFF_DIGITAL_ASSET, HH_EXTREMES_MONITORED}, m, c,
+                         monitor_every, include_start, payoffs, n_payoffs, out, path_values, stats);
 }
 
 int hh_mc_solve_path_ex(hh_ctx* ctx, const hh_model* m, const hh_config* c, uint32_t monitor_every, int32_t include_start,
                         int32_t extremes, const hh_path_payoff* payoffs, uint32_t n_payoffs, hh_result* out,
                         double* path_values, double* stats) {
-  return solve_path_call(ctx, "hh_mc_solve_path_ex", HH_PAYOFF_LOOKBACK_FIXED, m, c, monitor_every, include_start, extremes,
-                         payoffs, n_payoffs, out, path_values, stats);
+  return solve_path_call(ctx, {"hh_mc_solve_path_ex", HH_PAYOFF_LOOKBACK_FIXED, extremes}, m, c, monitor_every,
+                         include_start, payoffs, n_payoffs, out, path_values, stats);
 }
 
 // ---- Merton jump diffusion (hedgehog_mc.h, "Merton (1976) jump diffusion"; kernels: hh_jump.hip, hh_fourier.hip) ----
@@ -1548,11 +1586,8 @@ int hh_mc_solve_path_ex(hh_ctx* ctx, const hh_model* m, const hh_config* c, uint
 int hh_mc_solve_path_jump(hh_ctx* ctx, const hh_model* m, const hh_jump* jump, const hh_config* c, uint32_t monitor_every,
                           int32_t include_start, const hh_path_payoff* payoffs, uint32_t n_payoffs, hh_result* out,
                           double* path_values, double* stats) {
-  if (!ctx) return HH_ERR_INVALID;
-  std::lock_guard<std::recursive_mutex> lock__(ctx->mu);
-  if (!jump) return fail(ctx, HH_ERR_INVALID, "hh_mc_solve_path_jump: NULL argument");
-  return solve_path_call(ctx, "hh_mc_solve_path_jump", HH_PAYOFF_LOOKBACK_FIXED, m, c, monitor_every, include_start,
-                         HH_EXTREMES_MONITORED, payoffs, n_payoffs, out, path_values, stats, jump);
+  return solve_path_call(ctx, {"hh_mc_solve_path_jump", HH_PAYOFF_LOOKBACK_FIXED, jump}, m, c, monitor_every, include_start,
+                         payoffs, n_payoffs, out, path_values, stats);
 }
 
 int hh_mc_solve_jump(hh_ctx* ctx, const hh_model* m, const hh_jump* jump, const hh_config* c, hh_result* out,
@@ -1597,24 +1632,26 @@ int hh_mc_solve_jump(hh_ctx* ctx, const hh_model* m, const hh_jump* jump, const 
   return solve_times(ctx, clock, &out->kernel_ms, &out->total_ms);
 }
 
-int hh_carr_madan_jump(hh_ctx* ctx, const hh_model* m, const hh_jump* jump, double alpha, double bound,
-                       const double* strikes, const double* cps, const double* Ts, const double* r_drifts,
-                       const double* discounts, uint32_t n_payoffs, double* prices_out) {
+// hh_carr_madan_jump and hh_carr_madan_bates: launch_carr_madan_basket's rule with the jump term in the characteristic
+// function.  bad_scalars: the model's and the rule's scalars the entry point refuses.
+using CmJumpLaunch = int (*)(const hh_model&, const hh_jump&, double, double, const double*, uint32_t, double*, hipStream_t);
+static int carr_madan_jump_call(hh_ctx* ctx, const char* who, bool (*bad_scalars)(const hh_model&, double, double),
+                                CmJumpLaunch launch, const hh_model* m, const hh_jump* jump, double alpha, double bound,
+                                const double* strikes, const double* cps, const double* Ts, const double* r_drifts,
+                                const double* discounts, uint32_t n_payoffs, double* prices_out) {
   if (!ctx) return HH_ERR_INVALID;
   std::lock_guard<std::recursive_mutex> lock__(ctx->mu);
-  const char* who = "hh_carr_madan_jump";
   if (!m || !jump || !strikes || !cps || !Ts || !r_drifts || !discounts || !prices_out)
     return fail(ctx, HH_ERR_INVALID, "%s: NULL argument", who);
   if (n_payoffs == 0 || n_payoffs > (1u << 20)) return fail(ctx, HH_ERR_INVALID, "%s: 1 .. 2^20 payoffs per call", who);
-  if (!(m->S0 > 0.0) || !std::isfinite(m->S0) || !std::isfinite(m->sigma) || !(alpha > 0.0) || !(bound > 0.0))
-    return fail(ctx, HH_ERR_INVALID, "%s: bad scalars", who);
+  if (bad_scalars(*m, alpha, bound)) return fail(ctx, HH_ERR_INVALID, "%s: bad scalars", who);
   int rc = check_jump(ctx, who, jump, 0.0);  // no draw here: the mean of one is not limited
   if (rc) return rc;
   if (!hh::carr_madan_subpanels(alpha, bound)) return fail(ctx, HH_ERR_INVALID, HH_CM_BOUND_MSG, who);
   const size_t n = n_payoffs;
   std::vector<double> host(5 * n);  // log K | T | r_drift | discount | (out)
   if ((rc = cm_upload_payoffs(ctx, who, strikes, cps, Ts, r_drifts, discounts, n, n, host))) return rc;
-  HH_HIP(ctx, hh::launch_carr_madan_jump(*m, *jump, alpha, bound, ctx->payoffs, n_payoffs, ctx->payoffs + 4 * n, ctx->stream));
+  HH_HIP(ctx, launch(*m, *jump, alpha, bound, ctx->payoffs, n_payoffs, ctx->payoffs + 4 * n, ctx->stream));
   HH_HIP(ctx, hipMemcpyAsync(host.data() + 4 * n, ctx->payoffs + 4 * n, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   HH_HIP(ctx, hipStreamSynchronize(ctx->stream));
   for (size_t k = 0; k < n; ++k) {  // parity_transform (payoffs.jl:172-193): put = call − S + K·D
@@ -1624,25 +1661,30 @@ int hh_carr_madan_jump(hh_ctx* ctx, const hh_model* m, const hh_jump* jump, doub
   return HH_OK;
 }
 
+int hh_carr_madan_jump(hh_ctx* ctx, const hh_model* m, const hh_jump* jump, double alpha, double bound,
+                       const double* strikes, const double* cps, const double* Ts, const double* r_drifts,
+                       const double* discounts, uint32_t n_payoffs, double* prices_out) {
+  return carr_madan_jump_call(
+      ctx, "hh_carr_madan_jump",
+      [](const hh_model& m, double alpha, double bound) {
+        return !(m.S0 > 0.0) || !std::isfinite(m.S0) || !std::isfinite(m.sigma) || !(alpha > 0.0) || !(bound > 0.0);
+      },
+      hh::launch_carr_madan_jump, m, jump, alpha, bound, strikes, cps, Ts, r_drifts, discounts, n_payoffs, prices_out);
+}
+
 // ---- Heston paths by the quadratic-exponential scheme (hedgehog_mc.h; kernel: hh_qe.hip) ----------------------
 
 int hh_mc_path_stats_qe(hh_ctx* ctx, const hh_model* m, const hh_qe* qe, const hh_config* c, uint32_t monitor_every,
                         int32_t include_start, double* stats, int32_t stats_on_device, double* var_T, hh_result* out) {
-  if (!ctx) return HH_ERR_INVALID;
-  std::lock_guard<std::recursive_mutex> lock__(ctx->mu);
-  if (!qe) return fail(ctx, HH_ERR_INVALID, "hh_mc_path_stats_qe: NULL argument");
-  return path_stats_call(ctx, "hh_mc_path_stats_qe", m, c, monitor_every, include_start, HH_EXTREMES_MONITORED, stats,
-                         stats_on_device, out, qe, var_T);
+  return path_stats_call(ctx, {"hh_mc_path_stats_qe", 0, qe, var_T}, m, c, monitor_every, include_start, stats,
+                         stats_on_device, out);
 }
 
 int hh_mc_solve_path_qe(hh_ctx* ctx, const hh_model* m, const hh_qe* qe, const hh_config* c, uint32_t monitor_every,
                         int32_t include_start, const hh_path_payoff* payoffs, uint32_t n_payoffs, hh_result* out,
                         double* path_values, double* stats, double* var_T) {
-  if (!ctx) return HH_ERR_INVALID;
-  std::lock_guard<std::recursive_mutex> lock__(ctx->mu);
-  if (!qe) return fail(ctx, HH_ERR_INVALID, "hh_mc_solve_path_qe: NULL argument");
-  return solve_path_call(ctx, "hh_mc_solve_path_qe", HH_PAYOFF_LOOKBACK_FIXED, m, c, monitor_every, include_start,
-                         HH_EXTREMES_MONITORED, payoffs, n_payoffs, out, path_values, stats, nullptr, qe, var_T);
+  return solve_path_call(ctx, {"hh_mc_solve_path_qe", HH_PAYOFF_LOOKBACK_FIXED, qe, var_T}, m, c, monitor_every, include_start,
+                         payoffs, n_payoffs, out, path_values, stats);
 }
 
 // ---- several correlated lognormal assets (hedgehog_mc.h; kernel: hh_assets.hip) --------------------------------------
@@ -1650,22 +1692,15 @@ int hh_mc_solve_path_qe(hh_ctx* ctx, const hh_model* m, const hh_qe* qe, const h
 int hh_mc_path_stats_assets(hh_ctx* ctx, const hh_model* m, const hh_assets* assets, const hh_config* c,
                             uint32_t monitor_every, int32_t include_start, double* stats, int32_t stats_on_device,
                             hh_result* out) {
-  if (!ctx) return HH_ERR_INVALID;
-  std::lock_guard<std::recursive_mutex> lock__(ctx->mu);
-  if (!assets) return fail(ctx, HH_ERR_INVALID, "hh_mc_path_stats_assets: NULL argument");
-  return path_stats_call(ctx, "hh_mc_path_stats_assets", m, c, monitor_every, include_start, HH_EXTREMES_MONITORED, stats,
-                         stats_on_device, out, nullptr, nullptr, nullptr, assets);
+  return path_stats_call(ctx, {"hh_mc_path_stats_assets", 0, assets}, m, c, monitor_every, include_start, stats,
+                         stats_on_device, out);
 }
 
 int hh_mc_solve_path_assets(hh_ctx* ctx, const hh_model* m, const hh_assets* assets, const hh_config* c,
                             uint32_t monitor_every, int32_t include_start, const hh_path_payoff* payoffs,
                             uint32_t n_payoffs, hh_result* out, double* path_values, double* stats) {
-  if (!ctx) return HH_ERR_INVALID;
-  std::lock_guard<std::recursive_mutex> lock__(ctx->mu);
-  if (!assets) return fail(ctx, HH_ERR_INVALID, "hh_mc_solve_path_assets: NULL argument");
-  return solve_path_call(ctx, "hh_mc_solve_path_assets", HH_PAYOFF_LOOKBACK_FIXED, m, c, monitor_every, include_start,
-                         HH_EXTREMES_MONITORED, payoffs, n_payoffs, out, path_values, stats, nullptr, nullptr, nullptr,
-                         assets);
+  return solve_path_call(ctx, {"hh_mc_solve_path_assets", HH_PAYOFF_LOOKBACK_FIXED, assets}, m, c, monitor_every, include_start,
+                         payoffs, n_payoffs, out, path_values, stats);
 }
 
 // ---- Bates: the quadratic-exponential step with Merton jumps (hedgehog_mc.h; kernels: hh_bates.hip, hh_fourier.hip) ----
@@ -1673,48 +1708,26 @@ int hh_mc_solve_path_assets(hh_ctx* ctx, const hh_model* m, const hh_assets* ass
 int hh_mc_path_stats_bates(hh_ctx* ctx, const hh_model* m, const hh_qe* qe, const hh_jump* jump, const hh_config* c,
                            uint32_t monitor_every, int32_t include_start, double* stats, int32_t stats_on_device,
                            double* var_T, hh_result* out) {
-  if (!ctx) return HH_ERR_INVALID;
-  std::lock_guard<std::recursive_mutex> lock__(ctx->mu);
-  if (!qe || !jump) return fail(ctx, HH_ERR_INVALID, "hh_mc_path_stats_bates: NULL argument");
-  return path_stats_call(ctx, "hh_mc_path_stats_bates", m, c, monitor_every, include_start, HH_EXTREMES_MONITORED, stats,
-                         stats_on_device, out, qe, var_T, jump);
+  return path_stats_call(ctx, {"hh_mc_path_stats_bates", 0, qe, jump, var_T}, m, c, monitor_every, include_start, stats,
+                         stats_on_device, out);
 }
 
 int hh_mc_solve_path_bates(hh_ctx* ctx, const hh_model* m, const hh_qe* qe, const hh_jump* jump, const hh_config* c,
                            uint32_t monitor_every, int32_t include_start, const hh_path_payoff* payoffs,
                            uint32_t n_payoffs, hh_result* out, double* path_values, double* stats, double* var_T) {
-  if (!ctx) return HH_ERR_INVALID;
-  std::lock_guard<std::recursive_mutex> lock__(ctx->mu);
-  if (!qe || !jump) return fail(ctx, HH_ERR_INVALID, "hh_mc_solve_path_bates: NULL argument");
-  return solve_path_call(ctx, "hh_mc_solve_path_bates", HH_PAYOFF_LOOKBACK_FIXED, m, c, monitor_every, include_start,
-                         HH_EXTREMES_MONITORED, payoffs, n_payoffs, out, path_values, stats, jump, qe, var_T);
+  return solve_path_call(ctx, {"hh_mc_solve_path_bates", HH_PAYOFF_LOOKBACK_FIXED, qe, jump, var_T}, m, c, monitor_every, include_start,
+                         payoffs, n_payoffs, out, path_values, stats);
 }
 
 int hh_carr_madan_bates(hh_ctx* ctx, const hh_model* m, const hh_jump* jump, double alpha, double bound,
                         const double* strikes, const double* cps, const double* Ts, const double* r_drifts,
                         const double* discounts, uint32_t n_payoffs, double* prices_out) {
-  if (!ctx) return HH_ERR_INVALID;
-  std::lock_guard<std::recursive_mutex> lock__(ctx->mu);
-  const char* who = "hh_carr_madan_bates";
-  if (!m || !jump || !strikes || !cps || !Ts || !r_drifts || !discounts || !prices_out)
-    return fail(ctx, HH_ERR_INVALID, "%s: NULL argument", who);
-  if (n_payoffs == 0 || n_payoffs > (1u << 20)) return fail(ctx, HH_ERR_INVALID, "%s: 1 .. 2^20 payoffs per call", who);
-  if (!(m->S0 > 0.0) || !(alpha > 0.0) || !(bound > 0.0) || m->sigma == 0.0)  // hh_carr_madan_basket's, under HH_HESTON
-    return fail(ctx, HH_ERR_INVALID, "%s: bad scalars", who);
-  int rc = check_jump(ctx, who, jump, 0.0);  // no draw here: the mean of one is not limited
-  if (rc) return rc;
-  if (!hh::carr_madan_subpanels(alpha, bound)) return fail(ctx, HH_ERR_INVALID, HH_CM_BOUND_MSG, who);
-  const size_t n = n_payoffs;
-  std::vector<double> host(5 * n);  // log K | T | r_drift | discount | (out)
-  if ((rc = cm_upload_payoffs(ctx, who, strikes, cps, Ts, r_drifts, discounts, n, n, host))) return rc;
-  HH_HIP(ctx, hh::launch_carr_madan_bates(*m, *jump, alpha, bound, ctx->payoffs, n_payoffs, ctx->payoffs + 4 * n, ctx->stream));
-  HH_HIP(ctx, hipMemcpyAsync(host.data() + 4 * n, ctx->payoffs + 4 * n, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  HH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  for (size_t k = 0; k < n; ++k) {  // parity_transform (payoffs.jl:172-193): put = call − S + K·D
-    const double call = host[4 * n + k];
-    prices_out[k] = cps[k] > 0.0 ? call : call - m->S0 + strikes[k] * discounts[k];
-  }
-  return HH_OK;
+  return carr_madan_jump_call(
+      ctx, "hh_carr_madan_bates",
+      [](const hh_model& m, double alpha, double bound) {  // hh_carr_madan_basket's, under HH_HESTON
+        return !(m.S0 > 0.0) || !(alpha > 0.0) || !(bound > 0.0) || m.sigma == 0.0;
+      },
+      hh::launch_carr_madan_bates, m, jump, alpha, bound, strikes, cps, Ts, r_drifts, discounts, n_payoffs, prices_out);
 }
 
 // ---- LSM on an ensemble sharded over several devices ------------------------------------------------

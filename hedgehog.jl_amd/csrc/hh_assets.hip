@@ -51,6 +51,10 @@ __device__ __forceinline__ void step_assets(const AssetArgs& c, double (&x)[D], 
   }
 }
 
+// The dates, the first-term flag and the pair of Running objects are written out here as Monitor (hh_path_stats.h) writes
+// them for the other four kernels of the family: on the monitor (the index from a callable, on a date only) 38 of the 64
+// instantiations compiled to a prologue a few moves different from this text's, and timed against this text six of
+// them missed the bar of the comparison (the appendix of profiles/path_family_refactor.txt).
 template <int D, int KIND, bool ANTI>
 __global__ __launch_bounds__(256) void assets_stats_kernel(const AssetArgs c, const uint64_t* __restrict__ seeds,
                                                            const uint64_t n_paths, const uint32_t n_steps,
@@ -135,8 +139,8 @@ int launch_assets_stats(const hh_model& m, const hh_config& c, const hh_assets& 
   const AssetsKernel kernel = pick_kernel(assets.n_assets, assets.index_kind, c.antithetic != 0);
   if (!kernel || !cholesky(assets.corr, assets.n_assets, L)) return (int)hipErrorInvalidValue;  // the entry points check both
   const AssetArgs a = asset_args(assets, m.r_drift, m.T, c.n_steps, L);
-  const dim3 g((unsigned)((c.n_paths + 255) / 256)), blk(256);
-  hipLaunchKernelGGL(kernel, g, blk, 0, s, a, seeds_dev, (uint64_t)c.n_paths, (uint32_t)c.n_steps, monitor_every,
+  const StatsLaunch l(c);
+  hipLaunchKernelGGL(kernel, l.grid, l.block, 0, s, a, seeds_dev, (uint64_t)c.n_paths, (uint32_t)c.n_steps, monitor_every,
                      (int)include_start, stats);
   return (int)hipGetLastError();
 }

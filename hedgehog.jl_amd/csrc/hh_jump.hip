@@ -4,14 +4,14 @@
 //
 //   merton_exact_kernel  the terminal law: one normal for the diffusion, one jump count by inversion (hh_jump.h), one
 //                        normal for the whole jump sum; payoff and sums as exact_gbm_kernel's (finish_path);
-//   jump_stats_kernel    path_stats_kernel's lognormal form — the same increments, step, dates and Running arithmetic
-//                        (hh_path_stats.h) — with a jump count per step and, on the rare lane that has one, a jump.
-//                        Its output goes through path_payoff_kernel untouched.
+//   jump_stats_kernel    path_stats_kernel's lognormal form — the same increments and step around the shared monitor
+//                        (hh_path_stats.h) — with a jump count per step and, on the rare lane that has one, a jump
+//                        (hh_jump.h: jump_step, JumpUniforms).  Its output goes through path_payoff_kernel untouched.
 //
 // The jump parameters travel in JumpArgs beside SimArgs<0>, whose layout stays as it is.  Every loop is bounded by
 // n_steps, the per-lane trajectory count or HH_JUMP_MAX_COUNT; none by data.  The search of the inversion and the
 // N > 0 branch diverge: at λ·dt ≪ 1 nearly every lane leaves the search at n = 0 and the jump's Philox block is drawn
-// by the rare lane only — a branch, not a select over a block every lane would pay for.
+// by the rare lane only.
 #include <cmath>
 
 #include "hh_jump.h"
@@ -59,10 +59,9 @@ __global__ __launch_bounds__(kTile) void merton_exact_kernel(const SimArgs<0> a,
 // path form: the five monitored statistics under jumps
 // ------------------------------------------------------------------------------------------
 // path_stats_kernel<GbmModel<0>, ANTI, false> with two additions per step k: the jump count N_k from the uniform of
-// block (k >> 1, 0, 0, kDomJump) — words 0, 1 for an even step, 2, 3 for an odd one — and, only where N_k > 0, the jump
-// from the first normal of block (k, 1, 0, kDomJump), added to the state after the step and before the date.  The
-// mirror takes -dW, the same N_k and -z.  a.gdrift carries the compensator; with mean = 0 no lane ever jumps and every
-// operation left is path_stats_kernel's.
+// block (k >> 1, 0, 0, kDomJump) — words 0, 1 for an even step, 2, 3 for an odd one (JumpUniforms) — and jump_step,
+// after the step and before the date.  The mirror takes -dW, the same N_k and -z.  a.gdrift carries the compensator;
+// with mean = 0 no lane ever jumps and every operation left is path_stats_kernel's.
 template <bool ANTI>
 __global__ __launch_bounds__(256) void jump_stats_kernel(const SimArgs<0> a, const JumpArgs j, const double S0,
                                                          const uint32_t monitor_every, const int include_start,
@@ -76,50 +75,25 @@ __global__ __launch_bounds__(256) void jump_stats_kernel(const SimArgs<0> a, con
   State st, sa;
   M::init(st, a);
   if constexpr (ANTI) M::init(sa, a);
-  Running r, ra;
-  bool started = include_start != 0;
-  if (started) {
-    r.first(S0, a.x0.v);
-    if constexpr (ANTI) ra.first(S0, a.x0.v);
-  }
-  uint32_t left = monitor_every;
-  auto date = [&]() {  // a step has been taken
-    if (--left != 0u) return;
-    left = monitor_every;
-    const double S = exp(st.x.v);
-    if (started) r.next(S, st.x.v);
-    else r.first(S, st.x.v);
-    if constexpr (ANTI) {
-      const double Sa = exp(sa.x.v);
-      if (started) ra.next(Sa, sa.x.v);
-      else ra.first(Sa, sa.x.v);
-    }
-    started = true;
-  };
+  Monitor<ANTI> mon(monitor_every, include_start);
+  mon.start(S0, a.x0.v);
   const uint64_t key = a.seeds[i];
   const uint32_t k0 = (uint32_t)key, k1 = (uint32_t)(key >> 32);
   auto advance = [&](uint32_t k, double dW, double u) {
     M::step(st, a, dW, 0.0);
     if constexpr (ANTI) M::step(sa, a, -dW, 0.0);
-    const uint32_t N = poisson_inverse(u, j.mean, j.p0);
-    if (N > 0u) {
-      double z, unused;
-      normal_pair(key, k, 1u, 0u, kDomJump, z, unused);
-      st.x.v = st.x.v + jump_sum(j, N, z);
-      if constexpr (ANTI) sa.x.v = sa.x.v + jump_sum(j, N, -z);
-    }
-    date();
+    jump_step<ANTI>(j, key, k, u, st.x.v, sa.x.v);
+    mon.date(st.x.v, sa.x.v);
   };
   // scalar noise: one Philox block feeds two consecutive steps, and so does one block of jump uniforms
+  JumpUniforms ju;
   for (uint32_t s = 0; s < n_steps; s += 2) {
     double z1, z2;
     euler_scalar_normals(key, s >> 1, z1, z2);
-    const Philox4 b = philox4x32_10(s >> 1, 0u, 0u, kDomJump, k0, k1);
-    advance(s, a.sqrt_dt * z1, u01_fast(b.c0, b.c1));
-    if (s + 1 < n_steps) advance(s + 1, a.sqrt_dt * z2, u01_fast(b.c2, b.c3));
+    advance(s, a.sqrt_dt * z1, ju.even(s >> 1, k0, k1));
+    if (s + 1 < n_steps) advance(s + 1, a.sqrt_dt * z2, ju.odd());
   }
-  r.store(stats, at, i);
-  if constexpr (ANTI) ra.store(stats, at, a.n_paths + i);
+  mon.store(stats, at, i, a.n_paths);
 }
 
 }  // namespace
@@ -138,14 +112,11 @@ int launch_merton_exact(const hh_model& m, const hh_config& c, const hh_jump& ju
 
 int launch_jump_stats(const hh_model& m, const hh_config& c, const hh_jump& jump, const uint64_t* seeds_dev,
                       uint32_t monitor_every, bool include_start, double* stats, hipStream_t s) {
-  DevicePtrs p{};
-  p.seeds = seeds_dev;
-  SimArgs<0> a = make_args0(m, c, p);
-  a.gdrift.v = a.gdrift.v - merton_compensator(jump);  // (r − σ²/2) − λκ̄, in that order: λ = 0 leaves the lognormal drift
-  const JumpArgs j = jump_args(jump, a.dt);
-  const dim3 g((unsigned)((c.n_paths + 255) / 256)), blk(256);
+  StatsLaunch l(m, c, seeds_dev);
+  l.a.gdrift.v = l.a.gdrift.v - merton_compensator(jump);  // (r − σ²/2) − λκ̄, in that order: λ = 0 leaves the lognormal drift
+  const JumpArgs j = jump_args(jump, l.a.dt);
   auto kernel = c.antithetic ? jump_stats_kernel<true> : jump_stats_kernel<false>;
-  hipLaunchKernelGGL(kernel, g, blk, 0, s, a, j, m.S0, monitor_every, (int)include_start, stats);
+  hipLaunchKernelGGL(kernel, l.grid, l.block, 0, s, l.a, j, m.S0, monitor_every, (int)include_start, stats);
   return (int)hipGetLastError();
 }
 

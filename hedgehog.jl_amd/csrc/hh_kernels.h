@@ -267,6 +267,18 @@ int launch_gbm_grid(const uint64_t* seeds_dev, uint64_t n_paths, uint32_t n_step
 // state into var_grid when it is not NULL (lognormal: ignored).
 int launch_euler_grid(const hh_model& m, const hh_config& c, const uint64_t* seeds_dev, bool log_state,
                       double* grid, double* var_grid, hipStream_t s);
+// What every launch_*_stats starts from: one lane per trajectory in workgroups of 256 and, given the model, the argument
+// block that carries the seeds and no other pointer (launch_assets_stats passes its own block).
+struct StatsLaunch {
+  SimArgs<0> a{};
+  dim3 grid, block;
+  explicit StatsLaunch(const hh_config& c) : grid((unsigned)((c.n_paths + 255) / 256)), block(256) {}
+  StatsLaunch(const hh_model& m, const hh_config& c, const uint64_t* seeds_dev) : StatsLaunch(c) {
+    DevicePtrs p{};
+    p.seeds = seeds_dev;
+    a = make_args0(m, c, p);
+  }
+};
 // Path-dependent payoffs (hh_path.hip).  The same trajectories as launch_euler_grid's (c: dynamics, em_split,
 // antithetic, n_paths, n_steps), reduced per trajectory to the HH_PATH_STATS numbers of PathStatsLayout over the
 // monitoring dates monitor_every, 2·monitor_every, …, n_steps (a divisor of n_steps) and, include_start, step 0.

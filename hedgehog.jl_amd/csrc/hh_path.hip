@@ -11,7 +11,7 @@
 //
 // The 40 bytes per trajectory that go through memory between the two are about 1 % of the simulation's time at
 // 252 steps; in exchange one simulation serves every payoff of a call and the caller can have the statistics.
-#include "hh_path_stats.h"  // Running: the five statistics, shared with the jump form (hh_jump.hip)
+#include "hh_path_stats.h"  // Monitor: the five statistics and their dates, shared by the family
 #include "hh_sim.h"
 
 namespace hh {
@@ -42,8 +42,7 @@ struct Extremes {
 // One trajectory per lane (and its mirror, -dW, in the same lane: column n_paths + i), GENERATE noise, after
 // euler_grid_kernel.  The monitoring dates are the steps monitor_every, 2·monitor_every, …, n_steps — monitor_every
 // divides n_steps, so the last step is one, and S = exp(x) is formed there only, as euler_grid_kernel's `put` forms
-// it — and step 0 (S0, log S0: the grid's row 0) when include_start.  The countdown to the next date and the
-// "a first term is in" flag depend on kernel arguments alone: uniform branches.  No LDS.
+// it — and step 0 (S0, log S0: the grid's row 0) when include_start: Monitor (hh_path_stats.h).  No LDS.
 // BRIDGE: rows HH_STAT_CMAX_S, HH_STAT_CMIN_S as well (Extremes), over ALL steps whatever monitor_every; one more Philox
 // block and two logarithms per step (euler_bridge_draws), shared with the mirror: -dW has the negated bridge, the
 // excess of its maximum is the excess of the original's minimum, so the mirror's maximum takes L2 and its minimum L1.
@@ -61,31 +60,13 @@ __global__ __launch_bounds__(256) void path_stats_kernel(const SimArgs<0> a, con
   State st, sa;
   M::init(st, a);
   if constexpr (ANTI) M::init(sa, a);
-  Running r, ra;
-  bool started = include_start != 0;
-  if (started) {
-    r.first(S0, a.x0.v);
-    if constexpr (ANTI) ra.first(S0, a.x0.v);
-  }
+  Monitor<ANTI> mon(monitor_every, include_start);
+  mon.start(S0, a.x0.v);
   Extremes e, ea;
   if constexpr (BRIDGE) {
     e.first(a.x0.v);
     if constexpr (ANTI) ea.first(a.x0.v);
   }
-  uint32_t left = monitor_every;
-  auto date = [&]() {  // a step has been taken
-    if (--left != 0u) return;
-    left = monitor_every;
-    const double S = exp(st.x.v);
-    if (started) r.next(S, st.x.v);
-    else r.first(S, st.x.v);
-    if constexpr (ANTI) {
-      const double Sa = exp(sa.x.v);
-      if (started) ra.next(Sa, sa.x.v);
-      else ra.first(Sa, sa.x.v);
-    }
-    started = true;
-  };
   const uint64_t key = a.seeds[i];  // montecarlo.jl:331
   // step k: the trajectory and its mirror (montecarlo.jl:258: -W), the extremes of bridge k, the date
   auto advance = [&](uint32_t k, double d1, double d2) {
@@ -103,7 +84,7 @@ __global__ __launch_bounds__(256) void path_stats_kernel(const SimArgs<0> a, con
       M::step(st, a, d1, d2);
       if constexpr (ANTI) M::step(sa, a, -d1, -d2);
     }
-    date();
+    mon.date(st.x.v, sa.x.v);
   };
   if constexpr (NC == 2) {
     for (uint32_t s = 0; s < n_steps; ++s) {
@@ -120,8 +101,7 @@ __global__ __launch_bounds__(256) void path_stats_kernel(const SimArgs<0> a, con
       if (s + 1 < n_steps) advance(s + 1, a.sqrt_dt * z2, 0.0);
     }
   }
-  r.store(stats, at, i);
-  if constexpr (ANTI) ra.store(stats, at, a.n_paths + i);
+  mon.store(stats, at, i, a.n_paths);
   if constexpr (BRIDGE) {
     e.store(stats, at, i);
     if constexpr (ANTI) ea.store(stats, at, a.n_paths + i);
@@ -225,13 +205,10 @@ __global__ __launch_bounds__(256) void path_payoff_kernel(const PathPayoffArgs b
 
 int launch_path_stats(const hh_model& m, const hh_config& c, const uint64_t* seeds_dev, uint32_t monitor_every,
                       bool include_start, bool bridge, double* stats, hipStream_t s) {
-  DevicePtrs p{};
-  p.seeds = seeds_dev;
-  const SimArgs<0> a = make_args0(m, c, p);
-  const dim3 g((unsigned)((c.n_paths + 255) / 256)), blk(256);
+  const StatsLaunch l(m, c, seeds_dev);
   auto go = [&](auto model, auto anti, auto br) {
-    hipLaunchKernelGGL((path_stats_kernel<decltype(model), decltype(anti)::value, decltype(br)::value>), g, blk, 0, s, a,
-                       m.S0, monitor_every, (int)include_start, stats);
+    hipLaunchKernelGGL((path_stats_kernel<decltype(model), decltype(anti)::value, decltype(br)::value>), l.grid, l.block, 0,
+                       s, l.a, m.S0, monitor_every, (int)include_start, stats);
   };
   auto with_form = [&](auto model, auto anti) {
     if (bridge) go(model, anti, std::true_type{});

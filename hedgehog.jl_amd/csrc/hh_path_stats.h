@@ -1,5 +1,8 @@
-// The running statistics of one trajectory (enum hh_path_stat), shared by the kernels that keep them: path_stats_kernel
-// (hh_path.hip) and its jump form (hh_jump.hip).  Internal.
+// The monitored statistics of a trajectory and its mirror (enum hh_path_stat), stated once for the kernels that keep
+// them on log spots: path_stats_kernel (hh_path.hip), jump_stats_kernel (hh_jump.hip), qe_stats_kernel (hh_qe.hip) and
+// bates_stats_kernel (hh_bates.hip).  Running is the arithmetic of the five rows, Monitor the dates they are taken on; a
+// kernel supplies its states, its step and the call after it.  assets_stats_kernel (hh_assets.hip) uses Running and
+// writes the dates out itself (its head comment says why).  Internal.
 #pragma once
 #include "hh_sim.h"
 
@@ -45,6 +48,51 @@ struct Running {
     stats[at.row(HH_STAT_MAX_S) + col] = max_s;
     stats[at.row(HH_STAT_MIN_S) + col] = min_s;
     stats[at.row(HH_STAT_S_T) + col] = s_t;
+  }
+};
+
+// The monitoring dates of one lane: its trajectory and (ANTI) the mirror in the same lane, column n_paths + i.  The dates
+// are the steps monitor_every, 2·monitor_every, …, n_steps — monitor_every divides n_steps, so the last step is one —
+// and step 0 when include_start.  The countdown to the next date and the "a first term is in" flag depend on kernel
+// arguments alone: uniform branches.
+template <bool ANTI>
+struct Monitor {
+  // (the members in the reverse of the order the kernels once declared them as locals: promoted to registers in this
+  // order, eleven of the thirteen path_stats_kernel forms and every jump, QE and Bates kernel compile to the code they
+  // compiled to with those locals)
+  const uint32_t every;
+  uint32_t left;
+  bool started;
+  Running ra, r;
+  __device__ __forceinline__ Monitor(uint32_t monitor_every, int include_start)
+      : every(monitor_every), left(monitor_every), started(include_start != 0) {}
+  // step 0, taken when include_start alone: (S0, log S0), from which the mirror starts as well
+  __device__ __forceinline__ void start(double S0, double x0) {
+    if (!started) return;
+    r.first(S0, x0);
+    if constexpr (ANTI) ra.first(S0, x0);
+  }
+  // A step has been taken: x and (ANTI: read then alone) xa are the log spots after it.  S = exp(x) is formed on a date
+  // only, as euler_grid_kernel's `put` forms it, and the trajectory's pair goes into its sums before the mirror's is formed.
+  __device__ __forceinline__ void date(const double& x, const double& xa) {
+    if (--left != 0u) return;
+    left = every;
+    const double S = exp(x);
+    if (started) r.next(S, x);
+    else r.first(S, x);
+    if constexpr (ANTI) {
+      const double Sa = exp(xa);
+      if (started) ra.next(Sa, xa);
+      else ra.first(Sa, xa);
+    }
+    started = true;
+  }
+  // The rows of the trajectory, then of the mirror.  (A kernel that stores more per member — var_T — stores r and ra
+  // itself, each member's rows before its extra number: qe_stats_kernel.)
+  __device__ __forceinline__ void store(double* __restrict__ stats, const PathStatsLayout& at, uint64_t i,
+                                        uint64_t n_paths) const {
+    r.store(stats, at, i);
+    if constexpr (ANTI) ra.store(stats, at, n_paths + i);
   }
 };
 

@@ -1,7 +1,8 @@
 // One step of Andersen's quadratic-exponential scheme for the Heston variance and log spot (include/hedgehog_mc.h,
 // "Heston paths by the quadratic-exponential scheme" — every operation is stated there in this order), as functions the
-// device kernel (hh_qe.hip) and a host program share: it includes nothing of HIP, so that tests/c/qe_host_check.cpp can
-// hold them to long-double evaluations and run them under the host sanitizers.  Every operation is one rounded fp64
+// device kernels (hh_qe.hip, hh_bates.hip) and a host program share: a host compiler sees nothing of HIP in it, so that
+// tests/c/qe_host_check.cpp can hold them to long-double evaluations and run them under the host sanitizers; for hipcc
+// alone, the step of a trajectory and its mirror on their own draws (qe_pair_step).  Every operation is one rounded fp64
 // operation (the library is built with -ffp-contract=off); sqrt, log and the divisions are the correctly rounded or
 // 1-ulp ones of the language.  Internal; the public surface is include/hedgehog_mc.h.
 #pragma once
@@ -11,6 +12,7 @@
 #include "../../include/hedgehog_mc.h"
 
 #if defined(__HIPCC__)
+#include "hh_rng.h"
 #define HH_QE_HD __host__ __device__
 #else
 #define HH_QE_HD
@@ -111,5 +113,53 @@ HH_QE_HD inline double qe_log_spot(const QeArgs& q, double x, double v, double v
   const double drift = ((q.rdt + k0) + q.K1 * v) + q.K2 * vn;
   return (x + drift) + sqrt(q.K3 * v + q.K4 * vn) * zx;
 }
+
+// (x, v) -> (x′, v′) of one member: its own moments mo, its own normals and — exponential branch only — its own U
+struct QeState {
+  double x, v;
+};
+template <bool MART>
+HH_QE_HD inline __attribute__((always_inline)) void qe_member_step(QeState& s, const QeArgs& q, const QeMoments& mo,
+                                                                   bool quad, double zv, double zx, double U) {
+  double vn, k0 = q.K0;
+  if (quad) {
+    const QeQuad b = qe_quad(mo);
+    vn = qe_quad_next(b, zv);
+    if constexpr (MART) k0 = qe_k0_star(q, qe_quad_lnM(b, q.A), s.v);
+  } else {
+    const QeExp e = qe_exp(mo);
+    vn = qe_exp_next(e, U);
+    if constexpr (MART) k0 = qe_k0_star(q, qe_exp_lnM(e, q.A), s.v);
+  }
+  s.x = qe_log_spot(q, s.x, s.v, vn, k0, zx);
+  s.v = vn;
+}
+
+#if defined(__HIPCC__)
+// Step k of a trajectory and (ANTI) its mirror on the draws of domain kDomQe under the trajectory's key (hh_qe.hip,
+// hh_bates.hip): the normals of block (k, 0, 0, kDomQe); the mirror takes −Z_v, −Z_x and 1 − U.  The two branches
+// diverge within a wave, and block (k, 1, 0, kDomQe) is drawn only by a lane one of whose members is in the exponential
+// branch at step k — a branch, not a select over a block every lane would pay for.
+template <bool ANTI, bool MART>
+__device__ __forceinline__ void qe_pair_step(QeState& st, QeState& sa, const QeArgs& q, uint64_t key, uint32_t k) {
+  double zv, zx;
+  normal_pair(key, k, 0u, 0u, kDomQe, zv, zx);
+  const QeMoments mo = qe_moments(q, st.v);
+  const bool quad = mo.psi <= q.psi_c;
+  QeMoments moa = mo;
+  bool quada = true;
+  if constexpr (ANTI) {
+    moa = qe_moments(q, sa.v);
+    quada = moa.psi <= q.psi_c;
+  }
+  double U = 0.5;  // read by a member in the exponential branch only
+  if (!quad || !quada) {
+    const Philox4 b = philox4x32_10(k, 1u, 0u, kDomQe, (uint32_t)key, (uint32_t)(key >> 32));
+    U = u01_fast(b.c0, b.c1);
+  }
+  qe_member_step<MART>(st, q, mo, quad, zv, zx, U);
+  if constexpr (ANTI) qe_member_step<MART>(sa, q, moa, quada, -zv, -zx, 1.0 - U);  // 1 − U is exact
+}
+#endif
 
 }  // namespace hh
