@@ -20,6 +20,7 @@ test-cpu-asan:
 	  python -m pytest tests/test_oracle_pins.py tests/test_properties.py tests/test_math_host.py tests/test_bessel_host.py \
 	  tests/test_rng_host.py tests/test_scratch_layout_host.py -q -m "not gpu" -p no:cacheprovider
 	python -m pytest tests/test_bates_host.py -q -p no:cacheprovider -k step_host_program
+	python -m pytest tests/test_localvol_host.py -q -p no:cacheprovider -k host_program
 
 test-gpu: build
 	python -m pytest tests -q -m gpu

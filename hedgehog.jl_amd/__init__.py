@@ -26,6 +26,8 @@ from .montecarlo import (AbstractPricingMethod, Antithetic, BatesDynamics, Black
                          solve_montecarlo, solve_montecarlo_many, solve_path_payoffs)
 from .multiasset import (BestOf, GeometricMean, IndexOption, MultiAssetDynamics, MultiAssetInputs, WeightedSum, WorstOf,
                          solve_index_options)
+from .localvol import (LocalVolDynamics, LocalVolInputs, LocalVolSurface, dupire_from, dupire_local_vol, get_local_vol,
+                       refuse_other_methods, solve_localvol_payoffs)
 from .distributed import rank_device, shard_range, solve_lsm_sharded, solve_sharded
 from .domain import (American, ArithmeticAverage, AsianOption, AssetOrNothing, BarrierOption, BatesInputs, BlackScholesInputs,
                     Call, CashOrNothing, ContinuousMonitoring, DigitalOption, DownAndIn, DownAndOut, European,
@@ -57,6 +59,9 @@ def solve(*args, **kw):
         solve(prob::PricingProblem{IndexOption, MultiAssetInputs} | ::BasketPricingProblem of IndexOptions,
               ::MonteCarlo(MultiAssetDynamics(), EulerMaruyama(), …) | ::MultiAssetAnalytic)
                                   several correlated assets: baskets, spreads, best-of / worst-of (no reference method)
+        solve(prob::PricingProblem{…, LocalVolInputs} | ::BasketPricingProblem,
+              ::MonteCarlo(LocalVolDynamics(), EulerMaruyama(), …))
+                                  local volatility on a tabulated surface, Dupire's formula beside it (no reference method)
         solve(prob::PricingProblem{<:VanillaOption{…,American,…}}, ::LSM)     least_squares_montecarlo.jl:99
         solve(prob::PricingProblem{<:VanillaOption}, ::CoxRossRubinsteinMethod) cox_ross_rubinstein.jl:99
         solve(prob::BasketPricingProblem, ::CoxRossRubinsteinMethod)         basket.jl:35
@@ -75,6 +80,8 @@ def solve(*args, **kw):
     if len(args) == 2 and isinstance(args[0], (PricingProblem, BasketPricingProblem)) and \
             not isinstance(args[1], (MonteCarlo, CarrMadan)) and is_bates(args[0].market_inputs, args[1]):
         raise MethodError(f"{type(args[1]).__name__} does not price the Bates model: use {BATES_ROUTES}")
+    if len(args) == 2 and isinstance(args[0], (PricingProblem, BasketPricingProblem)):
+        refuse_other_methods(args[0].market_inputs, args[1])  # local volatility: its one route, or a MethodError naming it
     if len(args) == 2 and isinstance(args[0], PricingProblem) and isinstance(args[1], MonteCarlo):
         return solve_montecarlo(args[0], args[1], **kw)
     if len(args) == 2 and isinstance(args[0], PricingProblem) and isinstance(args[1], CarrMadan):

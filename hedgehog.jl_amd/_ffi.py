@@ -34,6 +34,7 @@ HH_JUMP_MAX_MEAN = 64.0
 HH_JUMP_MAX_COUNT = 255
 HH_QE_MAX_PSI = 1e9
 HH_MAX_ASSETS = 8
+HH_LV_MAX_NODES = 8192
 HH_INDEX_WEIGHTED_SUM, HH_INDEX_GEOMETRIC, HH_INDEX_BEST_OF, HH_INDEX_WORST_OF = 0, 1, 2, 3
 
 HH_OK, HH_ERR_INVALID, HH_ERR_UNSUPPORTED, HH_ERR_HIP, HH_ERR_NOMEM, HH_ERR_RCCL, HH_ERR_DEVICE_TIMEOUT = 0, -1, -2, -3, -4, -5, -6
@@ -110,6 +111,12 @@ class hh_assets(C.Structure):
     _fields_ = [("n_assets", C.c_uint32), ("index_kind", C.c_int32),
                 ("spots", C.c_double * HH_MAX_ASSETS), ("sigmas", C.c_double * HH_MAX_ASSETS),
                 ("weights", C.c_double * HH_MAX_ASSETS), ("corr", C.c_double * (HH_MAX_ASSETS * HH_MAX_ASSETS))]
+
+
+class hh_localvol(C.Structure):
+    """A local-volatility surface: σ at (times[j], x_lo + i·h), row-major [n_times][n_x], in host memory."""
+    _fields_ = [("times", _dp), ("vols", _dp), ("x_lo", C.c_double), ("h", C.c_double),
+                ("n_times", C.c_uint32), ("n_x", C.c_uint32)]
 
 
 HH_BK_ROOT_SECANT, HH_BK_ROOT_ORDER2 = 0, 1
@@ -202,6 +209,11 @@ SYMBOLS = [
                                           C.c_int32, _vp, C.c_int32, C.POINTER(hh_result)]),
     ("hh_mc_solve_path_assets", C.c_int, [_vp, C.POINTER(hh_model), C.POINTER(hh_assets), C.POINTER(hh_config), C.c_uint32,
                                           C.c_int32, C.POINTER(hh_path_payoff), C.c_uint32, C.POINTER(hh_result), _vp, _vp]),
+    ("hh_mc_path_stats_lv", C.c_int, [_vp, C.POINTER(hh_model), C.POINTER(hh_localvol), C.POINTER(hh_config), C.c_uint32,
+                                      C.c_int32, C.c_int32, _vp, C.c_int32, C.POINTER(hh_result)]),
+    ("hh_mc_solve_path_lv", C.c_int, [_vp, C.POINTER(hh_model), C.POINTER(hh_localvol), C.POINTER(hh_config), C.c_uint32,
+                                      C.c_int32, C.c_int32, C.POINTER(hh_path_payoff), C.c_uint32, C.POINTER(hh_result),
+                                      _vp, _vp]),
     ("hh_lsm_shard_xchg_elems", C.c_size_t, [C.c_uint32, C.c_int32]),
     ("hh_lsm_shard_begin", C.c_int, [_vp, C.POINTER(hh_model), C.POINTER(hh_config), C.c_int32, C.c_double, _vp]),
     ("hh_lsm_shard_phase", C.c_int, [_vp, C.c_int32, C.c_uint32, _vp, _vp]),
@@ -584,6 +596,21 @@ def make_assets(spots, sigmas, weights, corr, index_kind=HH_INDEX_WEIGHTED_SUM):
         for j in range(d):
             a.corr[i * HH_MAX_ASSETS + j] = float(corr[i][j])
     return a
+
+
+def make_localvol(times, vols, x_lo, h):
+    """hh_localvol from arrays (kept alive on the returned struct): times [n_times], vols [n_times][n_x]"""
+    import numpy as np
+    times = np.ascontiguousarray(times, dtype=np.float64).reshape(-1)
+    vols = np.ascontiguousarray(vols, dtype=np.float64)
+    if vols.ndim != 2 or vols.shape[0] != times.size:
+        raise ValueError("vols must be [n_times][n_x]")
+    lv = hh_localvol()
+    lv.times = times.ctypes.data_as(_dp)
+    lv.vols = vols.ctypes.data_as(_dp)
+    lv.x_lo, lv.h, lv.n_times, lv.n_x = float(x_lo), float(h), times.size, vols.shape[1]
+    lv._keep = [times, vols]
+    return lv
 
 
 def make_qe(psi_c=0.0, martingale=False):

@@ -75,6 +75,9 @@ def solve_basket(prob: BasketPricingProblem, method, ensemble: bool = False):
     from .multiasset import is_multiasset, solve_index_options
     if is_multiasset(prob.payoffs, prob.market_inputs, method):  # IndexOptions: one statistics pass per distinct index
         return BasketPricingSolution(prob, solve_index_options(prob.payoffs, prob.market_inputs, method, ensemble))
+    from .localvol import is_localvol, solve_localvol_basket
+    if is_localvol(prob.market_inputs, method):  # one hh_mc_solve_path_lv call per (expiry, monitoring)
+        return BasketPricingSolution(prob, solve_localvol_basket(prob.payoffs, prob.market_inputs, method, ensemble))
     if isinstance(method, CoxRossRubinsteinMethod):
         prices = solve_crr_basket(prob.payoffs, prob.market_inputs, method)
         return BasketPricingSolution(prob, [CRRSolution(PricingProblem(p, prob.market_inputs), method, float(x))

@@ -10,6 +10,7 @@
 
 #include "hh_assets.h"
 #include "hh_kernels.h"
+#include "hh_localvol.h"
 #include "hh_qe.h"
 
 #include "hh_ctx.h"
@@ -1351,15 +1352,68 @@ static int check_qe(hh_ctx* ctx, const char* who, const hh_model* m, const hh_co
   return HH_OK;
 }
 
+// The surface of a local-volatility entry point (`who`): everything that does not depend on the model or the configuration.
+static int check_localvol(hh_ctx* ctx, const char* who, const hh_localvol* lv) {
+  if (!lv->times || !lv->vols) return fail(ctx, HH_ERR_INVALID, "%s: NULL argument (the surface's times or vols)", who);
+  if (lv->n_times < 1u || lv->n_x < 2u)
+    return fail(ctx, HH_ERR_INVALID, "%s: the surface needs n_times >= 1 and n_x >= 2 (%u, %u)", who, lv->n_times, lv->n_x);
+  if ((uint64_t)lv->n_times * lv->n_x > (uint64_t)HH_LV_MAX_NODES)
+    return fail(ctx, HH_ERR_INVALID, "%s: n_times * n_x = %llu is above HH_LV_MAX_NODES = %d", who,
+                (unsigned long long)lv->n_times * lv->n_x, HH_LV_MAX_NODES);
+  if (!std::isfinite(lv->x_lo)) return fail(ctx, HH_ERR_INVALID, "%s: x_lo must be finite", who);
+  if (!(lv->h > 0.0) || !std::isfinite(lv->h) || !std::isfinite(1.0 / lv->h))
+    return fail(ctx, HH_ERR_INVALID, "%s: h must be finite and > 0", who);
+  for (uint32_t j = 0; j < lv->n_times; ++j) {
+    if (!(lv->times[j] >= 0.0) || !std::isfinite(lv->times[j]))
+      return fail(ctx, HH_ERR_INVALID, "%s: times[%u] must be finite and >= 0", who, j);
+    if (j && !(lv->times[j] > lv->times[j - 1]))
+      return fail(ctx, HH_ERR_INVALID, "%s: times must be strictly increasing (times[%u])", who, j);
+  }
+  const size_t n_nodes = (size_t)lv->n_times * lv->n_x;
+  for (size_t q = 0; q < n_nodes; ++q)
+    if (!(lv->vols[q] > 0.0) || !std::isfinite(lv->vols[q]))
+      return fail(ctx, HH_ERR_INVALID, "%s: vols[%u][%u] must be finite and > 0", who, (unsigned)(q / lv->n_x),
+                  (unsigned)(q % lv->n_x));
+  return HH_OK;
+}
+
+// The table, then w_k and j_k of every step (hh_localvol.h: localvol_row on t_k = (double)k·dt, dt as make_args forms
+// it), staged as one block; *out: what the kernel reads.
+static int stage_localvol(hh_ctx* ctx, const hh_localvol* lv, double T, uint32_t n_steps, hh::LocalVolArgs* out) {
+  const size_t n_nodes = (size_t)lv->n_times * lv->n_x;
+  std::vector<double> host(hh::localvol_stage_doubles(lv->n_times, lv->n_x, n_steps), 0.0);
+  std::memcpy(host.data(), lv->vols, n_nodes * sizeof(double));
+  double* const w = host.data() + n_nodes;
+  uint32_t* const rows = reinterpret_cast<uint32_t*>(w + n_steps);
+  const double dt = T / (double)n_steps;
+  for (uint32_t k = 0; k < n_steps; ++k) {
+    const hh::LocalVolRow r = hh::localvol_row(lv->times, lv->n_times, (double)k * dt);
+    w[k] = r.w;
+    rows[k] = r.j;
+  }
+  const double* dev = nullptr;
+  const int rc = stage_host(ctx, ctx->localvol, host.size(), host.data(), host.size(), &dev);
+  if (rc) return rc;
+  out->vols = dev;
+  out->step_w = dev + n_nodes;
+  out->step_row = reinterpret_cast<const uint32_t*>(dev + n_nodes + n_steps);
+  out->x_lo = lv->x_lo;
+  out->inv_h = 1.0 / lv->h;
+  out->n_times = lv->n_times;
+  out->n_x = lv->n_x;
+  return HH_OK;
+}
+
 // The path-statistics family: which kernel an entry point runs and what travels with it — one constructor per kernel.
 struct PathFamily {
-  enum Kernel { kEuler, kJump, kQe, kBates, kAssets } kernel;
+  enum Kernel { kEuler, kJump, kQe, kBates, kAssets, kLocalVol } kernel;
   const char* who;                           // the entry point, as its messages name it
   int32_t last_kind;                         // the last payoff kind it admits (the solve forms)
   int32_t extremes = HH_EXTREMES_MONITORED;  // enum hh_path_extremes: the bridge form is path_stats_kernel's alone
   const hh_jump* jump = nullptr;
   const hh_qe* qe = nullptr;
   const hh_assets* assets = nullptr;
+  const hh_localvol* localvol = nullptr;
   double* var_T = nullptr;  // host, nullable: the variance at expiry of every member (the QE step)
   bool missing = false;     // a struct the kernel needs came as NULL: the entry point's "NULL argument"
   // path_stats_kernel: lognormal or Heston dynamics by Euler–Maruyama
@@ -1374,6 +1428,10 @@ struct PathFamily {
       : kernel(kBates), who(w), last_kind(last), jump(j), qe(q), var_T(v), missing(!q || !j) {}
   // assets_stats_kernel: the index of several correlated lognormal assets; of the model only T, r_drift, discount are read
   PathFamily(const char* w, int32_t last, const hh_assets* a) : kernel(kAssets), who(w), last_kind(last), assets(a), missing(!a) {}
+  // localvol_stats_kernel: lognormal dynamics by Euler–Maruyama with the σ of every step read from the surface; both
+  // extremes forms; model->sigma is not read
+  PathFamily(const char* w, int32_t last, const hh_localvol* lv, int32_t ext)
+      : kernel(kLocalVol), who(w), last_kind(last), extremes(ext), localvol(lv), missing(!lv) {}
 };
 
 // The checks of every entry point, then the statistics of every trajectory into ctx->path_stats (one timing slot) and,
@@ -1381,6 +1439,12 @@ struct PathFamily {
 static int run_path_stats(hh_ctx* ctx, const PathFamily& f, const hh_model* m, const hh_config* c, uint32_t monitor_every,
                           int32_t include_start) {
   const char* who = f.who;
+  hh_model m_lv;  // local volatility: model->sigma is not read — nor checked
+  if (f.localvol) {
+    m_lv = *m;
+    m_lv.sigma = 0.0;
+    m = &m_lv;
+  }
   const bool hest = c->dynamics == HH_HESTON, logn = c->dynamics == HH_LOGNORMAL, em = c->strategy == HH_EULER_MARUYAMA;
   // the dynamics and strategy a kernel simulates, and how its entry points say so
   static const char kLognEm[] = "LognormalDynamics + EulerMaruyama";
@@ -1394,6 +1458,7 @@ static int run_path_stats(hh_ctx* ctx, const PathFamily& f, const hh_model* m, c
       if (hest || !em) needs = kLognEm;
       break;
     case PathFamily::kAssets:
+    case PathFamily::kLocalVol:
       ok = em && logn;
       needs = kLognEm;
       break;
@@ -1424,6 +1489,7 @@ static int run_path_stats(hh_ctx* ctx, const PathFamily& f, const hh_model* m, c
     return fail(ctx, HH_ERR_INVALID, "%s: S0, T > 0, |rho| <= 1, model scalars finite", who);
   int rc;
   if (f.assets && (rc = check_assets(ctx, who, f.assets))) return rc;
+  if (f.localvol && (rc = check_localvol(ctx, who, f.localvol))) return rc;
   if (f.jump && (rc = check_jump(ctx, who, f.jump, m->T / (double)c->n_steps))) return rc;
   hh_model m_c = *m;  // Bates: the step's constants, and their checks, on the compensated rate
   if (f.jump && f.qe) m_c.r_drift = m->r_drift - hh::merton_compensator(*f.jump);
@@ -1433,6 +1499,8 @@ static int run_path_stats(hh_ctx* ctx, const PathFamily& f, const hh_model* m, c
   if (f.qe && f.var_T && (rc = ensure(ctx, ctx->heston_var, (size_t)at.n_total))) return rc;
   const uint64_t* seeds_dev = nullptr;
   if ((rc = stage_path_seeds(ctx, c, &seeds_dev))) return rc;
+  hh::LocalVolArgs lv_args{};
+  if (f.localvol && (rc = stage_localvol(ctx, f.localvol, m->T, c->n_steps, &lv_args))) return rc;
   if ((rc = begin_timing(ctx))) return rc;
   const bool start = include_start != 0;
   double* const var_dev = f.var_T ? ctx->heston_var.p : nullptr;
@@ -1453,6 +1521,10 @@ static int run_path_stats(hh_ctx* ctx, const PathFamily& f, const hh_model* m, c
       break;
     case PathFamily::kAssets:
       HH_HIP(ctx, hh::launch_assets_stats(*m, *c, *f.assets, seeds_dev, monitor_every, start, ctx->path_stats, ctx->stream));
+      break;
+    case PathFamily::kLocalVol:
+      HH_HIP(ctx, hh::launch_localvol_stats(*m, *c, lv_args, seeds_dev, monitor_every, start, f.extremes == HH_EXTREMES_BRIDGE,
+                                            ctx->path_stats, ctx->stream));
       break;
   }
   return end_timing(ctx);
@@ -1701,6 +1773,21 @@ int hh_mc_solve_path_assets(hh_ctx* ctx, const hh_model* m, const hh_assets* ass
                             uint32_t n_payoffs, hh_result* out, double* path_values, double* stats) {
   return solve_path_call(ctx, {"hh_mc_solve_path_assets", HH_PAYOFF_LOOKBACK_FIXED, assets}, m, c, monitor_every, include_start,
                          payoffs, n_payoffs, out, path_values, stats);
+}
+
+// ---- local volatility on a tabulated surface (hedgehog_mc.h; kernel: hh_localvol.hip) -------------------------------
+
+int hh_mc_path_stats_lv(hh_ctx* ctx, const hh_model* m, const hh_localvol* lv, const hh_config* c, uint32_t monitor_every,
+                        int32_t include_start, int32_t extremes, double* stats, int32_t stats_on_device, hh_result* out) {
+  return path_stats_call(ctx, {"hh_mc_path_stats_lv", 0, lv, extremes}, m, c, monitor_every, include_start, stats,
+                         stats_on_device, out);
+}
+
+int hh_mc_solve_path_lv(hh_ctx* ctx, const hh_model* m, const hh_localvol* lv, const hh_config* c, uint32_t monitor_every,
+                        int32_t include_start, int32_t extremes, const hh_path_payoff* payoffs, uint32_t n_payoffs,
+                        hh_result* out, double* path_values, double* stats) {
+  return solve_path_call(ctx, {"hh_mc_solve_path_lv", HH_PAYOFF_LOOKBACK_FIXED, lv, extremes}, m, c, monitor_every,
+                         include_start, payoffs, n_payoffs, out, path_values, stats);
 }
 
 // ---- Bates: the quadratic-exponential step with Merton jumps (hedgehog_mc.h; kernels: hh_bates.hip, hh_fourier.hip) ----

@@ -47,6 +47,7 @@ struct hh_ctx {
   DevBuf<double> path_stats;           // hh::PathStatsLayout: [5 or 7 rows][n_total]
   DevBuf<double> path_values;          // [n_payoffs][n_total] payoffs per member (hh_mc_solve_path, when asked for)
   DevBuf<hh_path_payoff> path_payoffs; // [n_payoffs]
+  DevBuf<double> localvol;             // a local-vol call's table, per-step weights and rows (hh_localvol.h)
   DevBuf<double> lsm_val;
   DevBuf<int32_t> lsm_tau;
   DevBuf<double> lsm_scratch;

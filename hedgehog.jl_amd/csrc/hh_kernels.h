@@ -332,6 +332,13 @@ int launch_bates_stats(const hh_model& m, const hh_config& c, const hh_qe& qe, c
 // launch_carr_madan_basket (HH_HESTON, compat_sqrt_alpha = 0) with the Bates characteristic function
 int launch_carr_madan_bates(const hh_model& m, const hh_jump& jump, double alpha, double bound,
                             const double* per_payoff_dev, uint32_t n_payoffs, double* out_dev, hipStream_t s);
+// Local volatility on a tabulated surface (hh_localvol.hip; include/hedgehog_mc.h, "Local volatility on a tabulated
+// surface"): launch_path_stats' lognormal forms — the five monitored rows, or the seven under `bridge` — with the σ of
+// every step read from the surface.  m.sigma is not read.  The entry points have checked the surface and staged lv's
+// three arrays (hh_localvol.h); lv.n_times·lv.n_x doubles of dynamic LDS, at most HH_LV_MAX_NODES.
+struct LocalVolArgs;
+int launch_localvol_stats(const hh_model& m, const hh_config& c, const LocalVolArgs& lv, const uint64_t* seeds_dev,
+                          uint32_t monitor_every, bool include_start, bool bridge, double* stats, hipStream_t s);
 // Several correlated lognormal assets (hh_assets.hip; include/hedgehog_mc.h, "Several correlated lognormal assets"):
 // launch_path_stats' five monitored rows for the index of `assets`.  m: T, r_drift; c: antithetic, n_paths, n_steps.
 // The entry points have checked the assets (hh_assets.h: corr_defect, cholesky); the factor is formed again here.

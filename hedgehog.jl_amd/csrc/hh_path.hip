@@ -11,33 +11,11 @@
 //
 // The 40 bytes per trajectory that go through memory between the two are about 1 % of the simulation's time at
 // 252 steps; in exchange one simulation serves every payoff of a call and the caller can have the statistics.
-#include "hh_path_stats.h"  // Monitor: the five statistics and their dates, shared by the family
+#include "hh_path_stats.h"  // Monitor: the five statistics and their dates, shared by the family; Extremes
 #include "hh_sim.h"
 
 namespace hh {
 namespace {
-
-// The running extremes of the scheme's CONTINUOUS interpolation, in log space (the bridge form).  Between x0 and x1 an
-// Euler step with frozen diffusion coefficient g is a Brownian bridge of variance q = g²·dt, whose maximum and minimum
-// have the laws that one uniform each inverts:  ½(x0 + x1 ± sqrt((x1 - x0)² + q·L)),  L = -2 ln U.
-// The endpoint x1 goes in by itself, so cmax >= every state exactly whatever the formula's rounding.  q = 0 (a clipped
-// variance) gives the endpoints' max / min from the same formula; should x1 == x0 as well, sqrt_pos(0) is NaN, which
-// v_max_f64 / v_min_f64 drop in favour of their other operand: the endpoint is all there is.
-struct Extremes {
-  double cmax = 0.0, cmin = 0.0;
-  __device__ __forceinline__ void first(double x) { cmax = cmin = x; }  // time 0 always counts
-  __device__ __forceinline__ void next(double x0, double x1, double q, double Lmax, double Lmin) {
-    const double d = x1 - x0, d2 = d * d, m = x0 + x1;
-    const double up = 0.5 * (m + sqrt_pos(fma(q, Lmax, d2)));
-    const double dn = 0.5 * (m - sqrt_pos(fma(q, Lmin, d2)));
-    cmax = vmax(vmax(cmax, up), x1);
-    cmin = vmin(vmin(cmin, dn), x1);
-  }
-  __device__ __forceinline__ void store(double* __restrict__ stats, const PathStatsLayout& at, uint64_t col) const {
-    stats[at.row(HH_STAT_CMAX_S) + col] = exp(cmax);
-    stats[at.row(HH_STAT_CMIN_S) + col] = exp(cmin);
-  }
-};
 
 // One trajectory per lane (and its mirror, -dW, in the same lane: column n_paths + i), GENERATE noise, after
 // euler_grid_kernel.  The monitoring dates are the steps monitor_every, 2·monitor_every, …, n_steps — monitor_every

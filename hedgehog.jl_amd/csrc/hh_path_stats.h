@@ -1,8 +1,9 @@
 // The monitored statistics of a trajectory and its mirror (enum hh_path_stat), stated once for the kernels that keep
-// them on log spots: path_stats_kernel (hh_path.hip), jump_stats_kernel (hh_jump.hip), qe_stats_kernel (hh_qe.hip) and
-// bates_stats_kernel (hh_bates.hip).  Running is the arithmetic of the five rows, Monitor the dates they are taken on; a
-// kernel supplies its states, its step and the call after it.  assets_stats_kernel (hh_assets.hip) uses Running and
-// writes the dates out itself (its head comment says why).  Internal.
+// them on log spots: path_stats_kernel (hh_path.hip), jump_stats_kernel (hh_jump.hip), qe_stats_kernel (hh_qe.hip),
+// bates_stats_kernel (hh_bates.hip) and localvol_stats_kernel (hh_localvol.hip).  Running is the arithmetic of the five
+// rows, Monitor the dates they are taken on, Extremes the two rows of the bridge form; a kernel supplies its states, its
+// step and the call after it.  assets_stats_kernel (hh_assets.hip) uses Running and writes the dates out itself (its head
+// comment says why).  Internal.
 #pragma once
 #include "hh_sim.h"
 
@@ -93,6 +94,29 @@ struct Monitor {
                                         uint64_t n_paths) const {
     r.store(stats, at, i);
     if constexpr (ANTI) ra.store(stats, at, n_paths + i);
+  }
+};
+
+// The running extremes of the scheme's CONTINUOUS interpolation, in log space (the bridge form of path_stats_kernel and
+// localvol_stats_kernel).  Between x0 and x1 an Euler step with frozen diffusion coefficient g is a Brownian bridge of
+// variance q = g²·dt, whose maximum and minimum have the laws that one uniform each inverts:
+// ½(x0 + x1 ± sqrt((x1 - x0)² + q·L)),  L = -2 ln U.
+// The endpoint x1 goes in by itself, so cmax >= every state exactly whatever the formula's rounding.  q = 0 (a clipped
+// variance) gives the endpoints' max / min from the same formula; should x1 == x0 as well, sqrt_pos(0) is NaN, which
+// v_max_f64 / v_min_f64 drop in favour of their other operand: the endpoint is all there is.
+struct Extremes {
+  double cmax = 0.0, cmin = 0.0;
+  __device__ __forceinline__ void first(double x) { cmax = cmin = x; }  // time 0 always counts
+  __device__ __forceinline__ void next(double x0, double x1, double q, double Lmax, double Lmin) {
+    const double d = x1 - x0, d2 = d * d, m = x0 + x1;
+    const double up = 0.5 * (m + sqrt_pos(fma(q, Lmax, d2)));
+    const double dn = 0.5 * (m - sqrt_pos(fma(q, Lmin, d2)));
+    cmax = vmax(vmax(cmax, up), x1);
+    cmin = vmin(vmin(cmin, dn), x1);
+  }
+  __device__ __forceinline__ void store(double* __restrict__ stats, const PathStatsLayout& at, uint64_t col) const {
+    stats[at.row(HH_STAT_CMAX_S) + col] = exp(cmax);
+    stats[at.row(HH_STAT_CMIN_S) + col] = exp(cmin);
   }
 };
 

@@ -75,7 +75,8 @@ class ZeroRateSpineLens(GreekLens):
 
     def __call__(self, prob):
         m = prob.market_inputs
-        if not isinstance(m, BlackScholesInputs):
+        from .localvol import LocalVolInputs
+        if not isinstance(m, (BlackScholesInputs, LocalVolInputs)):
             raise TypeError("ZeroRateSpineLens getter: BlackScholesInputs only")
         if isinstance(m.rate, RateCurve):
             return m.rate.zeros[self.i - 1]

@@ -340,8 +340,13 @@ def solve_montecarlo(prob: PricingProblem, method: MonteCarlo, ensemble: bool = 
     `replay` (optional, build extension): Wiener increments to consume instead of drawing them —
     numpy array [path][step][comp] (or tile-major), the noise-replay parity mode of DESIGN.md."""
     from .multiasset import is_multiasset, solve_multiasset
+    from .localvol import is_localvol, solve_localvol_payoffs
     if is_multiasset([prob.payoff], prob.market_inputs, method):  # an index of several assets (hh_mc_solve_path_assets)
         return solve_multiasset(prob, method, ensemble, replay)
+    if is_localvol(prob.market_inputs, method):  # every payoff on the path statistics (hh_mc_solve_path_lv)
+        if replay is not None:
+            raise MethodError("local-volatility solves draw their own noise: no replay")
+        return solve_localvol_payoffs([prob.payoff], prob.market_inputs, method, ensemble)[0]
     if is_bates(prob.market_inputs, method):  # every payoff on the path statistics (hh_mc_solve_path_bates)
         if replay is not None:
             raise MethodError("Bates solves draw their own noise: no replay")
@@ -422,6 +427,9 @@ def solve_montecarlo_many(probs, method: MonteCarlo, replay=None, replay_layout=
     if any(is_multiasset([p.payoff], p.market_inputs, method) for p in probs):  # one solve after the other, on shared seeds
         return None
     if any(isinstance(p.payoff, PATH_PAYOFFS) for p in probs):  # one solve after the other (hh_mc_solve_path)
+        return None
+    from .localvol import is_localvol
+    if any(is_localvol(p.market_inputs, method) for p in probs):  # no hh_mc_solve_multi form: one after the other
         return None
     if is_qe(method) or any(is_merton(p.market_inputs, method) or is_bates(p.market_inputs, method) for p in probs):
         # no hh_mc_solve_multi form: one after the other

@@ -974,6 +974,68 @@ int hh_mc_solve_path_assets(hh_ctx* ctx, const hh_model* model, const hh_assets*
                             uint32_t n_payoffs, hh_result* out, double* path_values, double* stats);
 
 /*
+ * Local volatility on a tabulated surface: paths that reprice an observed vanilla surface.
+ *   d log S = (r − σ(t, S)²/2) dt + σ(t, S) dW
+ * with σ read off a rectangular table in (t, x = log S) — linear interpolation, constant extrapolation, as the
+ * reference's RectVolSurface interpolates; how the table is made (Dupire's formula on call prices, say) is the caller's
+ * business.  The parameters travel in the existing hh_model and in hh_localvol, with cfg->dynamics = HH_LOGNORMAL and
+ * cfg->strategy = HH_EULER_MARUYAMA: model->S0, r_drift, T and the discounting fields are read, model->sigma and the
+ * Heston fields are ignored.  No existing struct changes, no enum gains a value.
+ *
+ * ON THE HOST, once per call (csrc/hh_localvol.h — a host program can include it), every operation one rounded fp64
+ * operation in the order written:
+ *   dt = T/n_steps          sqrt_dt = sqrt(dt)          inv_h = 1/h
+ *   per step k = 0 .. n_steps−1, with t_k = (double)k·dt:
+ *     j_k = the largest j with times[j] <= t_k, clamped to [0, max(n_times − 2, 0)]
+ *     w_k = (t_k − times[j_k])/(times[j_k+1] − times[j_k]) clamped to [0, 1];  w_k = 0 when n_times == 1
+ *   so σ is constant in time before times[0] and after times[n_times−1].  j_k and w_k are the same for every trajectory.
+ *
+ * DRAWS: the lognormal Euler kernel's own.  Trajectory i is keyed by seeds[i]; the Philox4x32-10 block of counter
+ * (h, 0, 0, 0) gives the normals of steps 2h (first) and 2h + 1 (second), dW = sqrt_dt·z; under HH_EXTREMES_BRIDGE the
+ * block of counter (k, 0, 0, 3) gives the two bridge draws of step k, as for hh_mc_path_stats_ex.  No other draw.
+ *
+ * ONE STEP k of a trajectory at log spot x, operation by operation (a = row j_k of vols, b = row j_k + 1):
+ *   1. u = (x − x_lo)·inv_h, clamped to [0, n_x − 1]: constant extrapolation in x;
+ *   2. i = min((uint32)u, n_x − 2),  f = u − i;
+ *   3. c0 = fma(w_k, b_i − a_i, a_i),  c1 = fma(w_k, b_{i+1} − a_{i+1}, a_{i+1})   (time first; n_times == 1: c0 = a_i,
+ *      c1 = a_{i+1}, the same bits),  σ = fma(f, c1 − c0, c0)   (then x);
+ *   4. g = r_drift − (0.5·σ)·σ;
+ *   5. x′ = fma(σ, dW, fma(dt, g, x)): the lognormal Euler step with the σ and g of this step;
+ *   6. HH_EXTREMES_BRIDGE: σ is the frozen coefficient of bridge k, q = (σ·σ)·dt, in the extremes of hh_mc_path_stats_ex.
+ * The mirror of an antithetic pair takes −dW on its own state and its own σ, and the bridge draws swapped.
+ * One identity follows and is tested: a table whose entries all equal σ0 gives hh_mc_path_stats_ex's bits under
+ * model->sigma = σ0 in every row, in both extremes forms (fma(·, 0, c) = c exactly).
+ * The kernel holds the whole table in LDS (n_times·n_x·8 bytes, hence HH_LV_MAX_NODES); every device loop is bounded by
+ * n_steps or the table's size.
+ *
+ * hh_mc_path_stats_lv / hh_mc_solve_path_lv: hh_mc_path_stats_ex / hh_mc_solve_path_ex with `lv` after `model` — the
+ * same dates, the same statistics arithmetic, the five rows (seven under HH_EXTREMES_BRIDGE), payoff kinds 0 .. 7, the
+ * same layout (mirrors at n_paths + i) and timing slots.  Synchronous.
+ *
+ * Errors, checked on the host before any launch.  HH_ERR_INVALID: lv, lv->times or lv->vols is NULL; n_times = 0,
+ * n_x < 2 or n_times·n_x > HH_LV_MAX_NODES; a time not finite, negative or not above the one before it; a vol not finite
+ * or <= 0; x_lo not finite; h not finite or <= 0; everything hh_mc_solve_path_ex rejects (model->sigma excepted).
+ * HH_ERR_UNSUPPORTED: dynamics other than HH_LOGNORMAL, a strategy other than HH_EULER_MARUYAMA, REPLAY noise,
+ * n_partials > 0.
+ * Not provided: REPLAY noise, dual partials (bump the inputs: the solves share their seeds), LSM / American exercise,
+ * accumulate, hh_mc_solve_multi and multi-GPU forms, local volatility on the Crank–Nicolson grid, stochastic-local
+ * volatility, tables above 64 KiB, non-uniform log-spot grids, a Julia binding.
+ */
+#define HH_LV_MAX_NODES 8192          /* n_times · n_x doubles = 64 KiB of LDS */
+typedef struct hh_localvol {          /* 40 bytes */
+  const double* times;   /* host, [n_times], finite, >= 0, strictly increasing */
+  const double* vols;    /* host, [n_times][n_x] row-major: sigma at (times[j], x_lo + i*h), each finite and > 0 */
+  double x_lo, h;        /* log-spot grid: x_i = x_lo + i*h, h > 0 */
+  uint32_t n_times, n_x; /* n_times >= 1, n_x >= 2, n_times*n_x <= HH_LV_MAX_NODES */
+} hh_localvol;
+int hh_mc_path_stats_lv(hh_ctx* ctx, const hh_model* model, const hh_localvol* lv, const hh_config* cfg,
+                        uint32_t monitor_every, int32_t include_start, int32_t extremes, double* stats,
+                        int32_t stats_on_device, hh_result* out);
+int hh_mc_solve_path_lv(hh_ctx* ctx, const hh_model* model, const hh_localvol* lv, const hh_config* cfg,
+                        uint32_t monitor_every, int32_t include_start, int32_t extremes, const hh_path_payoff* payoffs,
+                        uint32_t n_payoffs, hh_result* out, double* path_values, double* stats);
+
+/*
  * The same solve for an ensemble SHARDED over several devices (one process and one hh_ctx per
  * device, trajectories split by contiguous ranges as for hh_mc_accumulate).  The backward induction
  * needs sums over ALL trajectories at three points — the in-the-money statistics of every row, the
