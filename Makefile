@@ -13,6 +13,8 @@ test-cpu: build
 # (hipcc, host side only) — each under AddressSanitizer + UBSan.  detect_leaks=0: the interpreter's own allocations.
 # Then the Bates step composed from hh_qe.h and hh_jump.h (tests/c/bates_host_check.cpp): a program of its own, built
 # with -fsanitize=address,undefined by its test and run as a program — nothing preloaded, nothing loaded into python.
+# The same for the local-volatility table and for the Sobol' expansion, point rule and bridge table of hh_sobol.h
+# (tests/c/sobol_host_check.cpp).
 ASAN_RT := $(shell gcc -print-file-name=libasan.so)
 test-cpu-asan:
 	$(MAKE) -C oracle -s asan
@@ -21,6 +23,7 @@ test-cpu-asan:
 	  tests/test_rng_host.py tests/test_scratch_layout_host.py -q -m "not gpu" -p no:cacheprovider
 	python -m pytest tests/test_bates_host.py -q -p no:cacheprovider -k step_host_program
 	python -m pytest tests/test_localvol_host.py -q -p no:cacheprovider -k host_program
+	python -m pytest tests/test_sobol_host.py -q -p no:cacheprovider -k host_program
 
 test-gpu: build
 	python -m pytest tests -q -m gpu

@@ -28,6 +28,7 @@ from .multiasset import (BestOf, GeometricMean, IndexOption, MultiAssetDynamics,
                          solve_index_options)
 from .localvol import (LocalVolDynamics, LocalVolInputs, LocalVolSurface, dupire_from, dupire_local_vol, get_local_vol,
                        refuse_other_methods, solve_localvol_payoffs)
+from .qmc import (BrownianBridge, Incremental, QuasiMonteCarlo, QuasiMonteCarloSolution, SobolConfig, solve_qmc)
 from .distributed import rank_device, shard_range, solve_lsm_sharded, solve_sharded
 from .domain import (American, ArithmeticAverage, AsianOption, AssetOrNothing, BarrierOption, BatesInputs, BlackScholesInputs,
                     Call, CashOrNothing, ContinuousMonitoring, DigitalOption, DownAndIn, DownAndOut, European,
@@ -62,6 +63,9 @@ def solve(*args, **kw):
         solve(prob::PricingProblem{…, LocalVolInputs} | ::BasketPricingProblem,
               ::MonteCarlo(LocalVolDynamics(), EulerMaruyama(), …))
                                   local volatility on a tabulated surface, Dupire's formula beside it (no reference method)
+        solve(prob::PricingProblem{<:VanillaOption{…,European,…,Spot}}, ::QuasiMonteCarlo(dynamics, strategy, SobolConfig(…)))
+                                  randomised Sobol' points through the REPLAY solve: LognormalDynamics with BlackScholesExact
+                                  or EulerMaruyama, HestonDynamics with EulerMaruyama (no reference method)
         solve(prob::PricingProblem{<:VanillaOption{…,American,…}}, ::LSM)     least_squares_montecarlo.jl:99
         solve(prob::PricingProblem{<:VanillaOption}, ::CoxRossRubinsteinMethod) cox_ross_rubinstein.jl:99
         solve(prob::BasketPricingProblem, ::CoxRossRubinsteinMethod)         basket.jl:35
@@ -71,6 +75,13 @@ def solve(*args, **kw):
     from . import greeks as _g
     from .montecarlo import BATES_ROUTES, is_bates
     from .multiasset import ROUTES as ASSET_ROUTES, is_multiasset, payoffs_of
+    if len(args) == 2 and isinstance(args[0], (PricingProblem, BasketPricingProblem)) and isinstance(args[1], QuasiMonteCarlo):
+        from .qmc import SUPPORTED  # every refusal of this method names what it does price
+        if not isinstance(args[0], PricingProblem):
+            raise MethodError(f"a basket has no many-strike quasi-Monte Carlo form: {SUPPORTED}")
+        if kw:
+            raise MethodError(f"QuasiMonteCarlo fills its own REPLAY buffer and takes no {sorted(kw)}: {SUPPORTED}")
+        return solve_qmc(args[0], args[1])
     if len(args) == 2 and isinstance(args[0], (PricingProblem, BasketPricingProblem)) and \
             is_multiasset(payoffs_of(args[0]), args[0].market_inputs, args[1]):
         if isinstance(args[0], PricingProblem) and isinstance(args[1], MultiAssetAnalytic):

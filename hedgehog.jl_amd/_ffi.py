@@ -36,6 +36,8 @@ HH_QE_MAX_PSI = 1e9
 HH_MAX_ASSETS = 8
 HH_LV_MAX_NODES = 8192
 HH_INDEX_WEIGHTED_SUM, HH_INDEX_GEOMETRIC, HH_INDEX_BEST_OF, HH_INDEX_WORST_OF = 0, 1, 2, 3
+HH_SOBOL_MAX_DIMS = 4096
+HH_SOBOL_INCREMENTAL, HH_SOBOL_BRIDGE = 0, 1
 
 HH_OK, HH_ERR_INVALID, HH_ERR_UNSUPPORTED, HH_ERR_HIP, HH_ERR_NOMEM, HH_ERR_RCCL, HH_ERR_DEVICE_TIMEOUT = 0, -1, -2, -3, -4, -5, -6
 HH_MGPU_AUTO, HH_MGPU_HOST_SUM, HH_MGPU_RCCL = 0, 1, 2
@@ -223,6 +225,10 @@ SYMBOLS = [
     ("hh_replay_elems", C.c_size_t, [C.c_uint64, C.c_uint32, C.c_int32]),
     ("hh_replay_pack", C.c_int, [_vp, C.c_int32, C.c_uint64, C.c_uint32, _vp, C.c_int32, _vp]),
     ("hh_wiener_fill", C.c_int, [_vp, C.c_int32, C.c_double, C.c_double, C.c_uint32, C.c_uint64, _vp, C.c_int32, _vp]),
+    ("hh_sobol_directions", C.c_int, [C.c_uint32, _vp]),
+    ("hh_sobol_points", C.c_int, [_vp, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.c_int32, _vp]),
+    ("hh_sobol_fill", C.c_int, [_vp, C.c_int32, C.c_double, C.c_double, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64,
+                                C.c_uint32, C.c_int32, C.c_int32, _vp]),
     ("hh_seeds_fingerprint", C.c_uint64, [_vp, C.c_uint64]),
     ("hh_seeds_cache", C.c_int, [_vp, _vp, C.c_uint64, C.c_uint64, C.POINTER(_vp)]),
     ("hh_seeds_cache_stats", C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),

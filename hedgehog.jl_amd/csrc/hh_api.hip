@@ -375,6 +375,88 @@ int hh_wiener_fill(hh_ctx* ctx, int32_t dynamics, double rho, double T, uint32_t
   return release_host_operands(ctx);
 }
 
+// ---- quasi-Monte Carlo (include/hedgehog_mc.h, "Quasi-Monte Carlo"; hh_sobol.hip) -------------------------------------------
+
+int hh_sobol_directions(uint32_t dim, uint32_t v[32]) {
+  if (!v || dim >= HH_SOBOL_MAX_DIMS) return HH_ERR_INVALID;
+  hh::sobol_expand(dim, v);
+  return HH_OK;
+}
+
+// the direction words in the context's device memory: expanded once per process, uploaded once per context
+static int sobol_directions_dev(hh_ctx* ctx) {
+  if (ctx->sobol_dirs_ready) return HH_OK;
+  const std::vector<uint32_t>& all = hh::sobol_all_directions();
+  const uint32_t* dev = nullptr;
+  const int rc = stage_host(ctx, ctx->sobol_dirs, all.size(), all.data(), all.size(), &dev);
+  if (rc) return rc;
+  ctx->sobol_dirs_ready = true;
+  return HH_OK;
+}
+
+// a point range every Sobol' entry point accepts: 1 .. 2^32 − 256 points (one launch), all below point 2^32
+static bool sobol_range_ok(uint64_t n_points, uint64_t point_offset) {
+  return n_points >= 1 && n_points <= kMaxPaths && point_offset < (1ull << 32) && point_offset + n_points <= (1ull << 32);
+}
+
+// the high words of n_dims dimensions for the tiles of [point_offset, point_offset + n_points) under one shift
+static int sobol_high_dev(hh_ctx* ctx, uint32_t n_dims, uint64_t n_points, uint64_t point_offset, uint64_t shift_seed,
+                          uint32_t randomization, int32_t shifted) {
+  int rc = sobol_directions_dev(ctx);
+  if (rc) return rc;
+  if ((rc = ensure(ctx, ctx->sobol_high, (size_t)hh::tiles_for(n_points) * n_dims * 2u))) return rc;
+  HH_HIP(ctx, hh::launch_sobol_high(ctx->sobol_dirs, n_dims, n_points, (uint32_t)point_offset, shift_seed, randomization,
+                                    shifted != 0, ctx->sobol_high, ctx->stream));
+  return HH_OK;
+}
+
+int hh_sobol_points(hh_ctx* ctx, uint32_t n_dims, uint64_t n_points, uint64_t point_offset, uint64_t shift_seed,
+                    uint32_t randomization, int32_t shifted, uint32_t* dst_dev) {
+  if (!ctx) return HH_ERR_INVALID;
+  std::lock_guard<std::recursive_mutex> lock__(ctx->mu);
+  if (!dst_dev || n_dims == 0 || !sobol_range_ok(n_points, point_offset))
+    return fail(ctx, HH_ERR_INVALID, "hh_sobol_points: bad arguments");
+  if (n_dims > HH_SOBOL_MAX_DIMS)
+    return fail(ctx, HH_ERR_UNSUPPORTED, "hh_sobol_points: %u dimensions, at most %d", n_dims, HH_SOBOL_MAX_DIMS);
+  HH_HIP(ctx, hipSetDevice(ctx->device));
+  const int rc = sobol_high_dev(ctx, n_dims, n_points, point_offset, shift_seed, randomization, shifted);
+  if (rc) return rc;
+  HH_HIP(ctx, hh::launch_sobol_points(ctx->sobol_dirs, ctx->sobol_high, n_dims, n_points, (uint32_t)point_offset, dst_dev,
+                                      ctx->stream));
+  return release_host_operands(ctx);
+}
+
+int hh_sobol_fill(hh_ctx* ctx, int32_t dynamics, double rho, double T, uint32_t n_steps, uint64_t n_points,
+                  uint64_t point_offset, uint64_t shift_seed, uint32_t randomization, int32_t shifted,
+                  int32_t construction, double* dst) {
+  if (!ctx) return HH_ERR_INVALID;
+  std::lock_guard<std::recursive_mutex> lock__(ctx->mu);
+  if (!dst || n_steps == 0 || !(T > 0.0) || !std::isfinite(T) || !(std::fabs(rho) <= 1.0) ||
+      !sobol_range_ok(n_points, point_offset) ||
+      (construction != HH_SOBOL_INCREMENTAL && construction != HH_SOBOL_BRIDGE))
+    return fail(ctx, HH_ERR_INVALID, "hh_sobol_fill: bad arguments");
+  const int nc = ncomp_of(dynamics);
+  if ((uint64_t)nc * n_steps > HH_SOBOL_MAX_DIMS)
+    return fail(ctx, HH_ERR_UNSUPPORTED, "hh_sobol_fill: %d x %u coordinates per point, at most %d", nc, n_steps,
+                HH_SOBOL_MAX_DIMS);
+  HH_HIP(ctx, hipSetDevice(ctx->device));
+  int rc = sobol_high_dev(ctx, (uint32_t)nc * n_steps, n_points, point_offset, shift_seed, randomization, shifted);
+  if (rc) return rc;
+  const bool bridge = construction == HH_SOBOL_BRIDGE;
+  if (bridge && ctx->sobol_ops_steps != n_steps) {  // tabulated per n_steps; the last table's upload has been waited for
+    ctx->sobol_ops_steps = 0;
+    ctx->sobol_ops_host = hh::sobol_bridge_ops(n_steps, &ctx->sobol_slots);
+    const hh::SobolOp* dev = nullptr;
+    const size_t n = ctx->sobol_ops_host.size();
+    if ((rc = stage_host(ctx, ctx->sobol_ops, n, ctx->sobol_ops_host.data(), n, &dev))) return rc;
+    ctx->sobol_ops_steps = n_steps;
+  }
+  HH_HIP(ctx, hh::launch_sobol_fill(dynamics, rho, std::sqrt(T / (double)n_steps), n_steps, n_points, (uint32_t)point_offset,
+                                    ctx->sobol_dirs, ctx->sobol_high, bridge ? (const hh::SobolOp*)ctx->sobol_ops : nullptr,
+                                    bridge ? (uint32_t)ctx->sobol_ops_host.size() : 0u, ctx->sobol_slots, dst, ctx->stream));
+  return release_host_operands(ctx);
+}
+
 // Shared body of hh_mc_accumulate / hh_mc_accumulate_basket: stage caller buffers, run the
 // simulation kernel (which also reduces the payoff of m->strike / m->cp into ctx->records) and
 // leave the terminal samples in device memory when asked.

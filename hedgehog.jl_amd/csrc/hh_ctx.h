@@ -6,6 +6,7 @@
 #include <cstdio>
 #include <cstring>
 #include <mutex>
+#include <vector>
 
 #include "hh_kernels.h"
 
@@ -48,6 +49,13 @@ struct hh_ctx {
   DevBuf<double> path_values;          // [n_payoffs][n_total] payoffs per member (hh_mc_solve_path, when asked for)
   DevBuf<hh_path_payoff> path_payoffs; // [n_payoffs]
   DevBuf<double> localvol;             // a local-vol call's table, per-step weights and rows (hh_localvol.h)
+  // quasi-Monte Carlo (hh_sobol_points, hh_sobol_fill)
+  DevBuf<uint32_t> sobol_dirs;            // [HH_SOBOL_MAX_DIMS][32] direction words, uploaded at the context's first Sobol' call
+  bool sobol_dirs_ready = false;
+  DevBuf<uint32_t> sobol_high;            // [tiles][n_dims][2]: a call's high words (launch_sobol_high)
+  DevBuf<hh::SobolOp> sobol_ops;          // the bridge's schedule for sobol_ops_steps steps (0: none yet)
+  std::vector<hh::SobolOp> sobol_ops_host;
+  uint32_t sobol_ops_steps = 0, sobol_slots = 0;
   DevBuf<double> lsm_val;
   DevBuf<int32_t> lsm_tau;
   DevBuf<double> lsm_scratch;

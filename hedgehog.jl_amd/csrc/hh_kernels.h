@@ -8,6 +8,7 @@
 #include "../../include/hedgehog_mc.h"
 #include "hh_jump.h"
 #include "hh_layout.h"
+#include "hh_sobol.h"
 
 namespace hh {
 
@@ -360,5 +361,15 @@ int launch_wiener_fill(int dynamics, double rho, double sqrt_dt, uint32_t n_step
                        const uint64_t* seeds_dev, double* dst, hipStream_t s);
 int launch_replay_pack(int ncomp, uint64_t n_paths, uint32_t n_steps, const double* src_dev,
                        double* dst_dev, hipStream_t s);
+// Quasi-Monte Carlo (hh_sobol.hip).  dirs_dev: [HH_SOBOL_MAX_DIMS][32] direction words; high_dev: [tiles][n_dims][2]
+// words, written by launch_sobol_high for one (point range, shift) and read by the other two; ops_dev: the bridge's
+// schedule (hh_sobol.h) with its n_ops and n_slots, or NULL for the incremental construction.
+int launch_sobol_high(const uint32_t* dirs_dev, uint32_t n_dims, uint64_t n_points, uint32_t offset, uint64_t seed,
+                      uint32_t randomization, int shifted, uint32_t* high_dev, hipStream_t s);
+int launch_sobol_points(const uint32_t* dirs_dev, const uint32_t* high_dev, uint32_t n_dims, uint64_t n_points,
+                        uint32_t offset, uint32_t* dst_dev, hipStream_t s);
+int launch_sobol_fill(int dynamics, double rho, double sqrt_dt, uint32_t n_steps, uint64_t n_points, uint32_t offset,
+                      const uint32_t* dirs_dev, const uint32_t* high_dev, const SobolOp* ops_dev, uint32_t n_ops,
+                      uint32_t n_slots, double* dst, hipStream_t s);
 
 }  // namespace hh

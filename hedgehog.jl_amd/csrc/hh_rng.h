@@ -18,6 +18,7 @@ constexpr uint32_t kDomBridge = 3u;  // the Brownian-bridge extremes between two
 constexpr uint32_t kDomJump = 4u;    // the jump counts and jump normals of the Merton model (hh_jump.hip)
 constexpr uint32_t kDomQe = 5u;      // the normals and uniforms of the quadratic-exponential Heston step (hh_qe.hip)
 constexpr uint32_t kDomAssets = 6u;  // the normals of the correlated assets of a multi-asset index (hh_assets.hip)
+constexpr uint32_t kDomSobol = 7u;   // the digital shifts of the randomised Sobol' points (hh_sobol.hip)
 
 struct Philox4 {
   uint32_t c0, c1, c2, c3;

@@ -29,7 +29,8 @@
  *     written on the ctx's stream, which does not wait for any other stream: data produced on another
  *     stream (PyTorch's, say) must be complete before the call — synchronize it, or lend that stream
  *     to the ctx with hh_ctx_set_stream — and results of the ASYNCHRONOUS entry points
- *     (hh_mc_accumulate, hh_wiener_fill, hh_replay_pack, the hh_lsm_shard_* phases) are ready only after
+ *     (hh_mc_accumulate, hh_wiener_fill, hh_sobol_fill, hh_sobol_points, hh_replay_pack, the hh_lsm_shard_* phases) are
+ *     ready only after
  *     hh_ctx_synchronize.  The synchronous ones (hh_mc_solve, hh_lsm_solve, …) return with their
  *     device outputs complete.
  *   - there is NO CPU fallback in this library: without a HIP device every compute entry point
@@ -1142,6 +1143,56 @@ int hh_replay_pack(hh_ctx* ctx, int32_t dynamics, uint64_t n_paths, uint32_t n_s
 int hh_wiener_fill(hh_ctx* ctx, int32_t dynamics, double rho, double T, uint32_t n_steps,
                    uint64_t n_paths, const uint64_t* seeds, int32_t seeds_on_device,
                    double* dst_tile_major_dev);
+
+/*
+ * Quasi-Monte Carlo: Sobol' points, and a tile-major REPLAY buffer filled from them (no reference method; every REPLAY
+ * consumer — hh_mc_solve and its kin — prices on such a buffer unchanged).
+ *
+ * THE POINT RULE.  Dimension d < HH_SOBOL_MAX_DIMS has 32 direction words v_d[j] = m_(j+1) << (31 − j), expanded from
+ * the Joe–Kuo set new-joe-kuo-6.21201 (csrc/hh_sobol_table.h; dimension 0 is the van der Corput sequence).
+ *   x      point i (0 <= i < 2^32) of dimension d is the XOR of v_d[b] over the set bits b of g = i ^ (i >> 1): Gray-code
+ *          order, the rows of the unscrambled engines of PyTorch and SciPy, row for row
+ *   shift  randomisation r XORs a digital shift into x: for dimension d the word d & 3 of the Philox4x32-10 block with
+ *          counter (d >> 2, r, 0, kDomSobol = 7) and key (shift_seed low word, shift_seed high word).  shifted = 0: none
+ *   u      (x + 1/2)·2^-32 — exact in fp64, never 0 or 1; the smallest tail is 2^-33 = 1.16e-10
+ *   z      the standard normal quantile of u (Wichura's AS 241, csrc/hh_math.h)
+ *
+ * THE CONSTRUCTION, on n_steps unit-variance steps of ncomp (1 lognormal, 2 Heston) independent factors; coordinate
+ * ncomp·j + comp of the point is the normal z_j of factor comp:
+ *   HH_SOBOL_INCREMENTAL   d_k = z_k, the step's own normal
+ *   HH_SOBOL_BRIDGE        W_0 = 0; bridge index 0 is the terminal value W_n = sqrt(n)·z_0; every later index j takes the
+ *                          next interval (l, r) with r − l >= 2 from a queue that starts with (0, n), sets m = (l + r) / 2
+ *                          (rounded down),  W_m = fma(wl, W_l, fma(wr, W_r, sd·z_j))  with  wl = (r − m)/(r − l),
+ *                          wr = (m − l)/(r − l),  sd = sqrt((m − l)·(r − m)/(r − l))  — each one rounded fp64 division or
+ *                          product of the integers as doubles, sqrt correctly rounded — and queues (l, m), then (m, r): any
+ *                          n_steps, not only powers of two; the first ncomp coordinates carry the terminal values.
+ *                          d_k = W_(k+1) − W_k.
+ * and the increments, in hh_wiener_fill's form and with its covariance dt·[1 ρ; ρ 1], dt = T/n_steps, sqrt_dt = sqrt(dt):
+ *   dW_k[0] = sqrt_dt·d_k[0];   Heston: dW_k[1] = sqrt_dt·fma(ρ, d_k[0], sqrt(1 − ρ²)·d_k[1]).
+ * Every operation named is one rounded fp64 operation, in the order written (fma: one rounding).
+ *
+ * hh_sobol_directions: the 32 words of dimension dim.  Host arithmetic, no context, no GPU.  HH_ERR_INVALID: v NULL or
+ *     dim >= HH_SOBOL_MAX_DIMS.
+ * hh_sobol_points: the raw words x (shifted or not) of points point_offset … point_offset + n_points − 1 in the first
+ *     n_dims dimensions, dst_dev[dim][point], n_dims·n_points uint32 in device memory.  HH_ERR_INVALID: NULL arguments,
+ *     n_dims = 0, n_points = 0 or above 2^32 − 256, point_offset + n_points > 2^32; HH_ERR_UNSUPPORTED:
+ *     n_dims > HH_SOBOL_MAX_DIMS.
+ * hh_sobol_fill: dW[tile][step][comp][HH_TILE_PATHS] of hh_replay_elems(n_points, n_steps, dynamics) doubles, lane p of
+ *     tile t being point point_offset + 256·t + p, the last tile zero-padded.  Shards of one point set compose: a fill of
+ *     [a, b) holds the columns of a fill of [0, b) bit for bit.  T = n_steps = 1 with HH_LOGNORMAL leaves one standard
+ *     normal per point: what the exact law's REPLAY mode reads.  HH_ERR_INVALID: NULL arguments, |rho| > 1, T <= 0,
+ *     n_steps = 0, n_points = 0 or above 2^32 − 256, point_offset + n_points > 2^32, an unknown construction;
+ *     HH_ERR_UNSUPPORTED: ncomp·n_steps > HH_SOBOL_MAX_DIMS.
+ * Both device entry points are asynchronous, like hh_wiener_fill.
+ */
+#define HH_SOBOL_MAX_DIMS 4096
+enum hh_sobol_construction { HH_SOBOL_INCREMENTAL = 0, HH_SOBOL_BRIDGE = 1 };
+int hh_sobol_directions(uint32_t dim, uint32_t v[32]);
+int hh_sobol_points(hh_ctx* ctx, uint32_t n_dims, uint64_t n_points, uint64_t point_offset, uint64_t shift_seed,
+                    uint32_t randomization, int32_t shifted, uint32_t* dst_dev);
+int hh_sobol_fill(hh_ctx* ctx, int32_t dynamics, double rho, double T, uint32_t n_steps, uint64_t n_points,
+                  uint64_t point_offset, uint64_t shift_seed, uint32_t randomization, int32_t shifted,
+                  int32_t construction, double* dst_tile_major_dev);
 
 /*
  * Measurement hooks (the reference has no tracing; the build supplies its own).  When
