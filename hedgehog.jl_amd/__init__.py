@@ -4,7 +4,7 @@ Host mirror (Python) of the reference's operator interface for this path; the ar
 hand-written HIP kernels behind the C-ABI of include/hedgehog_mc.h (lib/libhedgehog_mc.so).
 Import as `hedgehog_jl_amd` (shim at the repository root; the directory name carries a dot).
 """
-from . import _ffi
+from . import _ffi, multiasset, routes
 from ._ffi import Context, HedgehogMCError, get_context, load_library
 from .analytic import (AnalyticSolution, BlackScholesAnalytic, CarrMadan, MertonAnalytic, MultiAssetAnalytic, merton_series,
                        solve_black_scholes, solve_carr_madan, solve_merton_analytic, solve_multiasset_analytic)
@@ -73,8 +73,6 @@ def solve(*args, **kw):
                                                   (a Crank–Nicolson grid per option; no reference method)
     """
     from . import greeks as _g
-    from .montecarlo import BATES_ROUTES, is_bates
-    from .multiasset import ROUTES as ASSET_ROUTES, is_multiasset, payoffs_of
     if len(args) == 2 and isinstance(args[0], (PricingProblem, BasketPricingProblem)) and isinstance(args[1], QuasiMonteCarlo):
         from .qmc import SUPPORTED  # every refusal of this method names what it does price
         if not isinstance(args[0], PricingProblem):
@@ -82,17 +80,12 @@ def solve(*args, **kw):
         if kw:
             raise MethodError(f"QuasiMonteCarlo fills its own REPLAY buffer and takes no {sorted(kw)}: {SUPPORTED}")
         return solve_qmc(args[0], args[1])
-    if len(args) == 2 and isinstance(args[0], (PricingProblem, BasketPricingProblem)) and \
-            is_multiasset(payoffs_of(args[0]), args[0].market_inputs, args[1]):
-        if isinstance(args[0], PricingProblem) and isinstance(args[1], MultiAssetAnalytic):
-            return solve_multiasset_analytic(args[0], args[1])
-        if not isinstance(args[1], MonteCarlo):
-            raise MethodError(f"{type(args[1]).__name__} does not price multi-asset problems: use {ASSET_ROUTES}")
-    if len(args) == 2 and isinstance(args[0], (PricingProblem, BasketPricingProblem)) and \
-            not isinstance(args[1], (MonteCarlo, CarrMadan)) and is_bates(args[0].market_inputs, args[1]):
-        raise MethodError(f"{type(args[1]).__name__} does not price the Bates model: use {BATES_ROUTES}")
     if len(args) == 2 and isinstance(args[0], (PricingProblem, BasketPricingProblem)):
-        refuse_other_methods(args[0].market_inputs, args[1])  # local volatility: its one route, or a MethodError naming it
+        payoffs = multiasset.payoffs_of(args[0])
+        if isinstance(args[0], PricingProblem) and isinstance(args[1], MultiAssetAnalytic) and \
+                multiasset.is_multiasset(payoffs, args[0].market_inputs, args[1]):
+            return solve_multiasset_analytic(args[0], args[1])
+        routes.refuse_other_methods(payoffs, args[0].market_inputs, args[1])  # a model with routes of its own: them, or a MethodError naming them
     if len(args) == 2 and isinstance(args[0], PricingProblem) and isinstance(args[1], MonteCarlo):
         return solve_montecarlo(args[0], args[1], **kw)
     if len(args) == 2 and isinstance(args[0], PricingProblem) and isinstance(args[1], CarrMadan):

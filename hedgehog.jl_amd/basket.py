@@ -17,8 +17,8 @@ import numpy as np
 from . import _ffi
 from .domain import PATH_PAYOFFS, European, MonteCarloSolution, PricingProblem, Spot, VanillaOption
 from .dual import Dual
-from .montecarlo import (EulerMaruyama, HestonQE, MonteCarlo, _model_and_config, _price_from, is_bates, is_merton, is_qe, path_extremes,
-                         path_monitoring, solve_montecarlo, solve_path_payoffs)
+from .montecarlo import (_model_and_config, _path_structs, _price_from, path_extremes, path_monitoring, routes, solve_montecarlo,
+                         solve_path_payoffs)
 
 
 @dataclass(frozen=True)
@@ -72,12 +72,10 @@ def solve_basket(prob: BasketPricingProblem, method, ensemble: bool = False):
     from .analytic import AnalyticSolution, CarrMadan, solve_carr_madan_basket
     from .trees import CoxRossRubinsteinMethod, CRRSolution, solve_crr_basket
     from .pde import CrankNicolsonMethod, solve_pde_basket
-    from .multiasset import is_multiasset, solve_index_options
-    if is_multiasset(prob.payoffs, prob.market_inputs, method):  # IndexOptions: one statistics pass per distinct index
-        return BasketPricingSolution(prob, solve_index_options(prob.payoffs, prob.market_inputs, method, ensemble))
-    from .localvol import is_localvol, solve_localvol_basket
-    if is_localvol(prob.market_inputs, method):  # one hh_mc_solve_path_lv call per (expiry, monitoring)
-        return BasketPricingSolution(prob, solve_localvol_basket(prob.payoffs, prob.market_inputs, method, ensemble))
+    route = routes().route_of(prob.payoffs, prob.market_inputs, method)
+    if route.solve_all:  # IndexOptions: one statistics pass per distinct index
+        return BasketPricingSolution(prob, route.solve_all(prob.payoffs, prob.market_inputs, method, ensemble))
+    routes().LOCALVOL.refuse_method(prob.payoffs, prob.market_inputs, method)  # its inputs are no other method's
     if isinstance(method, CoxRossRubinsteinMethod):
         prices = solve_crr_basket(prob.payoffs, prob.market_inputs, method)
         return BasketPricingSolution(prob, [CRRSolution(PricingProblem(p, prob.market_inputs), method, float(x))
@@ -92,34 +90,29 @@ def solve_basket(prob: BasketPricingProblem, method, ensemble: bool = False):
     payoffs = list(prob.payoffs)
     sols: list = [None] * len(payoffs)
     groups: dict = {}
-    if any(isinstance(p, PATH_PAYOFFS) for p in payoffs):  # one hh_mc_solve_path call per (expiry, monitoring)
+    if route.checks_first:  # the route's refusals, before anything is grouped
+        _path_structs(payoffs[:1], prob.market_inputs, method, route)
+    if route.entry:  # a path-dependent payoff, or a model on paths alone: one path solve per (expiry, monitoring)
         for _, idx in path_groups(payoffs, method.config.steps):
-            for i, sol in zip(idx, solve_path_payoffs([payoffs[i] for i in idx], prob.market_inputs, method, ensemble)):
+            for i, sol in zip(idx, solve_path_payoffs([payoffs[i] for i in idx], prob.market_inputs, method, ensemble, route)):
                 sols[i] = sol
-    if is_merton(prob.market_inputs, method) or is_qe(method) or is_bates(prob.market_inputs, method):
-        # Merton jumps, HestonQE and Bates paths have no terminal-sample basket: what is left rides on one path simulation
-        # per expiry (EulerMaruyama: hh_mc_solve_path_jump, HestonQE: hh_mc_solve_path_qe or, under BatesDynamics,
-        # hh_mc_solve_path_bates; the vanilla kind), or is solved one by one (MertonExact: the same seed gives the same
-        # trajectories; a Bates mix no route serves: its MethodError)
-        on_paths = isinstance(method.strategy, (EulerMaruyama, HestonQE))
-        rest: dict = {}
-        for i, p in enumerate(payoffs):
-            if sols[i] is None:
-                rest.setdefault(getattr(p, "expiry", None) if on_paths else i, []).append(i)
-        for idx in rest.values():
-            if on_paths:
-                for i, sol in zip(idx, solve_path_payoffs([payoffs[i] for i in idx], prob.market_inputs, method, ensemble)):
-                    sols[i] = sol
-            else:
-                sols[idx[0]] = solve_montecarlo(PricingProblem(payoffs[idx[0]], prob.market_inputs), method, ensemble)
+    left = [i for i in range(len(payoffs)) if sols[i] is None]
+    if route.rest == "singles":  # the law at expiry: the same seed gives the same trajectories
+        for i in left:
+            sols[i] = solve_montecarlo(PricingProblem(payoffs[i], prob.market_inputs), method, ensemble)
         return BasketPricingSolution(prob, sols)
-    for i, p in enumerate(payoffs):
-        if sols[i] is not None:
-            continue
-        if isinstance(getattr(p, "strike", None), Dual):  # strike partials: plain per-payoff solve
-            sols[i] = solve_montecarlo(PricingProblem(p, prob.market_inputs), method, ensemble)
+    if route.rest == "paths":  # no terminal-sample basket: one path simulation per expiry, the vanilla kind
+        for i in left:
+            groups.setdefault(getattr(payoffs[i], "expiry", None), []).append(i)
+        for idx in groups.values():
+            for i, sol in zip(idx, solve_path_payoffs([payoffs[i] for i in idx], prob.market_inputs, method, ensemble, route)):
+                sols[i] = sol
+        return BasketPricingSolution(prob, sols)
+    for i in left:
+        if isinstance(getattr(payoffs[i], "strike", None), Dual):  # strike partials: plain per-payoff solve
+            sols[i] = solve_montecarlo(PricingProblem(payoffs[i], prob.market_inputs), method, ensemble)
         else:
-            groups.setdefault(getattr(p, "expiry", None), []).append(i)
+            groups.setdefault(getattr(payoffs[i], "expiry", None), []).append(i)
     cfg = method.config
     mg = _ffi.get_multi_gpu(tuple(method.devices)) if method.devices is not None else None
     ctx = None if mg is not None else _ffi.get_context(method.device)

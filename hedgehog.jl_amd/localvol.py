@@ -14,8 +14,6 @@ in its market inputs and lists Dupire local vol on its roadmap — it has neithe
 """
 from __future__ import annotations
 
-import ctypes as C
-import dataclasses
 import math
 from dataclasses import dataclass
 from typing import Any
@@ -24,11 +22,8 @@ import numpy as np
 
 from . import _ffi
 from .dates import MILLISECONDS_IN_YEAR_365, to_ticks
-from .domain import (American, Call, ContinuousMonitoring, European, FlatRateCurve, MonteCarloSolution, PricingProblem,  # noqa: F401
-                     RateCurve, Spot, VanillaOption, BlackScholesInputs)
-from .dual import Dual
-from .montecarlo import (EulerMaruyama, LognormalDynamics, MethodError, MonteCarlo, PriceDynamics, _model_and_config,
-                         pack_path_payoff, path_extremes, path_monitoring)
+from .domain import BlackScholesInputs, Call, European, FlatRateCurve, PricingProblem, RateCurve, Spot, VanillaOption
+from .montecarlo import MethodError, MonteCarlo, PriceDynamics, routes, solve_path_payoffs
 
 ROUTES = "MonteCarlo(LocalVolDynamics(), EulerMaruyama(), config) on LocalVolInputs"
 UNIFORM_RTOL = 1e-12
@@ -136,82 +131,14 @@ def is_localvol(market_inputs, method) -> bool:
 
 def refuse_other_methods(market_inputs, method):
     """CarrMadan, trees, PDE, LSM, analytic formulas on LocalVolInputs: a MethodError that names the route"""
-    if is_localvol(market_inputs, method) and not isinstance(method, MonteCarlo):
-        raise MethodError(f"{type(method).__name__} does not price local volatility: use {ROUTES}")
-
-
-def _structs(payoffs, market_inputs, method: MonteCarlo):
-    """(hh_model, hh_config, hh_localvol, monitor_every, include_start) of payoffs that share an expiry and a monitoring"""
-    dyn, strat = method.dynamics, method.strategy
-    if not (isinstance(dyn, LocalVolDynamics) and isinstance(market_inputs, LocalVolInputs) and isinstance(strat, EulerMaruyama)):
-        raise MethodError(f"no local-volatility solve for {type(dyn).__name__} + {type(strat).__name__} on "
-                          f"{type(market_inputs).__name__}: use {ROUTES}")
-    for p in payoffs:
-        if isinstance(getattr(p, "exercise_style", None), American):
-            raise MethodError(f"American exercise is not offered on local-volatility paths (no LSM on them): European payoffs on {ROUTES}")
-    if method.devices is not None:
-        raise MethodError("local-volatility solves run on one device (MonteCarlo.devices is not supported)")
-    expiries = {p.expiry for p in payoffs}
-    if len(expiries) != 1:
-        raise ValueError("payoffs of one path solve share an expiry")
-    steps = method.config.steps
-    mons = {m for m in (path_monitoring(p, steps) for p in payoffs) if m is not None}
-    if len(mons) > 1:
-        raise ValueError("payoffs of one path solve share a monitoring")
-    every, start = mons.pop() if mons else (steps, False)
-    european = VanillaOption(1.0, expiries.pop(), European(), Call(), Spot())
-    plain = dataclasses.replace(method, dynamics=LognormalDynamics())
-    model, c, keep, P, _ = _model_and_config(PricingProblem(european, market_inputs.black_scholes()), plain)
-    if P or isinstance(market_inputs.spot, Dual):
-        raise MethodError("local-volatility solves carry no dual partials (ForwardAD): use FiniteDifference — its solves share "
-                          "their seeds, the spot or the curve moves and the surface stays")
-    del keep
-    return model, c, market_inputs.surface.c_struct(), every, start
+    routes().LOCALVOL.refuse_method((), market_inputs, method)
 
 
 def solve_localvol_payoffs(payoffs, market_inputs, method: MonteCarlo, ensemble: bool = True):
     """Payoffs that share an expiry, a monitoring and an extremes mode on ONE simulation (hh_mc_solve_path_lv): a
     MonteCarloSolution each, in order.  `ensemble`: the (5, n_total) statistics — (7, n_total) under
-    ContinuousMonitoring() — shared by the solutions."""
-    model, c, lv, every, start = _structs(payoffs, market_inputs, method)
-    modes = {e for e in (path_extremes(p) for p in payoffs) if e is not None}
-    if len(modes) > 1:
-        raise ValueError("payoffs of one path solve share an extremes mode (Monitoring or ContinuousMonitoring)")
-    extremes = modes.pop() if modes else _ffi.HH_EXTREMES_MONITORED
-    bridge = extremes == _ffi.HH_EXTREMES_BRIDGE
-    packed = (_ffi.hh_path_payoff * len(payoffs))(*[pack_path_payoff(p) for p in payoffs])
-    cfg = method.config
-    ctx = _ffi.get_context(method.device)
-    c.seeds, c.seeds_on_device, c.seeds_len = cfg.device_seeds(ctx), 1, cfg.seeds.size
-    n_total = int(c.n_paths) * (2 if c.antithetic else 1)
-    stats = np.empty((_ffi.HH_PATH_STATS_BRIDGE if bridge else _ffi.HH_PATH_STATS, n_total)) if ensemble else None
-    res = (_ffi.hh_result * len(payoffs))()
-    ctx.check(ctx.lib.hh_mc_solve_path_lv(ctx.handle, C.byref(model), C.byref(lv), C.byref(c), every, int(start), extremes,
-                                          packed, len(payoffs), res, None, stats.ctypes.data if ensemble else None))
-    return [MonteCarloSolution(PricingProblem(p, market_inputs), method, res[k].price, stats,
-                               std_error=res[k].std_error, result=res[k]) for k, p in enumerate(payoffs)]
-
-
-def solve_localvol_basket(payoffs, market_inputs, method: MonteCarlo, ensemble: bool = False):
-    """every payoff of a basket: the path groups of basket.path_groups, then what is left (European vanillas of an expiry
-    without a group) on one simulation per expiry"""
-    from .basket import path_groups
-    payoffs = list(payoffs)
-    if not isinstance(method, MonteCarlo):
-        refuse_other_methods(market_inputs, method)
-    _structs(payoffs[:1], market_inputs, method)  # the route's refusals, before anything is grouped
-    sols: list = [None] * len(payoffs)
-    for _, idx in path_groups(payoffs, method.config.steps):
-        for i, sol in zip(idx, solve_localvol_payoffs([payoffs[i] for i in idx], market_inputs, method, ensemble)):
-            sols[i] = sol
-    rest: dict = {}
-    for i, p in enumerate(payoffs):
-        if sols[i] is None:
-            rest.setdefault(getattr(p, "expiry", None), []).append(i)
-    for idx in rest.values():
-        for i, sol in zip(idx, solve_localvol_payoffs([payoffs[i] for i in idx], market_inputs, method, ensemble)):
-            sols[i] = sol
-    return sols
+    ContinuousMonitoring() — shared by the solutions.  solve_path_payoffs held to this route: every other pair is refused."""
+    return solve_path_payoffs(payoffs, market_inputs, method, ensemble, routes().LOCALVOL)
 
 
 # ---- Dupire ------------------------------------------------------------------------------------------------------------

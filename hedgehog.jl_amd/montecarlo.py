@@ -14,7 +14,7 @@ import numpy as np
 from . import _ffi
 from .dates import yearfrac
 from .dual import Dual, n_partials, partials_of, value_of
-from .domain import (PATH_PAYOFFS, American, ArithmeticAverage, AsianOption, BarrierOption, BlackScholesInputs, Call,
+from .domain import (PATH_PAYOFFS, ArithmeticAverage, AsianOption, BarrierOption, BlackScholesInputs, Call,
                     CashOrNothing, ContinuousMonitoring, DigitalOption, DownAndIn, DownAndOut, European, HestonInputs,
                     LookbackOption, MertonInputs, BatesInputs, Monitoring,
                     MonteCarloSolution, PricingProblem, Spot, UpAndIn, UpAndOut, VanillaOption, _DeviceSamples, df,
@@ -200,28 +200,19 @@ def _model_and_config(prob: PricingProblem, method: MonteCarlo, n_paths=None, pa
     return model, c, keep, P, discount
 
 
+_ROUTES = None
+
+
+def routes():
+    """routes.py — the table of Monte Carlo routes — imported on first use: it imports this module"""
+    global _ROUTES
+    if _ROUTES is None:
+        from . import routes as _ROUTES
+    return _ROUTES
+
+
 def is_qe(method) -> bool:
     return isinstance(getattr(method, "strategy", None), HestonQE)
-
-
-def _qe_structs(prob: PricingProblem, method: MonteCarlo):
-    """(hh_model, hh_config, hh_qe) of a quadratic-exponential solve: the structs of the Euler–Maruyama Heston solve on
-    the same market (its dates and drift rate) under strategy HH_QE, and the scheme's options beside them.  Anything
-    but HestonDynamics on HestonInputs is a MethodError; so is a Dual anywhere: these solves carry no partials."""
-    import dataclasses
-    m, dyn, strat = prob.market_inputs, method.dynamics, method.strategy
-    if not (isinstance(dyn, HestonDynamics) and isinstance(m, HestonInputs)):
-        raise MethodError(f"HestonQE simulates HestonDynamics() on HestonInputs, not {type(dyn).__name__} on "
-                          f"{type(m).__name__}: use EulerMaruyama or the model's exact strategy there")
-    if method.devices is not None:
-        raise MethodError("HestonQE solves run on one device (MonteCarlo.devices is not supported)")
-    model, c, keep, P, _ = _model_and_config(prob, dataclasses.replace(method, strategy=EulerMaruyama()))
-    if P:
-        raise MethodError("HestonQE solves carry no dual partials (ForwardAD): use FiniteDifference — its solves share "
-                          "their seeds")
-    del keep
-    c.strategy = _ffi.HH_QE
-    return model, c, _ffi.make_qe(float(strat.psi_c), bool(strat.martingale))
 
 
 BATES_ROUTES = ("MonteCarlo(BatesDynamics(), HestonQE(psi_c, martingale), config) or "
@@ -233,62 +224,10 @@ def is_bates(market_inputs, method) -> bool:
     return isinstance(market_inputs, BatesInputs) or isinstance(getattr(method, "dynamics", None), BatesDynamics)
 
 
-def _require_bates_route(market_inputs, method):
-    """the one Monte Carlo route of the model, or a MethodError that names it"""
-    dyn, strat = method.dynamics, method.strategy
-    if not (isinstance(dyn, BatesDynamics) and isinstance(market_inputs, BatesInputs) and isinstance(strat, HestonQE)):
-        raise MethodError(f"no Bates solve for {type(dyn).__name__} + {type(strat).__name__} on "
-                          f"{type(market_inputs).__name__}: use {BATES_ROUTES}")
-
-
-def _bates_structs(prob: PricingProblem, method: MonteCarlo):
-    """(hh_model, hh_config, hh_qe, hh_jump) of a Bates solve: the structs of the HestonQE solve on the same market
-    without jumps (its dates and drift rate, strategy HH_QE) and the jump parameters beside them.  Every other mix of
-    dynamics, strategy and inputs is a MethodError that names the route; so is a Dual anywhere."""
-    import dataclasses
-    m = prob.market_inputs
-    _require_bates_route(m, method)
-    if method.devices is not None:
-        raise MethodError("Bates solves run on one device (MonteCarlo.devices is not supported)")
-    jumps = (m.jump_intensity, m.jump_mean, m.jump_std)
-    if any(isinstance(v, Dual) for v in jumps):
-        raise MethodError("Bates solves carry no dual partials (ForwardAD): use FiniteDifference — its solves share "
-                          "their seeds")
-    try:
-        model, c, qe = _qe_structs(PricingProblem(prob.payoff, m.heston()), dataclasses.replace(method, dynamics=HestonDynamics()))
-    except MethodError as e:
-        raise MethodError(str(e).replace("HestonQE solves", "Bates solves")) from None
-    return model, c, qe, _ffi.make_jump(*(float(v) for v in jumps))
-
-
 def is_merton(market_inputs, method) -> bool:
     """Does anything of the pair name the Merton model?  Then only the Merton routes may take it."""
     return isinstance(market_inputs, MertonInputs) or isinstance(getattr(method, "dynamics", None), MertonDynamics) or \
         isinstance(getattr(method, "strategy", None), MertonExact)
-
-
-def _merton_structs(prob: PricingProblem, method: MonteCarlo):
-    """(hh_model, hh_config, hh_jump) of a Merton solve: the structs of the lognormal solve on the same market without
-    jumps — EulerMaruyama as it stands, MertonExact as the exact law with the correct ·T drift — and the jump
-    parameters beside them.  Every other mix of dynamics, strategy and inputs is a MethodError; so is a Dual anywhere:
-    these solves carry no partials."""
-    import dataclasses
-    m, dyn, strat = prob.market_inputs, method.dynamics, method.strategy
-    if not (isinstance(dyn, MertonDynamics) and isinstance(m, MertonInputs) and isinstance(strat, (EulerMaruyama, MertonExact))):
-        raise MethodError(f"no sde_problem / marginal_law for {type(dyn).__name__} + {type(strat).__name__} on "
-                          f"{type(m).__name__}")
-    if method.devices is not None:
-        raise MethodError("Merton solves run on one device (MonteCarlo.devices is not supported)")
-    jumps = (m.jump_intensity, m.jump_mean, m.jump_std)
-    if any(isinstance(v, Dual) for v in jumps):
-        raise MethodError("Merton solves carry no dual partials: use FiniteDifference")
-    plain = dataclasses.replace(method, dynamics=LognormalDynamics(), compat_sqrt_alpha=False,
-                                strategy=strat if isinstance(strat, EulerMaruyama) else BlackScholesExact())
-    model, c, keep, P, _ = _model_and_config(PricingProblem(prob.payoff, m.black_scholes()), plain)
-    if P:
-        raise MethodError("Merton solves carry no dual partials: use FiniteDifference")
-    del keep
-    return model, c, _ffi.make_jump(*(float(v) for v in jumps))
 
 
 @dataclass(frozen=True)
@@ -327,6 +266,15 @@ def marginal_law(prob: PricingProblem, dynamics, t, compat_sqrt_alpha: bool = Tr
     return NormalLaw(dlog(m.spot) + (rate - sigma * sigma / 2) * (ra if compat_sqrt_alpha else alpha), sigma * ra)
 
 
+def _take_replay(c, replay, replay_layout):
+    """REPLAY mode where increments are given: the array the configuration points into, for the caller to keep"""
+    if replay is not None:
+        replay = np.ascontiguousarray(replay, dtype=np.float64)
+        c.noise_mode, c.replay_layout = _ffi.HH_NOISE_REPLAY, replay_layout
+        c.replay, c.replay_len = replay.ctypes.data, replay.size
+    return replay
+
+
 def _price_from(res, discount, P):
     if P == 0:
         return res.price
@@ -339,32 +287,15 @@ def solve_montecarlo(prob: PricingProblem, method: MonteCarlo, ensemble: bool = 
 
     `replay` (optional, build extension): Wiener increments to consume instead of drawing them —
     numpy array [path][step][comp] (or tile-major), the noise-replay parity mode of DESIGN.md."""
-    from .multiasset import is_multiasset, solve_multiasset
-    from .localvol import is_localvol, solve_localvol_payoffs
-    if is_multiasset([prob.payoff], prob.market_inputs, method):  # an index of several assets (hh_mc_solve_path_assets)
-        return solve_multiasset(prob, method, ensemble, replay)
-    if is_localvol(prob.market_inputs, method):  # every payoff on the path statistics (hh_mc_solve_path_lv)
-        if replay is not None:
-            raise MethodError("local-volatility solves draw their own noise: no replay")
-        return solve_localvol_payoffs([prob.payoff], prob.market_inputs, method, ensemble)[0]
-    if is_bates(prob.market_inputs, method):  # every payoff on the path statistics (hh_mc_solve_path_bates)
-        if replay is not None:
-            raise MethodError("Bates solves draw their own noise: no replay")
-        return solve_path_payoffs([prob.payoff], prob.market_inputs, method, ensemble)[0]
-    if is_qe(method):  # every payoff on the path statistics (hh_mc_solve_path_qe)
-        if replay is not None:
-            raise MethodError("HestonQE solves draw their own noise: no replay (EulerMaruyama takes one)")
-        return solve_path_payoffs([prob.payoff], prob.market_inputs, method, ensemble)[0]
-    if is_merton(prob.market_inputs, method):
-        if replay is not None:
-            raise MethodError("Merton solves draw their own noise: no replay")
-        if isinstance(method.strategy, EulerMaruyama):  # every payoff on the path statistics (hh_mc_solve_path_jump)
-            return solve_path_payoffs([prob.payoff], prob.market_inputs, method, ensemble)[0]
-        return _solve_merton_exact(prob, method, ensemble)
-    if isinstance(prob.payoff, PATH_PAYOFFS):
-        if replay is not None:
-            raise MethodError("path-dependent payoffs draw their own noise: no replay")
-        return solve_path_payoffs([prob.payoff], prob.market_inputs, method, ensemble)[0]
+    route = routes().route_of([prob.payoff], prob.market_inputs, method)
+    if route.no_replay and replay is not None:
+        raise MethodError(route.no_replay)
+    if route.solve_all:  # an index of several assets: its own grouping, then the path solve
+        return route.solve_all([prob.payoff], prob.market_inputs, method, ensemble)[0]
+    if route.law:
+        return _solve_terminal_law(route, prob, method, ensemble)
+    if route.entry:  # every payoff on the path statistics
+        return solve_path_payoffs([prob.payoff], prob.market_inputs, method, ensemble, route)[0]
     model, c, keep, P, discount = _model_and_config(prob, method)
     cfg = method.config
     if method.devices is not None:
@@ -372,12 +303,7 @@ def solve_montecarlo(prob: PricingProblem, method: MonteCarlo, ensemble: bool = 
     ctx = _ffi.get_context(method.device)
     c.seeds, c.seeds_on_device = cfg.device_seeds(ctx), 1
     c.seeds_len = cfg.seeds.size
-    if replay is not None:
-        replay = np.ascontiguousarray(replay, dtype=np.float64)
-        c.noise_mode = _ffi.HH_NOISE_REPLAY
-        c.replay_layout = replay_layout
-        c.replay = replay.ctypes.data
-        c.replay_len = replay.size
+    replay = _take_replay(c, replay, replay_layout)
     anti = bool(c.antithetic)
     term_dev, fetch = None, None
     n_paths = int(c.n_paths)
@@ -398,19 +324,19 @@ def solve_montecarlo(prob: PricingProblem, method: MonteCarlo, ensemble: bool = 
                               std_error=res.std_error, result=res)
 
 
-def _solve_merton_exact(prob: PricingProblem, method: MonteCarlo, ensemble: bool = True) -> MonteCarloSolution:
-    """MonteCarlo(MertonDynamics(), MertonExact(), config) on a European vanilla: the terminal law (hh_mc_solve_jump)."""
+def _solve_terminal_law(route, prob: PricingProblem, method: MonteCarlo, ensemble: bool = True) -> MonteCarloSolution:
+    """A European vanilla on a route that samples the law at expiry (MertonExact: hh_mc_solve_jump)."""
     if isinstance(method.strategy, MertonExact) and isinstance(prob.payoff, PATH_PAYOFFS):
-        raise MethodError("MertonExact samples the law at expiry: path-dependent payoffs need EulerMaruyama paths")
-    model, c, jump = _merton_structs(prob, method)
+        raise MethodError(route.no_paths)
+    model, c, extras = route.form_structs(prob.payoff, prob.market_inputs, method)
     cfg = method.config
     ctx = _ffi.get_context(method.device)
     c.seeds, c.seeds_on_device, c.seeds_len = cfg.device_seeds(ctx), 1, cfg.seeds.size
     n_paths, anti = int(c.n_paths), bool(c.antithetic)
     term = np.empty(n_paths * (2 if anti else 1)) if ensemble else None
     res = _ffi.hh_result()
-    ctx.check(ctx.lib.hh_mc_solve_jump(ctx.handle, C.byref(model), C.byref(jump), C.byref(c), C.byref(res),
-                                       term.ctypes.data if ensemble else None))
+    ctx.check(getattr(ctx.lib, route.entry)(ctx.handle, C.byref(model), *map(C.byref, extras), C.byref(c), C.byref(res),
+                                            term.ctypes.data if ensemble else None))
     ens = None if term is None else ((term[:n_paths], term[n_paths:]) if anti else term)
     return MonteCarloSolution(prob, method, res.price, ens, std_error=res.std_error, result=res)
 
@@ -423,17 +349,9 @@ def solve_montecarlo_many(probs, method: MonteCarlo, replay=None, replay_layout=
     problems): the caller then solves them one by one, as the reference does."""
     if not 1 < len(probs) <= _ffi.HH_MAX_MODELS:
         return None
-    from .multiasset import is_multiasset
-    if any(is_multiasset([p.payoff], p.market_inputs, method) for p in probs):  # one solve after the other, on shared seeds
-        return None
-    if any(isinstance(p.payoff, PATH_PAYOFFS) for p in probs):  # one solve after the other (hh_mc_solve_path)
-        return None
-    from .localvol import is_localvol
-    if any(is_localvol(p.market_inputs, method) for p in probs):  # no hh_mc_solve_multi form: one after the other
-        return None
-    if is_qe(method) or any(is_merton(p.market_inputs, method) or is_bates(p.market_inputs, method) for p in probs):
-        # no hh_mc_solve_multi form: one after the other
-        return None
+    route_of = routes().route_of
+    if not all(route_of([p.payoff], p.market_inputs, method).multi for p in probs):  # no hh_mc_solve_multi form: one solve
+        return None                                                                     # after the other, on shared seeds
     packed = [_model_and_config(p, method) for p in probs]
     if any(P for _, _, _, P, _ in packed):
         return None
@@ -449,10 +367,7 @@ def solve_montecarlo_many(probs, method: MonteCarlo, replay=None, replay_layout=
                 for k, p in enumerate(probs)]
     ctx = _ffi.get_context(method.device)
     c.seeds, c.seeds_on_device, c.seeds_len = cfg.device_seeds(ctx), 1, cfg.seeds.size
-    if replay is not None:
-        replay = np.ascontiguousarray(replay, dtype=np.float64)
-        c.noise_mode, c.replay_layout = _ffi.HH_NOISE_REPLAY, replay_layout
-        c.replay, c.replay_len = replay.ctypes.data, replay.size
+    replay = _take_replay(c, replay, replay_layout)
     models = (_ffi.hh_model * len(probs))(*[m for m, _, _, _, _ in packed])
     res = (_ffi.hh_result * len(probs))()
     ctx.check(ctx.lib.hh_mc_solve_multi(ctx.handle, models, len(probs), C.byref(c), res, None))
@@ -493,7 +408,7 @@ def pack_path_payoff(payoff) -> _ffi.hh_path_payoff:
     q = _ffi.hh_path_payoff()
     fields = [getattr(payoff, n, 0.0) for n in ("strike", "barrier", "rebate")] + [getattr(getattr(payoff, "payout", None), "cash", 0.0)]
     if any(isinstance(v, Dual) for v in fields):
-        raise MethodError("path-dependent payoffs carry no dual partials: use FiniteDifference")
+        raise MethodError(routes().EULER.no_duals)
     q.strike, q.cp = float(0.0 if payoff.strike is None else payoff.strike), payoff.call_put()
     if isinstance(payoff, LookbackOption):  # strike=None: floating, the strike field is not read
         q.kind = _ffi.HH_PAYOFF_LOOKBACK_FLOAT if payoff.strike is None else _ffi.HH_PAYOFF_LOOKBACK_FIXED
@@ -515,33 +430,14 @@ def pack_path_payoff(payoff) -> _ffi.hh_path_payoff:
     return q
 
 
-def _path_structs(payoffs, market_inputs, method: MonteCarlo):
-    """(hh_model, hh_config, monitor_every, include_start, hh_jump or None) of payoffs that share an expiry and a
-    monitoring.  The model and configuration are those of a European solve to that expiry (its strike and cp are not
-    read); Merton inputs bring their jump parameters, a HestonQE strategy its hh_qe in the same place, a Bates solve the
-    pair (hh_qe, hh_jump)."""
-    bates = is_bates(market_inputs, method)
-    if bates:
-        _require_bates_route(market_inputs, method)
-        for p in payoffs:
-            if isinstance(getattr(p, "exercise_style", None), American):
-                raise MethodError("American exercise is not offered on Bates paths (no LSM on them): European payoffs on "
-                                  + BATES_ROUTES)
-            if isinstance(getattr(p, "monitoring", None), ContinuousMonitoring):
-                raise MethodError("ContinuousMonitoring() is not offered on Bates paths (a bridge between two states is "
-                                  "wrong once a jump lies between them): monitor on the dates of a Monitoring")
-    elif is_qe(method):
-        for p in payoffs:
-            if isinstance(getattr(p, "exercise_style", None), American):
-                raise MethodError("American exercise is not offered on HestonQE paths: use LSM(HestonDynamics(), "
-                                  "EulerMaruyama() | HestonBroadieKaya(), …)")
-            if isinstance(getattr(p, "monitoring", None), ContinuousMonitoring):
-                raise MethodError("ContinuousMonitoring() is not offered on HestonQE paths (the step's interpolation is "
-                                  "no frozen-coefficient bridge): monitor on the dates of a Monitoring, or use EulerMaruyama()")
-    elif not isinstance(method.strategy, EulerMaruyama):
-        raise MethodError(f"path-dependent payoffs need EulerMaruyama paths, not {type(method.strategy).__name__}")
-    if method.devices is not None:
-        raise MethodError("path-dependent payoffs run on one device (MonteCarlo.devices is not supported)")
+def _path_structs(payoffs, market_inputs, method: MonteCarlo, route=None):
+    """(hh_model, hh_config, monitor_every, include_start, extras) of payoffs that share an expiry and a monitoring, after
+    the refusals of the route (routes.py; None: the one solve_path_payoffs finds).  The model and configuration are those
+    of a European solve to that expiry on the route's plain market (its strike and cp are not read); `extras` are the
+    structs the route brings, in the C argument order."""
+    route = route or routes().path_route_of(payoffs, market_inputs, method)
+    for refuse in route.early:
+        refuse(route, payoffs, market_inputs, method)
     expiries = {p.expiry for p in payoffs}
     if len(expiries) != 1:
         raise ValueError("payoffs of one path solve share an expiry")
@@ -551,67 +447,45 @@ def _path_structs(payoffs, market_inputs, method: MonteCarlo):
         raise ValueError("payoffs of one path solve share a monitoring")
     every, start = mons.pop() if mons else (steps, False)
     european = VanillaOption(1.0, expiries.pop(), European(), Call(), Spot())
-    if bates:
-        model, c, qe, jump = _bates_structs(PricingProblem(european, market_inputs), method)
-        return model, c, every, start, (qe, jump)
-    if is_qe(method):
-        model, c, qe = _qe_structs(PricingProblem(european, market_inputs), method)
-        return model, c, every, start, qe
-    if is_merton(market_inputs, method):
-        model, c, jump = _merton_structs(PricingProblem(european, market_inputs), method)
-        return model, c, every, start, jump
-    model, c, keep, P, discount = _model_and_config(PricingProblem(european, market_inputs), method)
-    if P:  # the policy of every full-path entry point: never drop partials silently
-        raise MethodError("path-dependent payoffs carry no dual partials: use FiniteDifference")
-    del keep
-    return model, c, every, start, None
+    model, c, extras = route.form_structs(european, market_inputs, method)
+    return model, c, every, start, extras
 
 
-def solve_path_payoffs(payoffs, market_inputs, method: MonteCarlo, ensemble: bool = True):
+def solve_path_payoffs(payoffs, market_inputs, method: MonteCarlo, ensemble: bool = True, route=None):
     """Payoffs that share an expiry, a monitoring and an extremes mode on ONE simulation: a MonteCarloSolution each, in
-    order.  hh_mc_solve_path as long as no payoff is a lookback or continuously monitored; hh_mc_solve_path_ex otherwise.
+    order.  `route` (routes.py) says what is refused, which structs travel and which entry point takes them; None: local
+    volatility, Bates, HestonQE or Merton jumps where the inputs or the method name one, else the Euler paths of the plain
+    models (hh_mc_solve_path as long as no payoff is a lookback or continuously monitored; hh_mc_solve_path_ex otherwise).
     `ensemble`: the (5, n_total) statistics of the trajectories — (7, n_total) in bridge mode — (rows: enum
-    hh_path_stat), shared by the solutions; n_total counts the antithetic mirrors, columns trajectories + i.
-    A HestonQE strategy: hh_mc_solve_path_qe, the monitored rows only.
-    BatesDynamics on BatesInputs under a HestonQE strategy: hh_mc_solve_path_bates, the monitored rows only.
-    Merton inputs: hh_mc_solve_path_jump, the monitored rows only — ContinuousMonitoring is a MethodError, a bridge
-    between two states being wrong once a jump lies between them."""
-    model, c, every, start, jump = _path_structs(payoffs, market_inputs, method)
-    if isinstance(jump, tuple):  # Bates: both
-        qe, jump = jump
-    else:
-        qe, jump = (jump, None) if isinstance(jump, _ffi.hh_qe) else (None, jump)
-    modes = {e for e in (path_extremes(p) for p in payoffs) if e is not None}
+    hh_path_stat), shared by the solutions; n_total counts the antithetic mirrors, columns trajectories + i."""
+    route = route or routes().path_route_of(payoffs, market_inputs, method)
+    return run_paths(route, payoffs, market_inputs, method, ensemble, _path_structs(payoffs, market_inputs, method, route))
+
+
+def run_paths(route, payoffs, market_inputs, method, ensemble, structs, inner=None):
+    """Every hh_mc_solve_path* call of the host: `structs` as _path_structs returns them, on the route's entry point;
+    `inner`: the payoffs on the path statistics where those of the problem wrap them (IndexOption)."""
+    model, c, every, start, extras = structs
+    inner = inner or payoffs
+    modes = {e for e in (path_extremes(p) for p in inner) if e is not None}
     if len(modes) > 1:
         raise ValueError("payoffs of one path solve share an extremes mode (Monitoring or ContinuousMonitoring)")
     extremes = modes.pop() if modes else _ffi.HH_EXTREMES_MONITORED
     bridge = extremes == _ffi.HH_EXTREMES_BRIDGE
-    if jump is not None and qe is None and bridge:
-        raise MethodError("ContinuousMonitoring is not offered under Merton jumps: monitor on the dates of a Monitoring")
-    extended = bridge or any(isinstance(p, LookbackOption) for p in payoffs)
-    packed = (_ffi.hh_path_payoff * len(payoffs))(*[pack_path_payoff(p) for p in payoffs])
+    if bridge and route.no_bridge:
+        raise MethodError(route.no_bridge)
+    packed = (_ffi.hh_path_payoff * len(inner))(*[pack_path_payoff(p) for p in inner])
+    entry, mode = route.entry, (extremes,) if route.takes_extremes else ()
+    if route.entry_ex and (bridge or any(isinstance(p, LookbackOption) for p in inner)):
+        entry, mode = route.entry_ex, (extremes,)
     cfg = method.config
     ctx = _ffi.get_context(method.device)
     c.seeds, c.seeds_on_device, c.seeds_len = cfg.device_seeds(ctx), 1, cfg.seeds.size
     n_total = int(c.n_paths) * (2 if c.antithetic else 1)
     stats = np.empty((_ffi.HH_PATH_STATS_BRIDGE if bridge else _ffi.HH_PATH_STATS, n_total)) if ensemble else None
-    res = (_ffi.hh_result * len(payoffs))()
-    if qe is not None and jump is not None:
-        ctx.check(ctx.lib.hh_mc_solve_path_bates(ctx.handle, C.byref(model), C.byref(qe), C.byref(jump), C.byref(c), every,
-                                                 int(start), packed, len(payoffs), res, None,
-                                                 stats.ctypes.data if ensemble else None, None))
-    elif qe is not None:
-        ctx.check(ctx.lib.hh_mc_solve_path_qe(ctx.handle, C.byref(model), C.byref(qe), C.byref(c), every, int(start), packed,
-                                              len(payoffs), res, None, stats.ctypes.data if ensemble else None, None))
-    elif jump is not None:
-        ctx.check(ctx.lib.hh_mc_solve_path_jump(ctx.handle, C.byref(model), C.byref(jump), C.byref(c), every, int(start),
-                                                packed, len(payoffs), res, None, stats.ctypes.data if ensemble else None))
-    elif extended:
-        ctx.check(ctx.lib.hh_mc_solve_path_ex(ctx.handle, C.byref(model), C.byref(c), every, int(start), extremes, packed,
-                                              len(payoffs), res, None, stats.ctypes.data if ensemble else None))
-    else:
-        ctx.check(ctx.lib.hh_mc_solve_path(ctx.handle, C.byref(model), C.byref(c), every, int(start), packed,
-                                           len(payoffs), res, None, stats.ctypes.data if ensemble else None))
+    res = (_ffi.hh_result * len(inner))()
+    ctx.check(getattr(ctx.lib, entry)(ctx.handle, C.byref(model), *map(C.byref, extras), C.byref(c), every, int(start), *mode,
+                                      packed, len(inner), res, None, stats.ctypes.data if ensemble else None, *route.tail))
     return [MonteCarloSolution(PricingProblem(p, market_inputs), method, res[k].price, stats,
                                std_error=res[k].std_error, result=res[k]) for k, p in enumerate(payoffs)]
 
@@ -623,10 +497,7 @@ def _solve_multi_gpu(prob, method, model, c, P, discount, ensemble, replay, repl
     cfg = method.config
     mg = _ffi.get_multi_gpu(tuple(method.devices))
     c.seeds, c.seeds_len = cfg.seeds.ctypes.data, cfg.seeds.size
-    if replay is not None:
-        replay = np.ascontiguousarray(replay, dtype=np.float64)
-        c.noise_mode, c.replay_layout = _ffi.HH_NOISE_REPLAY, replay_layout
-        c.replay, c.replay_len = replay.ctypes.data, replay.size
+    replay = _take_replay(c, replay, replay_layout)
     n, anti = int(c.n_paths), bool(c.antithetic)
     term = np.empty(n * (2 if anti else 1), dtype=np.float64) if ensemble else None
     res = mg.solve(model, c, term)

@@ -12,24 +12,19 @@ partials: Greeks come from FiniteDifference through AssetSpotLens, AssetVolLens 
 """
 from __future__ import annotations
 
-import ctypes as C
 import math
 from dataclasses import dataclass
 from typing import Any
 
-import numpy as np
-
 from . import _ffi
 from .dates import to_ticks, yearfrac
-from .domain import (PATH_PAYOFFS, American, ContinuousMonitoring, European, FlatRateCurve, MonteCarloSolution, PricingProblem,
-                     RateCurve, Spot, VanillaOption, df, zero_rate)
+from .domain import (PATH_PAYOFFS, American, AsianOption, ContinuousMonitoring, European, FlatRateCurve, GeometricAverage, RateCurve,
+                     Spot, VanillaOption, df, zero_rate)
 from .dual import Dual, value_of
-from .montecarlo import Antithetic, EulerMaruyama, MethodError, MonteCarlo, pack_path_payoff, path_monitoring
+from .montecarlo import Antithetic, MethodError, MonteCarlo, path_monitoring, routes, run_paths
 
 ROUTES = ("MonteCarlo(MultiAssetDynamics(), EulerMaruyama(), config) or MultiAssetAnalytic() on "
           "PricingProblem(IndexOption(index, payoff), MultiAssetInputs(…))")
-NO_DUALS = ("multi-asset solves carry no dual partials (ForwardAD): use FiniteDifference with AssetSpotLens, AssetVolLens or "
-            "CorrelationLens — its solves share their seeds")
 
 
 class MultiAssetDynamics:
@@ -204,32 +199,31 @@ def payoffs_of(prob):
 # ---- the route ----------------------------------------------------------------------------------------------------------------
 
 def _require_route(payoffs, m, method):
-    """every refusal that needs no device, or nothing"""
+    """every refusal that needs no device, or nothing; the words are the route's (routes.MULTIASSET)"""
+    rt = routes()
+    route = rt.MULTIASSET
     if not isinstance(method, MonteCarlo):
-        raise MethodError(f"{type(method).__name__} does not price multi-asset problems: use {ROUTES}")
-    dyn, strat = method.dynamics, method.strategy
-    if not (isinstance(m, MultiAssetInputs) and isinstance(dyn, MultiAssetDynamics) and isinstance(strat, EulerMaruyama)):
-        raise MethodError(f"no multi-asset solve for {type(dyn).__name__} + {type(strat).__name__} on {type(m).__name__}: "
-                          f"use {ROUTES}")
+        raise MethodError(route.other_methods.format(type(method).__name__))
+    rt.admitted(route, payoffs, m, method)
     for p in payoffs:
         if not isinstance(p, IndexOption):
             raise MethodError(f"a {type(p).__name__} names no index of the assets of MultiAssetInputs: wrap it in "
                               "IndexOption(index, payoff)")
         q = p.payoff
         if isinstance(getattr(q, "exercise_style", None), American):
-            raise MethodError("American exercise is not offered on an index of several assets: European payoffs on " + ROUTES)
+            raise MethodError(route.no_american)
         if isinstance(q, VanillaOption) and not (isinstance(q.exercise_style, European) and isinstance(q.underlying, Spot)):
             raise MethodError("an IndexOption takes a European VanillaOption on Spot")
         if isinstance(getattr(q, "monitoring", None), ContinuousMonitoring):
-            raise MethodError("ContinuousMonitoring() is not offered on an index of several assets (no bridge form): monitor "
-                              "on the dates of a Monitoring")
+            raise MethodError(route.no_continuous)
     if method.devices is not None:
-        raise MethodError("multi-asset solves run on one device (MonteCarlo.devices is not supported)")
+        raise MethodError(route.one_device)
     flat = list(m.spots) + list(m.sigmas) + [t for row in m.correlation for t in row] + [zero_rate(m.rate, 0.0)]
     for p in payoffs:
         flat += list(p.index.weights or ())
     if any(isinstance(t, Dual) for t in flat):
-        raise MethodError(NO_DUALS)
+        raise MethodError(route.no_duals)
+    return route
 
 
 def index_weights(index, d):
@@ -260,17 +254,16 @@ def index_groups(options, steps):
     return [(k, sorted(idx)) for k, idx in groups.items()]
 
 
-def _solve_group(key, options, m, method, ensemble):
+def _solve_group(route, key, options, m, method, ensemble):
+    """one pass: the options of one index that share an expiry and a monitoring.  The model carries the dates and the curve
+    alone, the assets everything else: formed here, by hand."""
     index, expiry, mon = key
     cfg = method.config
-    every, start = mon if mon is not None else (cfg.steps, False)
     inner = [o.payoff for o in options]
-    packed = (_ffi.hh_path_payoff * len(inner))(*[pack_path_payoff(q) for q in inner])
     if index.kind == _ffi.HH_INDEX_WEIGHTED_SUM and any(w < 0.0 for w in index_weights(index, m.n_assets)) and \
-            any(q.kind == _ffi.HH_PAYOFF_ASIAN_GEOM for q in packed):
+            any(isinstance(q, AsianOption) and isinstance(q.averaging, GeometricAverage) for q in inner):
         raise MethodError("a geometric Asian on a WeightedSum with a negative weight: the index may be <= 0, where its "
                           "logarithm is not defined")
-    assets = pack_assets(index, m)
     model = _ffi.hh_model()
     model.T = float(yearfrac(m.referenceDate, expiry))
     model.r_drift = float(zero_rate(m.rate, 0.0))
@@ -280,32 +273,19 @@ def _solve_group(key, options, m, method, ensemble):
     c.dynamics, c.strategy, c.noise_mode = _ffi.HH_LOGNORMAL, _ffi.HH_EULER_MARUYAMA, _ffi.HH_NOISE_GENERATE
     c.antithetic = int(isinstance(cfg.variance_reduction, Antithetic))
     c.n_steps, c.n_paths = cfg.steps, cfg.trajectories
-    ctx = _ffi.get_context(method.device)
-    c.seeds, c.seeds_on_device, c.seeds_len = cfg.device_seeds(ctx), 1, cfg.seeds.size
-    n_total = int(c.n_paths) * (2 if c.antithetic else 1)
-    stats = np.empty((_ffi.HH_PATH_STATS, n_total)) if ensemble else None
-    res = (_ffi.hh_result * len(inner))()
-    ctx.check(ctx.lib.hh_mc_solve_path_assets(ctx.handle, C.byref(model), C.byref(assets), C.byref(c), every, int(start), packed,
-                                              len(inner), res, None, stats.ctypes.data if ensemble else None))
-    return [MonteCarloSolution(PricingProblem(o, m), method, res[k].price, stats, std_error=res[k].std_error, result=res[k])
-            for k, o in enumerate(options)]
+    every, start = mon if mon is not None else (cfg.steps, False)
+    return run_paths(route, options, m, method, ensemble, (model, c, every, start, (pack_assets(index, m),)), inner)
 
 
 def solve_index_options(options, market_inputs, method, ensemble: bool = True):
     """IndexOptions on one market under one method: a MonteCarloSolution each, in order.  `ensemble`: the (5, n_total)
     statistics of the index (rows: enum hh_path_stat), shared by the solutions of a pass."""
     options = list(options)
-    _require_route(options, market_inputs, method)
+    route = _require_route(options, market_inputs, method)
     for o in options:  # sizes, before any device is touched
         index_weights(o.index, market_inputs.n_assets)
     sols: list = [None] * len(options)
     for key, idx in index_groups(options, method.config.steps):
-        for i, sol in zip(idx, _solve_group(key, [options[i] for i in idx], market_inputs, method, ensemble)):
+        for i, sol in zip(idx, _solve_group(route, key, [options[i] for i in idx], market_inputs, method, ensemble)):
             sols[i] = sol
     return sols
-
-
-def solve_multiasset(prob: PricingProblem, method, ensemble: bool = True, replay=None) -> MonteCarloSolution:
-    if replay is not None:
-        raise MethodError("multi-asset solves draw their own noise: no replay")
-    return solve_index_options([prob.payoff], prob.market_inputs, method, ensemble)[0]

@@ -20,6 +20,7 @@ mp = pytest.importorskip("mpmath")
 import hedgehog_jl_amd as hh  # noqa: E402
 from hedgehog_jl_amd import _ffi  # noqa: E402
 from hedgehog_jl_amd import montecarlo as hmc  # noqa: E402
+from hedgehog_jl_amd import routes  # noqa: E402
 from tests import bates_cases as bt  # noqa: E402
 from tests import merton_cases as mc  # noqa: E402
 from tests import oracle_ffi  # noqa: E402
@@ -261,7 +262,7 @@ def test_inputs_and_structs():
     assert "BatesDynamics" in hh.solve.__doc__ and "BatesInputs" in hh.solve.__doc__
     curve = hh.RateCurve(REF, [0.5, 6.0], zeros=[0.01, 0.04])
     mkt = hh.BatesInputs(REF, curve, 100.0, 0.04, 0.3, 0.04, 0.9, -0.5, 0.8, -0.1, 0.15)
-    model, c, q, j = hmc._bates_structs(hh.PricingProblem(vanilla(), mkt), _mc(hh.BatesDynamics(), hh.HestonQE(1.25, True), steps=12))
+    model, c, (q, j) = routes.BATES.form_structs(vanilla(), mkt, _mc(hh.BatesDynamics(), hh.HestonQE(1.25, True), steps=12))
     assert (c.dynamics, c.strategy, c.n_steps, c.n_partials, c.antithetic) == (_ffi.HH_HESTON, _ffi.HH_QE, 12, 0, 0)
     assert model.r_drift == hh.zero_rate(curve, 0.0) and model.T == hh.yearfrac(REF, EXP) and model.discount == hh.df(curve, EXP)
     assert (model.V0, model.kappa, model.theta, model.sigma, model.rho) == (0.04, 0.3, 0.04, 0.9, -0.5)
@@ -318,7 +319,7 @@ def test_basket_groups_share_one_simulation(monkeypatch):
                hh.BarrierOption(100.0, 80.0, EXP, hh.Call(), hh.DownAndOut(), monitoring=hh.Monitoring(2))]
     calls = []
 
-    def fake_paths(group, market_inputs, method, ensemble=True):
+    def fake_paths(group, market_inputs, method, ensemble=True, route=None):
         calls.append([payoffs.index(p) if p in payoffs else p.strike for p in group])
         return [hh.MonteCarloSolution(hh.PricingProblem(p, market_inputs), method, 0.0) for p in group]
 

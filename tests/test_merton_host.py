@@ -18,6 +18,7 @@ mp = pytest.importorskip("mpmath")
 import hedgehog_jl_amd as hh  # noqa: E402
 from hedgehog_jl_amd import _ffi  # noqa: E402
 from hedgehog_jl_amd import montecarlo as hmc  # noqa: E402
+from hedgehog_jl_amd import routes  # noqa: E402
 from tests import merton_cases as mc  # noqa: E402
 from tests import oracle_ffi  # noqa: E402
 from tests.conftest import host_env  # noqa: E402
@@ -256,11 +257,11 @@ def test_structs_of_a_merton_solve():
     curve = hh.RateCurve(REF, [0.5, 2.0], zeros=[0.01, 0.04])
     mi = hh.MertonInputs(REF, curve, 100.0, 0.2, 0.8, -0.1, 0.15)
     prob = hh.PricingProblem(vanilla(), mi)
-    model, c, jump = hmc._merton_structs(prob, _mc(hh.MertonDynamics(), hh.MertonExact(), compat_sqrt_alpha=True))
+    model, c, (jump,) = routes.MERTON_LAW.form_structs(prob.payoff, mi, _mc(hh.MertonDynamics(), hh.MertonExact(), compat_sqrt_alpha=True))
     assert (c.dynamics, c.strategy, c.compat_sqrt_alpha, c.n_partials) == (mc.GBM, mc.EXACT, 0, 0)
     assert model.r_drift == hh.zero_rate(curve, EXP) and model.T == hh.yearfrac(REF, EXP) and model.sigma == 0.2
     assert (jump.lambda_, jump.mu_j, jump.sigma_j) == (0.8, -0.1, 0.15)
-    model, c, jump = hmc._merton_structs(prob, _mc(hh.MertonDynamics(), hh.EulerMaruyama(), steps=12))
+    model, c, (jump,) = routes.MERTON.form_structs(prob.payoff, mi, _mc(hh.MertonDynamics(), hh.EulerMaruyama(), steps=12))
     assert (c.dynamics, c.strategy, c.n_steps) == (mc.GBM, mc.EULER, 12) and model.r_drift == hh.zero_rate(curve, 0.0)
     assert model.discount == hh.df(curve, EXP)
 
@@ -276,7 +277,7 @@ def test_basket_grouping(monkeypatch):
                hh.BarrierOption(100.0, 80.0, EXP, hh.Call(), hh.DownAndOut(), monitoring=hh.Monitoring(2))]
     calls = []
 
-    def fake_paths(group, market_inputs, method, ensemble=True):
+    def fake_paths(group, market_inputs, method, ensemble=True, route=None):
         calls.append(("path", [payoffs.index(p) for p in group]))
         assert market_inputs is mi
         return [hh.MonteCarloSolution(hh.PricingProblem(p, market_inputs), method, 0.0) for p in group]

@@ -20,6 +20,7 @@ mp = pytest.importorskip("mpmath")
 import hedgehog_jl_amd as hh  # noqa: E402
 from hedgehog_jl_amd import _ffi  # noqa: E402
 from hedgehog_jl_amd import montecarlo as hmc  # noqa: E402
+from hedgehog_jl_amd import routes  # noqa: E402
 from tests import oracle_ffi  # noqa: E402
 from tests import qe_cases as qc  # noqa: E402
 from tests.conftest import host_env  # noqa: E402
@@ -271,7 +272,7 @@ def test_strategy_and_structs():
             hh.HestonQE(psi_c=bad)
     curve = hh.RateCurve(REF, [0.5, 6.0], zeros=[0.01, 0.04])
     mkt = hh.HestonInputs(REF, curve, 100.0, 0.04, 0.3, 0.04, 0.9, -0.5)
-    model, c, q = hmc._qe_structs(hh.PricingProblem(vanilla(), mkt), _mc(hh.HestonDynamics(), hh.HestonQE(1.25, True), steps=12))
+    model, c, (q,) = routes.QE.form_structs(vanilla(), mkt, _mc(hh.HestonDynamics(), hh.HestonQE(1.25, True), steps=12))
     assert (c.dynamics, c.strategy, c.n_steps, c.n_partials, c.antithetic) == (_ffi.HH_HESTON, _ffi.HH_QE, 12, 0, 0)
     assert model.r_drift == hh.zero_rate(curve, 0.0) and model.T == hh.yearfrac(REF, EXP) and model.discount == hh.df(curve, EXP)
     assert (model.V0, model.kappa, model.theta, model.sigma, model.rho) == (0.04, 0.3, 0.04, 0.9, -0.5)
@@ -310,7 +311,7 @@ def test_basket_groups_share_one_simulation(monkeypatch):
                hh.BarrierOption(100.0, 80.0, EXP, hh.Call(), hh.DownAndOut(), monitoring=hh.Monitoring(2))]
     calls = []
 
-    def fake_paths(group, market_inputs, method, ensemble=True):
+    def fake_paths(group, market_inputs, method, ensemble=True, route=None):
         calls.append([payoffs.index(p) if p in payoffs else p.strike for p in group])
         return [hh.MonteCarloSolution(hh.PricingProblem(p, market_inputs), method, 0.0) for p in group]
 
