@@ -126,23 +126,23 @@ def _fma(a, b, c):
     return float(Fraction(a) * Fraction(b) + Fraction(c))
 
 
-def jump_of(case, N, z, num):
+def jump_of(case, N, z, num, mut=None):
     """J = (σ_J·√N)·z + N·μ_J as a qe_cases.VA: value and a from tests/merton_cases._jump, b by qe_cases' rules on the
-    same operations.  In floats the value is the device's: one fma."""
+    same operations.  In floats the value is the device's: one fma.  mut "sqrt_N": N in place of √N."""
     c = {k: bc.VA(num(case[k])) for k in ("sigma_j", "mu_j")}
-    J = mc._jump(c, int(N), bc.VA(z.v, z.a), num)
+    J = mc._jump(c, int(N), bc.VA(z.v, z.a), num, mut)
     n = VA(num(float(N)))
     Jq = (VA(num(case["sigma_j"])) * qc._sqrt(n)) * z + n * VA(num(case["mu_j"]))
     v = J.v
     if num is float:
-        v = _fma(case["sigma_j"] * math.sqrt(float(N)), z.v, float(N) * case["mu_j"])
+        v = _fma(case["sigma_j"] * (float(N) if mut == "sqrt_N" else math.sqrt(float(N))), z.v, float(N) * case["mu_j"])
     return VA(v, J.a, Jq.b)
 
 
 def walk(case, n_steps, num, d, i, N, mirror, mart, record=None, mut=None, psi_c=0.0):
     """one member of trajectory i on the draws d and the jump counts N[k]: -> (xs, v_T), xs the log spot a date after
     step k would see, as VAs"""
-    q = constants(case, n_steps, num, psi_c, mut)
+    q = constants(case, n_steps, num, 0.0 if mut == "psi_fixed" else psi_c, mut)
     x, v = qc._log_input(num, case["S0"]), VA(num(case["V0"]))
     xs = []
     for k in range(n_steps):
@@ -150,11 +150,11 @@ def walk(case, n_steps, num, d, i, N, mirror, mart, record=None, mut=None, psi_c
         u = VA(num(float(d["U"][i][k])))
         if mirror:
             zv, zx, u = -zv, -zx, q["one"] - u
-        x, v = qc.step(q, x, v, zv, zx, u, mart, num, record)
+        x, v = qc.step(q, x, v, zv, zx, u, mart, num, record, mut if mut in qc.MUTATIONS + qc.SWEEP_MUTATIONS else None)
         seen = x
         if N[k] > 0:
             z = VA(num(d["zJ"][i][k]))
-            x = x + jump_of(case, N[k], -z if mirror and mut != "keep_z" else z, num)
+            x = x + jump_of(case, N[k], -z if mirror and mut != "keep_z" else z, num, mut)
         xs.append(seen if mut == "late_jump" else x)
     return xs, v
 
@@ -172,10 +172,11 @@ def _float_draws(d, i):
     return dict(Z={i: [(float(a), float(b)) for a, b in d["Z"][i]]}, U=d["U"], zJ={i: [float(z) for z in d["zJ"][i]]})
 
 
-def walks(case, n_steps, d, N, anti, mart, n=None, check=True):
+def walks(case, n_steps, d, N, anti, mart, n=None, check=True, psi_c=0.0, unusable=None, mut=None):
     """both runs of every member of the first n trajectories -> [member][path] of (xs_mp, vT_mp, xs_64, vT_64), and what
-    the members saw: QE branches and jump counts"""
+    the members saw: QE branches and jump counts; `check` and `unusable` as qe_cases.walks takes them"""
     n = len(d["Z"]) if n is None else n
+    threshold = 1.5 if psi_c == 0.0 else psi_c
     members = 2 if anti else 1
     out = [[None] * n for _ in range(members)]
     seen = dict(quadratic=0, exponential=0, zero=0, N={})
@@ -184,12 +185,15 @@ def walks(case, n_steps, d, N, anti, mart, n=None, check=True):
             d64 = _float_draws(d, i)
             for m in range(members):
                 rm, r6 = [], []
-                xs_mp, v_mp = walk(case, n_steps, mp.mpf, d, i, N[i], m == 1, mart, rm)
-                xs_64, v_64 = walk(case, n_steps, float, d64, i, N[i], m == 1, mart, r6)
-                if check:
+                xs_mp, v_mp = walk(case, n_steps, mp.mpf, d, i, N[i], m == 1, mart, rm, mut, psi_c)
+                xs_64, v_64 = walk(case, n_steps, float, d64, i, N[i], m == 1, mart, r6, mut, psi_c)
+                if check and unusable is not None:
+                    if not qc.same_branches(rm, r6, threshold):
+                        unusable.add(i)
+                elif check:
                     for (psi, quad, zero, du), (_, quad6, zero6, _) in zip(rm, r6):
                         assert quad == quad6 and zero == zero6, (i, m)
-                        assert abs(psi - mp.mpf(1.5)) > qc.MARGIN and (du is None or abs(du) > qc.MARGIN), (i, m, psi, du)
+                        assert abs(psi - mp.mpf(threshold)) > qc.MARGIN and (du is None or abs(du) > qc.MARGIN), (i, m, psi, du)
                 for _, quad, zero, _ in rm:
                     seen["quadratic" if quad else "exponential"] += 1
                     seen["zero"] += bool(zero)

@@ -228,11 +228,16 @@ def path_normals(oracle, seeds, N):
                  for k in range(len(N[i]))] for i, s in enumerate(seeds)]
 
 
-def counts_of(U, mean):
-    """the exact jump count of every uniform; every uniform keeps MARGIN from every cumulative boundary (asserted)"""
+def counts_of(U, mean, unusable=None):
+    """the exact jump count of every uniform; every uniform keeps MARGIN from every cumulative boundary (asserted) — or,
+    given a set `unusable`, the first index (the trajectory) of a uniform that does not is added to it"""
     N = np.empty(U.shape, dtype=np.int64)
     for idx, u in np.ndenumerate(U):
         N[idx], dist = poisson_exact(float(u), mean)
+        if unusable is not None:
+            if dist < MARGIN or N[idx] != poisson_fp64(float(u), mean):
+                unusable.add(idx[0])
+            continue
         assert dist >= MARGIN, (idx, float(u), mean, dist)
         assert N[idx] == poisson_fp64(float(u), mean)
     return N
@@ -256,10 +261,10 @@ def _model(case, num):
     return c
 
 
-def _jump(c, N, z, num):
-    """J = (σ_J·√N)·z + N·μ_J"""
+def _jump(c, N, z, num, mut=None):
+    """J = (σ_J·√N)·z + N·μ_J; mut "sqrt_N" (qe_cases.SWEEP_MUTATIONS): N in place of √N"""
     n = VA(num(float(N)))
-    return (c["sigma_j"] * _sqrt(n)) * z + n * c["mu_j"]
+    return (c["sigma_j"] * (n if mut == "sqrt_N" else _sqrt(n))) * z + n * c["mu_j"]
 
 
 def terminal_member(case, num, z1, z2, N, mirror):

@@ -28,6 +28,10 @@ exceed MARGIN at every step.
 MUTATIONS of the restatement (tests/test_qe_host.py holds each to the golden values): `mut` names one of
   swap_K   K1 and K2 exchanged            b_not_b2  a = m/(1 + b)             p_over_psi  p = (ψ − 1)/ψ
   keep_U   the mirror keeps U             K3_full   the correction with K3 for K3/2
+Three more that only a sweep over model values can see (SWEEP_MUTATIONS; tests/test_path_sweep_host.py): the golden models
+run at ψ_c = 1.5 with |ρ| < 1, where the first two change nothing
+  psi_fixed  ψ_c ignored: 1.5 always      var_floor  K3·v + K4·v′ floored at VAR_FLOOR before its root
+  sqrt_N     (tests/merton_cases._jump, tests/bates_cases.jump_of) N in place of sqrt((double)N)
 """
 import json
 import os
@@ -45,6 +49,8 @@ DOM_QE = 5
 MARGIN = 1e-9
 DPS = ex.DPS
 MUTATIONS = ("swap_K", "b_not_b2", "p_over_psi", "keep_U", "K3_full")
+SWEEP_MUTATIONS = ("psi_fixed", "var_floor", "sqrt_N")
+VAR_FLOOR = 1e-12
 
 # the model of the issue's first section (2κθ = 0.024 against σ² = 0.81: far inside the region Euler is biased in)
 LAW = dict(S0=100.0, V0=0.04, kappa=0.3, theta=0.04, sigma=0.9, rho=-0.5, r_drift=0.0, T=5.0)
@@ -233,13 +239,16 @@ def step(q, x, v, zv, zx, U, mart, num, record=None, mut=None):
         k13 = q["K1"] + q["K3"] if mut == "K3_full" else q["k13"]
         k0 = -lnM - k13 * v
     drift = ((q["rdt"] + k0) + K1 * v) + K2 * vn
-    xn = (x + drift) + _sqrt(q["K3"] * v + q["K4"] * vn) * zx
+    w = q["K3"] * v + q["K4"] * vn
+    if mut == "var_floor" and w.v < VAR_FLOOR:
+        w = VA(num(VAR_FLOOR))
+    xn = (x + drift) + _sqrt(w) * zx
     return xn, vn
 
 
 def walk(case, n_steps, num, Z, U, mirror, mart, record=None, mut=None, psi_c=0.0):
     """one member of one trajectory: -> (xs, v_T): the log spot after every step and the variance at expiry, as VAs"""
-    q = constants(case, n_steps, num, psi_c)
+    q = constants(case, n_steps, num, 0.0 if mut == "psi_fixed" else psi_c)
     x, v = _log_input(num, case["S0"]), VA(num(case["V0"]))
     xs = []
     for k in range(n_steps):
@@ -271,10 +280,18 @@ def rows_of(case, xs, num, monitor_every, include_start):
     return rows
 
 
-def walks(case, n_steps, Z, U, anti, mart, n=None, mut=None, check=True):
+def same_branches(rm, r6, psi_c):
+    """the records of a 50-digit and an fp64 walk: the same branches, |ψ − ψ_c| and |U − p| above MARGIN at every step"""
+    return all(quad == quad6 and zero == zero6 and abs(psi - mp.mpf(psi_c)) > MARGIN and (du is None or abs(du) > MARGIN)
+               for (psi, quad, zero, du), (_, quad6, zero6, _) in zip(rm, r6))
+
+
+def walks(case, n_steps, Z, U, anti, mart, n=None, mut=None, check=True, psi_c=0.0, unusable=None):
     """both runs of every member of the first n trajectories -> list [member][path] of (xs_mp, vT_mp, xs_64, vT_64) and
-    the branch counts; `check`: the two runs take the same branches with MARGIN to spare (asserted)"""
+    the branch counts; `check`: the two runs take the same branches with MARGIN to spare (asserted) — or, given a set
+    `unusable`, the index of a trajectory that does not is added to it and the walk goes on"""
     n = len(Z) if n is None else n
+    threshold = 1.5 if psi_c == 0.0 else psi_c
     members = 2 if anti else 1
     out = [[None] * n for _ in range(members)]
     counts = dict(quadratic=0, exponential=0, zero=0)
@@ -283,12 +300,15 @@ def walks(case, n_steps, Z, U, anti, mart, n=None, mut=None, check=True):
             Z64 = [(float(a), float(b)) for a, b in Z[i]]
             for m in range(members):
                 rm, r6 = [], []
-                xs_mp, v_mp = walk(case, n_steps, mp.mpf, Z[i], U[i], m == 1, mart, rm, mut)
-                xs_64, v_64 = walk(case, n_steps, float, Z64, U[i], m == 1, mart, r6, mut)
-                if check:
+                xs_mp, v_mp = walk(case, n_steps, mp.mpf, Z[i], U[i], m == 1, mart, rm, mut, psi_c)
+                xs_64, v_64 = walk(case, n_steps, float, Z64, U[i], m == 1, mart, r6, mut, psi_c)
+                if check and unusable is not None:
+                    if not same_branches(rm, r6, threshold):
+                        unusable.add(i)
+                elif check:
                     for (psi, quad, zero, du), (_, quad6, zero6, _) in zip(rm, r6):
                         assert quad == quad6 and zero == zero6, (i, m)
-                        assert abs(psi - mp.mpf(1.5)) > MARGIN and (du is None or abs(du) > MARGIN), (i, m, psi, du)
+                        assert abs(psi - mp.mpf(threshold)) > MARGIN and (du is None or abs(du) > MARGIN), (i, m, psi, du)
                 for _, quad, zero, _ in rm:
                     counts["quadratic" if quad else "exponential"] += 1
                     counts["zero"] += bool(zero)
