@@ -29,6 +29,7 @@ from .multiasset import (BestOf, GeometricMean, IndexOption, MultiAssetDynamics,
 from .localvol import (LocalVolDynamics, LocalVolInputs, LocalVolSurface, dupire_from, dupire_local_vol, get_local_vol,
                        refuse_other_methods, solve_localvol_payoffs)
 from .qmc import (BrownianBridge, Incremental, QuasiMonteCarlo, QuasiMonteCarloSolution, SobolConfig, solve_qmc)
+from .mlmc import MLMCConfig, MultilevelLevel, MultilevelMonteCarlo, MultilevelSolution, solve_mlmc
 from .distributed import rank_device, shard_range, solve_lsm_sharded, solve_sharded
 from .domain import (American, ArithmeticAverage, AsianOption, AssetOrNothing, BarrierOption, BatesInputs, BlackScholesInputs,
                     Call, CashOrNothing, ContinuousMonitoring, DigitalOption, DownAndIn, DownAndOut, European,
@@ -66,6 +67,9 @@ def solve(*args, **kw):
         solve(prob::PricingProblem{<:VanillaOption{…,European,…,Spot}}, ::QuasiMonteCarlo(dynamics, strategy, SobolConfig(…)))
                                   randomised Sobol' points through the REPLAY solve: LognormalDynamics with BlackScholesExact
                                   or EulerMaruyama, HestonDynamics with EulerMaruyama (no reference method)
+        solve(prob::PricingProblem, ::MultilevelMonteCarlo(dynamics, EulerMaruyama(), MLMCConfig(steps, …)))
+                                  multilevel Monte Carlo on coupled Euler levels of steps·2^l steps: European vanillas and the
+                                  path-dependent payoffs under a Monitoring, lognormal or Heston (no reference method)
         solve(prob::PricingProblem{<:VanillaOption{…,American,…}}, ::LSM)     least_squares_montecarlo.jl:99
         solve(prob::PricingProblem{<:VanillaOption}, ::CoxRossRubinsteinMethod) cox_ross_rubinstein.jl:99
         solve(prob::BasketPricingProblem, ::CoxRossRubinsteinMethod)         basket.jl:35
@@ -80,6 +84,10 @@ def solve(*args, **kw):
         if kw:
             raise MethodError(f"QuasiMonteCarlo fills its own REPLAY buffer and takes no {sorted(kw)}: {SUPPORTED}")
         return solve_qmc(args[0], args[1])
+    if len(args) == 2 and isinstance(args[0], (PricingProblem, BasketPricingProblem)) and isinstance(args[1], MultilevelMonteCarlo):
+        from .mlmc import check_supported  # every refusal of this method names what it does price
+        check_supported(args[0], args[1], kw)
+        return solve_mlmc(args[0], args[1])
     if len(args) == 2 and isinstance(args[0], (PricingProblem, BasketPricingProblem)):
         payoffs = multiasset.payoffs_of(args[0])
         if isinstance(args[0], PricingProblem) and isinstance(args[1], MultiAssetAnalytic) and \

@@ -190,6 +190,11 @@ SYMBOLS = [
                                       C.c_int32, C.POINTER(hh_result)]),
     ("hh_mc_solve_path_ex", C.c_int, [_vp, C.POINTER(hh_model), C.POINTER(hh_config), C.c_uint32, C.c_int32, C.c_int32,
                                       C.POINTER(hh_path_payoff), C.c_uint32, C.POINTER(hh_result), _vp, _vp]),
+    ("hh_mc_path_stats_coupled", C.c_int, [_vp, C.POINTER(hh_model), C.POINTER(hh_config), C.c_uint32, C.c_int32, _vp,
+                                           C.c_int32, C.POINTER(hh_result)]),
+    ("hh_mc_solve_path_coupled", C.c_int, [_vp, C.POINTER(hh_model), C.POINTER(hh_config), C.c_uint32, C.c_int32,
+                                           C.POINTER(hh_path_payoff), C.c_uint32, C.POINTER(hh_result), C.POINTER(hh_result),
+                                           _vp, _vp]),
     ("hh_mc_solve_jump", C.c_int, [_vp, C.POINTER(hh_model), C.POINTER(hh_jump), C.POINTER(hh_config), C.POINTER(hh_result),
                                    _vp]),
     ("hh_mc_solve_path_jump", C.c_int, [_vp, C.POINTER(hh_model), C.POINTER(hh_jump), C.POINTER(hh_config), C.c_uint32,

@@ -1488,7 +1488,8 @@ static int stage_localvol(hh_ctx* ctx, const hh_localvol* lv, double T, uint32_t
 
 // The path-statistics family: which kernel an entry point runs and what travels with it — one constructor per kernel.
 struct PathFamily {
-  enum Kernel { kEuler, kJump, kQe, kBates, kAssets, kLocalVol } kernel;
+  enum Kernel { kEuler, kJump, kQe, kBates, kAssets, kLocalVol, kCoupled } kernel;
+  enum CoupledForm { kCoupledForm };  // names the constructor of the coupled form
   const char* who;                           // the entry point, as its messages name it
   int32_t last_kind;                         // the last payoff kind it admits (the solve forms)
   int32_t extremes = HH_EXTREMES_MONITORED;  // enum hh_path_extremes: the bridge form is path_stats_kernel's alone
@@ -1514,6 +1515,13 @@ struct PathFamily {
   // extremes forms; model->sigma is not read
   PathFamily(const char* w, int32_t last, const hh_localvol* lv, int32_t ext)
       : kernel(kLocalVol), who(w), last_kind(last), extremes(ext), localvol(lv), missing(!lv) {}
+  // coupled_stats_kernel: path_stats_kernel's monitored trajectories on cfg->n_steps steps, each with its partner on
+  // half as many steps and the summed increments (multilevel Monte Carlo)
+  PathFamily(const char* w, int32_t last, CoupledForm) : kernel(kCoupled), who(w), last_kind(last) {}
+  // the rows and columns of the statistics: the coupled form's are the antithetic layout's
+  hh::PathStatsLayout layout(const hh_config* c) const {
+    return hh::PathStatsLayout(c->n_paths, c->antithetic != 0 || kernel == kCoupled, path_stat_rows(extremes));
+  }
 };
 
 // The checks of every entry point, then the statistics of every trajectory into ctx->path_stats (one timing slot) and,
@@ -1534,7 +1542,8 @@ static int run_path_stats(hh_ctx* ctx, const PathFamily& f, const hh_model* m, c
   bool ok = false;
   const char* needs = kAnyEm;
   switch (f.kernel) {
-    case PathFamily::kEuler: ok = em && (logn || hest); break;
+    case PathFamily::kEuler:
+    case PathFamily::kCoupled: ok = em && (logn || hest); break;
     case PathFamily::kJump:  // dynamics that are neither are told what the plain entry points tell them
       ok = em && logn;
       if (hest || !em) needs = kLognEm;
@@ -1553,6 +1562,9 @@ static int run_path_stats(hh_ctx* ctx, const PathFamily& f, const hh_model* m, c
   if (!ok) return fail(ctx, HH_ERR_UNSUPPORTED, "%s needs %s", who, needs);
   if (c->noise_mode == HH_NOISE_REPLAY || c->n_partials != 0)
     return fail(ctx, HH_ERR_UNSUPPORTED, "%s: GENERATE noise, no dual partials", who);
+  const bool coupled = f.kernel == PathFamily::kCoupled;
+  if (coupled && c->antithetic)
+    return fail(ctx, HH_ERR_UNSUPPORTED, "%s: no antithetic pairs (the second column of a trajectory is its coarse partner)", who);
   if (c->noise_mode != HH_NOISE_GENERATE) return fail(ctx, HH_ERR_INVALID, "unknown noise_mode %d", c->noise_mode);
   if (f.extremes != HH_EXTREMES_MONITORED && f.extremes != HH_EXTREMES_BRIDGE)
     return fail(ctx, HH_ERR_INVALID, "%s: unknown extremes %d", who, f.extremes);
@@ -1561,6 +1573,9 @@ static int run_path_stats(hh_ctx* ctx, const PathFamily& f, const hh_model* m, c
   if (monitor_every == 0 || c->n_steps % monitor_every != 0)
     return fail(ctx, HH_ERR_INVALID, "%s: monitor_every (%u) must be >= 1 and divide n_steps (%u)", who, monitor_every,
                 c->n_steps);
+  if (coupled && ((c->n_steps & 1u) || (monitor_every & 1u)))
+    return fail(ctx, HH_ERR_INVALID, "%s: n_steps (%u, the fine grid) and monitor_every (%u) must be even: the coarse grid "
+                "has half the steps and the same dates", who, c->n_steps, monitor_every);
   if (f.assets) {
     if (!(m->T > 0.0) || !std::isfinite(m->T) || !std::isfinite(m->r_drift) || !std::isfinite(m->discount))
       return fail(ctx, HH_ERR_INVALID, "%s: T > 0, r_drift and discount finite", who);
@@ -1576,7 +1591,7 @@ static int run_path_stats(hh_ctx* ctx, const PathFamily& f, const hh_model* m, c
   hh_model m_c = *m;  // Bates: the step's constants, and their checks, on the compensated rate
   if (f.jump && f.qe) m_c.r_drift = m->r_drift - hh::merton_compensator(*f.jump);
   if (f.qe && (rc = check_qe(ctx, who, &m_c, c, f.qe))) return rc;
-  const hh::PathStatsLayout at(c->n_paths, c->antithetic != 0, path_stat_rows(f.extremes));
+  const hh::PathStatsLayout at = f.layout(c);
   if ((rc = ensure(ctx, ctx->path_stats, at.total))) return rc;
   if (f.qe && f.var_T && (rc = ensure(ctx, ctx->heston_var, (size_t)at.n_total))) return rc;
   const uint64_t* seeds_dev = nullptr;
@@ -1608,6 +1623,9 @@ static int run_path_stats(hh_ctx* ctx, const PathFamily& f, const hh_model* m, c
       HH_HIP(ctx, hh::launch_localvol_stats(*m, *c, lv_args, seeds_dev, monitor_every, start, f.extremes == HH_EXTREMES_BRIDGE,
                                             ctx->path_stats, ctx->stream));
       break;
+    case PathFamily::kCoupled:
+      HH_HIP(ctx, hh::launch_coupled_stats(*m, *c, seeds_dev, monitor_every, start, ctx->path_stats, ctx->stream));
+      break;
   }
   return end_timing(ctx);
 }
@@ -1624,7 +1642,7 @@ static int path_stats_call(hh_ctx* ctx, const PathFamily& f, const hh_model* m, 
   int rc = run_path_stats(ctx, f, m, c, monitor_every, include_start);
   if (rc) return rc;
   HH_HIP(ctx, hipEventRecord(ctx->ev1, ctx->stream));
-  const hh::PathStatsLayout at(c->n_paths, c->antithetic != 0, path_stat_rows(f.extremes));
+  const hh::PathStatsLayout at = f.layout(c);
   HH_HIP(ctx, hipMemcpyAsync(stats, ctx->path_stats, at.total * sizeof(double),
                              stats_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, ctx->stream));
   if (f.var_T)
@@ -1651,14 +1669,10 @@ int hh_mc_path_stats_ex(hh_ctx* ctx, const hh_model* m, const hh_config* c, uint
 
 // the solve entry points: hh_mc_solve_path (kinds up to HH_PAYOFF_DIGITAL_ASSET) and its _ex, _jump, _qe, _bates and
 // _assets forms (the lookbacks too) — the payoffs on the statistics, under kPathAssets those of the index
-static int solve_path_call(hh_ctx* ctx, const PathFamily& f, const hh_model* m, const hh_config* c, uint32_t monitor_every,
-                           int32_t include_start, const hh_path_payoff* payoffs, uint32_t n_payoffs, hh_result* out,
-                           double* path_values, double* stats) {
-  if (!ctx) return HH_ERR_INVALID;
-  std::lock_guard<std::recursive_mutex> lock__(ctx->mu);
+// the payoffs of a solve entry point, checked before anything runs
+static int check_path_payoffs(hh_ctx* ctx, const PathFamily& f, const hh_path_payoff* payoffs, uint32_t n_payoffs) {
   const char* who = f.who;
   const hh_assets* assets = f.assets;
-  if (!m || !c || !payoffs || !out || f.missing) return fail(ctx, HH_ERR_INVALID, "%s: NULL argument", who);
   if (n_payoffs == 0 || n_payoffs > HH_MAX_PATH_PAYOFFS)
     return fail(ctx, HH_ERR_INVALID, "%s: 1 .. %d payoffs", who, HH_MAX_PATH_PAYOFFS);
   for (uint32_t k = 0; k < n_payoffs; ++k) {
@@ -1677,13 +1691,26 @@ static int solve_path_call(hh_ctx* ctx, const PathFamily& f, const hh_model* m, 
                       "%s: payoff %u: a geometric Asian on a weighted sum with a negative weight: the sum of logarithms "
                       "is not defined where the index is <= 0", who, k);
   }
+  return HH_OK;
+}
+
+// The coupled form (level_payoff_kernel) leaves 2·n_payoffs accumulators — those of Y = p_f − p_c, for `out`, then those of
+// p_f, for out_fine (nullable).
+static int solve_path_call(hh_ctx* ctx, const PathFamily& f, const hh_model* m, const hh_config* c, uint32_t monitor_every,
+                           int32_t include_start, const hh_path_payoff* payoffs, uint32_t n_payoffs, hh_result* out,
+                           double* path_values, double* stats, hh_result* out_fine = nullptr) {
+  if (!ctx) return HH_ERR_INVALID;
+  std::lock_guard<std::recursive_mutex> lock__(ctx->mu);
+  const char* who = f.who;
+  if (!m || !c || !payoffs || !out || f.missing) return fail(ctx, HH_ERR_INVALID, "%s: NULL argument", who);
+  int rc = check_path_payoffs(ctx, f, payoffs, n_payoffs);
+  if (rc) return rc;
   const WallClock clock;
   HH_HIP(ctx, hipSetDevice(ctx->device));
   HH_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-  int rc = run_path_stats(ctx, f, m, c, monitor_every, include_start);
-  if (rc) return rc;
+  if ((rc = run_path_stats(ctx, f, m, c, monitor_every, include_start))) return rc;
 
-  const hh::PathStatsLayout at(c->n_paths, c->antithetic != 0, path_stat_rows(f.extremes));
+  const hh::PathStatsLayout at = f.layout(c);
   hh::PathPayoffArgs b{};
   b.stats = ctx->path_stats;
   b.n_paths = c->n_paths;
@@ -1692,16 +1719,19 @@ static int solve_path_call(hh_ctx* ctx, const PathFamily& f, const hh_model* m, 
   b.extremes = f.extremes;
   b.n_mon = (double)(c->n_steps / monitor_every + (include_start ? 1u : 0u));
   if ((rc = stage_host(ctx, ctx->path_payoffs, (size_t)n_payoffs, payoffs, (size_t)n_payoffs, &b.payoffs))) return rc;
-  const size_t n_acc = (size_t)n_payoffs * HH_ACC_LEN;
-  if ((rc = ensure(ctx, ctx->basket_records, (size_t)n_payoffs * b.n_chunks * hh::kRecStride))) return rc;
+  const bool coupled = f.kernel == PathFamily::kCoupled;
+  const uint32_t n_groups = coupled ? 2u * n_payoffs : n_payoffs;
+  const size_t n_acc = (size_t)n_groups * HH_ACC_LEN;
+  if ((rc = ensure(ctx, ctx->basket_records, (size_t)n_groups * b.n_chunks * hh::kRecStride))) return rc;
   if ((rc = ensure(ctx, ctx->basket_accum, n_acc))) return rc;
   if (path_values && (rc = ensure(ctx, ctx->path_values, (size_t)n_payoffs * at.n_total))) return rc;
   b.values = path_values ? ctx->path_values.p : nullptr;
   b.records = ctx->basket_records;
   if ((rc = begin_timing(ctx))) return rc;
-  HH_HIP(ctx, hh::launch_path_payoffs(b, n_payoffs, ctx->stream));
+  if (coupled) HH_HIP(ctx, hh::launch_level_payoffs(b, n_payoffs, ctx->stream));
+  else HH_HIP(ctx, hh::launch_path_payoffs(b, n_payoffs, ctx->stream));
   HH_HIP(ctx, hh::launch_reduce_records(ctx->basket_records, b.n_chunks, (double)c->n_paths, ctx->basket_accum,
-                                        ctx->stream, n_payoffs));
+                                        ctx->stream, n_groups));
   if ((rc = end_timing(ctx))) return rc;
   HH_HIP(ctx, hipEventRecord(ctx->ev1, ctx->stream));
   std::vector<double> host(n_acc);
@@ -1718,6 +1748,8 @@ static int solve_path_call(hh_ctx* ctx, const PathFamily& f, const hh_model* m, 
   double kernel_ms, total_ms;
   if ((rc = solve_times(ctx, clock, &kernel_ms, &total_ms))) return rc;
   rc = finalize_results(m, 0, c, host.data(), n_payoffs, kernel_ms, total_ms, out);
+  if (!rc && coupled && out_fine)
+    rc = finalize_results(m, 0, c, host.data() + (size_t)n_payoffs * HH_ACC_LEN, n_payoffs, kernel_ms, total_ms, out_fine);
   return rc ? fail(ctx, rc, "finalize failed: the accumulator holds no trajectories") : HH_OK;
 }
 
@@ -1733,6 +1765,21 @@ int hh_mc_solve_path_ex(hh_ctx* ctx, const hh_model* m, const hh_config* c, uint
                         double* path_values, double* stats) {
   return solve_path_call(ctx, {"hh_mc_solve_path_ex", HH_PAYOFF_LOOKBACK_FIXED, extremes}, m, c, monitor_every,
                          include_start, payoffs, n_payoffs, out, path_values, stats);
+}
+
+// ---- multilevel Monte Carlo (hedgehog_mc.h, "Multilevel Monte Carlo"; kernels: hh_path.hip) ----
+
+int hh_mc_path_stats_coupled(hh_ctx* ctx, const hh_model* m, const hh_config* c, uint32_t monitor_every,
+                             int32_t include_start, double* stats, int32_t stats_on_device, hh_result* out) {
+  return path_stats_call(ctx, {"hh_mc_path_stats_coupled", 0, PathFamily::kCoupledForm}, m, c, monitor_every, include_start,
+                         stats, stats_on_device, out);
+}
+
+int hh_mc_solve_path_coupled(hh_ctx* ctx, const hh_model* m, const hh_config* c, uint32_t monitor_every,
+                             int32_t include_start, const hh_path_payoff* payoffs, uint32_t n_payoffs, hh_result* out_diff,
+                             hh_result* out_fine, double* path_values, double* stats) {
+  return solve_path_call(ctx, {"hh_mc_solve_path_coupled", HH_PAYOFF_LOOKBACK_FIXED, PathFamily::kCoupledForm}, m, c,
+                         monitor_every, include_start, payoffs, n_payoffs, out_diff, path_values, stats, out_fine);
 }
 
 // ---- Merton jump diffusion (hedgehog_mc.h, "Merton (1976) jump diffusion"; kernels: hh_jump.hip, hh_fourier.hip) ----

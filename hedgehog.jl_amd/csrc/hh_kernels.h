@@ -299,6 +299,14 @@ struct PathPayoffArgs {
   int extremes;                   // enum hh_path_extremes: which rows a payoff's MAX / MIN are
 };
 int launch_path_payoffs(const PathPayoffArgs& b, uint32_t n_payoffs, hipStream_t s);
+// Multilevel Monte Carlo (hh_path.hip; include/hedgehog_mc.h, "Multilevel Monte Carlo").  launch_path_stats' monitored,
+// non-antithetic trajectories (c.n_steps even: the FINE grid) in columns [0, n_paths) and, in [n_paths, 2·n_paths), those
+// of c.n_steps/2 steps on the summed increments; monitor_every even, counted in fine steps.  PathStatsLayout(n_paths, true).
+int launch_coupled_stats(const hh_model& m, const hh_config& c, const uint64_t* seeds_dev, uint32_t monitor_every,
+                         bool include_start, double* stats, hipStream_t s);
+// … and the payoffs on both legs: b as for launch_path_payoffs on that layout (antithetic and extremes are not read),
+// b.records [2·n_payoffs][n_chunks][kRecStride] — group k sums Y = p_f − p_c, group n_payoffs + k sums p_f
+int launch_level_payoffs(const PathPayoffArgs& b, uint32_t n_payoffs, hipStream_t s);
 // Merton jump diffusion (hh_jump.hip; include/hedgehog_mc.h, "Merton (1976) jump diffusion").  The scalars are checked
 // by the entry points.  λ·κ̄, the drift's compensator, as every launcher forms it: hh_jump.h's merton_compensator.
 // the terminal law: a lane takes kMertonPerLane trajectories whatever the call, a workgroup leaves one record

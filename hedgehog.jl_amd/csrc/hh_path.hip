@@ -179,7 +179,132 @@ __global__ __launch_bounds__(256) void path_payoff_kernel(const PathPayoffArgs b
   }
 }
 
+// ------------------------------------------------------------------------------------------
+// multilevel Monte Carlo: a fine and a coarse trajectory on the same draws
+// ------------------------------------------------------------------------------------------
+
+// One lane per trajectory, GENERATE noise, no LDS.  The lane carries the FINE trajectory of path_stats_kernel<M, false,
+// false> — a.n_steps steps of a.dt, the same draws, steps and dates, so column i is that kernel's bit for bit — and a
+// COARSE one of a.n_steps/2 steps of ac.dt = 2·a.dt (ac: make_args0 on the coarse grid, a plain solve's argument block
+// there to the last bit), whose increment is the sum of the fine pair's, one rounded addition per component — for
+// Heston on the correlated components.  monitor_every is even: the coarse monitor counts monitor_every/2 coarse steps,
+// both legs see the same dates.  The layout is the antithetic one: column n_paths + i is trajectory i's coarse partner.
+template <class M>
+__global__ __launch_bounds__(256) void coupled_stats_kernel(const SimArgs<0> a, const SimArgs<0> ac, const double S0,
+                                                            const uint32_t monitor_every, const int include_start,
+                                                            double* __restrict__ stats) {
+  using State = typename M::State;
+  const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= a.n_paths) return;
+  const PathStatsLayout at(a.n_paths, true);
+  const uint32_t n_coarse = ac.n_steps;  // a.n_steps / 2
+  State sf, sc;
+  M::init(sf, a);
+  M::init(sc, ac);
+  Monitor<false> mf(monitor_every, include_start), mc(monitor_every >> 1, include_start);
+  mf.start(S0, a.x0.v);
+  mc.start(S0, ac.x0.v);
+  const uint64_t key = a.seeds[i];
+  for (uint32_t j = 0; j < n_coarse; ++j) {
+    double d1a, d2a = 0.0, d1b, d2b = 0.0;
+    if constexpr (M::NCOMP == 2) {
+      euler_pair_increments(key, 2u * j, a, d1a, d2a);
+      euler_pair_increments(key, 2u * j + 1u, a, d1b, d2b);
+    } else {
+      double z1, z2;
+      euler_scalar_normals(key, j, z1, z2);  // one Philox block is one fine pair of steps
+      d1a = a.sqrt_dt * z1;
+      d1b = a.sqrt_dt * z2;
+    }
+    M::step(sf, a, d1a, d2a);
+    mf.date(sf.x.v, sf.x.v);
+    M::step(sf, a, d1b, d2b);
+    mf.date(sf.x.v, sf.x.v);
+    M::step(sc, ac, d1a + d1b, d2a + d2b);
+    mc.date(sc.x.v, sc.x.v);
+  }
+  mf.store(stats, at, i, a.n_paths);
+  mc.store(stats, at, a.n_paths + i, a.n_paths);
+}
+
+// path_payoff_kernel's sibling on coupled_stats_kernel's rows: the same block -> (chunk, payoff group) map, payoffs per
+// load and lane order.  Per trajectory and payoff p_f on the fine rows, p_c on the coarse ones and Y = p_f − p_c, one
+// rounded subtraction; Σ Y, Σ Y² into record group k and Σ p_f, Σ p_f² into group n_payoffs + k — the latter exactly as
+// path_payoff_kernel accumulates a payoff that is not antithetic, so the fine sums are a plain solve's bit for bit.
+__global__ __launch_bounds__(256) void level_payoff_kernel(const PathPayoffArgs b, const uint32_t n_payoffs) {
+  const uint32_t per_xcd = (b.n_chunks + 7u) / 8u;
+  const uint32_t xcd = blockIdx.x & 7u, idx = blockIdx.x >> 3;
+  const uint32_t grp = idx / per_xcd, chunk = (idx % per_xcd) * 8u + xcd;
+  if (chunk >= b.n_chunks) return;
+  const uint32_t k0 = grp * kPathKB;
+  hh_path_payoff q[kPathKB];
+#pragma unroll
+  for (int g = 0; g < kPathKB; ++g) q[g] = b.payoffs[min(k0 + g, n_payoffs - 1)];
+  const PathStatsLayout at(b.n_paths, true);
+  double acc_y[kPathKB][2], acc_f[kPathKB][2];
+#pragma unroll
+  for (int g = 0; g < kPathKB; ++g) acc_y[g][0] = acc_y[g][1] = acc_f[g][0] = acc_f[g][1] = 0.0;
+  const uint64_t i0 = (uint64_t)chunk * kBasketChunk;
+  for (uint32_t j = threadIdx.x; j < (uint32_t)kBasketChunk; j += 256) {
+    const uint64_t i = i0 + j;
+    if (i >= b.n_paths) break;
+    double tf[HH_PATH_STATS], tc[HH_PATH_STATS];
+#pragma unroll
+    for (int s = 0; s < HH_PATH_STATS; ++s) {
+      tf[s] = b.stats[at.row(s) + i];
+      tc[s] = b.stats[at.row(s) + b.n_paths + i];
+    }
+#pragma unroll
+    for (int g = 0; g < kPathKB; ++g) {
+      const bool live = k0 + g < n_payoffs;  // uniform over the workgroup
+      const double pf = path_payoff_of(q[g], tf, b.n_mon);
+      const double pc = path_payoff_of(q[g], tc, b.n_mon);
+      if (b.values && live) {
+        b.values[(size_t)(k0 + g) * at.n_total + i] = pf;
+        b.values[(size_t)(k0 + g) * at.n_total + b.n_paths + i] = pc;
+      }
+      const double y = pf - pc;
+      acc_y[g][0] += y;
+      acc_y[g][1] = fma(y, y, acc_y[g][1]);
+      acc_f[g][0] += pf;
+      acc_f[g][1] = fma(pf, pf, acc_f[g][1]);
+    }
+  }
+#pragma unroll
+  for (int g = 0; g < kPathKB; ++g) {
+    if (k0 + g >= n_payoffs) break;  // uniform over the workgroup
+    if (g) __syncthreads();          // the reduction's LDS staging is reused
+    block_reduce_store<2, 4, 0>(acc_y[g], b.records + ((size_t)(k0 + g) * b.n_chunks + chunk) * kRecStride);
+    __syncthreads();
+    block_reduce_store<2, 4, 0>(acc_f[g], b.records + ((size_t)(n_payoffs + k0 + g) * b.n_chunks + chunk) * kRecStride);
+  }
+}
+
 }  // namespace
+
+int launch_coupled_stats(const hh_model& m, const hh_config& c, const uint64_t* seeds_dev, uint32_t monitor_every,
+                         bool include_start, double* stats, hipStream_t s) {
+  const StatsLaunch fine(m, c, seeds_dev);
+  hh_config cc = c;
+  cc.n_steps = c.n_steps / 2;
+  const StatsLaunch coarse(m, cc, seeds_dev);
+  auto go = [&](auto model) {
+    hipLaunchKernelGGL((coupled_stats_kernel<decltype(model)>), fine.grid, fine.block, 0, s, fine.a, coarse.a, m.S0,
+                       monitor_every, (int)include_start, stats);
+  };
+  if (c.dynamics == HH_LOGNORMAL) go(GbmModel<0>{});
+  else if (c.em_split) go(HestonModel<0, true>{});
+  else go(HestonModel<0, false>{});
+  return (int)hipGetLastError();
+}
+
+int launch_level_payoffs(const PathPayoffArgs& b, uint32_t n_payoffs, hipStream_t s) {
+  const uint32_t n_groups = (n_payoffs + kPathKB - 1) / kPathKB;
+  if ((uint64_t)((b.n_chunks + 7u) / 8u) * 8u * n_groups > 0x7fffffffull) return (int)hipErrorInvalidConfiguration;
+  const dim3 grid(((b.n_chunks + 7u) / 8u) * 8u * n_groups), block(256);
+  hipLaunchKernelGGL(level_payoff_kernel, grid, block, 0, s, b, n_payoffs);
+  return (int)hipGetLastError();
+}
 
 int launch_path_stats(const hh_model& m, const hh_config& c, const uint64_t* seeds_dev, uint32_t monitor_every,
                       bool include_start, bool bridge, double* stats, hipStream_t s) {

@@ -707,6 +707,51 @@ int hh_mc_solve_path_ex(hh_ctx* ctx, const hh_model* model, const hh_config* cfg
                         hh_result* out, double* path_values, double* stats);
 
 /*
+ * Multilevel Monte Carlo (Giles 2008): one level's correction E[P_fine − P_coarse], sampled on a fine and a coarse
+ * Euler–Maruyama trajectory driven by the same Brownian increments.  The reference has no multilevel method; the
+ * conventions below are this library's.  The host method (MultilevelMonteCarlo) chooses levels and trajectory counts;
+ * these two entry points are one level.
+ *
+ * cfg->n_steps is the FINE step count, even.  Trajectory i takes seeds[i] and carries two states in one lane:
+ *   fine    n_steps steps of dt = T/n_steps, drawn, stepped and monitored exactly as hh_mc_path_stats' trajectory i:
+ *           per coarse step j, Heston takes the Philox pairs of steps 2j and 2j + 1 (correlated as there), lognormal
+ *           dynamics the one block of pair j (sqrt(dt)·z1, then sqrt(dt)·z2);
+ *   coarse  n_steps/2 steps of 2·dt on the increment dW_c = dW_a + dW_b of that fine pair — one rounded fp64 addition
+ *           per component, for Heston on the already correlated components — with the step constants a plain solve on
+ *           n_steps/2 steps forms (its dt is T/(n_steps/2), not 2·(T/n_steps)).
+ * monitor_every counts FINE steps and is even: the coarse leg monitors every monitor_every/2 of its steps, so both see
+ * the same dates; include_start is the same on both.  The statistics are HH_PATH_STATS rows (monitored extremes only) in
+ * the ANTITHETIC layout, n_total = 2·n_paths: column i is the fine trajectory, column n_paths + i its coarse partner.
+ *   hh_mc_path_stats_coupled  arguments and outputs of hh_mc_path_stats on that layout.
+ *   hh_mc_solve_path_coupled  per trajectory and payoff k (kinds 0 .. 7; the lookbacks read the monitored extremes)
+ *                             p_f on the fine rows, p_c on the coarse rows, Y = p_f − p_c (one rounded subtraction).
+ *                             out_diff[k]: price = discount·mean Y, std_error, sum_payoff = Σ Y, sumsq_payoff = Σ Y²,
+ *                             n_paths_done and the call's times; out_fine[k] (nullable array): the same on p_f.
+ *                             path_values (nullable, host): row k = p_f on columns [0, n_paths), p_c on [n_paths,
+ *                             2·n_paths); stats (nullable, host): as above.
+ * Two identities hold bit for bit:
+ *   1. Columns [0, n_paths) of the statistics are hh_mc_path_stats' on the same seeds and n_steps, and out_fine[k] is
+ *      result k of hh_mc_solve_path_ex (HH_EXTREMES_MONITORED) — price, std_error and both sums.
+ *   2. Columns [n_paths, 2·n_paths) are the statistics of a REPLAY solve on n_steps/2 steps whose increments are the
+ *      pairwise sums of hh_wiener_fill's for the fine grid (HH_STAT_SUM_X up to the rounding of log(exp(x))).
+ * A payoff's sums do not depend on what else is in the call.  Under lognormal dynamics the log-Euler step is exact in
+ * law, so the two legs' S_T differ by rounding alone and every correction is noise: multilevel is for Heston.
+ * Synchronous.  hh_ctx_enable_timing: the statistics kernel, then the payoff kernel with its record reduction; one slot
+ * for hh_mc_path_stats_coupled.
+ * HH_ERR_INVALID: n_steps odd; monitor_every odd, 0 or not a divisor of n_steps; everything hh_mc_solve_path_ex
+ * rejects.  HH_ERR_UNSUPPORTED: antithetic, REPLAY noise, dual partials, a strategy other than HH_EULER_MARUYAMA,
+ * dynamics other than HH_LOGNORMAL and HH_HESTON.
+ * Not provided: local volatility (its per-step table would be staged for two grids), Merton, QE, Bates and multi-asset
+ * paths, antithetic pairs, the bridge extremes (the two levels' bridges would have to be coupled), refinement factors
+ * other than 2, an accumulate (asynchronous) form, a multi-GPU form, a Julia binding.
+ */
+int hh_mc_path_stats_coupled(hh_ctx* ctx, const hh_model* model, const hh_config* cfg, uint32_t monitor_every,
+                             int32_t include_start, double* stats, int32_t stats_on_device, hh_result* out);
+int hh_mc_solve_path_coupled(hh_ctx* ctx, const hh_model* model, const hh_config* cfg, uint32_t monitor_every,
+                             int32_t include_start, const hh_path_payoff* payoffs, uint32_t n_payoffs,
+                             hh_result* out_diff, hh_result* out_fine, double* path_values, double* stats);
+
+/*
  * Merton (1976) jump diffusion: lognormal dynamics plus a compound Poisson sum of normal jumps in log S, the drift
  * compensated so that e^{-rt}·S stays a martingale.  The reference has no jump model (its roadmap lists "Merton model
  * with Carr–Madan, Merton model with Monte Carlo" as open); the conventions below are this library's.
