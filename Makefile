@@ -14,7 +14,7 @@ test-cpu: build
 # Then the Bates step composed from hh_qe.h and hh_jump.h (tests/c/bates_host_check.cpp): a program of its own, built
 # with -fsanitize=address,undefined by its test and run as a program — nothing preloaded, nothing loaded into python.
 # The same for the local-volatility table and for the Sobol' expansion, point rule and bridge table of hh_sobol.h
-# (tests/c/sobol_host_check.cpp).
+# (tests/c/sobol_host_check.cpp), and for the gamma sampler of hh_vg.h (tests/c/vg_host_check.cpp).
 ASAN_RT := $(shell gcc -print-file-name=libasan.so)
 test-cpu-asan:
 	$(MAKE) -C oracle -s asan
@@ -24,6 +24,7 @@ test-cpu-asan:
 	python -m pytest tests/test_bates_host.py -q -p no:cacheprovider -k step_host_program
 	python -m pytest tests/test_localvol_host.py -q -p no:cacheprovider -k host_program
 	python -m pytest tests/test_sobol_host.py -q -p no:cacheprovider -k host_program
+	python -m pytest tests/test_vg_host.py -q -p no:cacheprovider -k host_program
 
 test-gpu: build
 	python -m pytest tests -q -m gpu

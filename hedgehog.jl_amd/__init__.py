@@ -6,8 +6,9 @@ Import as `hedgehog_jl_amd` (shim at the repository root; the directory name car
 """
 from . import _ffi, multiasset, routes
 from ._ffi import Context, HedgehogMCError, get_context, load_library
-from .analytic import (AnalyticSolution, BlackScholesAnalytic, CarrMadan, MertonAnalytic, MultiAssetAnalytic, merton_series,
-                       solve_black_scholes, solve_carr_madan, solve_merton_analytic, solve_multiasset_analytic)
+from .analytic import (AnalyticSolution, BlackScholesAnalytic, CarrMadan, MertonAnalytic, MultiAssetAnalytic,
+                       VarianceGammaAnalytic, merton_series, solve_black_scholes, solve_carr_madan, solve_merton_analytic,
+                       solve_multiasset_analytic, solve_vg_analytic, vg_mixing_price)
 from .basket import BasketPricingProblem, BasketPricingSolution, solve_basket
 from .trees import CoxRossRubinsteinMethod, CRRSolution, solve_crr, solve_crr_basket
 from .pde import CrankNicolsonMethod, PDESolution, fd_inputs, solve_pde, solve_pde_basket
@@ -22,7 +23,8 @@ from .lsm import (LSM, EulerPaths, HestonExactPaths, LSMSolution, simulate_euler
                   simulate_heston_exact_paths, solve_lsm)
 from .montecarlo import (AbstractPricingMethod, Antithetic, BatesDynamics, BlackScholesExact, EulerMaruyama,
                          HestonBroadieKaya, HestonDynamics, HestonQE, LognormalDynamics, MertonDynamics, MertonExact, MethodError,
-                         MonteCarlo, NoVarianceReduction, NormalLaw, SimulationConfig, marginal_law,
+                         MonteCarlo, NoVarianceReduction, NormalLaw, SimulationConfig, VarianceGammaDynamics,
+                         VarianceGammaExact, marginal_law,
                          solve_montecarlo, solve_montecarlo_many, solve_path_payoffs)
 from .multiasset import (BestOf, GeometricMean, IndexOption, MultiAssetDynamics, MultiAssetInputs, WeightedSum, WorstOf,
                          solve_index_options)
@@ -36,7 +38,8 @@ from .domain import (American, ArithmeticAverage, AsianOption, AssetOrNothing, B
                     FlatRateCurve, FlatVolSurface, Forward, GeometricAverage, HestonInputs, LookbackOption, MertonInputs,
                     Monitoring,
                     MonteCarloSolution,
-                    PricingProblem, Put, RateCurve, Spot, UpAndIn, UpAndOut, VanillaOption, df, df_yf, get_vol,
+                    PricingProblem, Put, RateCurve, Spot, UpAndIn, UpAndOut, VanillaOption, VarianceGammaInputs, df, df_yf,
+                    get_vol,
                     spine_zeros, zero_rate, zero_rate_yf)
 
 
@@ -58,6 +61,9 @@ def solve(*args, **kw):
                                                                               Andersen's QE scheme (no reference method)
         solve(prob::PricingProblem{…, BatesInputs}, ::MonteCarlo(BatesDynamics(), HestonQE(psi_c, martingale), …)
               | ::CarrMadan(α, bound, BatesDynamics()))   Bates: Heston QE paths with Merton jumps (no reference method)
+        solve(prob::PricingProblem{…, VarianceGammaInputs} | ::BasketPricingProblem,
+              ::MonteCarlo(VarianceGammaDynamics(), VarianceGammaExact(), …) | ::CarrMadan(α, bound, VarianceGammaDynamics())
+              | ::VarianceGammaAnalytic)   Variance Gamma: gamma time-changed paths, exact on any dates (no reference method)
         solve(prob::PricingProblem{IndexOption, MultiAssetInputs} | ::BasketPricingProblem of IndexOptions,
               ::MonteCarlo(MultiAssetDynamics(), EulerMaruyama(), …) | ::MultiAssetAnalytic)
                                   several correlated assets: baskets, spreads, best-of / worst-of (no reference method)
@@ -101,6 +107,8 @@ def solve(*args, **kw):
     if len(args) == 2 and isinstance(args[0], PricingProblem) and \
             isinstance(args[1], BlackScholesAnalytic):
         return solve_black_scholes(args[0], args[1])
+    if len(args) == 2 and isinstance(args[0], PricingProblem) and isinstance(args[1], VarianceGammaAnalytic):
+        return solve_vg_analytic(args[0], args[1])
     if len(args) == 2 and isinstance(args[0], PricingProblem) and isinstance(args[1], MertonAnalytic):
         return solve_merton_analytic(args[0], args[1])
     if len(args) == 2 and isinstance(args[0], PricingProblem) and isinstance(args[1], LSM):

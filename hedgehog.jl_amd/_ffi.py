@@ -32,6 +32,7 @@ HH_PATH_STATS_BRIDGE = 7
 HH_MAX_PATH_PAYOFFS = 1024
 HH_JUMP_MAX_MEAN = 64.0
 HH_JUMP_MAX_COUNT = 255
+HH_VG_MAX_ATTEMPTS = 64
 HH_QE_MAX_PSI = 1e9
 HH_MAX_ASSETS = 8
 HH_LV_MAX_NODES = 8192
@@ -100,6 +101,11 @@ class hh_path_payoff(C.Structure):
 class hh_jump(C.Structure):
     """The Merton jump parameters: intensity λ, mean μ_J and standard deviation σ_J of one jump in log S."""
     _fields_ = [("lambda_", C.c_double), ("mu_j", C.c_double), ("sigma_j", C.c_double)]
+
+
+class hh_vg(C.Structure):
+    """The Variance Gamma parameters: drift θ of the time-changed Brownian motion and variance rate ν of the gamma clock."""
+    _fields_ = [("theta", C.c_double), ("nu", C.c_double)]
 
 
 class hh_qe(C.Structure):
@@ -201,6 +207,13 @@ SYMBOLS = [
                                         C.c_int32, C.POINTER(hh_path_payoff), C.c_uint32, C.POINTER(hh_result), _vp, _vp]),
     ("hh_carr_madan_jump", C.c_int, [_vp, C.POINTER(hh_model), C.POINTER(hh_jump), C.c_double, C.c_double,
                                      _vp, _vp, _vp, _vp, _vp, C.c_uint32, _vp]),
+    ("hh_mc_solve_vg", C.c_int, [_vp, C.POINTER(hh_model), C.POINTER(hh_vg), C.POINTER(hh_config), C.POINTER(hh_result), _vp]),
+    ("hh_mc_path_stats_vg", C.c_int, [_vp, C.POINTER(hh_model), C.POINTER(hh_vg), C.POINTER(hh_config), C.c_uint32, C.c_int32,
+                                      _vp, C.c_int32, C.POINTER(hh_result)]),
+    ("hh_mc_solve_path_vg", C.c_int, [_vp, C.POINTER(hh_model), C.POINTER(hh_vg), C.POINTER(hh_config), C.c_uint32,
+                                      C.c_int32, C.POINTER(hh_path_payoff), C.c_uint32, C.POINTER(hh_result), _vp, _vp]),
+    ("hh_carr_madan_vg", C.c_int, [_vp, C.POINTER(hh_model), C.POINTER(hh_vg), C.c_double, C.c_double,
+                                   _vp, _vp, _vp, _vp, _vp, C.c_uint32, _vp]),
     ("hh_mc_path_stats_qe", C.c_int, [_vp, C.POINTER(hh_model), C.POINTER(hh_qe), C.POINTER(hh_config), C.c_uint32,
                                       C.c_int32, _vp, C.c_int32, _vp, C.POINTER(hh_result)]),
     ("hh_mc_solve_path_qe", C.c_int, [_vp, C.POINTER(hh_model), C.POINTER(hh_qe), C.POINTER(hh_config), C.c_uint32,
@@ -591,6 +604,13 @@ def make_jump(lam=0.0, mu_j=0.0, sigma_j=0.0):
     j = hh_jump()
     j.lambda_, j.mu_j, j.sigma_j = lam, mu_j, sigma_j
     return j
+
+
+def make_vg(theta=0.0, nu=1.0):
+    """hh_vg from plain numbers"""
+    g = hh_vg()
+    g.theta, g.nu = theta, nu
+    return g
 
 
 def make_assets(spots, sigmas, weights, corr, index_kind=HH_INDEX_WEIGHTED_SUM):

@@ -8,6 +8,8 @@ so that such scripts run unchanged:
                          integral runs on the device (`hh_carr_madan`, csrc/hh_fourier.hip)
   MultiAssetAnalytic()   a European vanilla on a geometric index of several correlated lognormal assets, and Margrabe's
                          exchange option (the reference prices one underlying only): scalar code on the host
+  VarianceGammaAnalytic() a European vanilla under the Variance Gamma model (the reference has none): the Black price
+                         mixed over the gamma clock, a fixed trapezoidal rule on the host
   MertonAnalytic(n_terms) Merton's (1976) series for a European vanilla under jump diffusion (the reference has no
                          jump model): a Poisson-weighted sum of Black prices, scalar code on the host
 """
@@ -20,10 +22,10 @@ from typing import Any
 
 from . import _ffi
 from .dates import yearfrac
-from .domain import (BlackScholesInputs, European, HestonInputs, MertonInputs, PricingProblem, VanillaOption, df,
-                     get_vol, zero_rate)
-from .montecarlo import (BATES_ROUTES, AbstractPricingMethod, BatesDynamics, HestonDynamics, LognormalDynamics, MertonDynamics,
-                         MethodError, is_bates)
+from .domain import (BlackScholesInputs, European, HestonInputs, MertonInputs, PricingProblem, VanillaOption,
+                     VarianceGammaInputs, df, get_vol, zero_rate)
+from .montecarlo import (BATES_ROUTES, VG_ROUTES, AbstractPricingMethod, BatesDynamics, HestonDynamics, LognormalDynamics,
+                         MertonDynamics, MethodError, VarianceGammaDynamics, is_bates, is_vg)
 from .multiasset import GeometricMean, IndexOption, MultiAssetInputs, WeightedSum, index_weights
 from .domain import Spot
 
@@ -115,6 +117,110 @@ def solve_merton_analytic(prob: PricingProblem, method: MertonAnalytic) -> Analy
                           float(m.jump_intensity), float(m.jump_mean), float(m.jump_std), T,
                           float(df(m.rate, payoff.expiry)), method.n_terms)
     return AnalyticSolution(prob, method, price)
+
+
+# ---- Variance Gamma (include/hedgehog_mc.h, "Variance Gamma") -------------------------------------------------------
+
+@dataclass(frozen=True)
+class VarianceGammaAnalytic(AbstractPricingMethod):
+    """The gamma-mixing integral of a European vanilla: E_G[Black price given the clock G], G ~ Gamma(T/ν, ν)."""
+    n_nodes: int = 4096
+
+
+VG_MIX_CUT = 50.0  # the rule's nodes cover the clock's density down to e^-50 of its peak
+
+
+def vg_mixing_price(S0, K, cp, sigma, theta, nu, T, r, D, n_nodes=4096):
+    """D·E_G[cp·(F_G·Φ(cp·d1) − K·Φ(cp·d2))] with log F_G = log S0 + (r + ω)T + θG + σ²G/2 and log-variance σ²G over
+    G ~ Gamma(a = T/ν, scale ν), ω = log(1 − θν − σ²ν/2)/ν.  The density's g^(a−1) singularity at 0 (a < 1) goes with the
+    substitution g = ν·e^u: the weight becomes exp(a·u − e^u)/Γ(a), analytic on the whole line, decaying like e^{a·u} on
+    the left and doubly exponentially on the right, and the trapezoidal rule converges geometrically in its step.  The
+    rule is fixed: n_nodes equal steps between the two points where the weight has fallen to e^-50 of its peak at
+    u = log a, so a sharply peaked clock (ν → 0) is resolved like a diffuse one."""
+    arg = 1.0 - theta * nu - 0.5 * sigma * sigma * nu
+    if not (nu > 0.0 and arg > 0.0):
+        raise ValueError("Variance Gamma needs nu > 0 and 1 - theta nu - sigma^2 nu / 2 > 0")
+    a = T / nu
+    m0 = math.log(S0) + (r + math.log(arg) / nu) * T
+    logK = math.log(K)
+    phi = lambda u: a * u - math.exp(u)
+    u0 = math.log(a)
+    top = phi(u0)
+
+    def edge(step):  # the point on that side of the mode where phi = top − VG_MIX_CUT, by doubling then bisection
+        far = u0 + step
+        while phi(far) > top - VG_MIX_CUT:
+            step *= 2.0
+            far = u0 + step
+        near = u0
+        for _ in range(200):
+            mid = 0.5 * (near + far)
+            if phi(mid) > top - VG_MIX_CUT:
+                near = mid
+            else:
+                far = mid
+        return far
+    lo, hi = edge(-1.0), edge(1.0)
+    n = int(n_nodes)
+    h = (hi - lo) / n
+    lg = math.lgamma(a)
+    terms = []
+    for i in range(n + 1):
+        u = lo + i * h
+        g = nu * math.exp(u)
+        w = math.exp(phi(u) - lg) * (0.5 if i in (0, n) else 1.0)
+        V = sigma * sigma * g
+        M = m0 + theta * g
+        if V <= 0.0:
+            val = max(cp * (math.exp(M) - K), 0.0)
+        else:
+            sd = math.sqrt(V)
+            d2 = (M - logK) / sd
+            val = cp * (math.exp(M + 0.5 * V) * _ncdf(cp * (d2 + sd)) - K * _ncdf(cp * d2))
+        terms.append(w * val)
+    return D * math.fsum(terms) * h
+
+
+def solve_vg_analytic(prob: PricingProblem, method: VarianceGammaAnalytic) -> AnalyticSolution:
+    payoff, m = prob.payoff, prob.market_inputs
+    if not (isinstance(payoff, VanillaOption) and isinstance(payoff.exercise_style, European)
+            and isinstance(m, VarianceGammaInputs)):
+        raise MethodError("VarianceGammaAnalytic: European VanillaOption on VarianceGammaInputs")
+    T = yearfrac(m.rate.reference_date, payoff.expiry)
+    price = vg_mixing_price(float(m.spot), float(payoff.strike), payoff.call_put(), float(get_vol(m.sigma, None, None)),
+                            float(m.theta), float(m.nu), T, float(zero_rate(m.rate, payoff.expiry)),
+                            float(df(m.rate, payoff.expiry)), method.n_nodes)
+    return AnalyticSolution(prob, method, price)
+
+
+def _solve_carr_madan_vg(payoffs, m, method: CarrMadan):
+    """CarrMadan(α, bound, VarianceGammaDynamics()) on VarianceGammaInputs: every payoff's integral in one launch
+    (`hh_carr_madan_vg`).  No gradient form: a Dual anywhere is a MethodError."""
+    import numpy as np
+    from .dual import Dual
+    if not (isinstance(method.dynamics, VarianceGammaDynamics) and isinstance(m, VarianceGammaInputs)):
+        raise MethodError(f"no Variance Gamma characteristic function for {type(method.dynamics).__name__} on "
+                          f"{type(m).__name__}: use {VG_ROUTES}")
+    vol = get_vol(m.sigma, None, None)
+    r_k = [zero_rate(m.rate, p.expiry) for p in payoffs]
+    D_k = [df(m.rate, p.expiry) for p in payoffs]
+    scal = [m.spot, vol, m.theta, m.nu, *r_k, *D_k, *(p.strike for p in payoffs)]
+    if any(isinstance(v, Dual) for v in scal):
+        raise MethodError("CarrMadan under VarianceGammaDynamics carries no dual partials (ForwardAD): use FiniteDifference")
+    model = _ffi.hh_model()
+    model.S0, model.sigma = float(m.spot), float(vol)
+    vg = _ffi.make_vg(float(m.theta), float(m.nu))
+    K = len(payoffs)
+    strikes = np.array([float(p.strike) for p in payoffs])
+    cps = np.array([p.call_put() for p in payoffs], dtype=np.float64)
+    Ts = np.array([yearfrac(m.rate.reference_date, p.expiry) for p in payoffs])
+    rs, Ds = np.array([float(x) for x in r_k]), np.array([float(x) for x in D_k])
+    out = np.empty(K)
+    ctx = _ffi.get_context(method.device)
+    ctx.check(ctx.lib.hh_carr_madan_vg(ctx.handle, C.byref(model), C.byref(vg), float(method.α), float(method.bound),
+                                       strikes.ctypes.data, cps.ctypes.data, Ts.ctypes.data, rs.ctypes.data,
+                                       Ds.ctypes.data, K, out.ctypes.data))
+    return out
 
 
 def _solve_carr_madan_merton(payoffs, m, method: CarrMadan):
@@ -213,6 +319,8 @@ def solve_carr_madan_basket(payoffs, market_inputs, method: CarrMadan):
     from .dual import Dual, n_partials, partials_of, value_of
     if is_bates(m, method):
         return _solve_carr_madan_bates(payoffs, m, method)
+    if is_vg(m, method):
+        return _solve_carr_madan_vg(payoffs, m, method)
     if isinstance(method.dynamics, MertonDynamics) or isinstance(m, MertonInputs):
         return _solve_carr_madan_merton(payoffs, m, method)
     model, dyn, scal = _carr_madan_model(m, method)
@@ -255,6 +363,8 @@ def solve_carr_madan(prob: PricingProblem, method: CarrMadan) -> AnalyticSolutio
     from .dual import n_partials
     if is_bates(m, method):  # a basket of one
         return AnalyticSolution(prob, method, float(_solve_carr_madan_bates([payoff], m, method)[0]))
+    if is_vg(m, method):  # a basket of one
+        return AnalyticSolution(prob, method, float(_solve_carr_madan_vg([payoff], m, method)[0]))
     if isinstance(method.dynamics, MertonDynamics) or isinstance(m, MertonInputs):  # a basket of one
         return AnalyticSolution(prob, method, float(_solve_carr_madan_merton([payoff], m, method)[0]))
     model, dyn, scal = _carr_madan_model(m, method)

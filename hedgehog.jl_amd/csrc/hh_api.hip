@@ -1383,6 +1383,22 @@ static int check_jump(hh_ctx* ctx, const char* who, const hh_jump* jump, double 
   return HH_OK;
 }
 
+// The parameters of a Variance Gamma entry point (`who`) with the model's σ; p: the moment of S_T the entry point needs
+// finite — 1 for the martingale compensator ω, 1 + α under the damped transform.
+static int check_vg(hh_ctx* ctx, const char* who, const hh_model* m, const hh_vg* vg, double p) {
+  if (!(vg->nu > 0.0) || !std::isfinite(vg->nu)) return fail(ctx, HH_ERR_INVALID, "%s: vg nu must be finite and > 0", who);
+  if (!std::isfinite(vg->theta)) return fail(ctx, HH_ERR_INVALID, "%s: vg theta must be finite", who);
+  if (!(m->sigma >= 0.0)) return fail(ctx, HH_ERR_INVALID, "%s: sigma must be >= 0", who);
+  if (!(hh::vg_moment_arg(m->sigma, *vg, 1.0) > 0.0))
+    return fail(ctx, HH_ERR_INVALID, "%s: 1 - theta nu - sigma^2 nu / 2 = %g must be > 0 (E S_T is infinite otherwise)", who,
+                hh::vg_moment_arg(m->sigma, *vg, 1.0));
+  if (p != 1.0 && !(hh::vg_moment_arg(m->sigma, *vg, p) > 0.0))
+    return fail(ctx, HH_ERR_INVALID,
+                "%s: 1 - theta nu (1 + alpha) - sigma^2 nu (1 + alpha)^2 / 2 = %g must be > 0 (the damped transform needs the "
+                "(1 + alpha)-th moment)", who, hh::vg_moment_arg(m->sigma, *vg, p));
+  return HH_OK;
+}
+
 // The assets and the index of a multi-asset entry point (`who`): everything that does not depend on the model or the
 // configuration, the positive definiteness of the correlation matrix included.
 static int check_assets(hh_ctx* ctx, const char* who, const hh_assets* as) {
@@ -1488,7 +1504,7 @@ static int stage_localvol(hh_ctx* ctx, const hh_localvol* lv, double T, uint32_t
 
 // The path-statistics family: which kernel an entry point runs and what travels with it — one constructor per kernel.
 struct PathFamily {
-  enum Kernel { kEuler, kJump, kQe, kBates, kAssets, kLocalVol, kCoupled } kernel;
+  enum Kernel { kEuler, kJump, kQe, kBates, kAssets, kLocalVol, kCoupled, kVg } kernel;
   enum CoupledForm { kCoupledForm };  // names the constructor of the coupled form
   const char* who;                           // the entry point, as its messages name it
   int32_t last_kind;                         // the last payoff kind it admits (the solve forms)
@@ -1497,6 +1513,7 @@ struct PathFamily {
   const hh_qe* qe = nullptr;
   const hh_assets* assets = nullptr;
   const hh_localvol* localvol = nullptr;
+  const hh_vg* vg = nullptr;
   double* var_T = nullptr;  // host, nullable: the variance at expiry of every member (the QE step)
   bool missing = false;     // a struct the kernel needs came as NULL: the entry point's "NULL argument"
   // path_stats_kernel: lognormal or Heston dynamics by Euler–Maruyama
@@ -1518,6 +1535,8 @@ struct PathFamily {
   // coupled_stats_kernel: path_stats_kernel's monitored trajectories on cfg->n_steps steps, each with its partner on
   // half as many steps and the summed increments (multilevel Monte Carlo)
   PathFamily(const char* w, int32_t last, CoupledForm) : kernel(kCoupled), who(w), last_kind(last) {}
+  // vg_stats_kernel: the Variance Gamma increments, exact in law on any dates — lognormal dynamics, HH_EXACT_LAW
+  PathFamily(const char* w, int32_t last, const hh_vg* g) : kernel(kVg), who(w), last_kind(last), vg(g), missing(!g) {}
   // the rows and columns of the statistics: the coupled form's are the antithetic layout's
   hh::PathStatsLayout layout(const hh_config* c) const {
     return hh::PathStatsLayout(c->n_paths, c->antithetic != 0 || kernel == kCoupled, path_stat_rows(extremes));
@@ -1558,6 +1577,10 @@ static int run_path_stats(hh_ctx* ctx, const PathFamily& f, const hh_model* m, c
       ok = hest && c->strategy == HH_QE;
       needs = "HestonDynamics + the quadratic-exponential strategy (HH_QE)";
       break;
+    case PathFamily::kVg:
+      ok = logn && c->strategy == HH_EXACT_LAW;
+      needs = "LognormalDynamics + the exact law (HH_EXACT_LAW)";
+      break;
   }
   if (!ok) return fail(ctx, HH_ERR_UNSUPPORTED, "%s needs %s", who, needs);
   if (c->noise_mode == HH_NOISE_REPLAY || c->n_partials != 0)
@@ -1588,6 +1611,7 @@ static int run_path_stats(hh_ctx* ctx, const PathFamily& f, const hh_model* m, c
   if (f.assets && (rc = check_assets(ctx, who, f.assets))) return rc;
   if (f.localvol && (rc = check_localvol(ctx, who, f.localvol))) return rc;
   if (f.jump && (rc = check_jump(ctx, who, f.jump, m->T / (double)c->n_steps))) return rc;
+  if (f.vg && (rc = check_vg(ctx, who, m, f.vg, 1.0))) return rc;
   hh_model m_c = *m;  // Bates: the step's constants, and their checks, on the compensated rate
   if (f.jump && f.qe) m_c.r_drift = m->r_drift - hh::merton_compensator(*f.jump);
   if (f.qe && (rc = check_qe(ctx, who, &m_c, c, f.qe))) return rc;
@@ -1625,6 +1649,9 @@ static int run_path_stats(hh_ctx* ctx, const PathFamily& f, const hh_model* m, c
       break;
     case PathFamily::kCoupled:
       HH_HIP(ctx, hh::launch_coupled_stats(*m, *c, seeds_dev, monitor_every, start, ctx->path_stats, ctx->stream));
+      break;
+    case PathFamily::kVg:
+      HH_HIP(ctx, hh::launch_vg_stats(*m, *c, *f.vg, seeds_dev, monitor_every, start, ctx->path_stats, ctx->stream));
       break;
   }
   return end_timing(ctx);
@@ -1871,6 +1898,88 @@ int hh_carr_madan_jump(hh_ctx* ctx, const hh_model* m, const hh_jump* jump, doub
         return !(m.S0 > 0.0) || !std::isfinite(m.S0) || !std::isfinite(m.sigma) || !(alpha > 0.0) || !(bound > 0.0);
       },
       hh::launch_carr_madan_jump, m, jump, alpha, bound, strikes, cps, Ts, r_drifts, discounts, n_payoffs, prices_out);
+}
+
+// ---- Variance Gamma (hedgehog_mc.h, "Variance Gamma"; kernels: hh_vg.hip, hh_fourier.hip) ----
+
+int hh_mc_path_stats_vg(hh_ctx* ctx, const hh_model* m, const hh_vg* vg, const hh_config* c, uint32_t monitor_every,
+                        int32_t include_start, double* stats, int32_t stats_on_device, hh_result* out) {
+  return path_stats_call(ctx, {"hh_mc_path_stats_vg", 0, vg}, m, c, monitor_every, include_start, stats, stats_on_device, out);
+}
+
+int hh_mc_solve_path_vg(hh_ctx* ctx, const hh_model* m, const hh_vg* vg, const hh_config* c, uint32_t monitor_every,
+                        int32_t include_start, const hh_path_payoff* payoffs, uint32_t n_payoffs, hh_result* out,
+                        double* path_values, double* stats) {
+  return solve_path_call(ctx, {"hh_mc_solve_path_vg", HH_PAYOFF_LOOKBACK_FIXED, vg}, m, c, monitor_every, include_start,
+                         payoffs, n_payoffs, out, path_values, stats);
+}
+
+int hh_mc_solve_vg(hh_ctx* ctx, const hh_model* m, const hh_vg* vg, const hh_config* c, hh_result* out, double* terminal) {
+  if (!ctx) return HH_ERR_INVALID;
+  std::lock_guard<std::recursive_mutex> lock__(ctx->mu);
+  const char* who = "hh_mc_solve_vg";
+  if (!m || !vg || !c || !out) return fail(ctx, HH_ERR_INVALID, "%s: NULL argument", who);
+  if (c->dynamics == HH_HESTON || c->strategy != HH_EXACT_LAW)
+    return fail(ctx, HH_ERR_UNSUPPORTED, "%s needs LognormalDynamics + the exact law (HH_EXACT_LAW)", who);
+  if (c->noise_mode == HH_NOISE_REPLAY || c->n_partials != 0)
+    return fail(ctx, HH_ERR_UNSUPPORTED, "%s: GENERATE noise, no dual partials", who);
+  int rc = validate(ctx, m, c);
+  if (rc) return rc;
+  if ((rc = check_vg(ctx, who, m, vg, 1.0))) return rc;
+  const WallClock clock;
+  std::memset(out, 0, sizeof(*out));
+  HH_HIP(ctx, hipSetDevice(ctx->device));
+  HH_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+  const uint32_t n_rec = hh::vg_records(c->n_paths);
+  if ((rc = ensure(ctx, ctx->records, (size_t)n_rec * hh::kRecStride))) return rc;
+  hh::DevicePtrs p{};
+  p.records = ctx->records;
+  if ((rc = stage_noise(ctx, c, p, false))) return rc;  // seeds[0]
+  if (terminal && c->terminal_on_device) {
+    p.terminal = terminal;
+  } else if (terminal) {
+    if ((rc = ensure(ctx, ctx->terminal, (size_t)c->n_paths * (c->antithetic ? 2 : 1)))) return rc;
+    p.terminal = ctx->terminal;
+  }
+  if ((rc = begin_timing(ctx))) return rc;
+  HH_HIP(ctx, hh::launch_vg_exact(*m, *c, *vg, p, ctx->stream));
+  HH_HIP(ctx, hh::launch_reduce_records(ctx->records, n_rec, (double)c->n_paths, ctx->accum, ctx->stream, 1, m, c));
+  if ((rc = end_timing(ctx))) return rc;
+  HH_HIP(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+  HH_HIP(ctx, hipMemcpyAsync(ctx->accum_host, ctx->accum, HH_ACC_LEN * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  HH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  if ((rc = release_host_operands(ctx))) return rc;
+  if ((rc = copy_back_terminal(ctx, c, terminal))) return rc;
+  rc = hh_mc_finalize(m, c, ctx->accum_host, out);
+  if (rc) return fail(ctx, rc, "finalize failed: the accumulator holds no trajectories");
+  return solve_times(ctx, clock, &out->kernel_ms, &out->total_ms);
+}
+
+int hh_carr_madan_vg(hh_ctx* ctx, const hh_model* m, const hh_vg* vg, double alpha, double bound, const double* strikes,
+                     const double* cps, const double* Ts, const double* r_drifts, const double* discounts,
+                     uint32_t n_payoffs, double* prices_out) {
+  if (!ctx) return HH_ERR_INVALID;
+  std::lock_guard<std::recursive_mutex> lock__(ctx->mu);
+  const char* who = "hh_carr_madan_vg";
+  if (!m || !vg || !strikes || !cps || !Ts || !r_drifts || !discounts || !prices_out)
+    return fail(ctx, HH_ERR_INVALID, "%s: NULL argument", who);
+  if (n_payoffs == 0 || n_payoffs > (1u << 20)) return fail(ctx, HH_ERR_INVALID, "%s: 1 .. 2^20 payoffs per call", who);
+  if (!(m->S0 > 0.0) || !std::isfinite(m->S0) || !std::isfinite(m->sigma) || !(alpha > 0.0) || !(bound > 0.0))
+    return fail(ctx, HH_ERR_INVALID, "%s: bad scalars", who);
+  int rc = check_vg(ctx, who, m, vg, 1.0 + alpha);
+  if (rc) return rc;
+  if (!hh::carr_madan_subpanels(alpha, bound)) return fail(ctx, HH_ERR_INVALID, HH_CM_BOUND_MSG, who);
+  const size_t n = n_payoffs;
+  std::vector<double> host(5 * n);  // log K | T | r_drift | discount | (out)
+  if ((rc = cm_upload_payoffs(ctx, who, strikes, cps, Ts, r_drifts, discounts, n, n, host))) return rc;
+  HH_HIP(ctx, hh::launch_carr_madan_vg(*m, *vg, alpha, bound, ctx->payoffs, n_payoffs, ctx->payoffs + 4 * n, ctx->stream));
+  HH_HIP(ctx, hipMemcpyAsync(host.data() + 4 * n, ctx->payoffs + 4 * n, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  HH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  for (size_t k = 0; k < n; ++k) {  // parity_transform: put = call − S + K·D
+    const double call = host[4 * n + k];
+    prices_out[k] = cps[k] > 0.0 ? call : call - m->S0 + strikes[k] * discounts[k];
+  }
+  return HH_OK;
 }
 
 // ---- Heston paths by the quadratic-exponential scheme (hedgehog_mc.h; kernel: hh_qe.hip) ----------------------

@@ -75,8 +75,11 @@ struct FourierArgs {
   // Merton jumps (dynamics = kDynMerton, a code internal to this unit): the lognormal law above with the compensated
   // drift, times exp(λT·(exp(iu·μ_J − σ_J²u²/2) − 1)); Bates (carr_madan_bates_kernel): the Heston law with them
   double lam, mu_j, sigma_j, lam_kbar;
+  // Variance Gamma (dynamics = kDynVg): θ·ν, σ²ν/2, ν and the compensator ω (hh_vg.h: vg_omega), formed on the host
+  double vg_theta_nu, vg_half_s2nu, vg_nu, vg_omega;
 };
 constexpr int kDynMerton = 2;  // beside HH_LOGNORMAL = 0 and HH_HESTON = 1; never crosses the C-ABI
+constexpr int kDynVg = 3;      // … and neither does this one
 
 // heston.jl:307-319, complex argument u.  JUMP (Bates 1996): a.r carries r − λκ̄ and the jump term
 // (λ·T)·(exp(μ_J·iu − (½σ_J²)·u²) − 1) is added to the exponent last.
@@ -114,6 +117,18 @@ __device__ cz merton_cf(const FourierArgs& a, cz t) {
   return zexp(a.law_mu * it - (0.5 * a.law_sd * a.law_sd) * t2 + (a.lam * a.T) * jump);
 }
 
+// Variance Gamma: exp(it·(log S0 + (r + ω)T)) · base^(−T/ν), base = 1 − θν·it + (σ²ν/2)·t², law_mu carrying the first
+// factor's mean.  The power is exp(−(T/ν)·log base) with this unit's zlog, the principal branch: on the contour
+// Im t = −(1+α) the real part of base is 1 − θν(1+α) + (σ²ν/2)(v² − (1+α)²) >= 1 − θν(1+α) − σ²ν(1+α)²/2, which the
+// entry point has checked to be positive — base never crosses the negative real axis, so the branch is continuous
+// along the whole contour.
+__device__ cz vg_cf(const FourierArgs& a, cz t) {
+  const cz it = {-t.im, t.re};
+  const cz one = {1.0, 0.0};
+  const cz base = one - a.vg_theta_nu * it + a.vg_half_s2nu * (t * t);
+  return zexp(a.law_mu * it - (a.T / a.vg_nu) * zlog(base));
+}
+
 // carr_madan.jl:59-61, 88-92: damp · call_transform(v) · exp(−i v log K), real part.  BATES: the Heston law with jumps,
 // whatever a.dynamics says
 template <bool BATES>
@@ -121,7 +136,8 @@ __device__ __forceinline__ double integrand_law(const FourierArgs& a, double v) 
   const cz u = {v, -(a.alpha + 1.0)};
   cz phi;
   if constexpr (BATES) phi = heston_cf_law<true>(a, u);
-  else phi = a.dynamics == HH_HESTON ? heston_cf(a, u) : a.dynamics == kDynMerton ? merton_cf(a, u) : normal_cf(a, u);
+  else phi = a.dynamics == HH_HESTON ? heston_cf(a, u) : a.dynamics == kDynMerton ? merton_cf(a, u)
+          : a.dynamics == kDynVg ? vg_cf(a, u) : normal_cf(a, u);
   const cz den = {a.alpha * a.alpha + a.alpha - v * v, v * (2.0 * a.alpha + 1.0)};
   const cz val = zdiv(a.discount * phi, den) * zexp({0.0, -v * a.logK});
   return exp(-a.alpha * a.logK) / 6.28318530717958647692 * val.re;
@@ -342,6 +358,7 @@ __global__ __launch_bounds__(256) void carr_madan_kernel(const FourierArgs a0) {
     a.law_sd = a0.sigma_ln * sqT;
     if (a0.dynamics == kDynMerton)  // ((r − σ²/2) − λκ̄)·T, in that order: λ = 0 leaves the lognormal mean
       a.law_mu = a.logS0 + ((a.r - 0.5 * a0.sigma_ln * a0.sigma_ln) - a0.lam_kbar) * a.T;
+    if (a0.dynamics == kDynVg) a.law_mu = a.logS0 + (a.r + a0.vg_omega) * a.T;
     a.out = a0.out + k;
   }
   const double w = 2.0 * a.bound / 256.0;  // panel width
@@ -436,6 +453,24 @@ int launch_carr_madan_jump(const hh_model& m, const hh_jump& jump, double alpha,
   a.sigma_ln = m.sigma;
   a.lam = jump.lambda; a.mu_j = jump.mu_j; a.sigma_j = jump.sigma_j;
   a.lam_kbar = merton_compensator(jump);
+  a.out = out_dev;
+  a.per_payoff = per_payoff_dev;
+  a.n_payoffs = n_payoffs;
+  if (const int rc = set_rule(a, alpha, bound)) return rc;
+  hipLaunchKernelGGL(carr_madan_kernel, dim3(n_payoffs), dim3(256), 0, s, a);
+  return (int)hipGetLastError();
+}
+
+int launch_carr_madan_vg(const hh_model& m, const hh_vg& vg, double alpha, double bound, const double* per_payoff_dev,
+                         uint32_t n_payoffs, double* out_dev, hipStream_t s) {
+  FourierArgs a{};
+  a.dynamics = kDynVg;
+  a.logS0 = log(m.S0);
+  a.sigma_ln = m.sigma;
+  a.vg_theta_nu = vg.theta * vg.nu;
+  a.vg_half_s2nu = (0.5 * (m.sigma * m.sigma)) * vg.nu;
+  a.vg_nu = vg.nu;
+  a.vg_omega = vg_omega(m.sigma, vg);
   a.out = out_dev;
   a.per_payoff = per_payoff_dev;
   a.n_payoffs = n_payoffs;

@@ -9,6 +9,7 @@
 #include "hh_jump.h"
 #include "hh_layout.h"
 #include "hh_sobol.h"
+#include "hh_vg.h"
 
 namespace hh {
 
@@ -323,6 +324,21 @@ int launch_jump_stats(const hh_model& m, const hh_config& c, const hh_jump& jump
 // launch_carr_madan_basket (lognormal dynamics, compat_sqrt_alpha = 0) with the Merton characteristic function
 int launch_carr_madan_jump(const hh_model& m, const hh_jump& jump, double alpha, double bound,
                            const double* per_payoff_dev, uint32_t n_payoffs, double* out_dev, hipStream_t s);
+// Variance Gamma (hh_vg.hip, hh_fourier.hip; include/hedgehog_mc.h, "Variance Gamma").  The scalars are checked by the
+// entry points.  The terminal law: a lane takes kVgPerLane trajectories whatever the call, a workgroup leaves one record
+constexpr int kVgPerLane = 8;
+inline uint32_t vg_records(uint64_t n_paths) {
+  const uint64_t per = (uint64_t)kTile * kVgPerLane;
+  return (uint32_t)((n_paths + per - 1) / per);
+}
+// c: antithetic, n_paths, path_offset; p: seeds (seeds[0] is read), records [vg_records][kRecStride], terminal
+int launch_vg_exact(const hh_model& m, const hh_config& c, const hh_vg& vg, const DevicePtrs& p, hipStream_t s);
+// the five monitored rows of launch_path_stats on the gamma clock: one gamma variate of shape dt/ν per step
+int launch_vg_stats(const hh_model& m, const hh_config& c, const hh_vg& vg, const uint64_t* seeds_dev,
+                    uint32_t monitor_every, bool include_start, double* stats, hipStream_t s);
+// launch_carr_madan_basket (lognormal dynamics, compat_sqrt_alpha = 0) with the Variance Gamma characteristic function
+int launch_carr_madan_vg(const hh_model& m, const hh_vg& vg, double alpha, double bound, const double* per_payoff_dev,
+                         uint32_t n_payoffs, double* out_dev, hipStream_t s);
 // Heston paths by the quadratic-exponential scheme (hh_qe.hip; include/hedgehog_mc.h, "Heston paths by the
 // quadratic-exponential scheme").  The scalars are checked by the entry points, which ask qe_launch_args for the
 // host-formed constants (A decides whether the martingale correction is admitted).

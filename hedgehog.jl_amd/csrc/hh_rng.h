@@ -19,6 +19,7 @@ constexpr uint32_t kDomJump = 4u;    // the jump counts and jump normals of the 
 constexpr uint32_t kDomQe = 5u;      // the normals and uniforms of the quadratic-exponential Heston step (hh_qe.hip)
 constexpr uint32_t kDomAssets = 6u;  // the normals of the correlated assets of a multi-asset index (hh_assets.hip)
 constexpr uint32_t kDomSobol = 7u;   // the digital shifts of the randomised Sobol' points (hh_sobol.hip)
+constexpr uint32_t kDomVg = 8u;      // the gamma variates and the terminal law's normal of the Variance Gamma model (hh_vg.hip)
 
 struct Philox4 {
   uint32_t c0, c1, c2, c3;

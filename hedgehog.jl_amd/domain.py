@@ -356,6 +356,33 @@ class MertonInputs:
 
 
 @dataclass(frozen=True)
+class VarianceGammaInputs:
+    """Variance Gamma (Madan, Carr and Chang 1998; include/hedgehog_mc.h, "Variance Gamma"; the reference has no such
+    model): a Brownian motion with drift θ and volatility σ run on a gamma clock of variance rate ν.  A class of its own, a
+    subclass of nothing, so that no route of another model takes it silently.  The drift is compensated by
+    ω = log(1 − θν − σ²ν/2)/ν inside the solvers."""
+    referenceDate: int
+    rate: FlatRateCurve
+    spot: Any
+    sigma: FlatVolSurface
+    theta: Any
+    nu: Any
+
+    def __init__(self, reference_date, rate, spot, sigma, theta, nu):
+        ref = to_ticks(reference_date)
+        if not isinstance(rate, (FlatRateCurve, RateCurve)):
+            rate = FlatRateCurve(ref, rate)
+        if not isinstance(sigma, FlatVolSurface):
+            sigma = FlatVolSurface(ref, sigma)
+        for k, v in (("referenceDate", ref), ("rate", rate), ("spot", spot), ("sigma", sigma), ("theta", theta), ("nu", nu)):
+            object.__setattr__(self, k, v)
+
+    def black_scholes(self):
+        """the market the C structs are formed on: the same curve, spot and σ"""
+        return BlackScholesInputs(self.referenceDate, self.rate, self.spot, self.sigma)
+
+
+@dataclass(frozen=True)
 class HestonInputs:
     """market_inputs.jl:55-88; positional order (ref, rate, spot, V0, κ, θ, σ, ρ)."""
     referenceDate: int

@@ -16,7 +16,7 @@ from .dates import yearfrac
 from .dual import Dual, n_partials, partials_of, value_of
 from .domain import (PATH_PAYOFFS, ArithmeticAverage, AsianOption, BarrierOption, BlackScholesInputs, Call,
                     CashOrNothing, ContinuousMonitoring, DigitalOption, DownAndIn, DownAndOut, European, HestonInputs,
-                    LookbackOption, MertonInputs, BatesInputs, Monitoring,
+                    LookbackOption, MertonInputs, BatesInputs, Monitoring, VarianceGammaInputs,
                     MonteCarloSolution, PricingProblem, Spot, UpAndIn, UpAndOut, VanillaOption, _DeviceSamples, df,
                     get_vol, zero_rate)
 
@@ -39,9 +39,12 @@ class MertonDynamics(PriceDynamics): pass
 class MertonExact(ExactSimulation): pass
 # ---- Bates: Heston variance with Merton jumps (the reference has none; include/hedgehog_mc.h) ----
 class BatesDynamics(PriceDynamics): pass
+# ---- Variance Gamma (the reference has none; include/hedgehog_mc.h) ----
+class VarianceGammaDynamics(PriceDynamics): pass
+class VarianceGammaExact(ExactSimulation): pass
 
 for _c in (LognormalDynamics, HestonDynamics, NoVarianceReduction, Antithetic, EulerMaruyama,
-           HestonBroadieKaya, BlackScholesExact, MertonDynamics, MertonExact):
+           HestonBroadieKaya, BlackScholesExact, MertonDynamics, MertonExact, VarianceGammaDynamics, VarianceGammaExact):
     _c.__eq__ = lambda a, b: type(a) is type(b)
     _c.__hash__ = lambda a: hash(type(a).__name__)
     _c.__repr__ = lambda a: type(a).__name__ + "()"
@@ -228,6 +231,17 @@ def is_merton(market_inputs, method) -> bool:
     """Does anything of the pair name the Merton model?  Then only the Merton routes may take it."""
     return isinstance(market_inputs, MertonInputs) or isinstance(getattr(method, "dynamics", None), MertonDynamics) or \
         isinstance(getattr(method, "strategy", None), MertonExact)
+
+
+VG_ROUTES = ("MonteCarlo(VarianceGammaDynamics(), VarianceGammaExact(), config), CarrMadan(alpha, bound, "
+             "VarianceGammaDynamics()) or VarianceGammaAnalytic() on VarianceGammaInputs")
+
+
+def is_vg(market_inputs, method) -> bool:
+    """Does anything of the pair name the Variance Gamma model?  Then only its routes may take it."""
+    return isinstance(market_inputs, VarianceGammaInputs) or \
+        isinstance(getattr(method, "dynamics", None), VarianceGammaDynamics) or \
+        isinstance(getattr(method, "strategy", None), VarianceGammaExact)
 
 
 @dataclass(frozen=True)

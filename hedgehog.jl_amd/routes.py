@@ -13,13 +13,14 @@ from dataclasses import dataclass
 from typing import Any, Callable
 
 from . import _ffi
-from .analytic import CarrMadan
-from .domain import (PATH_PAYOFFS, American, BatesInputs, ContinuousMonitoring, HestonInputs, MertonInputs, PricingProblem)
+from .analytic import CarrMadan, VarianceGammaAnalytic
+from .domain import (PATH_PAYOFFS, American, BatesInputs, ContinuousMonitoring, European, HestonInputs, MertonInputs,
+                     PricingProblem, Spot, VanillaOption, VarianceGammaInputs)
 from .dual import Dual
 from .localvol import ROUTES as LOCALVOL_ROUTES, LocalVolDynamics, LocalVolInputs, is_localvol
 from .montecarlo import (BATES_ROUTES, BatesDynamics, BlackScholesExact, EulerMaruyama, HestonDynamics, HestonQE,
-                         LognormalDynamics, MertonDynamics, MertonExact, MethodError, MonteCarlo,
-                         _model_and_config, is_bates, is_merton, is_qe)
+                         LognormalDynamics, MertonDynamics, MertonExact, MethodError, MonteCarlo, VG_ROUTES,
+                         VarianceGammaDynamics, VarianceGammaExact, _model_and_config, is_bates, is_merton, is_qe, is_vg)
 from .multiasset import ROUTES as ASSET_ROUTES, MultiAssetDynamics, MultiAssetInputs, is_multiasset, solve_index_options
 
 # ---- what a path route may refuse before the expiry and the monitoring of its payoffs are looked at (Route.early) ----
@@ -110,6 +111,15 @@ def _jump(m, method):
     return (_ffi.make_jump(float(m.jump_intensity), float(m.jump_mean), float(m.jump_std)),)
 
 
+def _vg(m, method):
+    return (_ffi.make_vg(float(m.theta), float(m.nu)),)
+
+
+def _one_european_vanilla(payoffs):
+    p = payoffs[0] if len(payoffs) == 1 else None
+    return isinstance(p, VanillaOption) and isinstance(p.exercise_style, European) and isinstance(p.underlying, Spot)
+
+
 def _qe(m, method):
     return (_ffi.make_qe(float(method.strategy.psi_c), bool(method.strategy.martingale)),)
 
@@ -196,6 +206,26 @@ MERTON_LAW = dataclasses.replace(  # MertonExact: the law at expiry (and whateve
     one_device="Merton solves run on one device (MonteCarlo.devices is not supported)", no_bridge=None,
     no_paths="MertonExact samples the law at expiry: path-dependent payoffs need EulerMaruyama paths", rest="singles")
 
+VG = Route(  # Variance Gamma: every payoff on the path statistics, exact in law on any dates
+    "Variance Gamma paths", lambda payoffs, m, method: is_vg(m, method),
+    admits=(VarianceGammaDynamics, VarianceGammaInputs, VarianceGammaExact),
+    not_admitted="no Variance Gamma solve for {dyn} + {strat} on {m}: use " + VG_ROUTES,
+    base=_on_lognormal(compat_sqrt_alpha=False, strategy=BlackScholesExact()), dual_fields=("theta", "nu"), extras=_vg,
+    entry="hh_mc_solve_path_vg", early=(admitted, european_discrete, one_device),
+    no_replay="Variance Gamma solves draw their own noise (gamma variates by rejection): no replay; use " + VG_ROUTES,
+    one_device="Variance Gamma solves run on one device (MonteCarlo.devices is not supported): use " + VG_ROUTES,
+    no_duals="Variance Gamma solves carry no dual partials (ForwardAD): use FiniteDifference with SpotLens, VolLens, "
+             "optic(\"market_inputs.theta\") or optic(\"market_inputs.nu\") — its solves share their seeds",
+    no_american="American exercise is not offered on Variance Gamma paths (no LSM on them): European payoffs on " + VG_ROUTES,
+    no_continuous="ContinuousMonitoring() is not offered on Variance Gamma paths (between two dates the path is no diffusion "
+                  "bridge): monitor on the dates of a Monitoring",
+    methods=(MonteCarlo, CarrMadan, VarianceGammaAnalytic), other_methods="{} does not price the Variance Gamma model: use " + VG_ROUTES,
+    rest="paths")
+
+VG_LAW = dataclasses.replace(  # one European vanilla on the spot: the law at expiry, one gamma variate per trajectory
+    VG, name="Variance Gamma law", claims=lambda payoffs, m, method: is_vg(m, method) and _one_european_vanilla(payoffs),
+    entry="hh_mc_solve_vg", law=True, early=(), rest="singles")
+
 EULER = Route(  # a path-dependent payoff on the Euler paths of the plain models; vanillas of its basket: the plain route's
     "Euler paths", lambda payoffs, m, method: any(isinstance(p, PATH_PAYOFFS) for p in payoffs),
     entry="hh_mc_solve_path", entry_ex="hh_mc_solve_path_ex", early=(euler_paths, one_device),
@@ -205,9 +235,9 @@ EULER = Route(  # a path-dependent payoff on the Euler paths of the plain models
 
 PLAIN = Route("plain European", lambda payoffs, m, method: True, multi=True)  # hh_mc_solve, _basket, _multi; replay, devices, duals
 
-ROUTES = (MULTIASSET, LOCALVOL, BATES, QE, MERTON, MERTON_LAW, EULER, PLAIN)
-SPOT_PATHS = (LOCALVOL, BATES, QE, MERTON)  # what solve_path_payoffs looks a pair up in; whatever none claims: EULER
-OTHER_METHODS = (MULTIASSET, BATES, LOCALVOL)  # in the order hh.solve asks them
+ROUTES = (MULTIASSET, LOCALVOL, BATES, QE, VG_LAW, VG, MERTON, MERTON_LAW, EULER, PLAIN)
+SPOT_PATHS = (LOCALVOL, BATES, QE, VG, MERTON)  # what solve_path_payoffs looks a pair up in; whatever none claims: EULER
+OTHER_METHODS = (MULTIASSET, BATES, LOCALVOL, VG)  # in the order hh.solve asks them
 
 
 def route_of(payoffs, market_inputs, method, routes=ROUTES) -> Route:

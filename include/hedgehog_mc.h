@@ -1253,6 +1253,90 @@ int hh_ctx_enable_timing(hh_ctx* ctx, int32_t on);
 int hh_ctx_read_timings(hh_ctx* ctx, double* ms, int32_t cap, int32_t* n_out);
 
 /*
+ * Variance Gamma (Madan, Carr and Chang 1998): a Brownian motion with drift θ and volatility σ run on a gamma clock — a
+ * pure-jump Lévy model with infinitely many jumps, no Brownian part of its own, and skew and kurtosis at every expiry.
+ * The reference has no such model; the conventions below are this library's.
+ *   X_t = θ·G_t + σ·W(G_t)        G a gamma process, G_t ~ Gamma(shape t/ν, scale ν)  (mean t, variance ν·t)
+ *   log S_t = log S0 + (r + ω)·t + X_t        ω = log(1 − θν − σ²ν/2)/ν,   requires 1 − θν − σ²ν/2 > 0
+ *   ϕ(u) = E exp(iu·log S_T) = exp(iu·(log S0 + (r + ω)T)) · (1 − iuθν + σ²νu²/2)^(−T/ν)      (principal branch)
+ *   call = E_G[ discounted Black call on a lognormal with log-mean log S0 + (r + ω)T + θG and log-variance σ²G ]
+ * hh_vg carries θ and ν; σ = model->sigma, r = model->r_drift.  No existing struct changes.  The increments of X over
+ * disjoint spans are independent and exact in law, so the states on any set of dates carry no discretisation bias.
+ *
+ * ON THE HOST, once per call (csrc/hh_vg.h, vg_args), each a single rounded fp64 operation in this order, τ being what
+ * one gamma draw covers — T (terminal law), dt = T/n_steps (path form):
+ *   arg = (1 − (θ·ν)) − ((0.5·(σ·σ))·ν)        ω = log(arg)/ν        drift = (r + ω)·τ
+ *   a = τ/ν        boost = a < 1        a′ = boost ? a + 1 : a        d = a′ − 1/3  (1/3 the double 1.0/3.0)
+ *   c = 1/sqrt(9·d)        inv_a = 1/a        nu_d = ν·d
+ *
+ * THE GAMMA VARIATE Gamma(a, ν) by Marsaglia and Tsang (2000) with the shape boost (csrc/hh_vg.h, gamma_mt — a function
+ * of a draw source, which a host program can call on draws of its choosing).  Attempt t = 0, 1, … takes a standard
+ * normal z, a uniform U and, boosted, a uniform U′, all of its own, then — one rounded operation each, in this order —
+ *   x = 1 + c·z        v = (x·x)·x        and only where v > 0:
+ *   rhs = (((0.5·z)·z + d) − d·v) + d·log v        val = nu_d·v,  boosted: val·exp(log(U′)·inv_a)
+ * and accepts val when log U < rhs.  The loop ends after HH_VG_MAX_ATTEMPTS attempts at the latest with the val of the
+ * last attempt that had v > 0 (+0 when none had); an attempt is accepted with probability > 0.95 whatever the shape, so
+ * the cap is met with probability below 0.05⁶⁴ — it is there because no device loop may be bounded by data alone.
+ * The boosted product may underflow to +0 (a = 0.008: 0.3 % of the variates): the span then adds the drift alone.
+ * Every draw is a Philox4x32-10 block whose counter word 3 is 8, a domain no other draw of the library uses; z is the
+ * FIRST normal of a block's Box–Muller pair (as every normal pair of the library; the second is not used),
+ * U = u01(words 0, 1) and U′ = u01(words 2, 3) of a second block, u01(lo, hi) = ((w >> 12) + ½)·2⁻⁵² of
+ * w = (hi << 32) | lo as everywhere.
+ *
+ * THE INCREMENT over a span, from its variate g and a standard normal z_B independent of it:
+ *   inc = (drift + θ·g) + (σ·sqrt(g))·z_B        sqrt correctly rounded; the antithetic mirror takes the same g and −z_B.
+ *
+ * hh_mc_solve_vg — the TERMINAL LAW, cfg->strategy = HH_EXACT_LAW.  Trajectory i of the call has the global index
+ * g = cfg->path_offset + i and is keyed by seeds[0], as the exact lognormal law is.
+ *   attempt t:  z from block (lo32 g, hi32 g, 2t, 8);  U, U′ from block (lo32 g, hi32 g, 2t + 1, 8)
+ *   z_B:        the first normal of block (lo32 g, hi32 g, 2·HH_VG_MAX_ATTEMPTS, 8)
+ *   x_T = log S0 + inc        with τ = T
+ * terminal (nullable; host, or device when cfg->terminal_on_device): exp(x_T) of the n_paths trajectories, then of their
+ * mirrors.  The payoff (model->strike, model->cp), the sums and hh_result are hh_mc_solve's.  1 .. 2^32 − 256
+ * trajectories per call; a lane takes eight of them whatever the call, so a call's sums are reproducible, and [0, n) is
+ * [0, k) followed by [k, n) with path_offset = k, sample for sample.  Timing: one slot, as hh_mc_solve.
+ *
+ * hh_mc_path_stats_vg, hh_mc_solve_path_vg — the PATH FORM, cfg->strategy = HH_EXACT_LAW with cfg->n_steps spans of
+ * dt = T/n_steps: hh_mc_path_stats / hh_mc_solve_path_ex under HH_EXTREMES_MONITORED on these paths.  Trajectory i is
+ * keyed by seeds[i].  Step k = 0 .. n_steps − 1:
+ *   attempt t:  z from block (k, t, 0, 8);  U, U′ from block (k, t, 1, 8)
+ *   z_B:        the normal the lognormal hh_mc_path_stats draws for step k — block (k >> 1, 0, 0, 0), its first normal for
+ *               an even k, its second for an odd one: one block per two steps, an odd n_steps leaving the last half read
+ *   x ← x + inc        with τ = dt, then the monitoring date
+ * The statistics are the five rows of HH_EXTREMES_MONITORED over the same monitoring dates with the same arithmetic;
+ * payoff kinds 0 .. 7 are admitted, the lookbacks read the monitored rows.  There are no continuous (bridge) extremes:
+ * between two dates the path is no diffusion bridge.  Arguments, outputs and timing slots are hh_mc_path_stats' and
+ * hh_mc_solve_path's.
+ *
+ * hh_carr_madan_vg — hh_carr_madan_basket (lognormal dynamics, compat_sqrt_alpha = 0) with ϕ above, the power taken as
+ * exp(−(T/ν)·log(base)) on the principal branch: the same fixed quadrature rule, one workgroup per payoff, the same
+ * parity transform for puts.  On the contour Im u = −(1+α) the base's real part is at least
+ * 1 − θν(1+α) − σ²ν(1+α)²/2, which the entry point requires to be positive (the (1+α)-th moment is then finite): the
+ * base never crosses the negative real axis and the principal branch is continuous along the whole contour.
+ *
+ * All four are synchronous.  Errors, checked on the host before any launch.  HH_ERR_INVALID: vg is NULL; ν <= 0 or not
+ * finite; θ not finite; σ < 0; 1 − θν − σ²ν/2 <= 0; for hh_carr_madan_vg 1 − θν(1+α) − σ²ν(1+α)²/2 <= 0; everything
+ * hh_mc_solve / hh_mc_solve_path_ex / hh_carr_madan_basket reject.  HH_ERR_UNSUPPORTED: Heston dynamics, REPLAY noise,
+ * n_partials > 0, a strategy other than HH_EXACT_LAW.  After any refusal the context stays usable.
+ * Not provided: NIG and CGMY, the difference-of-gammas form, bridge or continuous monitoring, REPLAY and quasi-Monte
+ * Carlo, dual partials (bump the inputs: the solves of a finite difference share their seeds), multilevel coupling,
+ * LSM / American exercise, accumulate, hh_mc_solve_multi and multi-GPU forms, a gradient of hh_carr_madan_vg, a Julia
+ * binding.
+ */
+#define HH_VG_MAX_ATTEMPTS 64    /* the rejection loop of one gamma variate stops here at the latest */
+typedef struct hh_vg { double theta, nu; } hh_vg;                        /* 16 bytes */
+int hh_mc_solve_vg(hh_ctx* ctx, const hh_model* model, const hh_vg* vg, const hh_config* cfg, hh_result* out,
+                   double* terminal);
+int hh_mc_path_stats_vg(hh_ctx* ctx, const hh_model* model, const hh_vg* vg, const hh_config* cfg, uint32_t monitor_every,
+                        int32_t include_start, double* stats, int32_t stats_on_device, hh_result* out);
+int hh_mc_solve_path_vg(hh_ctx* ctx, const hh_model* model, const hh_vg* vg, const hh_config* cfg, uint32_t monitor_every,
+                        int32_t include_start, const hh_path_payoff* payoffs, uint32_t n_payoffs, hh_result* out,
+                        double* path_values, double* stats);
+int hh_carr_madan_vg(hh_ctx* ctx, const hh_model* model, const hh_vg* vg, double alpha, double bound,
+                     const double* strikes, const double* cps, const double* Ts, const double* r_drifts,
+                     const double* discounts, uint32_t n_payoffs, double* prices_out);
+
+/*
  * A SimulationConfig's seed vector in the device memory of ctx, uploaded once and kept — repeated solves on one
  * config (finite-difference Greeks, calibration loops) would otherwise move 8 MB per 10^6 trajectories at
  * every call, about a third of a GENERATE solve of that size.  The reference reads seeds[i] at every solve
