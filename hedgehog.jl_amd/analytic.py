@@ -22,7 +22,7 @@ from typing import Any
 
 from . import _ffi
 from .dates import yearfrac
-from .domain import (BlackScholesInputs, European, HestonInputs, MertonInputs, PricingProblem, VanillaOption,
+from .domain import (BatesInputs, BlackScholesInputs, European, HestonInputs, MertonInputs, PricingProblem, VanillaOption,
                      VarianceGammaInputs, df, get_vol, zero_rate)
 from .montecarlo import (BATES_ROUTES, VG_ROUTES, AbstractPricingMethod, BatesDynamics, HestonDynamics, LognormalDynamics,
                          MertonDynamics, MethodError, VarianceGammaDynamics, is_bates, is_vg)
@@ -193,94 +193,73 @@ def solve_vg_analytic(prob: PricingProblem, method: VarianceGammaAnalytic) -> An
     return AnalyticSolution(prob, method, price)
 
 
-def _solve_carr_madan_vg(payoffs, m, method: CarrMadan):
-    """CarrMadan(α, bound, VarianceGammaDynamics()) on VarianceGammaInputs: every payoff's integral in one launch
-    (`hh_carr_madan_vg`).  No gradient form: a Dual anywhere is a MethodError."""
+def _cm_payoff_arrays(payoffs, m, r_k, D_k, num=float):
+    """The five arrays every Carr–Madan basket entry point takes — strikes, call/put signs, expiries, and the values
+    (`num`) of the zero rates r_k and discount factors D_k of those expiries."""
+    import numpy as np
+    return (np.array([float(p.strike) for p in payoffs]), np.array([p.call_put() for p in payoffs], dtype=np.float64),
+            np.array([yearfrac(m.rate.reference_date, p.expiry) for p in payoffs]),   # montecarlo.jl:301,317
+            np.array([num(x) for x in r_k]), np.array([num(x) for x in D_k]))
+
+
+# The laws beside the lognormal and Heston ones, in the order a problem is routed (first match of `routed`).  Per row: the
+# guard of the dynamics / market-input pair and the MethodError text where it fails; the scalars scanned for Duals (no
+# gradient form: a Dual anywhere is a MethodError, with the row's text) — first those of the hh_model fields named by
+# `fields`, in that order, then the arguments of `struct`, the law's own C struct; the entry point.
+_CM_LAWS = (
+    dict(routed=is_bates,
+         guard=lambda m, method: isinstance(method.dynamics, BatesDynamics) and isinstance(m, BatesInputs),
+         guard_text=lambda m, method: (f"no Bates characteristic function for {type(method.dynamics).__name__} on "
+                                       f"{type(m).__name__}: use {BATES_ROUTES}"),
+         scalars=lambda m: [m.spot, m.V0, m.κ, m.θ, m.σ, m.ρ, m.jump_intensity, m.jump_mean, m.jump_std],
+         fields=("S0", "V0", "kappa", "theta", "sigma", "rho"), struct=_ffi.make_jump, entry="hh_carr_madan_bates",
+         dual_text="CarrMadan under BatesDynamics carries no dual partials (ForwardAD): use FiniteDifference"),
+    dict(routed=is_vg,
+         guard=lambda m, method: isinstance(method.dynamics, VarianceGammaDynamics) and isinstance(m, VarianceGammaInputs),
+         guard_text=lambda m, method: (f"no Variance Gamma characteristic function for {type(method.dynamics).__name__} on "
+                                       f"{type(m).__name__}: use {VG_ROUTES}"),
+         scalars=lambda m: [m.spot, get_vol(m.sigma, None, None), m.theta, m.nu],
+         fields=("S0", "sigma"), struct=_ffi.make_vg, entry="hh_carr_madan_vg",
+         dual_text="CarrMadan under VarianceGammaDynamics carries no dual partials (ForwardAD): use FiniteDifference"),
+    dict(routed=lambda m, method: isinstance(method.dynamics, MertonDynamics) or isinstance(m, MertonInputs),
+         guard=lambda m, method: isinstance(method.dynamics, MertonDynamics) and isinstance(m, MertonInputs),
+         guard_text=lambda m, method: "no marginal_law for this dynamics / market-input pair",
+         scalars=lambda m: [m.spot, get_vol(m.sigma, None, None), m.jump_intensity, m.jump_mean, m.jump_std],
+         fields=("S0", "sigma"), struct=_ffi.make_jump, entry="hh_carr_madan_jump",
+         dual_text="CarrMadan under MertonDynamics carries no dual partials: use FiniteDifference"),
+)
+
+
+def _carr_madan_law(m, method: CarrMadan):
+    """the row of _CM_LAWS a problem on these market inputs is routed to, or None: the lognormal and Heston laws"""
+    for law in _CM_LAWS:  # a plain loop: this runs in front of every hh_carr_madan call, which takes 47 µs in all
+        if law["routed"](m, method):
+            return law
+    return None
+
+
+def _solve_carr_madan_law(payoffs, m, method: CarrMadan, law):
+    """CarrMadan(α, bound, dynamics) under a law of _CM_LAWS: every payoff's integral in one launch of the law's entry
+    point.  No gradient form: a Dual anywhere is a MethodError."""
     import numpy as np
     from .dual import Dual
-    if not (isinstance(method.dynamics, VarianceGammaDynamics) and isinstance(m, VarianceGammaInputs)):
-        raise MethodError(f"no Variance Gamma characteristic function for {type(method.dynamics).__name__} on "
-                          f"{type(m).__name__}: use {VG_ROUTES}")
-    vol = get_vol(m.sigma, None, None)
+    if not law["guard"](m, method):
+        raise MethodError(law["guard_text"](m, method))
+    scal = law["scalars"](m)
     r_k = [zero_rate(m.rate, p.expiry) for p in payoffs]
     D_k = [df(m.rate, p.expiry) for p in payoffs]
-    scal = [m.spot, vol, m.theta, m.nu, *r_k, *D_k, *(p.strike for p in payoffs)]
-    if any(isinstance(v, Dual) for v in scal):
-        raise MethodError("CarrMadan under VarianceGammaDynamics carries no dual partials (ForwardAD): use FiniteDifference")
-    model = _ffi.hh_model()
-    model.S0, model.sigma = float(m.spot), float(vol)
-    vg = _ffi.make_vg(float(m.theta), float(m.nu))
-    K = len(payoffs)
-    strikes = np.array([float(p.strike) for p in payoffs])
-    cps = np.array([p.call_put() for p in payoffs], dtype=np.float64)
-    Ts = np.array([yearfrac(m.rate.reference_date, p.expiry) for p in payoffs])
-    rs, Ds = np.array([float(x) for x in r_k]), np.array([float(x) for x in D_k])
-    out = np.empty(K)
+    if any(isinstance(v, Dual) for v in [*scal, *r_k, *D_k, *(p.strike for p in payoffs)]):
+        raise MethodError(law["dual_text"])
+    scal = [float(v) for v in scal]
+    model, fields = _ffi.hh_model(), law["fields"]
+    for name, v in zip(fields, scal):
+        setattr(model, name, v)
+    second = law["struct"](*scal[len(fields):])
+    arrays = _cm_payoff_arrays(payoffs, m, r_k, D_k)
+    out = np.empty(len(payoffs))
     ctx = _ffi.get_context(method.device)
-    ctx.check(ctx.lib.hh_carr_madan_vg(ctx.handle, C.byref(model), C.byref(vg), float(method.α), float(method.bound),
-                                       strikes.ctypes.data, cps.ctypes.data, Ts.ctypes.data, rs.ctypes.data,
-                                       Ds.ctypes.data, K, out.ctypes.data))
-    return out
-
-
-def _solve_carr_madan_merton(payoffs, m, method: CarrMadan):
-    """CarrMadan(α, bound, MertonDynamics()) on MertonInputs: every payoff's integral in one launch
-    (`hh_carr_madan_jump`).  No gradient form: a Dual anywhere is a MethodError."""
-    import numpy as np
-    from .dual import Dual
-    if not (isinstance(method.dynamics, MertonDynamics) and isinstance(m, MertonInputs)):
-        raise MethodError("no marginal_law for this dynamics / market-input pair")
-    vol = get_vol(m.sigma, None, None)
-    r_k = [zero_rate(m.rate, p.expiry) for p in payoffs]
-    D_k = [df(m.rate, p.expiry) for p in payoffs]
-    scal = [m.spot, vol, m.jump_intensity, m.jump_mean, m.jump_std, *r_k, *D_k, *(p.strike for p in payoffs)]
-    if any(isinstance(v, Dual) for v in scal):
-        raise MethodError("CarrMadan under MertonDynamics carries no dual partials: use FiniteDifference")
-    model = _ffi.hh_model()
-    model.S0, model.sigma = float(m.spot), float(vol)
-    jump = _ffi.make_jump(float(m.jump_intensity), float(m.jump_mean), float(m.jump_std))
-    K = len(payoffs)
-    strikes = np.array([float(p.strike) for p in payoffs])
-    cps = np.array([p.call_put() for p in payoffs], dtype=np.float64)
-    Ts = np.array([yearfrac(m.rate.reference_date, p.expiry) for p in payoffs])
-    rs, Ds = np.array([float(x) for x in r_k]), np.array([float(x) for x in D_k])
-    out = np.empty(K)
-    ctx = _ffi.get_context(method.device)
-    ctx.check(ctx.lib.hh_carr_madan_jump(ctx.handle, C.byref(model), C.byref(jump), float(method.α), float(method.bound),
-                                         strikes.ctypes.data, cps.ctypes.data, Ts.ctypes.data, rs.ctypes.data,
-                                         Ds.ctypes.data, K, out.ctypes.data))
-    return out
-
-
-def _solve_carr_madan_bates(payoffs, m, method: CarrMadan):
-    """CarrMadan(α, bound, BatesDynamics()) on BatesInputs: every payoff's integral in one launch
-    (`hh_carr_madan_bates`).  No gradient form: a Dual anywhere is a MethodError."""
-    import numpy as np
-    from .dual import Dual
-    from .domain import BatesInputs
-    if not (isinstance(method.dynamics, BatesDynamics) and isinstance(m, BatesInputs)):
-        raise MethodError(f"no Bates characteristic function for {type(method.dynamics).__name__} on {type(m).__name__}: "
-                          f"use {BATES_ROUTES}")
-    r_k = [zero_rate(m.rate, p.expiry) for p in payoffs]
-    D_k = [df(m.rate, p.expiry) for p in payoffs]
-    scal = [m.spot, m.V0, m.κ, m.θ, m.σ, m.ρ, m.jump_intensity, m.jump_mean, m.jump_std, *r_k, *D_k,
-            *(p.strike for p in payoffs)]
-    if any(isinstance(v, Dual) for v in scal):
-        raise MethodError("CarrMadan under BatesDynamics carries no dual partials (ForwardAD): use FiniteDifference")
-    model = _ffi.hh_model()
-    model.S0, model.V0, model.kappa, model.theta = float(m.spot), float(m.V0), float(m.κ), float(m.θ)
-    model.sigma, model.rho = float(m.σ), float(m.ρ)
-    jump = _ffi.make_jump(float(m.jump_intensity), float(m.jump_mean), float(m.jump_std))
-    K = len(payoffs)
-    strikes = np.array([float(p.strike) for p in payoffs])
-    cps = np.array([p.call_put() for p in payoffs], dtype=np.float64)
-    Ts = np.array([yearfrac(m.rate.reference_date, p.expiry) for p in payoffs])
-    rs, Ds = np.array([float(x) for x in r_k]), np.array([float(x) for x in D_k])
-    out = np.empty(K)
-    ctx = _ffi.get_context(method.device)
-    ctx.check(ctx.lib.hh_carr_madan_bates(ctx.handle, C.byref(model), C.byref(jump), float(method.α), float(method.bound),
-                                          strikes.ctypes.data, cps.ctypes.data, Ts.ctypes.data, rs.ctypes.data,
-                                          Ds.ctypes.data, K, out.ctypes.data))
+    ctx.check(getattr(ctx.lib, law["entry"])(ctx.handle, C.byref(model), C.byref(second), float(method.α), float(method.bound),
+                                             *[a.ctypes.data for a in arrays], len(payoffs), out.ctypes.data))
     return out
 
 
@@ -317,27 +296,20 @@ def solve_carr_madan_basket(payoffs, market_inputs, method: CarrMadan):
         if not (isinstance(payoff, VanillaOption) and isinstance(payoff.exercise_style, European)):
             raise MethodError("CarrMadan: European VanillaOption")
     from .dual import Dual, n_partials, partials_of, value_of
-    if is_bates(m, method):
-        return _solve_carr_madan_bates(payoffs, m, method)
-    if is_vg(m, method):
-        return _solve_carr_madan_vg(payoffs, m, method)
-    if isinstance(method.dynamics, MertonDynamics) or isinstance(m, MertonInputs):
-        return _solve_carr_madan_merton(payoffs, m, method)
+    law = _carr_madan_law(m, method)
+    if law is not None:
+        return _solve_carr_madan_law(payoffs, m, method, law)
     model, dyn, scal = _carr_madan_model(m, method)
     K = len(payoffs)
     if any(isinstance(p.strike, Dual) for p in payoffs):
         raise MethodError("CarrMadan basket: partials along a strike are not carried")
-    strikes = np.array([float(p.strike) for p in payoffs])
-    cps = np.array([p.call_put() for p in payoffs], dtype=np.float64)
-    Ts = np.array([yearfrac(m.rate.reference_date, p.expiry) for p in payoffs])   # montecarlo.jl:301,317
     r_k = [zero_rate(m.rate, p.expiry) for p in payoffs]                          # montecarlo.jl:299,318
     D_k = [df(m.rate, p.expiry) for p in payoffs]                                 # carr_madan.jl:89
-    rs, Ds = np.array([value_of(x) for x in r_k]), np.array([value_of(x) for x in D_k])
+    arrays = _cm_payoff_arrays(payoffs, m, r_k, D_k, value_of)
     out = np.empty(K)
     ctx = _ffi.get_context(method.device)
     args = (ctx.handle, C.byref(model), dyn, int(method.compat_sqrt_alpha), float(method.α),
-            float(method.bound), strikes.ctypes.data, cps.ctypes.data, Ts.ctypes.data, rs.ctypes.data,
-            Ds.ctypes.data, K, out.ctypes.data)
+            float(method.bound), *[a.ctypes.data for a in arrays], K, out.ctypes.data)
     P = n_partials(*scal, *r_k, *D_k)
     if P == 0:
         ctx.check(ctx.lib.hh_carr_madan_basket(*args))
@@ -361,12 +333,9 @@ def solve_carr_madan(prob: PricingProblem, method: CarrMadan) -> AnalyticSolutio
     if not (isinstance(payoff, VanillaOption) and isinstance(payoff.exercise_style, European)):
         raise MethodError("CarrMadan: European VanillaOption")
     from .dual import n_partials
-    if is_bates(m, method):  # a basket of one
-        return AnalyticSolution(prob, method, float(_solve_carr_madan_bates([payoff], m, method)[0]))
-    if is_vg(m, method):  # a basket of one
-        return AnalyticSolution(prob, method, float(_solve_carr_madan_vg([payoff], m, method)[0]))
-    if isinstance(method.dynamics, MertonDynamics) or isinstance(m, MertonInputs):  # a basket of one
-        return AnalyticSolution(prob, method, float(_solve_carr_madan_merton([payoff], m, method)[0]))
+    law = _carr_madan_law(m, method)
+    if law is not None:  # a basket of one
+        return AnalyticSolution(prob, method, float(_solve_carr_madan_law([payoff], m, method, law)[0]))
     model, dyn, scal = _carr_madan_model(m, method)
     r_k, D_k = zero_rate(m.rate, payoff.expiry), df(m.rate, payoff.expiry)
     if n_partials(*scal, r_k, D_k) > 0:

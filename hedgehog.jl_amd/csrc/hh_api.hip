@@ -5,6 +5,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <functional>
 #include <mutex>
 #include <vector>
 
@@ -933,36 +934,78 @@ static int cm_upload_payoffs(hh_ctx* ctx, const char* who, const double* strikes
   return HH_OK;
 }
 
+// One Carr–Madan basket entry point: who it is, what it refuses about the model and the rule, and what it launches.
+struct CmBasket {
+  const char* who;
+  std::function<bool()> bad_scalars;  // the model's and the rule's scalars the entry point refuses …
+  const char* bad_scalars_text;       // … and what it says then, after "<who>: "
+  std::function<int()> law_check;     // the law's own parameters
+  bool law_check_first;               // the forms that take a dynamics code name an unknown one before they count the payoffs
+  std::function<int(const double* per_payoff_dev, uint32_t n_payoffs, double* out_dev)> launch;
+};
+struct CmPayoffs {
+  const double *strikes, *cps, *Ts, *r_drifts, *discounts;
+  uint32_t n;
+};
+
+// Everything of such a call up to the results on the host: the checks in the entry points' order, the upload, the launch
+// and the copy back of `width` doubles per payoff into host[4n ..).
+static int cm_basket_run(hh_ctx* ctx, const CmBasket& f, bool null_arg, double alpha, double bound, const CmPayoffs& q,
+                         size_t width, std::vector<double>& host) {
+  if (null_arg || !q.strikes || !q.cps || !q.Ts || !q.r_drifts || !q.discounts)
+    return fail(ctx, HH_ERR_INVALID, "%s: NULL argument", f.who);
+  int rc;
+  if (f.law_check_first && (rc = f.law_check())) return rc;
+  if (q.n == 0 || q.n > (1u << 20)) return fail(ctx, HH_ERR_INVALID, "%s: 1 .. 2^20 payoffs per call", f.who);
+  if (f.bad_scalars()) return fail(ctx, HH_ERR_INVALID, "%s: %s", f.who, f.bad_scalars_text);
+  if (!f.law_check_first && (rc = f.law_check())) return rc;
+  if (!hh::carr_madan_subpanels(alpha, bound)) return fail(ctx, HH_ERR_INVALID, HH_CM_BOUND_MSG, f.who);
+  const size_t n = q.n;
+  host.resize(4 * n + width * n);  // log K | T | r_drift | discount | out [n][width]
+  if ((rc = cm_upload_payoffs(ctx, f.who, q.strikes, q.cps, q.Ts, q.r_drifts, q.discounts, n, width * n, host))) return rc;
+  double* out_dev = ctx->payoffs + 4 * n;
+  HH_HIP(ctx, f.launch(ctx->payoffs, q.n, out_dev));
+  HH_HIP(ctx, hipMemcpyAsync(host.data() + 4 * n, out_dev, width * n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  HH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return HH_OK;
+}
+
+// parity_transform (payoffs.jl:172-193): put = call − S + K·D
+static double cm_parity(double call, double cp, double S0, double strike, double discount) {
+  return cp > 0.0 ? call : call - S0 + strike * discount;
+}
+
+// hh_carr_madan_basket, _jump, _bates and _vg: the call prices of the launch, puts by parity
+static int carr_madan_basket_call(hh_ctx* ctx, const CmBasket& f, bool null_arg, const hh_model* m, double alpha, double bound,
+                                  const CmPayoffs& q, double* prices_out) {
+  if (!ctx) return HH_ERR_INVALID;
+  std::lock_guard<std::recursive_mutex> lock__(ctx->mu);
+  std::vector<double> host;
+  const int rc = cm_basket_run(ctx, f, null_arg || !m || !prices_out, alpha, bound, q, 1, host);
+  if (rc) return rc;
+  for (size_t k = 0, n = q.n; k < n; ++k)
+    prices_out[k] = cm_parity(host[4 * n + k], q.cps[k], m->S0, q.strikes[k], q.discounts[k]);
+  return HH_OK;
+}
+
+static int check_cm_dynamics(hh_ctx* ctx, int32_t dynamics) {
+  if (dynamics != HH_LOGNORMAL && dynamics != HH_HESTON) return fail(ctx, HH_ERR_INVALID, "unknown dynamics %d", dynamics);
+  return HH_OK;
+}
+
 int hh_carr_madan_basket(hh_ctx* ctx, const hh_model* m, int32_t dynamics, int32_t compat_sqrt_alpha,
                          double alpha, double bound, const double* strikes, const double* cps,
                          const double* Ts, const double* r_drifts, const double* discounts,
                          uint32_t n_payoffs, double* prices_out) {
-  if (!ctx) return HH_ERR_INVALID;
-  std::lock_guard<std::recursive_mutex> lock__(ctx->mu);
-  if (!m || !strikes || !cps || !Ts || !r_drifts || !discounts || !prices_out)
-    return fail(ctx, HH_ERR_INVALID, "hh_carr_madan_basket: NULL argument");
-  if (dynamics != HH_LOGNORMAL && dynamics != HH_HESTON)
-    return fail(ctx, HH_ERR_INVALID, "unknown dynamics %d", dynamics);
-  if (n_payoffs == 0 || n_payoffs > (1u << 20))
-    return fail(ctx, HH_ERR_INVALID, "hh_carr_madan_basket: 1 .. 2^20 payoffs per call");
-  if (!(m->S0 > 0.0) || !(alpha > 0.0) || !(bound > 0.0) || (dynamics == HH_HESTON && m->sigma == 0.0))
-    return fail(ctx, HH_ERR_INVALID, "hh_carr_madan_basket: bad scalars");
-  if (!hh::carr_madan_subpanels(alpha, bound))
-    return fail(ctx, HH_ERR_INVALID, HH_CM_BOUND_MSG, "hh_carr_madan_basket");
-  const size_t n = n_payoffs;
-  std::vector<double> host(5 * n);  // log K | T | r_drift | discount | (out)
-  const int rc = cm_upload_payoffs(ctx, "hh_carr_madan_basket", strikes, cps, Ts, r_drifts, discounts, n, n, host);
-  if (rc) return rc;
-  HH_HIP(ctx, hh::launch_carr_madan_basket(*m, dynamics, compat_sqrt_alpha, alpha, bound, ctx->payoffs,
-                                           n_payoffs, ctx->payoffs + 4 * n, ctx->stream));
-  HH_HIP(ctx, hipMemcpyAsync(host.data() + 4 * n, ctx->payoffs + 4 * n, n * sizeof(double),
-                             hipMemcpyDeviceToHost, ctx->stream));
-  HH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  for (size_t k = 0; k < n; ++k) {  // parity_transform (payoffs.jl:172-193): put = call − S + K·D
-    const double call = host[4 * n + k];
-    prices_out[k] = cps[k] > 0.0 ? call : call - m->S0 + strikes[k] * discounts[k];
-  }
-  return HH_OK;
+  return carr_madan_basket_call(
+      ctx,
+      {"hh_carr_madan_basket",
+       [&] { return !(m->S0 > 0.0) || !(alpha > 0.0) || !(bound > 0.0) || (dynamics == HH_HESTON && m->sigma == 0.0); },
+       "bad scalars", [&] { return check_cm_dynamics(ctx, dynamics); }, true,
+       [&](const double* per_payoff, uint32_t n, double* out) {
+         return hh::launch_carr_madan_basket(*m, dynamics, compat_sqrt_alpha, alpha, bound, per_payoff, n, out, ctx->stream);
+       }},
+      false, m, alpha, bound, {strikes, cps, Ts, r_drifts, discounts, n_payoffs}, prices_out);
 }
 
 int hh_carr_madan_basket_grad(hh_ctx* ctx, const hh_model* m, int32_t dynamics,
@@ -972,40 +1015,30 @@ int hh_carr_madan_basket_grad(hh_ctx* ctx, const hh_model* m, int32_t dynamics,
                               double* prices_out, double* grad_out) {
   if (!ctx) return HH_ERR_INVALID;
   std::lock_guard<std::recursive_mutex> lock__(ctx->mu);
-  if (!m || !strikes || !cps || !Ts || !r_drifts || !discounts || !prices_out || !grad_out)
-    return fail(ctx, HH_ERR_INVALID, "hh_carr_madan_basket_grad: NULL argument");
-  if (dynamics != HH_LOGNORMAL && dynamics != HH_HESTON)
-    return fail(ctx, HH_ERR_INVALID, "unknown dynamics %d", dynamics);
-  if (n_payoffs == 0 || n_payoffs > (1u << 20))
-    return fail(ctx, HH_ERR_INVALID, "hh_carr_madan_basket_grad: 1 .. 2^20 payoffs per call");
-  if (!(m->S0 > 0.0) || !(alpha > 0.0) || !(bound > 0.0) ||
-      (dynamics == HH_HESTON && (m->sigma == 0.0 || m->theta == 0.0)))
-    return fail(ctx, HH_ERR_INVALID, "hh_carr_madan_basket_grad: bad scalars (Heston: sigma, theta != 0)");
-  if (!hh::carr_madan_subpanels(alpha, bound))
-    return fail(ctx, HH_ERR_INVALID, HH_CM_BOUND_MSG, "hh_carr_madan_basket_grad");
-  const size_t n = n_payoffs;
-  std::vector<double> host(4 * n + HH_CM_GRAD_LEN * n);  // log K | T | r_drift | discount | out [n][8]
-  const int rc = cm_upload_payoffs(ctx, "hh_carr_madan_basket_grad", strikes, cps, Ts, r_drifts, discounts, n,
-                                   HH_CM_GRAD_LEN * n, host);
+  const CmBasket f = {
+      "hh_carr_madan_basket_grad",
+      [&] {
+        return !(m->S0 > 0.0) || !(alpha > 0.0) || !(bound > 0.0) ||
+               (dynamics == HH_HESTON && (m->sigma == 0.0 || m->theta == 0.0));
+      },
+      "bad scalars (Heston: sigma, theta != 0)", [&] { return check_cm_dynamics(ctx, dynamics); }, true,
+      [&](const double* per_payoff, uint32_t n, double* out) {
+        return hh::launch_carr_madan_grad(*m, dynamics, compat_sqrt_alpha, alpha, bound, per_payoff, n, out, ctx->stream);
+      }};
+  std::vector<double> host;
+  const int rc = cm_basket_run(ctx, f, !m || !prices_out || !grad_out, alpha, bound,
+                               {strikes, cps, Ts, r_drifts, discounts, n_payoffs}, HH_CM_GRAD_LEN, host);
   if (rc) return rc;
-  double* out_dev = ctx->payoffs + 4 * n;
-  HH_HIP(ctx, hh::launch_carr_madan_grad(*m, dynamics, compat_sqrt_alpha, alpha, bound, ctx->payoffs,
-                                         n_payoffs, out_dev, ctx->stream));
-  HH_HIP(ctx, hipMemcpyAsync(host.data() + 4 * n, out_dev, HH_CM_GRAD_LEN * n * sizeof(double),
-                             hipMemcpyDeviceToHost, ctx->stream));
-  HH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  for (size_t k = 0; k < n; ++k) {
+  for (size_t k = 0, n = n_payoffs; k < n; ++k) {
     const double* o = host.data() + 4 * n + HH_CM_GRAD_LEN * k;  // call, then d/d(S0 V0 κ θ σ ρ r_drift)
     double* g = grad_out + HH_CM_GRAD_LEN * k;
     for (int i = 0; i < 7; ++i) g[i] = o[1 + i];
     g[HH_CM_GRAD_DISCOUNT] = o[0] / discounts[k];  // the price is linear in the discount factor
-    double price = o[0];
-    if (cps[k] < 0.0) {  // parity_transform (payoffs.jl:172-193): put = call − S + K·D
-      price = price - m->S0 + strikes[k] * discounts[k];
+    if (cps[k] < 0.0) {                            // the put's parity terms: −S0 + K·D
       g[HH_CM_GRAD_S0] -= 1.0;
       g[HH_CM_GRAD_DISCOUNT] += strikes[k];
     }
-    prices_out[k] = price;
+    prices_out[k] = cm_parity(o[0], cps[k], m->S0, strikes[k], discounts[k]);
   }
   return HH_OK;
 }
@@ -1818,24 +1851,34 @@ int hh_mc_solve_path_jump(hh_ctx* ctx, const hh_model* m, const hh_jump* jump, c
                          payoffs, n_payoffs, out, path_values, stats);
 }
 
-int hh_mc_solve_jump(hh_ctx* ctx, const hh_model* m, const hh_jump* jump, const hh_config* c, hh_result* out,
-                     double* terminal) {
+// One solve on a terminal law drawn in one kernel (hh_mc_solve_jump, hh_mc_solve_vg): who it is, the strategies it
+// refuses, the law's check, the records of its launch and the launch.
+struct TerminalLaw {
+  const char* who;
+  bool (*bad_strategy)(const hh_config&);
+  std::function<int()> law_check;
+  uint32_t (*n_records)(uint64_t n_paths);
+  std::function<int(const hh::DevicePtrs&)> launch;
+};
+
+static int terminal_law_call(hh_ctx* ctx, const TerminalLaw& f, bool null_law, const hh_model* m, const hh_config* c,
+                             hh_result* out, double* terminal) {
   if (!ctx) return HH_ERR_INVALID;
   std::lock_guard<std::recursive_mutex> lock__(ctx->mu);
-  const char* who = "hh_mc_solve_jump";
-  if (!m || !jump || !c || !out) return fail(ctx, HH_ERR_INVALID, "%s: NULL argument", who);
-  if (c->dynamics == HH_HESTON || c->strategy == HH_EULER_MARUYAMA || c->strategy == HH_BROADIE_KAYA)
+  const char* who = f.who;
+  if (!m || null_law || !c || !out) return fail(ctx, HH_ERR_INVALID, "%s: NULL argument", who);
+  if (c->dynamics == HH_HESTON || f.bad_strategy(*c))
     return fail(ctx, HH_ERR_UNSUPPORTED, "%s needs LognormalDynamics + the exact law (HH_EXACT_LAW)", who);
   if (c->noise_mode == HH_NOISE_REPLAY || c->n_partials != 0)
     return fail(ctx, HH_ERR_UNSUPPORTED, "%s: GENERATE noise, no dual partials", who);
   int rc = validate(ctx, m, c);
   if (rc) return rc;
-  if ((rc = check_jump(ctx, who, jump, m->T))) return rc;
+  if ((rc = f.law_check())) return rc;
   const WallClock clock;
   std::memset(out, 0, sizeof(*out));
   HH_HIP(ctx, hipSetDevice(ctx->device));
   HH_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-  const uint32_t n_rec = hh::merton_records(c->n_paths);
+  const uint32_t n_rec = f.n_records(c->n_paths);
   if ((rc = ensure(ctx, ctx->records, (size_t)n_rec * hh::kRecStride))) return rc;
   hh::DevicePtrs p{};
   p.records = ctx->records;
@@ -1847,7 +1890,7 @@ int hh_mc_solve_jump(hh_ctx* ctx, const hh_model* m, const hh_jump* jump, const 
     p.terminal = ctx->terminal;
   }
   if ((rc = begin_timing(ctx))) return rc;
-  HH_HIP(ctx, hh::launch_merton_exact(*m, *c, *jump, p, ctx->stream));
+  HH_HIP(ctx, f.launch(p));
   HH_HIP(ctx, hh::launch_reduce_records(ctx->records, n_rec, (double)c->n_paths, ctx->accum, ctx->stream, 1, m, c));
   if ((rc = end_timing(ctx))) return rc;
   HH_HIP(ctx, hipEventRecord(ctx->ev1, ctx->stream));
@@ -1860,44 +1903,33 @@ int hh_mc_solve_jump(hh_ctx* ctx, const hh_model* m, const hh_jump* jump, const 
   return solve_times(ctx, clock, &out->kernel_ms, &out->total_ms);
 }
 
-// hh_carr_madan_jump and hh_carr_madan_bates: launch_carr_madan_basket's rule with the jump term in the characteristic
-// function.  bad_scalars: the model's and the rule's scalars the entry point refuses.
-using CmJumpLaunch = int (*)(const hh_model&, const hh_jump&, double, double, const double*, uint32_t, double*, hipStream_t);
-static int carr_madan_jump_call(hh_ctx* ctx, const char* who, bool (*bad_scalars)(const hh_model&, double, double),
-                                CmJumpLaunch launch, const hh_model* m, const hh_jump* jump, double alpha, double bound,
-                                const double* strikes, const double* cps, const double* Ts, const double* r_drifts,
-                                const double* discounts, uint32_t n_payoffs, double* prices_out) {
-  if (!ctx) return HH_ERR_INVALID;
-  std::lock_guard<std::recursive_mutex> lock__(ctx->mu);
-  if (!m || !jump || !strikes || !cps || !Ts || !r_drifts || !discounts || !prices_out)
-    return fail(ctx, HH_ERR_INVALID, "%s: NULL argument", who);
-  if (n_payoffs == 0 || n_payoffs > (1u << 20)) return fail(ctx, HH_ERR_INVALID, "%s: 1 .. 2^20 payoffs per call", who);
-  if (bad_scalars(*m, alpha, bound)) return fail(ctx, HH_ERR_INVALID, "%s: bad scalars", who);
-  int rc = check_jump(ctx, who, jump, 0.0);  // no draw here: the mean of one is not limited
-  if (rc) return rc;
-  if (!hh::carr_madan_subpanels(alpha, bound)) return fail(ctx, HH_ERR_INVALID, HH_CM_BOUND_MSG, who);
-  const size_t n = n_payoffs;
-  std::vector<double> host(5 * n);  // log K | T | r_drift | discount | (out)
-  if ((rc = cm_upload_payoffs(ctx, who, strikes, cps, Ts, r_drifts, discounts, n, n, host))) return rc;
-  HH_HIP(ctx, launch(*m, *jump, alpha, bound, ctx->payoffs, n_payoffs, ctx->payoffs + 4 * n, ctx->stream));
-  HH_HIP(ctx, hipMemcpyAsync(host.data() + 4 * n, ctx->payoffs + 4 * n, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  HH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  for (size_t k = 0; k < n; ++k) {  // parity_transform (payoffs.jl:172-193): put = call − S + K·D
-    const double call = host[4 * n + k];
-    prices_out[k] = cps[k] > 0.0 ? call : call - m->S0 + strikes[k] * discounts[k];
-  }
-  return HH_OK;
+int hh_mc_solve_jump(hh_ctx* ctx, const hh_model* m, const hh_jump* jump, const hh_config* c, hh_result* out,
+                     double* terminal) {
+  return terminal_law_call(
+      ctx,
+      {"hh_mc_solve_jump",  // HH_QE is left to validate
+       [](const hh_config& c) { return c.strategy == HH_EULER_MARUYAMA || c.strategy == HH_BROADIE_KAYA; },
+       [&] { return check_jump(ctx, "hh_mc_solve_jump", jump, m->T); }, hh::merton_records,
+       [&](const hh::DevicePtrs& p) { return hh::launch_merton_exact(*m, *c, *jump, p, ctx->stream); }},
+      !jump, m, c, out, terminal);
+}
+
+// The scalars hh_carr_madan_jump and hh_carr_madan_vg refuse: their model is S0 and sigma
+static bool cm_bad_lognormal_scalars(const hh_model& m, double alpha, double bound) {
+  return !(m.S0 > 0.0) || !std::isfinite(m.S0) || !std::isfinite(m.sigma) || !(alpha > 0.0) || !(bound > 0.0);
 }
 
 int hh_carr_madan_jump(hh_ctx* ctx, const hh_model* m, const hh_jump* jump, double alpha, double bound,
                        const double* strikes, const double* cps, const double* Ts, const double* r_drifts,
                        const double* discounts, uint32_t n_payoffs, double* prices_out) {
-  return carr_madan_jump_call(
-      ctx, "hh_carr_madan_jump",
-      [](const hh_model& m, double alpha, double bound) {
-        return !(m.S0 > 0.0) || !std::isfinite(m.S0) || !std::isfinite(m.sigma) || !(alpha > 0.0) || !(bound > 0.0);
-      },
-      hh::launch_carr_madan_jump, m, jump, alpha, bound, strikes, cps, Ts, r_drifts, discounts, n_payoffs, prices_out);
+  return carr_madan_basket_call(
+      ctx,
+      {"hh_carr_madan_jump", [&] { return cm_bad_lognormal_scalars(*m, alpha, bound); }, "bad scalars",
+       [&] { return check_jump(ctx, "hh_carr_madan_jump", jump, 0.0); }, false,  // no draw here: the mean of one is not limited
+       [&](const double* per_payoff, uint32_t n, double* out) {
+         return hh::launch_carr_madan_jump(*m, *jump, alpha, bound, per_payoff, n, out, ctx->stream);
+       }},
+      !jump, m, alpha, bound, {strikes, cps, Ts, r_drifts, discounts, n_payoffs}, prices_out);
 }
 
 // ---- Variance Gamma (hedgehog_mc.h, "Variance Gamma"; kernels: hh_vg.hip, hh_fourier.hip) ----
@@ -1915,71 +1947,25 @@ int hh_mc_solve_path_vg(hh_ctx* ctx, const hh_model* m, const hh_vg* vg, const h
 }
 
 int hh_mc_solve_vg(hh_ctx* ctx, const hh_model* m, const hh_vg* vg, const hh_config* c, hh_result* out, double* terminal) {
-  if (!ctx) return HH_ERR_INVALID;
-  std::lock_guard<std::recursive_mutex> lock__(ctx->mu);
-  const char* who = "hh_mc_solve_vg";
-  if (!m || !vg || !c || !out) return fail(ctx, HH_ERR_INVALID, "%s: NULL argument", who);
-  if (c->dynamics == HH_HESTON || c->strategy != HH_EXACT_LAW)
-    return fail(ctx, HH_ERR_UNSUPPORTED, "%s needs LognormalDynamics + the exact law (HH_EXACT_LAW)", who);
-  if (c->noise_mode == HH_NOISE_REPLAY || c->n_partials != 0)
-    return fail(ctx, HH_ERR_UNSUPPORTED, "%s: GENERATE noise, no dual partials", who);
-  int rc = validate(ctx, m, c);
-  if (rc) return rc;
-  if ((rc = check_vg(ctx, who, m, vg, 1.0))) return rc;
-  const WallClock clock;
-  std::memset(out, 0, sizeof(*out));
-  HH_HIP(ctx, hipSetDevice(ctx->device));
-  HH_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-  const uint32_t n_rec = hh::vg_records(c->n_paths);
-  if ((rc = ensure(ctx, ctx->records, (size_t)n_rec * hh::kRecStride))) return rc;
-  hh::DevicePtrs p{};
-  p.records = ctx->records;
-  if ((rc = stage_noise(ctx, c, p, false))) return rc;  // seeds[0]
-  if (terminal && c->terminal_on_device) {
-    p.terminal = terminal;
-  } else if (terminal) {
-    if ((rc = ensure(ctx, ctx->terminal, (size_t)c->n_paths * (c->antithetic ? 2 : 1)))) return rc;
-    p.terminal = ctx->terminal;
-  }
-  if ((rc = begin_timing(ctx))) return rc;
-  HH_HIP(ctx, hh::launch_vg_exact(*m, *c, *vg, p, ctx->stream));
-  HH_HIP(ctx, hh::launch_reduce_records(ctx->records, n_rec, (double)c->n_paths, ctx->accum, ctx->stream, 1, m, c));
-  if ((rc = end_timing(ctx))) return rc;
-  HH_HIP(ctx, hipEventRecord(ctx->ev1, ctx->stream));
-  HH_HIP(ctx, hipMemcpyAsync(ctx->accum_host, ctx->accum, HH_ACC_LEN * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  HH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  if ((rc = release_host_operands(ctx))) return rc;
-  if ((rc = copy_back_terminal(ctx, c, terminal))) return rc;
-  rc = hh_mc_finalize(m, c, ctx->accum_host, out);
-  if (rc) return fail(ctx, rc, "finalize failed: the accumulator holds no trajectories");
-  return solve_times(ctx, clock, &out->kernel_ms, &out->total_ms);
+  return terminal_law_call(
+      ctx,
+      {"hh_mc_solve_vg", [](const hh_config& c) { return c.strategy != HH_EXACT_LAW; },
+       [&] { return check_vg(ctx, "hh_mc_solve_vg", m, vg, 1.0); }, hh::vg_records,
+       [&](const hh::DevicePtrs& p) { return hh::launch_vg_exact(*m, *c, *vg, p, ctx->stream); }},
+      !vg, m, c, out, terminal);
 }
 
 int hh_carr_madan_vg(hh_ctx* ctx, const hh_model* m, const hh_vg* vg, double alpha, double bound, const double* strikes,
                      const double* cps, const double* Ts, const double* r_drifts, const double* discounts,
                      uint32_t n_payoffs, double* prices_out) {
-  if (!ctx) return HH_ERR_INVALID;
-  std::lock_guard<std::recursive_mutex> lock__(ctx->mu);
-  const char* who = "hh_carr_madan_vg";
-  if (!m || !vg || !strikes || !cps || !Ts || !r_drifts || !discounts || !prices_out)
-    return fail(ctx, HH_ERR_INVALID, "%s: NULL argument", who);
-  if (n_payoffs == 0 || n_payoffs > (1u << 20)) return fail(ctx, HH_ERR_INVALID, "%s: 1 .. 2^20 payoffs per call", who);
-  if (!(m->S0 > 0.0) || !std::isfinite(m->S0) || !std::isfinite(m->sigma) || !(alpha > 0.0) || !(bound > 0.0))
-    return fail(ctx, HH_ERR_INVALID, "%s: bad scalars", who);
-  int rc = check_vg(ctx, who, m, vg, 1.0 + alpha);
-  if (rc) return rc;
-  if (!hh::carr_madan_subpanels(alpha, bound)) return fail(ctx, HH_ERR_INVALID, HH_CM_BOUND_MSG, who);
-  const size_t n = n_payoffs;
-  std::vector<double> host(5 * n);  // log K | T | r_drift | discount | (out)
-  if ((rc = cm_upload_payoffs(ctx, who, strikes, cps, Ts, r_drifts, discounts, n, n, host))) return rc;
-  HH_HIP(ctx, hh::launch_carr_madan_vg(*m, *vg, alpha, bound, ctx->payoffs, n_payoffs, ctx->payoffs + 4 * n, ctx->stream));
-  HH_HIP(ctx, hipMemcpyAsync(host.data() + 4 * n, ctx->payoffs + 4 * n, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  HH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  for (size_t k = 0; k < n; ++k) {  // parity_transform: put = call − S + K·D
-    const double call = host[4 * n + k];
-    prices_out[k] = cps[k] > 0.0 ? call : call - m->S0 + strikes[k] * discounts[k];
-  }
-  return HH_OK;
+  return carr_madan_basket_call(
+      ctx,
+      {"hh_carr_madan_vg", [&] { return cm_bad_lognormal_scalars(*m, alpha, bound); }, "bad scalars",
+       [&] { return check_vg(ctx, "hh_carr_madan_vg", m, vg, 1.0 + alpha); }, false,
+       [&](const double* per_payoff, uint32_t n, double* out) {
+         return hh::launch_carr_madan_vg(*m, *vg, alpha, bound, per_payoff, n, out, ctx->stream);
+       }},
+      !vg, m, alpha, bound, {strikes, cps, Ts, r_drifts, discounts, n_payoffs}, prices_out);
 }
 
 // ---- Heston paths by the quadratic-exponential scheme (hedgehog_mc.h; kernel: hh_qe.hip) ----------------------
@@ -2047,12 +2033,15 @@ int hh_mc_solve_path_bates(hh_ctx* ctx, const hh_model* m, const hh_qe* qe, cons
 int hh_carr_madan_bates(hh_ctx* ctx, const hh_model* m, const hh_jump* jump, double alpha, double bound,
                         const double* strikes, const double* cps, const double* Ts, const double* r_drifts,
                         const double* discounts, uint32_t n_payoffs, double* prices_out) {
-  return carr_madan_jump_call(
-      ctx, "hh_carr_madan_bates",
-      [](const hh_model& m, double alpha, double bound) {  // hh_carr_madan_basket's, under HH_HESTON
-        return !(m.S0 > 0.0) || !(alpha > 0.0) || !(bound > 0.0) || m.sigma == 0.0;
-      },
-      hh::launch_carr_madan_bates, m, jump, alpha, bound, strikes, cps, Ts, r_drifts, discounts, n_payoffs, prices_out);
+  return carr_madan_basket_call(
+      ctx,
+      {"hh_carr_madan_bates",  // hh_carr_madan_basket's scalars, under HH_HESTON
+       [&] { return !(m->S0 > 0.0) || !(alpha > 0.0) || !(bound > 0.0) || m->sigma == 0.0; }, "bad scalars",
+       [&] { return check_jump(ctx, "hh_carr_madan_bates", jump, 0.0); }, false,
+       [&](const double* per_payoff, uint32_t n, double* out) {
+         return hh::launch_carr_madan_bates(*m, *jump, alpha, bound, per_payoff, n, out, ctx->stream);
+       }},
+      !jump, m, alpha, bound, {strikes, cps, Ts, r_drifts, discounts, n_payoffs}, prices_out);
 }
 
 // ---- LSM on an ensemble sharded over several devices ------------------------------------------------

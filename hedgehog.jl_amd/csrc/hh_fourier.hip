@@ -21,6 +21,10 @@
 // the expiry at hand; κ − ρσ(α+1) > 0 and (κ − ρσ(α+1))² ≥ σ²·α(α+1) make the (α+1)-th moment finite
 // for every T.  Outside it the transform's own singularities approach the real line and no fixed rule
 // converges; the kernels do not detect this.
+//
+// The unit is one rule (RuleArgs, carr_madan_kernel, carr_madan_grad_kernel) over one small type per law.  A law holds
+// its own constants and has two members: set_payoff(T, r) forms what depends on a payoff's expiry and drift rate, cf(u)
+// is the characteristic function of log S_T.  A further law is a further such type and a launcher of three lines.
 #include <cmath>
 
 #include "hh_kernels.h"
@@ -60,90 +64,131 @@ __device__ __forceinline__ cz zexp(cz z) {
 }
 __device__ __forceinline__ cz zlog(cz z) { return {log(hypot(z.re, z.im)), atan2(z.im, z.re)}; }
 
-struct FourierArgs {
-  int dynamics;
-  double logS0, V0, kappa, theta, sigma, rho, r, T;  // Heston law (montecarlo.jl:310-320)
-  double law_mu, law_sd;                             // lognormal law (montecarlo.jl:293-303)
-  double alpha, bound, logK, discount;
-  double* out;  // [0] = damped-call integral (the call price)
-  // basket form (one workgroup per payoff): per-payoff scalars in device memory, [4][n]:
-  // log K, T, r_drift, discount; NULL = the fields above
+// ---- the rule and the payoffs ---------------------------------------------------------------------------------------------
+struct RuleArgs {
+  double alpha, bound;
+  uint32_t m_sub;  // sub-panels per lane (carr_madan_subpanels)
+  // basket form (one workgroup per payoff): per-payoff scalars in device memory, [4][n]: log K, T, r_drift, discount;
+  // NULL = the one payoff of the scalars below, whose T and r the launcher has given to the law already
   const double* per_payoff;
-  uint32_t n_payoffs, compat_sqrt_alpha;
-  uint32_t m_sub;   // sub-panels per lane (carr_madan_subpanels)
-  double sigma_ln;  // lognormal volatility (law_mu / law_sd are formed per payoff)
-  // Merton jumps (dynamics = kDynMerton, a code internal to this unit): the lognormal law above with the compensated
-  // drift, times exp(λT·(exp(iu·μ_J − σ_J²u²/2) − 1)); Bates (carr_madan_bates_kernel): the Heston law with them
-  double lam, mu_j, sigma_j, lam_kbar;
-  // Variance Gamma (dynamics = kDynVg): θ·ν, σ²ν/2, ν and the compensator ω (hh_vg.h: vg_omega), formed on the host
-  double vg_theta_nu, vg_half_s2nu, vg_nu, vg_omega;
+  uint32_t n_payoffs;
+  double* out;  // [blockIdx.x] = damped-call integral (the call price); the gradient form: [blockIdx.x][kGradVals]
+  double logK, T, r, discount;
 };
-constexpr int kDynMerton = 2;  // beside HH_LOGNORMAL = 0 and HH_HESTON = 1; never crosses the C-ABI
-constexpr int kDynVg = 3;      // … and neither does this one
 
-// heston.jl:307-319, complex argument u.  JUMP (Bates 1996): a.r carries r − λκ̄ and the jump term
-// (λ·T)·(exp(μ_J·iu − (½σ_J²)·u²) − 1) is added to the exponent last.
-template <bool JUMP>
-__device__ __forceinline__ cz heston_cf_law(const FourierArgs& a, cz u) {
-  const cz iu = {-u.im, u.re};
-  const cz kri = {a.kappa - a.rho * a.sigma * iu.re, -a.rho * a.sigma * iu.im};  // κ − ρσ·iu
-  const cz u2 = u * u;
-  const cz d1 = zsqrt(kri * kri + (a.sigma * a.sigma) * (iu + u2));
-  const cz g = zdiv(kri - d1, kri + d1);
-  const cz ed = zexp({-d1.re * a.T, -d1.im * a.T});
-  const cz one = {1.0, 0.0};
-  const cz one_m_ged = one - g * ed;
-  const cz C = (a.kappa * a.theta / (a.sigma * a.sigma)) *
-               (a.T * (kri - d1) - 2.0 * zlog(zdiv(one_m_ged, one - g)));
-  const cz Dv = (1.0 / (a.sigma * a.sigma)) * ((kri - d1) * zdiv(one - ed, one_m_ged));
-  cz e = C + a.V0 * Dv + a.logS0 * iu + (a.r * a.T) * iu;
-  if constexpr (JUMP) e = e + (a.lam * a.T) * (zexp(a.mu_j * iu - (0.5 * a.sigma_j * a.sigma_j) * u2) - one);
-  return zexp(e);
+struct Payoff {
+  double logK, T, r, discount;
+};
+__device__ __forceinline__ Payoff load_payoff(const RuleArgs& a, uint32_t k) {
+  const uint32_t n = a.n_payoffs;
+  return {a.per_payoff[k], a.per_payoff[n + k], a.per_payoff[2 * n + k], a.per_payoff[3 * n + k]};
 }
-__device__ cz heston_cf(const FourierArgs& a, cz u) { return heston_cf_law<false>(a, u); }
 
-// sample_from_cf.jl:14-16: cf(Normal(μ, σ), t) = exp(i t μ − σ² t²/2)
-__device__ cz normal_cf(const FourierArgs& a, cz t) {
-  const cz it = {-t.im, t.re};
-  return zexp(a.law_mu * it - (0.5 * a.law_sd * a.law_sd) * (t * t));
-}
+// ---- the laws ---------------------------------------------------------------------------------------------------------------
+// lognormal law (montecarlo.jl:293-303); sample_from_cf.jl:14-16: cf(Normal(μ, σ), t) = exp(i t μ − σ² t²/2)
+struct NormalLaw {
+  double logS0, sigma_ln;
+  uint32_t compat_sqrt_alpha;
+  double T, tmul, law_mu, law_sd;  // of the payoff
+  __host__ __device__ void set_payoff(double T_, double r) {
+    T = T_;
+    const double sqT = sqrt(T);
+    tmul = compat_sqrt_alpha ? sqT : T;
+    law_mu = logS0 + (r - 0.5 * sigma_ln * sigma_ln) * tmul;  // montecarlo.jl:302
+    law_sd = sigma_ln * sqT;
+  }
+  __device__ cz cf(cz t) const {
+    const cz it = {-t.im, t.re};
+    return zexp(law_mu * it - (0.5 * law_sd * law_sd) * (t * t));
+  }
+};
+
+// Heston law (montecarlo.jl:310-320); heston.jl:307-319, complex argument u
+struct HestonLaw {
+  double logS0, V0, kappa, theta, sigma, rho;
+  double T, r;  // of the payoff
+  __host__ __device__ void set_payoff(double T_, double r_) { T = T_; r = r_; }
+  __device__ __forceinline__ cz log_cf(cz u) const {
+    const cz iu = {-u.im, u.re};
+    const cz kri = {kappa - rho * sigma * iu.re, -rho * sigma * iu.im};  // κ − ρσ·iu
+    const cz u2 = u * u;
+    const cz d1 = zsqrt(kri * kri + (sigma * sigma) * (iu + u2));
+    const cz g = zdiv(kri - d1, kri + d1);
+    const cz ed = zexp({-d1.re * T, -d1.im * T});
+    const cz one = {1.0, 0.0};
+    const cz one_m_ged = one - g * ed;
+    const cz C = (kappa * theta / (sigma * sigma)) * (T * (kri - d1) - 2.0 * zlog(zdiv(one_m_ged, one - g)));
+    const cz Dv = (1.0 / (sigma * sigma)) * ((kri - d1) * zdiv(one - ed, one_m_ged));
+    return C + V0 * Dv + logS0 * iu + (r * T) * iu;
+  }
+  __device__ cz cf(cz u) const { return zexp(log_cf(u)); }
+};
 
 // Merton (1976): log S_T = the lognormal law (law_mu carries the compensator −λκ̄T) + a compound Poisson sum of N(μ_J, σ_J²)
-__device__ cz merton_cf(const FourierArgs& a, cz t) {
-  const cz it = {-t.im, t.re};
-  const cz t2 = t * t;
-  const cz one = {1.0, 0.0};
-  const cz jump = zexp(a.mu_j * it - (0.5 * a.sigma_j * a.sigma_j) * t2) - one;
-  return zexp(a.law_mu * it - (0.5 * a.law_sd * a.law_sd) * t2 + (a.lam * a.T) * jump);
-}
+struct MertonLaw {
+  NormalLaw n;
+  double lam, mu_j, sigma_j, lam_kbar;
+  __host__ __device__ void set_payoff(double T, double r) {
+    n.set_payoff(T, r);
+    // ((r − σ²/2) − λκ̄)·T, in that order: λ = 0 leaves the lognormal mean
+    n.law_mu = n.logS0 + ((r - 0.5 * n.sigma_ln * n.sigma_ln) - lam_kbar) * T;
+  }
+  __device__ cz cf(cz t) const {
+    const cz it = {-t.im, t.re};
+    const cz t2 = t * t;
+    const cz one = {1.0, 0.0};
+    const cz jump = zexp(mu_j * it - (0.5 * sigma_j * sigma_j) * t2) - one;
+    return zexp(n.law_mu * it - (0.5 * n.law_sd * n.law_sd) * t2 + (lam * n.T) * jump);
+  }
+};
+
+// Bates (1996): the Heston law at r − λκ̄, the jump term (λ·T)·(exp(μ_J·iu − (½σ_J²)·u²) − 1) added to the exponent last
+struct BatesLaw {
+  HestonLaw h;
+  double lam, mu_j, sigma_j, lam_kbar;
+  __host__ __device__ void set_payoff(double T, double r) { h.set_payoff(T, r - lam_kbar); }  // λ = 0 leaves the Heston drift
+  __device__ cz cf(cz u) const {
+    const cz iu = {-u.im, u.re};
+    const cz u2 = u * u;
+    const cz one = {1.0, 0.0};
+    cz e = h.log_cf(u);
+    e = e + (lam * h.T) * (zexp(mu_j * iu - (0.5 * sigma_j * sigma_j) * u2) - one);
+    return zexp(e);
+  }
+};
 
 // Variance Gamma: exp(it·(log S0 + (r + ω)T)) · base^(−T/ν), base = 1 − θν·it + (σ²ν/2)·t², law_mu carrying the first
 // factor's mean.  The power is exp(−(T/ν)·log base) with this unit's zlog, the principal branch: on the contour
 // Im t = −(1+α) the real part of base is 1 − θν(1+α) + (σ²ν/2)(v² − (1+α)²) >= 1 − θν(1+α) − σ²ν(1+α)²/2, which the
 // entry point has checked to be positive — base never crosses the negative real axis, so the branch is continuous
 // along the whole contour.
-__device__ cz vg_cf(const FourierArgs& a, cz t) {
-  const cz it = {-t.im, t.re};
-  const cz one = {1.0, 0.0};
-  const cz base = one - a.vg_theta_nu * it + a.vg_half_s2nu * (t * t);
-  return zexp(a.law_mu * it - (a.T / a.vg_nu) * zlog(base));
-}
+struct VgLaw {
+  double logS0;
+  double theta_nu, half_s2nu, nu, omega;  // θ·ν, σ²ν/2, ν and the compensator ω (hh_vg.h: vg_omega), formed on the host
+  double T, law_mu;                       // of the payoff
+  __host__ __device__ void set_payoff(double T_, double r) {
+    T = T_;
+    law_mu = logS0 + (r + omega) * T;
+  }
+  __device__ cz cf(cz t) const {
+    const cz it = {-t.im, t.re};
+    const cz one = {1.0, 0.0};
+    const cz base = one - theta_nu * it + half_s2nu * (t * t);
+    return zexp(law_mu * it - (T / nu) * zlog(base));
+  }
+};
 
-// carr_madan.jl:59-61, 88-92: damp · call_transform(v) · exp(−i v log K), real part.  BATES: the Heston law with jumps,
-// whatever a.dynamics says
-template <bool BATES>
-__device__ __forceinline__ double integrand_law(const FourierArgs& a, double v) {
+// carr_madan.jl:59-61, 88-92: damp · call_transform(v) · exp(−i v log K), real part
+template <class Law>
+__device__ double integrand(const Law& law, const RuleArgs& a, const Payoff& p, double v) {
   const cz u = {v, -(a.alpha + 1.0)};
-  cz phi;
-  if constexpr (BATES) phi = heston_cf_law<true>(a, u);
-  else phi = a.dynamics == HH_HESTON ? heston_cf(a, u) : a.dynamics == kDynMerton ? merton_cf(a, u)
-          : a.dynamics == kDynVg ? vg_cf(a, u) : normal_cf(a, u);
+  const cz phi = law.cf(u);
   const cz den = {a.alpha * a.alpha + a.alpha - v * v, v * (2.0 * a.alpha + 1.0)};
-  const cz val = zdiv(a.discount * phi, den) * zexp({0.0, -v * a.logK});
-  return exp(-a.alpha * a.logK) / 6.28318530717958647692 * val.re;
+  const cz val = zdiv(p.discount * phi, den) * zexp({0.0, -v * p.logK});
+  return exp(-a.alpha * p.logK) / 6.28318530717958647692 * val.re;
 }
-__device__ double integrand(const FourierArgs& a, double v) { return integrand_law<false>(a, v); }
 
+// ---- the rule's pieces ------------------------------------------------------------------------------------------------------
 // 16-point Gauss–Legendre on [-1, 1] (positive half; symmetric)
 __constant__ double kGLx[8] = {0.0950125098376374401853193, 0.2816035507792589132304605,
                                0.4580167776572273863424194, 0.6178762444026437484466718,
@@ -161,6 +206,56 @@ __constant__ double kGLw[8] = {0.1894506104550684962853967, 0.182603415044923588
 __device__ __forceinline__ double subpanel_centre(double mid, double hsub, uint32_t m, uint32_t j) {
   if (m == 1) return mid;
   return (double)(2 * (int)(threadIdx.x * m + j) + 1 - 256 * (int)m) * hsub;
+}
+
+// This lane's panel, sub-panel by sub-panel: body(centre, half-width)
+template <class Body>
+__device__ __forceinline__ void for_each_subpanel(const RuleArgs& a, Body body) {
+  const double w = 2.0 * a.bound / 256.0;  // panel width
+  const double mid = -a.bound + (threadIdx.x + 0.5) * w, half = 0.5 * w;
+  const double hsub = half / (double)a.m_sub;
+#pragma unroll 1
+  for (uint32_t j = 0; j < a.m_sub; ++j) body(subpanel_centre(mid, hsub, a.m_sub, j), hsub);
+}
+
+// out[i] = the workgroup's sum of acc[i]: down each wave by shuffles, then the four waves in order
+template <int N>
+__device__ __forceinline__ void block_sum(const double (&acc)[N], double* out) {
+  __shared__ double sm[4][N];
+#pragma unroll
+  for (int i = 0; i < N; ++i) {
+    double s = acc[i];
+    for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
+    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6][i] = s;
+  }
+  __syncthreads();
+  if (threadIdx.x < N)
+    out[threadIdx.x] = ((sm[0][threadIdx.x] + sm[1][threadIdx.x]) + sm[2][threadIdx.x]) + sm[3][threadIdx.x];
+}
+
+// The law and the payoff of this workgroup: payoff blockIdx.x of a basket with its expiry-dependent scalars, or the one
+// payoff of the rule's own scalars
+template <class Law>
+__device__ __forceinline__ Payoff payoff_of_block(const RuleArgs& a, Law& law) {
+  if (!a.per_payoff) return {a.logK, a.T, a.r, a.discount};
+  const Payoff p = load_payoff(a, blockIdx.x);
+  law.set_payoff(p.T, p.r);
+  return p;
+}
+
+template <class Law>
+__global__ __launch_bounds__(256) void carr_madan_kernel(const Law law0, const RuleArgs a) {
+  Law law = law0;
+  const Payoff p = payoff_of_block(a, law);
+  double s[1] = {0.0};
+  for_each_subpanel(a, [&](double msub, double hsub) {
+    double sj = 0.0;
+#pragma unroll 1
+    for (int k = 0; k < 8; ++k)
+      sj += kGLw[k] * (integrand(law, a, p, msub - hsub * kGLx[k]) + integrand(law, a, p, msub + hsub * kGLx[k]));
+    s[0] += sj * hsub;
+  });
+  block_sum(s, a.out + blockIdx.x);
 }
 
 // ---- gradient of the price: complex numbers carrying P complex partials --------------------------
@@ -254,8 +349,8 @@ __device__ __forceinline__ zd<P> zconst(double x, int dir = -1) {  // a real par
   return r;
 }
 
-// C and D of heston.jl:307-319 with their partials along (κ, σ, ρ); same expressions as heston_cf
-__device__ void heston_CD(const FourierArgs& a, cz u, zd<3>& C, zd<3>& Dv) {
+// C and D of heston.jl:307-319 with their partials along (κ, σ, ρ); same expressions as HestonLaw::log_cf
+__device__ void heston_CD(const HestonLaw& a, cz u, zd<3>& C, zd<3>& Dv) {
   const zd<3> kappa = zconst<3>(a.kappa, 0), sigma = zconst<3>(a.sigma, 1), rho = zconst<3>(a.rho, 2);
   const cz iu = {-u.im, u.re};
   const zd<3> rs = rho * sigma;
@@ -271,145 +366,65 @@ __device__ void heston_CD(const FourierArgs& a, cz u, zd<3>& C, zd<3>& Dv) {
   Dv = zdivd((kri - d1) * zdivd(one - ed, one_m_ged), s2);
 }
 
+// ϕ(u) and ∂ log ϕ along S0, V0, κ, θ, σ, ρ, r (dl comes in zeroed), law by law
+__device__ __forceinline__ cz cf_with_partials(const HestonLaw& a, cz u, double S0, cz* dl) {
+  const cz iu = {-u.im, u.re};
+  zd<3> C, Dv;
+  heston_CD(a, u, C, Dv);
+  dl[0] = (1.0 / S0) * iu;
+  dl[1] = Dv.v;
+  dl[2] = C.d[0] + a.V0 * Dv.d[0];
+  dl[3] = (1.0 / a.theta) * C.v;
+  dl[4] = C.d[1] + a.V0 * Dv.d[1];
+  dl[5] = C.d[2] + a.V0 * Dv.d[2];
+  dl[6] = a.T * iu;
+  return zexp(C.v + a.V0 * Dv.v + (a.logS0 + a.r * a.T) * iu);
+}
+// sample_from_cf.jl:14-16: log ϕ = i t μ − σ_T² t²/2, μ = log S0 + (r − σ²/2)·tmul
+__device__ __forceinline__ cz cf_with_partials(const NormalLaw& a, cz t, double S0, cz* dl) {
+  const cz it = {-t.im, t.re}, t2 = t * t;
+  dl[0] = (1.0 / S0) * it;
+  dl[4] = (-a.sigma_ln * a.tmul) * it - (a.sigma_ln * a.T) * t2;
+  dl[6] = a.tmul * it;
+  return zexp(a.law_mu * it - (0.5 * a.law_sd * a.law_sd) * t2);
+}
+
 // Price and gradient of one payoff per workgroup.  out[k][0] = call price, out[k][1..7] = its partials
 // along S0, V0, κ, θ, σ, ρ, r_drift (lognormal: S0, σ, r_drift in slots 1, 5, 7; the others 0).
 constexpr int kGradVals = 8;
-__global__ __launch_bounds__(256) void carr_madan_grad_kernel(const FourierArgs a0) {
-  FourierArgs a = a0;
-  const uint32_t kp = blockIdx.x, n = a0.n_payoffs;
-  a.logK = a0.per_payoff[kp];
-  a.T = a0.per_payoff[n + kp];
-  a.r = a0.per_payoff[2 * n + kp];
-  a.discount = a0.per_payoff[3 * n + kp];
-  const double sqT = sqrt(a.T), tmul = a0.compat_sqrt_alpha ? sqT : a.T;
-  a.law_mu = a.logS0 + (a.r - 0.5 * a0.sigma_ln * a0.sigma_ln) * tmul;
-  a.law_sd = a0.sigma_ln * sqT;
-  const double S0 = exp(a.logS0);
-  const double w = 2.0 * a.bound / 256.0;
-  const double mid = -a.bound + (threadIdx.x + 0.5) * w, half = 0.5 * w;
-  const double damp = exp(-a.alpha * a.logK) / 6.28318530717958647692;
+template <class Law>
+__global__ __launch_bounds__(256) void carr_madan_grad_kernel(const Law law0, const RuleArgs a) {
+  Law law = law0;
+  const Payoff p = payoff_of_block(a, law);
+  const double S0 = exp(law.logS0);
+  const double damp = exp(-a.alpha * p.logK) / 6.28318530717958647692;
   double acc[kGradVals];
 #pragma unroll
   for (int i = 0; i < kGradVals; ++i) acc[i] = 0.0;
   auto node = [&](double v, double wt) {
     const cz u = {v, -(a.alpha + 1.0)};
-    const cz iu = {-u.im, u.re};
     const cz den = {a.alpha * a.alpha + a.alpha - v * v, v * (2.0 * a.alpha + 1.0)};
-    const cz kern = (wt * damp * a.discount) * (zdiv({1.0, 0.0}, den) * zexp({0.0, -v * a.logK}));
-    cz phi, dl[7];  // ∂ log ϕ along S0, V0, κ, θ, σ, ρ, r
+    const cz kern = (wt * damp * p.discount) * (zdiv({1.0, 0.0}, den) * zexp({0.0, -v * p.logK}));
+    cz dl[7];
 #pragma unroll
     for (int i = 0; i < 7; ++i) dl[i] = {0.0, 0.0};
-    if (a.dynamics == HH_HESTON) {
-      zd<3> C, Dv;
-      heston_CD(a, u, C, Dv);
-      phi = zexp(C.v + a.V0 * Dv.v + (a.logS0 + a.r * a.T) * iu);
-      dl[0] = (1.0 / S0) * iu;
-      dl[1] = Dv.v;
-      dl[2] = C.d[0] + a.V0 * Dv.d[0];
-      dl[3] = (1.0 / a.theta) * C.v;
-      dl[4] = C.d[1] + a.V0 * Dv.d[1];
-      dl[5] = C.d[2] + a.V0 * Dv.d[2];
-      dl[6] = a.T * iu;
-    } else {  // sample_from_cf.jl:14-16: log ϕ = i t μ − σ_T² t²/2, μ = log S0 + (r − σ²/2)·tmul
-      const cz t = u, it = iu, t2 = t * t;
-      phi = zexp(a.law_mu * it - (0.5 * a.law_sd * a.law_sd) * t2);
-      dl[0] = (1.0 / S0) * it;
-      dl[4] = (-a0.sigma_ln * tmul) * it - (a0.sigma_ln * a.T) * t2;
-      dl[6] = tmul * it;
-    }
+    const cz phi = cf_with_partials(law, u, S0, dl);
     const cz base = kern * phi;
     acc[0] += base.re;
 #pragma unroll
     for (int i = 0; i < 7; ++i) acc[1 + i] += (base * dl[i]).re;
   };
-  const double hsub = half / (double)a.m_sub;
-#pragma unroll 1
-  for (uint32_t j = 0; j < a.m_sub; ++j) {
-    const double msub = subpanel_centre(mid, hsub, a.m_sub, j);
+  for_each_subpanel(a, [&](double msub, double hsub) {
 #pragma unroll 1
     for (int k = 0; k < 8; ++k) {
-      node(msub - hsub * kGLx[k], kGLw[k] * hsub);
-      node(msub + hsub * kGLx[k], kGLw[k] * hsub);
+      // the node below and the node above the centre, in that order, through ONE copy of the node's code: two copies
+      // side by side are scheduled into each other and cost the Heston instance 100 more registers (408 against 304)
+#pragma unroll 1
+      for (int side = 0; side < 2; ++side)
+        node(side ? msub + hsub * kGLx[k] : msub - hsub * kGLx[k], kGLw[k] * hsub);
     }
-  }
-  __shared__ double sm[4][kGradVals];
-#pragma unroll
-  for (int i = 0; i < kGradVals; ++i) {
-    double s = acc[i];
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
-    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6][i] = s;
-  }
-  __syncthreads();
-  if (threadIdx.x < kGradVals)
-    a0.out[(size_t)kp * kGradVals + threadIdx.x] =
-        ((sm[0][threadIdx.x] + sm[1][threadIdx.x]) + sm[2][threadIdx.x]) + sm[3][threadIdx.x];
-}
-
-__global__ __launch_bounds__(256) void carr_madan_kernel(const FourierArgs a0) {
-  FourierArgs a = a0;
-  if (a0.per_payoff) {  // payoff blockIdx.x of a basket: its expiry-dependent scalars
-    const uint32_t k = blockIdx.x, n = a0.n_payoffs;
-    a.logK = a0.per_payoff[k];
-    a.T = a0.per_payoff[n + k];
-    a.r = a0.per_payoff[2 * n + k];
-    a.discount = a0.per_payoff[3 * n + k];
-    const double sqT = sqrt(a.T), tmul = a0.compat_sqrt_alpha ? sqT : a.T;
-    a.law_mu = a.logS0 + (a.r - 0.5 * a0.sigma_ln * a0.sigma_ln) * tmul;  // montecarlo.jl:302
-    a.law_sd = a0.sigma_ln * sqT;
-    if (a0.dynamics == kDynMerton)  // ((r − σ²/2) − λκ̄)·T, in that order: λ = 0 leaves the lognormal mean
-      a.law_mu = a.logS0 + ((a.r - 0.5 * a0.sigma_ln * a0.sigma_ln) - a0.lam_kbar) * a.T;
-    if (a0.dynamics == kDynVg) a.law_mu = a.logS0 + (a.r + a0.vg_omega) * a.T;
-    a.out = a0.out + k;
-  }
-  const double w = 2.0 * a.bound / 256.0;  // panel width
-  const double mid = -a.bound + (threadIdx.x + 0.5) * w, half = 0.5 * w;
-  const double hsub = half / (double)a.m_sub;
-  double s = 0.0;
-#pragma unroll 1
-  for (uint32_t j = 0; j < a.m_sub; ++j) {
-    const double msub = subpanel_centre(mid, hsub, a.m_sub, j);
-    double sj = 0.0;
-#pragma unroll 1
-    for (int k = 0; k < 8; ++k)
-      sj += kGLw[k] * (integrand(a, msub - hsub * kGLx[k]) + integrand(a, msub + hsub * kGLx[k]));
-    s += sj * hsub;
-  }
-  for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
-  __shared__ double sm[4];
-  if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) a.out[0] = ((sm[0] + sm[1]) + sm[2]) + sm[3];
-}
-
-// hh_carr_madan_bates: carr_madan_kernel's basket form (per_payoff is never NULL) under the Bates law — the same panels,
-// nodes and sums with integrand_law<true>; a sibling, so that the kernel above compiles to what it compiled to
-__device__ double integrand_bates(const FourierArgs& a, double v) { return integrand_law<true>(a, v); }
-__global__ __launch_bounds__(256) void carr_madan_bates_kernel(const FourierArgs a0) {
-  FourierArgs a = a0;
-  const uint32_t kp = blockIdx.x, n = a0.n_payoffs;
-  a.logK = a0.per_payoff[kp];
-  a.T = a0.per_payoff[n + kp];
-  a.r = a0.per_payoff[2 * n + kp] - a0.lam_kbar;  // r_c = r_k − λκ̄: λ = 0 leaves the Heston drift
-  a.discount = a0.per_payoff[3 * n + kp];
-  a.out = a0.out + kp;
-  const double w = 2.0 * a.bound / 256.0;  // panel width
-  const double mid = -a.bound + (threadIdx.x + 0.5) * w, half = 0.5 * w;
-  const double hsub = half / (double)a.m_sub;
-  double s = 0.0;
-#pragma unroll 1
-  for (uint32_t j = 0; j < a.m_sub; ++j) {
-    const double msub = subpanel_centre(mid, hsub, a.m_sub, j);
-    double sj = 0.0;
-#pragma unroll 1
-    for (int k = 0; k < 8; ++k)
-      sj += kGLw[k] * (integrand_bates(a, msub - hsub * kGLx[k]) + integrand_bates(a, msub + hsub * kGLx[k]));
-    s += sj * hsub;
-  }
-  for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
-  __shared__ double sm[4];
-  if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) a.out[0] = ((sm[0] + sm[1]) + sm[2]) + sm[3];
+  });
+  block_sum(acc, a.out + (size_t)blockIdx.x * kGradVals);
 }
 
 }  // namespace
@@ -422,111 +437,98 @@ uint32_t carr_madan_subpanels(double alpha, double bound) {
 
 // The rule of a launch: α, the bound and the sub-panels they ask for.  Refused where carr_madan_subpanels refuses: a
 // rule of no sub-panels would write 0.0 as the price.
-static int set_rule(FourierArgs& a, double alpha, double bound) {
+static int set_rule(RuleArgs& a, double alpha, double bound) {
   a.alpha = alpha; a.bound = bound;
   a.m_sub = carr_madan_subpanels(alpha, bound);
   return a.m_sub ? (int)hipSuccess : (int)hipErrorInvalidValue;
 }
 
+// One workgroup per payoff of `a` (one workgroup where it has no per_payoff) under `law`; GRAD: the gradient form
+template <bool GRAD = false, class Law>
+static int launch_rule(const Law& law, RuleArgs a, double alpha, double bound, hipStream_t s) {
+  if (const int rc = set_rule(a, alpha, bound)) return rc;
+  const dim3 grid(a.per_payoff ? a.n_payoffs : 1u);
+  if constexpr (GRAD) hipLaunchKernelGGL(carr_madan_grad_kernel<Law>, grid, dim3(256), 0, s, law, a);
+  else hipLaunchKernelGGL(carr_madan_kernel<Law>, grid, dim3(256), 0, s, law, a);
+  return (int)hipGetLastError();
+}
+
+static RuleArgs basket_of(const double* per_payoff_dev, uint32_t n_payoffs, double* out_dev) {
+  RuleArgs a{};
+  a.per_payoff = per_payoff_dev;
+  a.n_payoffs = n_payoffs;
+  a.out = out_dev;
+  return a;
+}
+
+static NormalLaw normal_law(const hh_model& m, int compat_sqrt_alpha) {
+  NormalLaw l{};
+  l.logS0 = log(m.S0);
+  l.sigma_ln = m.sigma;
+  l.compat_sqrt_alpha = (uint32_t)(compat_sqrt_alpha != 0);
+  return l;
+}
+
+static HestonLaw heston_law(const hh_model& m) {
+  HestonLaw l{};
+  l.logS0 = log(m.S0); l.V0 = m.V0; l.kappa = m.kappa; l.theta = m.theta; l.sigma = m.sigma;
+  l.rho = m.rho;
+  return l;
+}
+
 int launch_carr_madan_basket(const hh_model& m, int dynamics, int compat_sqrt_alpha, double alpha,
                              double bound, const double* per_payoff_dev, uint32_t n_payoffs,
                              double* out_dev, hipStream_t s) {
-  FourierArgs a{};
-  a.dynamics = dynamics;
-  a.logS0 = log(m.S0); a.V0 = m.V0; a.kappa = m.kappa; a.theta = m.theta; a.sigma = m.sigma;
-  a.rho = m.rho;
-  a.sigma_ln = m.sigma;
-  a.out = out_dev;
-  a.per_payoff = per_payoff_dev;
-  a.n_payoffs = n_payoffs;
-  a.compat_sqrt_alpha = (uint32_t)(compat_sqrt_alpha != 0);
-  if (const int rc = set_rule(a, alpha, bound)) return rc;
-  hipLaunchKernelGGL(carr_madan_kernel, dim3(n_payoffs), dim3(256), 0, s, a);
-  return (int)hipGetLastError();
-}
-
-int launch_carr_madan_jump(const hh_model& m, const hh_jump& jump, double alpha, double bound,
-                           const double* per_payoff_dev, uint32_t n_payoffs, double* out_dev, hipStream_t s) {
-  FourierArgs a{};
-  a.dynamics = kDynMerton;
-  a.logS0 = log(m.S0);
-  a.sigma_ln = m.sigma;
-  a.lam = jump.lambda; a.mu_j = jump.mu_j; a.sigma_j = jump.sigma_j;
-  a.lam_kbar = merton_compensator(jump);
-  a.out = out_dev;
-  a.per_payoff = per_payoff_dev;
-  a.n_payoffs = n_payoffs;
-  if (const int rc = set_rule(a, alpha, bound)) return rc;
-  hipLaunchKernelGGL(carr_madan_kernel, dim3(n_payoffs), dim3(256), 0, s, a);
-  return (int)hipGetLastError();
-}
-
-int launch_carr_madan_vg(const hh_model& m, const hh_vg& vg, double alpha, double bound, const double* per_payoff_dev,
-                         uint32_t n_payoffs, double* out_dev, hipStream_t s) {
-  FourierArgs a{};
-  a.dynamics = kDynVg;
-  a.logS0 = log(m.S0);
-  a.sigma_ln = m.sigma;
-  a.vg_theta_nu = vg.theta * vg.nu;
-  a.vg_half_s2nu = (0.5 * (m.sigma * m.sigma)) * vg.nu;
-  a.vg_nu = vg.nu;
-  a.vg_omega = vg_omega(m.sigma, vg);
-  a.out = out_dev;
-  a.per_payoff = per_payoff_dev;
-  a.n_payoffs = n_payoffs;
-  if (const int rc = set_rule(a, alpha, bound)) return rc;
-  hipLaunchKernelGGL(carr_madan_kernel, dim3(n_payoffs), dim3(256), 0, s, a);
-  return (int)hipGetLastError();
-}
-
-int launch_carr_madan_bates(const hh_model& m, const hh_jump& jump, double alpha, double bound,
-                            const double* per_payoff_dev, uint32_t n_payoffs, double* out_dev, hipStream_t s) {
-  FourierArgs a{};
-  a.dynamics = HH_HESTON;
-  a.logS0 = log(m.S0); a.V0 = m.V0; a.kappa = m.kappa; a.theta = m.theta; a.sigma = m.sigma;
-  a.rho = m.rho;
-  a.sigma_ln = m.sigma;
-  a.lam = jump.lambda; a.mu_j = jump.mu_j; a.sigma_j = jump.sigma_j;
-  a.lam_kbar = merton_compensator(jump);
-  a.out = out_dev;
-  a.per_payoff = per_payoff_dev;
-  a.n_payoffs = n_payoffs;
-  if (const int rc = set_rule(a, alpha, bound)) return rc;
-  hipLaunchKernelGGL(carr_madan_bates_kernel, dim3(n_payoffs), dim3(256), 0, s, a);
-  return (int)hipGetLastError();
+  const RuleArgs a = basket_of(per_payoff_dev, n_payoffs, out_dev);
+  if (dynamics == HH_HESTON) return launch_rule(heston_law(m), a, alpha, bound, s);
+  return launch_rule(normal_law(m, compat_sqrt_alpha), a, alpha, bound, s);
 }
 
 int launch_carr_madan_grad(const hh_model& m, int dynamics, int compat_sqrt_alpha, double alpha,
                            double bound, const double* per_payoff_dev, uint32_t n_payoffs,
                            double* out_dev, hipStream_t s) {
-  FourierArgs a{};
-  a.dynamics = dynamics;
-  a.logS0 = log(m.S0); a.V0 = m.V0; a.kappa = m.kappa; a.theta = m.theta; a.sigma = m.sigma;
-  a.rho = m.rho;
-  a.sigma_ln = m.sigma;
-  a.out = out_dev;
-  a.per_payoff = per_payoff_dev;
-  a.n_payoffs = n_payoffs;
-  a.compat_sqrt_alpha = (uint32_t)(compat_sqrt_alpha != 0);
-  if (const int rc = set_rule(a, alpha, bound)) return rc;
-  hipLaunchKernelGGL(carr_madan_grad_kernel, dim3(n_payoffs), dim3(256), 0, s, a);
-  return (int)hipGetLastError();
+  const RuleArgs a = basket_of(per_payoff_dev, n_payoffs, out_dev);
+  if (dynamics == HH_HESTON) return launch_rule<true>(heston_law(m), a, alpha, bound, s);
+  return launch_rule<true>(normal_law(m, compat_sqrt_alpha), a, alpha, bound, s);
 }
 
+int launch_carr_madan_jump(const hh_model& m, const hh_jump& jump, double alpha, double bound,
+                           const double* per_payoff_dev, uint32_t n_payoffs, double* out_dev, hipStream_t s) {
+  const MertonLaw law{normal_law(m, 0), jump.lambda, jump.mu_j, jump.sigma_j, merton_compensator(jump)};
+  return launch_rule(law, basket_of(per_payoff_dev, n_payoffs, out_dev), alpha, bound, s);
+}
+
+int launch_carr_madan_bates(const hh_model& m, const hh_jump& jump, double alpha, double bound,
+                            const double* per_payoff_dev, uint32_t n_payoffs, double* out_dev, hipStream_t s) {
+  const BatesLaw law{heston_law(m), jump.lambda, jump.mu_j, jump.sigma_j, merton_compensator(jump)};
+  return launch_rule(law, basket_of(per_payoff_dev, n_payoffs, out_dev), alpha, bound, s);
+}
+
+int launch_carr_madan_vg(const hh_model& m, const hh_vg& vg, double alpha, double bound, const double* per_payoff_dev,
+                         uint32_t n_payoffs, double* out_dev, hipStream_t s) {
+  VgLaw law{};
+  law.logS0 = log(m.S0);
+  law.theta_nu = vg.theta * vg.nu;
+  law.half_s2nu = (0.5 * (m.sigma * m.sigma)) * vg.nu;
+  law.nu = vg.nu;
+  law.omega = vg_omega(m.sigma, vg);
+  return launch_rule(law, basket_of(per_payoff_dev, n_payoffs, out_dev), alpha, bound, s);
+}
+
+// the single payoff of m: its scalars travel in the kernel's arguments, the law is given its T and r here
 int launch_carr_madan(const hh_model& m, int dynamics, int compat_sqrt_alpha, double alpha,
                       double bound, double* out_dev, hipStream_t s) {
-  FourierArgs a{};
-  a.dynamics = dynamics;
-  a.logS0 = log(m.S0); a.V0 = m.V0; a.kappa = m.kappa; a.theta = m.theta; a.sigma = m.sigma;
-  a.rho = m.rho; a.r = m.r_drift; a.T = m.T;
-  const double sqT = sqrt(m.T), tmul = compat_sqrt_alpha ? sqT : m.T;
-  a.law_mu = a.logS0 + (m.r_drift - 0.5 * m.sigma * m.sigma) * tmul;  // montecarlo.jl:302
-  a.law_sd = m.sigma * sqT;
-  a.logK = log(m.strike); a.discount = m.discount;
+  RuleArgs a{};
+  a.logK = log(m.strike); a.T = m.T; a.r = m.r_drift; a.discount = m.discount;
   a.out = out_dev;
-  if (const int rc = set_rule(a, alpha, bound)) return rc;
-  hipLaunchKernelGGL(carr_madan_kernel, dim3(1), dim3(256), 0, s, a);
-  return (int)hipGetLastError();
+  if (dynamics == HH_HESTON) {
+    HestonLaw law = heston_law(m);
+    law.set_payoff(m.T, m.r_drift);
+    return launch_rule(law, a, alpha, bound, s);
+  }
+  NormalLaw law = normal_law(m, compat_sqrt_alpha);
+  law.set_payoff(m.T, m.r_drift);
+  return launch_rule(law, a, alpha, bound, s);
 }
 
 }  // namespace hh

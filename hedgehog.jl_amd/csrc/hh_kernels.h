@@ -217,18 +217,27 @@ int launch_basket_payoffs(const BasketArgs& b, uint32_t n_payoffs, uint32_t n_ac
 // 0 = more than kCarrMadanMaxSubpanels would be needed (bound/alpha > 196608): the entry points refuse it.
 constexpr uint32_t kCarrMadanMaxSubpanels = 1024;
 uint32_t carr_madan_subpanels(double alpha, double bound);
+// the single payoff of m (strike, T, r_drift, discount): out_dev[0] receives the CALL price
 int launch_carr_madan(const hh_model& m, int dynamics, int compat_sqrt_alpha, double alpha,
                       double bound, double* out_dev, hipStream_t s);
 // n_payoffs Carr–Madan integrals in one launch (one workgroup each); per_payoff_dev = [4][n_payoffs]:
 // log K, T, r_drift, discount; out_dev[n_payoffs] receives the CALL prices
+int launch_carr_madan_basket(const hh_model& m, int dynamics, int compat_sqrt_alpha, double alpha,
+                             double bound, const double* per_payoff_dev, uint32_t n_payoffs,
+                             double* out_dev, hipStream_t s);
 // the same with the gradient: out_dev[n_payoffs][8] = call price, then its partials along
 // S0, V0, kappa, theta, sigma, rho, r_drift
 int launch_carr_madan_grad(const hh_model& m, int dynamics, int compat_sqrt_alpha, double alpha,
                            double bound, const double* per_payoff_dev, uint32_t n_payoffs,
                            double* out_dev, hipStream_t s);
-int launch_carr_madan_basket(const hh_model& m, int dynamics, int compat_sqrt_alpha, double alpha,
-                             double bound, const double* per_payoff_dev, uint32_t n_payoffs,
-                             double* out_dev, hipStream_t s);
+// launch_carr_madan_basket under the Merton law (m: S0, sigma), the Bates law (m: the Heston scalars) and the Variance
+// Gamma law (m: S0, sigma); compat_sqrt_alpha = 0
+int launch_carr_madan_jump(const hh_model& m, const hh_jump& jump, double alpha, double bound,
+                           const double* per_payoff_dev, uint32_t n_payoffs, double* out_dev, hipStream_t s);
+int launch_carr_madan_bates(const hh_model& m, const hh_jump& jump, double alpha, double bound,
+                            const double* per_payoff_dev, uint32_t n_payoffs, double* out_dev, hipStream_t s);
+int launch_carr_madan_vg(const hh_model& m, const hh_vg& vg, double alpha, double bound, const double* per_payoff_dev,
+                         uint32_t n_payoffs, double* out_dev, hipStream_t s);
 // Cox–Ross–Rubinstein trees (hh_crr.hip): one tree's scalars as hh_crr_solve stages them (8 doubles)
 struct CrrTree {
   double F, K, cp, u, p, q, disc;  // forward, strike, ±1, up factor, p = 1/(1+u), q = 1 − p, per-step discount
@@ -321,9 +330,6 @@ int launch_merton_exact(const hh_model& m, const hh_config& c, const hh_jump& ju
 // launch_path_stats' lognormal, monitored form under jumps: the same five rows
 int launch_jump_stats(const hh_model& m, const hh_config& c, const hh_jump& jump, const uint64_t* seeds_dev,
                       uint32_t monitor_every, bool include_start, double* stats, hipStream_t s);
-// launch_carr_madan_basket (lognormal dynamics, compat_sqrt_alpha = 0) with the Merton characteristic function
-int launch_carr_madan_jump(const hh_model& m, const hh_jump& jump, double alpha, double bound,
-                           const double* per_payoff_dev, uint32_t n_payoffs, double* out_dev, hipStream_t s);
 // Variance Gamma (hh_vg.hip, hh_fourier.hip; include/hedgehog_mc.h, "Variance Gamma").  The scalars are checked by the
 // entry points.  The terminal law: a lane takes kVgPerLane trajectories whatever the call, a workgroup leaves one record
 constexpr int kVgPerLane = 8;
@@ -336,9 +342,6 @@ int launch_vg_exact(const hh_model& m, const hh_config& c, const hh_vg& vg, cons
 // the five monitored rows of launch_path_stats on the gamma clock: one gamma variate of shape dt/ν per step
 int launch_vg_stats(const hh_model& m, const hh_config& c, const hh_vg& vg, const uint64_t* seeds_dev,
                     uint32_t monitor_every, bool include_start, double* stats, hipStream_t s);
-// launch_carr_madan_basket (lognormal dynamics, compat_sqrt_alpha = 0) with the Variance Gamma characteristic function
-int launch_carr_madan_vg(const hh_model& m, const hh_vg& vg, double alpha, double bound, const double* per_payoff_dev,
-                         uint32_t n_payoffs, double* out_dev, hipStream_t s);
 // Heston paths by the quadratic-exponential scheme (hh_qe.hip; include/hedgehog_mc.h, "Heston paths by the
 // quadratic-exponential scheme").  The scalars are checked by the entry points, which ask qe_launch_args for the
 // host-formed constants (A decides whether the martingale correction is admitted).
@@ -354,9 +357,6 @@ QeArgs bates_launch_args(const hh_model& m, const hh_config& c, const hh_qe& qe,
 int launch_bates_stats(const hh_model& m, const hh_config& c, const hh_qe& qe, const hh_jump& jump,
                        const uint64_t* seeds_dev, uint32_t monitor_every, bool include_start, double* stats,
                        double* var_T, hipStream_t s);
-// launch_carr_madan_basket (HH_HESTON, compat_sqrt_alpha = 0) with the Bates characteristic function
-int launch_carr_madan_bates(const hh_model& m, const hh_jump& jump, double alpha, double bound,
-                            const double* per_payoff_dev, uint32_t n_payoffs, double* out_dev, hipStream_t s);
 // Local volatility on a tabulated surface (hh_localvol.hip; include/hedgehog_mc.h, "Local volatility on a tabulated
 // surface"): launch_path_stats' lognormal forms — the five monitored rows, or the seven under `bridge` — with the σ of
 // every step read from the surface.  m.sigma is not read.  The entry points have checked the surface and staged lv's

@@ -34,11 +34,11 @@ import numpy as np
 
 from hedgehog_jl_amd import _ffi
 from oracle import carr_madan_exact as cx
-from oracle import carr_madan_fp64 as fp
 from oracle import euler_exact as ex
 from tests import merton_cases as mc
 from tests import path_bridge_cases as bc
 from tests import qe_cases as qc
+from tests.carr_madan_law_cases import cm_case
 from tests.lognormal_exact_cases import box_muller
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "bates_exact.json")
@@ -228,46 +228,30 @@ def step_expectation(case, n_steps, v, mart=True, mut=None, terms=80):
 
 # ---- Carr–Madan ------------------------------------------------------------------------------------------------------------
 
-def cm_case(c, K, alpha, bound, cp=1.0):
-    return dict(c, K=K, alpha=alpha, bound=bound, cp=cp, discount=c.get("discount", math.exp(-c["r_drift"] * c["T"])))
+def log_cf(case):
+    """tests/carr_madan_law_cases.py's law, exactly: log ϕ = heston_log_cf at the compensated drift +
+    λT·(exp(iμ_J·t − σ_J²t²/2) − 1) at t = v − i(α+1)"""
+    lam, mu, sj = (cx._mpf(case[k]) for k in ("lam", "mu_j", "sigma_j"))
+    p = {k: cx._mpf(case[k]) for k in ("S0", "K", "T", "r_drift", "discount", "alpha", "bound", "V0", "kappa", "theta",
+                                        "sigma", "rho")}
+    p["compat_sqrt_alpha"] = False
+    p["r_drift"] = p["r_drift"] - lam * mc.kappa_bar(case)
+    alpha = p["alpha"]
+    assert cx.moment_exists_at(p["kappa"], p["sigma"], p["rho"], alpha, p["T"]), "no (α+1)-th moment"
+    unwrapped = cx.UnwrappedLog(p, p["bound"])
+
+    def f(v):
+        t = mp.mpc(v, -(alpha + 1))
+        return cx.heston_log_cf(p, t, lambda z: unwrapped(v, z)) + lam * p["T"] * (mp.exp(mp.mpc(0, 1) * t * mu - sj * sj * t * t / 2) - 1)
+    return f
 
 
-def cm_exact_call(case):
-    """The truncated Carr–Madan call of a Bates case, exactly integrated: oracle/carr_madan_exact.py's integrand and
-    graded sub-intervals with log ϕ = heston_log_cf at the compensated drift + λT·(exp(iμ_J·t − σ_J²t²/2) − 1)"""
-    with mp.workdps(DPS):
-        lam, mu, sj = (cx._mpf(case[k]) for k in ("lam", "mu_j", "sigma_j"))
-        p = {k: cx._mpf(case[k]) for k in ("S0", "K", "T", "r_drift", "discount", "alpha", "bound", "V0", "kappa", "theta",
-                                            "sigma", "rho")}
-        p["compat_sqrt_alpha"] = False
-        p["r_drift"] = p["r_drift"] - lam * mc.kappa_bar(case)
-        logK, alpha = mp.log(p["K"]), p["alpha"]
-        assert cx.moment_exists_at(p["kappa"], p["sigma"], p["rho"], alpha, p["T"]), "no (α+1)-th moment"
-        unwrapped = cx.UnwrappedLog(p, p["bound"])
-
-        def log_cf(v):
-            t = mp.mpc(v, -(alpha + 1))
-            return cx.heston_log_cf(p, t, lambda z: unwrapped(v, z)) + lam * p["T"] * (mp.exp(mp.mpc(0, 1) * t * mu - sj * sj * t * t / 2) - 1)
-
-        def f(v):
-            den = alpha * alpha + alpha - v * v + mp.mpc(0, 1) * v * (2 * alpha + 1)
-            return (mp.exp(log_cf(v) - mp.mpc(0, 1) * v * logK) / den).real
-
-        pts = cx._breakpoints(alpha, p["bound"])
-        total = mp.fsum(mp.quad(f, [a, b], method="gauss-legendre") for a, b in zip(pts, pts[1:]))
-        return +(2 * total * p["discount"] * mp.exp(-alpha * logK) / (2 * mp.pi))
-
-
-def cm_rule_fp64(case, panels):
-    """hh_fourier.hip's rule for the Bates law in numpy complex128 on `panels` equal Gauss–Legendre panels: heston_cf's
-    expression with r_c in it, the jump term added to the exponent last"""
-    v, w = fp._nodes(case["bound"], panels)
-    alpha, logK, T = case["alpha"], math.log(case["K"]), case["T"]
+def phi(case, u):
+    """… and as hh_fourier.hip's BatesLaw forms it, in numpy complex128: HestonLaw's expression with r_c in it, the jump
+    term added to the exponent last"""
+    T = case["T"]
     kap, th, sg, rho, V0 = (case[k] for k in ("kappa", "theta", "sigma", "rho", "V0"))
-    u = v - 1j * (alpha + 1.0)
     iu = 1j * u
-    den = alpha * alpha + alpha - v * v + 1j * v * (2.0 * alpha + 1.0)
-    kern = w * (math.exp(-alpha * logK) / (2 * math.pi) * case["discount"]) / den * np.exp(-1j * v * logK)
     r_c = case["r_drift"] - case["lam"] * math.expm1(case["mu_j"] + 0.5 * case["sigma_j"] * case["sigma_j"])
     kri = kap - rho * sg * iu
     u2 = u * u
@@ -279,18 +263,10 @@ def cm_rule_fp64(case, panels):
     Dv = (1.0 / (sg * sg)) * ((kri - d1) * ((1.0 - ed) / one_m_ged))
     e = Cc + V0 * Dv + math.log(case["S0"]) * iu + (r_c * T) * iu
     e = e + (case["lam"] * T) * (np.exp(case["mu_j"] * iu - (0.5 * case["sigma_j"] * case["sigma_j"]) * u2) - 1.0)
-    return math.fsum((kern * np.exp(e)).real)
-
-
-def cm_e64(case, exact_call):
-    """merton_cases.cm_e64's form: the rule's worst distance from the exact integral on 2, 4 and 8 times the kernel's
-    sub-panel count"""
-    m = fp.subpanels(case["alpha"], case["bound"])
-    return max(float(abs(mp.mpf(cm_rule_fp64(case, fp.PANELS * m * k)) - exact_call)) for k in (2, 4, 8))
+    return np.exp(e)
 
 
 cm_bar = mc.cm_bar
-cm_parity = mc.cm_parity
 
 # the Carr–Madan cases: a Feller-violating model (carr_madan_cases' own, 2κθ = 0.08 against σ² = 0.36, with its α and
 # bound), a put, λ = 0, σ_J = 0, a short expiry

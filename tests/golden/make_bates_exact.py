@@ -26,6 +26,7 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 from tests import bates_cases as bt  # noqa: E402
+from tests import carr_madan_law_cases as cl  # noqa: E402
 from tests import euler_tangent_cases as etc  # noqa: E402
 from tests import oracle_ffi  # noqa: E402
 
@@ -54,9 +55,9 @@ def build(oracle):
                 rows.append(dict(model=name, martingale=mart, want=want, bars=[[list(map(float, b)) for b in bm] for bm in bars]))
     cm = {}
     for key, case in bt.cm_cases().items():
-        exact = bt.cm_exact_call(case)
+        exact = cl.cm_exact_call(case, bt.log_cf)
         with mp.workdps(bt.DPS):
-            cm[key] = dict(call=mp.nstr(exact, 30), e64=bt.cm_e64(case, exact))
+            cm[key] = dict(call=mp.nstr(exact, 30), e64=cl.cm_e64(case, exact, bt.phi))
     return dict(note="written by tests/golden/make_bates_exact.py; see its docstring", margin=bt.qc.MARGIN,
                 n_paths=bt.PATH_N, golden_n=bt.GOLDEN_N, golden_shape=list(bt.GOLDEN_SHAPE), seen=seen, rows=rows, carr_madan=cm)
 

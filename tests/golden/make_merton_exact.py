@@ -24,6 +24,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
+from tests import carr_madan_law_cases as cl  # noqa: E402
 from tests import merton_cases as mc  # noqa: E402
 from tests import oracle_ffi  # noqa: E402
 
@@ -69,11 +70,11 @@ def carr_madan_fixtures():
     for name, (model, alpha, bound, payoffs) in cm_baskets().items():
         rows = []
         for K, cp, T in payoffs:
-            case = mc.cm_case(dict(model, T=T), K, alpha, bound, cp)
-            call = mc.cm_exact_call(case)
+            case = cl.cm_case(dict(model, T=T), K, alpha, bound, cp)
+            call = cl.cm_exact_call(case, mc.log_cf)
             with mp.workdps(mc.DPS):
-                price = call if cp > 0 else call + mc.cm_parity(case)
-                rows.append(dict(K=K, cp=cp, T=T, price=mp.nstr(price, 30), e64=mc.cm_e64(case, call)))
+                price = call if cp > 0 else call + cl.cm_parity(case)
+                rows.append(dict(K=K, cp=cp, T=T, price=mp.nstr(price, 30), e64=cl.cm_e64(case, call, mc.phi)))
         out.append(dict(id=name, model={k: float(v) for k, v in model.items()}, alpha=alpha, bound=bound, payoffs=rows))
     return out
 

@@ -25,6 +25,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
+from tests import carr_madan_law_cases as cl  # noqa: E402
 from tests import oracle_ffi  # noqa: E402
 from tests import vg_cases as vc  # noqa: E402
 
@@ -86,12 +87,12 @@ def price_fixtures():
 def _cm_rows(case, alpha, bound):
     rows = []
     for K in vc.STRIKES:
-        cmc = vc.cm_case(case, K, alpha, bound)
-        call = vc.cm_exact_call(cmc)
-        e64 = vc.cm_e64(cmc, call)
+        cmc = cl.cm_case(case, K, alpha, bound)
+        call = cl.cm_exact_call(cmc, vc.log_cf)
+        e64 = cl.cm_e64(cmc, call, vc.phi)
         for cp in (1.0, -1.0):
             with mp.workdps(vc.DPS):
-                price = call if cp > 0 else call + vc.cm_parity(cmc)
+                price = call if cp > 0 else call + cl.cm_parity(cmc)
                 rows.append(dict(K=K, cp=cp, T=case["T"], price=mp.nstr(price, 30), e64=e64))
     return rows
 
@@ -103,7 +104,7 @@ def carr_madan_fixtures():
         out.append(dict(id=f"set{i}", model={k: float(v) for k, v in case.items()}, alpha=CM_ALPHA, bound=CM_BOUND,
                         payoffs=_cm_rows(case, CM_ALPHA, CM_BOUND)))
     case = vc.params_case(vc.PARAMS[2])
-    tails = [float(vc.cm_tail_bound(vc.cm_case(case, K, CM_ALPHA, TAIL_BOUND))) for K in vc.STRIKES]
+    tails = [float(vc.cm_tail_bound(cl.cm_case(case, K, CM_ALPHA, TAIL_BOUND))) for K in vc.STRIKES]
     assert max(tails) < 1e-10 * case["S0"], tails
     tail = dict(id="tail", model={k: float(v) for k, v in case.items()}, alpha=CM_ALPHA, bound=TAIL_BOUND, tail=max(tails),
                 payoffs=_cm_rows(case, CM_ALPHA, TAIL_BOUND))

@@ -26,7 +26,6 @@ import numpy as np
 
 from hedgehog_jl_amd import _ffi
 from oracle import carr_madan_exact as cx
-from oracle import carr_madan_fp64 as fp
 from oracle import euler_exact as ex
 from tests import path_payoff_cases as pc
 from tests.lognormal_exact_cases import box_muller
@@ -89,60 +88,29 @@ def black_scholes(c, K, cp):
         return +(cp * (S0 * _ncdf(cp * d1) - mp.mpf(K) * mp.exp(-r * T) * _ncdf(cp * (d1 - sd))))
 
 
-def cm_case(c, K, alpha, bound, cp=1.0):
-    """a model and a payoff in the form the Carr–Madan functions below take"""
-    return dict(c, K=K, alpha=alpha, bound=bound, cp=cp, discount=c.get("discount", math.exp(-c["r_drift"] * c["T"])))
+def log_cf(case):
+    """tests/carr_madan_law_cases.py's law, exactly: log ϕ = (the normal law's log ϕ at the compensated drift) +
+    λT·(exp(iμ_J·t − σ_J²t²/2) − 1) at t = v − i(α+1)"""
+    lam, mu, sj = (cx._mpf(case[k]) for k in ("lam", "mu_j", "sigma_j"))
+    p = {k: cx._mpf(case[k]) for k in ("S0", "K", "T", "r_drift", "discount", "alpha", "bound", "sigma")}
+    p["compat_sqrt_alpha"] = False
+    p["r_drift"] = p["r_drift"] - lam * kappa_bar(case)
+    alpha = p["alpha"]
+
+    def f(v):
+        t = mp.mpc(v, -(alpha + 1))
+        return cx.normal_log_cf(p, t) + lam * p["T"] * (mp.exp(mp.mpc(0, 1) * t * mu - sj * sj * t * t / 2) - 1)
+    return f
 
 
-def cm_exact_call(case):
-    """The truncated Carr–Madan call of a Merton case, exactly integrated: oracle/carr_madan_exact.py's integrand and
-    graded sub-intervals with log ϕ = (the normal law's log ϕ at the compensated drift) + λT·(exp(iμ_J·t − σ_J²t²/2) − 1)."""
-    with mp.workdps(DPS):
-        lam, mu, sj = (cx._mpf(case[k]) for k in ("lam", "mu_j", "sigma_j"))
-        p = {k: cx._mpf(case[k]) for k in ("S0", "K", "T", "r_drift", "discount", "alpha", "bound", "sigma")}
-        p["compat_sqrt_alpha"] = False
-        p["r_drift"] = p["r_drift"] - lam * kappa_bar(case)
-        logK, alpha = mp.log(p["K"]), p["alpha"]
-
-        def log_cf(v):
-            t = mp.mpc(v, -(alpha + 1))
-            return cx.normal_log_cf(p, t) + lam * p["T"] * (mp.exp(mp.mpc(0, 1) * t * mu - sj * sj * t * t / 2) - 1)
-
-        def f(v):
-            den = alpha * alpha + alpha - v * v + mp.mpc(0, 1) * v * (2 * alpha + 1)
-            return (mp.exp(log_cf(v) - mp.mpc(0, 1) * v * logK) / den).real
-
-        pts = cx._breakpoints(alpha, p["bound"])
-        total = mp.fsum(mp.quad(f, [a, b], method="gauss-legendre") for a, b in zip(pts, pts[1:]))
-        return +(2 * total * p["discount"] * mp.exp(-alpha * logK) / (2 * mp.pi))
-
-
-def cm_parity(case):
-    """put − call of the truncated integral: −S0 + K·D"""
-    return -mp.mpf(case["S0"]) + mp.mpf(case["K"]) * mp.mpf(case["discount"])
-
-
-def cm_rule_fp64(case, panels):
-    """hh_fourier.hip's rule for the Merton law in numpy complex128 on `panels` equal Gauss–Legendre panels"""
-    v, w = fp._nodes(case["bound"], panels)
-    alpha, logK, T = case["alpha"], math.log(case["K"]), case["T"]
-    u = v - 1j * (alpha + 1.0)
-    iu = 1j * u
-    den = alpha * alpha + alpha - v * v + 1j * v * (2.0 * alpha + 1.0)
-    kern = w * (math.exp(-alpha * logK) / (2 * math.pi) * case["discount"]) / den * np.exp(-1j * v * logK)
+def phi(case, u):
+    """… and as hh_fourier.hip's MertonLaw forms it, in numpy complex128"""
+    iu, T = 1j * u, case["T"]
     lam_kbar = case["lam"] * math.expm1(case["mu_j"] + 0.5 * case["sigma_j"] ** 2)
     mu = math.log(case["S0"]) + ((case["r_drift"] - 0.5 * case["sigma"] ** 2) - lam_kbar) * T
     sd = case["sigma"] * math.sqrt(T)
     jump = np.exp(case["mu_j"] * iu - (0.5 * case["sigma_j"] ** 2) * (u * u)) - 1.0
-    phi = np.exp(mu * iu - (0.5 * sd * sd) * (u * u) + (case["lam"] * T) * jump)
-    return math.fsum((kern * phi).real)
-
-
-def cm_e64(case, exact_call):
-    """fp64 rounding of the rule on this case: its worst distance from the exact integral on 2, 4 and 8 times the
-    kernel's sub-panel count (converged rules: what is left is rounding, as oracle/carr_madan_fp64.converged says)"""
-    m = fp.subpanels(case["alpha"], case["bound"])
-    return max(float(abs(mp.mpf(cm_rule_fp64(case, fp.PANELS * m * k)) - exact_call)) for k in (2, 4, 8))
+    return np.exp(mu * iu - (0.5 * sd * sd) * (u * u) + (case["lam"] * T) * jump)
 
 
 def cm_bar(S0, e64):

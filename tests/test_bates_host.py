@@ -22,6 +22,7 @@ from hedgehog_jl_amd import _ffi  # noqa: E402
 from hedgehog_jl_amd import montecarlo as hmc  # noqa: E402
 from hedgehog_jl_amd import routes  # noqa: E402
 from tests import bates_cases as bt  # noqa: E402
+from tests import carr_madan_law_cases as cl  # noqa: E402
 from tests import merton_cases as mc  # noqa: E402
 from tests import oracle_ffi  # noqa: E402
 from tests import qe_cases as qc  # noqa: E402
@@ -226,16 +227,16 @@ def test_carr_madan_rule_against_the_exact_integral(key):
     case, rec = bt.cm_cases()[key], DOC["carr_madan"][key]
     with mp.workdps(qc.DPS):
         exact = mp.mpf(rec["call"])
-        rule = bt.cm_rule_fp64(case, fp.PANELS * fp.subpanels(case["alpha"], case["bound"]))
+        rule = cl.cm_rule_fp64(case, fp.PANELS * fp.subpanels(case["alpha"], case["bound"]), bt.phi)
         miss, bar = float(abs(mp.mpf(rule) - exact)), bt.cm_bar(case["S0"], rec["e64"])
         print(f"\n{key}: rule {rule!r}, |rule − exact| = {miss:.3g}, bar {bar:.3g}")
         assert miss <= bar
         if case["cp"] < 0:
             put = rule + (-case["S0"] + case["K"] * case["discount"])
-            assert abs(mp.mpf(put) - (exact + bt.cm_parity(case))) <= bar and put > 0
+            assert abs(mp.mpf(put) - (exact + cl.cm_parity(case))) <= bar and put > 0
     if case["lam"] == 0.0:  # no jumps: the rule is the Heston rule's, and the compensator is an exact zero
-        other = bt.cm_rule_fp64(dict(case, mu_j=0.3, sigma_j=0.4), fp.PANELS)
-        assert other == bt.cm_rule_fp64(case, fp.PANELS)
+        other = cl.cm_rule_fp64(dict(case, mu_j=0.3, sigma_j=0.4), fp.PANELS, bt.phi)
+        assert other == cl.cm_rule_fp64(case, fp.PANELS, bt.phi)
 
 
 # ---- routing ---------------------------------------------------------------------------------------------------------------

@@ -144,3 +144,26 @@ def test_plain_256_panel_rule_misses_where_h_over_alpha_is_large():
                 assert miss > 1e-10 * c["S0"], (r["id"], ratio, miss)
             seen["large"] += 1
     assert seen["small"] >= 15 and seen["large"] >= 15
+
+
+def test_the_shared_rule_restatement_computes_what_the_three_copies_did():
+    """tests/carr_madan_law_cases.cm_rule_fp64 on the 256-panel rule under each law's phi, against the doubles that
+    merton_cases, vg_cases and bates_cases returned from their own copies of the frame before it was stated once
+    (tests/golden/carr_madan_rule_fp64.json, float.hex()): every case of bates_cases.cm_cases() and every payoff of the
+    Carr–Madan records of merton_exact.json and vg_exact.json, ==."""
+    import json
+
+    from tests import bates_cases as bt
+    from tests import carr_madan_law_cases as cl
+    from tests import merton_cases as mc
+    from tests import vg_cases as vc
+    want = json.load(open(os.path.join(GOLDEN_DIR, "carr_madan_rule_fp64.json")))
+    got = {"bates": {key: cl.cm_rule_fp64(case, fp64.PANELS, bt.phi).hex() for key, case in bt.cm_cases().items()}}
+    for law, mod in (("merton", mc), ("vg", vc)):
+        got[law] = {}
+        for rec in mod.load_golden()["carr_madan"]:
+            for k, p in enumerate(rec["payoffs"]):
+                case = cl.cm_case(dict(rec["model"], T=p["T"]), p["K"], rec["alpha"], rec["bound"], p["cp"])
+                got[law][f"{rec['id']}/{k}"] = cl.cm_rule_fp64(case, fp64.PANELS, mod.phi).hex()
+    assert {law: len(v) for law, v in got.items()} == {"bates": 5, "merton": 37, "vg": 24}
+    assert got == want

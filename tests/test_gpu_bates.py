@@ -24,6 +24,7 @@ import hedgehog_jl_amd as hh  # noqa: E402
 from hedgehog_jl_amd import _ffi  # noqa: E402
 from tests import bates_cases as bt  # noqa: E402
 from tests import carr_madan_cases as cmc  # noqa: E402
+from tests import carr_madan_law_cases as cl  # noqa: E402
 from tests import euler_tangent_cases as etc  # noqa: E402
 from tests import merton_cases as mc  # noqa: E402
 from tests import path_payoff_cases as pc  # noqa: E402
@@ -259,7 +260,7 @@ def test_carr_madan_against_the_exact_integral(hhlib, worst, key):
     assert case["discount"] == math.exp(-case["r_drift"] * case["T"])
     got = cm_call(hhlib, None, case, [(case["K"], case["cp"], case["T"])])[0]
     with mp.workdps(qc.DPS):
-        want = mp.mpf(rec["call"]) + (bt.cm_parity(case) if case["cp"] < 0 else 0)
+        want = mp.mpf(rec["call"]) + (cl.cm_parity(case) if case["cp"] < 0 else 0)
         assert not worst.check("carr-madan", got, want, bt.cm_bar(case["S0"], rec["e64"]), key)
     if case["cp"] < 0:
         call = cm_call(hhlib, None, case, [(case["K"], 1.0, case["T"])])[0]

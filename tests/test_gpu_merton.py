@@ -25,6 +25,7 @@ mp = pytest.importorskip("mpmath")
 
 import hedgehog_jl_amd as hh  # noqa: E402
 from hedgehog_jl_amd import _ffi  # noqa: E402
+from tests import carr_madan_law_cases as cl  # noqa: E402
 from tests import euler_tangent_cases as etc  # noqa: E402
 from tests import merton_cases as mc  # noqa: E402
 from tests import path_bridge_cases as bc  # noqa: E402
@@ -320,7 +321,7 @@ def test_carr_madan_against_the_exact_integral(hhlib, worst, name):
     arrs = cm_arrays(rec)
     n = len(rec["payoffs"])
     for p, D in zip(rec["payoffs"], arrs[4]):  # the fixture's discount factors are these doubles
-        assert D == mc.cm_case(dict(model, T=p["T"]), p["K"], rec["alpha"], rec["bound"])["discount"]
+        assert D == cl.cm_case(dict(model, T=p["T"]), p["K"], rec["alpha"], rec["bound"])["discount"]
     m, j, out = mc.model_of(model), mc.jump_of(model), np.empty(n)
     hhlib.check(hhlib.lib.hh_carr_madan_jump(hhlib.handle, C.byref(m), C.byref(j), rec["alpha"], rec["bound"],
                                              *[a.ctypes.data for a in arrs], n, out.ctypes.data))

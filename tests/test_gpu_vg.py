@@ -24,6 +24,7 @@ mp = pytest.importorskip("mpmath")
 import hedgehog_jl_amd as hh  # noqa: E402
 from hedgehog_jl_amd import _ffi  # noqa: E402
 from hedgehog_jl_amd import montecarlo as hmc  # noqa: E402
+from tests import carr_madan_law_cases as cl  # noqa: E402
 from tests import euler_tangent_cases as etc  # noqa: E402
 from tests import path_bridge_cases as bc  # noqa: E402
 from tests import path_payoff_cases as pc  # noqa: E402
@@ -267,7 +268,7 @@ def test_carr_madan_against_the_exact_integral(hhlib, worst, name):
                                            *[a.ctypes.data for a in arrs], n, out.ctypes.data))
     bad = []
     for k, p in enumerate(rec["payoffs"]):
-        case = vc.cm_case(dict(model, T=p["T"]), p["K"], rec["alpha"], rec["bound"], p["cp"])
+        case = cl.cm_case(dict(model, T=p["T"]), p["K"], rec["alpha"], rec["bound"], p["cp"])
         assert case["discount"] == arrs[4][k]
         bad.append(worst.check("carr-madan", out[k], mp.mpf(p["price"]), vc.cm_bar(case, p["e64"]), f"{name} payoff {k}"))
         if name == "tail":

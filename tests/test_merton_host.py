@@ -19,6 +19,7 @@ import hedgehog_jl_amd as hh  # noqa: E402
 from hedgehog_jl_amd import _ffi  # noqa: E402
 from hedgehog_jl_amd import montecarlo as hmc  # noqa: E402
 from hedgehog_jl_amd import routes  # noqa: E402
+from tests import carr_madan_law_cases as cl  # noqa: E402
 from tests import merton_cases as mc  # noqa: E402
 from tests import oracle_ffi  # noqa: E402
 from tests.conftest import host_env  # noqa: E402
@@ -88,10 +89,10 @@ def test_series_equals_the_exactly_integrated_carr_madan_integral(bound):
     Merton's series is the same number — two formulas that share nothing but the model."""
     assert mc.BASE["sigma"] ** 2 * mc.BASE["T"] * bound ** 2 / 2 > 1000
     for K in (105.0, 80.0):  # (puts are calls by parity in both formulas: test_parity_and_the_limit_without_jumps)
-        case = mc.cm_case(mc.BASE, K, 1.0, bound)
+        case = cl.cm_case(mc.BASE, K, 1.0, bound)
         with mp.workdps(mc.DPS):
             # (the case carries its discount factor, a double: the series takes the same one)
-            assert abs(mc.cm_exact_call(case) - mc.series(case, K, 1.0)) < mp.mpf(10) ** -30, K
+            assert abs(cl.cm_exact_call(case, mc.log_cf) - mc.series(case, K, 1.0)) < mp.mpf(10) ** -30, K
     assert mp.nstr(mc.series(mc.BASE, 105.0, 1.0), 18) == "8.97843684569237133"
     assert DOC["series"]["price"] == mp.nstr(mc.series(mc.BASE, 105.0, 1.0), 30)
 

@@ -26,7 +26,6 @@ import numpy as np
 
 from hedgehog_jl_amd import _ffi
 from oracle import carr_madan_exact as cx
-from oracle import carr_madan_fp64 as fp
 from oracle import euler_exact as ex
 from tests import path_payoff_cases as pc
 from tests.euler_tangent_cases import path_bar
@@ -108,36 +107,19 @@ def black_scholes(c, K, cp, vol=None):
         return +(cp * (S0 * mp.ncdf(cp * d1) - mp.mpf(K) * mp.exp(-r * T) * mp.ncdf(cp * (d1 - sd))))
 
 
-def cm_case(c, K, alpha, bound, cp=1.0):
-    return dict(c, K=K, alpha=alpha, bound=bound, cp=cp, discount=discount_of(c))
-
-
-def _cm_integral(case, bound_lo, bound_hi):
-    """∫ Re(e^{−ivk}·ϕ(v − i(α+1))/den) dv over [bound_lo, bound_hi] at 50 digits, on oracle/carr_madan_exact.py's graded
-    breakpoints inside the bound"""
+def log_cf(case):
+    """tests/carr_madan_law_cases.py's law, exactly: log ϕ = it·(log S0 + (r + ω)T) − (T/ν)·log(1 − θν·it + σ²ν·t²/2) at
+    t = v − i(α+1)"""
     p = {k: cx._mpf(case[k]) for k in ("S0", "K", "T", "r_drift", "alpha", "sigma", "theta", "nu")}
-    logK, alpha, a = mp.log(p["K"]), p["alpha"], p["T"] / p["nu"]
+    alpha, a = p["alpha"], p["T"] / p["nu"]
     mu = mp.log(p["S0"]) + (p["r_drift"] + omega(case)) * p["T"]
 
     def f(v):
         t = mp.mpc(v, -(alpha + 1))
         it = mp.mpc(0, 1) * t
         base = 1 - p["theta"] * p["nu"] * it + p["sigma"] ** 2 * p["nu"] * t * t / 2
-        den = alpha * alpha + alpha - v * v + mp.mpc(0, 1) * v * (2 * alpha + 1)
-        return (mp.exp(mu * it - a * mp.log(base) - mp.mpc(0, 1) * v * logK) / den).real
-
-    pts = [t for t in cx._breakpoints(alpha, cx._mpf(bound_hi)) if t >= bound_lo]
-    if pts[0] > bound_lo:
-        pts = [cx._mpf(bound_lo)] + pts
-    return mp.fsum(mp.quad(f, [x, y], method="gauss-legendre") for x, y in zip(pts, pts[1:]))
-
-
-def cm_exact_call(case):
-    """the truncated Carr–Madan call of a Variance Gamma case, exactly integrated on [−bound, bound] (the integrand's real
-    part is even: twice the half)"""
-    with mp.workdps(DPS):
-        alpha, logK = cx._mpf(case["alpha"]), mp.log(cx._mpf(case["K"]))
-        return +(2 * _cm_integral(case, 0, case["bound"]) * cx._mpf(case["discount"]) * mp.exp(-alpha * logK) / (2 * mp.pi))
+        return mu * it - a * mp.log(base)
+    return f
 
 
 def cm_tail_bound(case):
@@ -155,31 +137,14 @@ def cm_tail_bound(case):
         return +(2 * tail * p["discount"] * mp.exp(-al * mp.log(p["K"])) / (2 * mp.pi))
 
 
-def cm_parity(case):
-    return -mp.mpf(case["S0"]) + mp.mpf(case["K"]) * mp.mpf(case["discount"])
-
-
-def cm_rule_fp64(case, panels):
-    """hh_fourier.hip's rule for the Variance Gamma law in numpy complex128 on `panels` equal Gauss–Legendre panels"""
-    v, w = fp._nodes(case["bound"], panels)
-    alpha, logK, T = case["alpha"], math.log(case["K"]), case["T"]
-    u = v - 1j * (alpha + 1.0)
-    iu = 1j * u
-    den = alpha * alpha + alpha - v * v + 1j * v * (2.0 * alpha + 1.0)
-    kern = w * (math.exp(-alpha * logK) / (2 * math.pi) * case["discount"]) / den * np.exp(-1j * v * logK)
+def phi(case, u):
+    """… and as hh_fourier.hip's VgLaw forms it, in numpy complex128"""
+    iu, T = 1j * u, case["T"]
     th_nu, half_s2nu = case["theta"] * case["nu"], (0.5 * (case["sigma"] * case["sigma"])) * case["nu"]
     om = math.log((1.0 - th_nu) - half_s2nu) / case["nu"]
     mu = math.log(case["S0"]) + (case["r_drift"] + om) * T
     base = 1.0 - th_nu * iu + half_s2nu * (u * u)
-    phi = np.exp(mu * iu - (T / case["nu"]) * np.log(base))
-    return math.fsum((kern * phi).real)
-
-
-def cm_e64(case, exact_call):
-    """fp64 rounding of the rule on this case: its worst distance from the exact integral on 2, 4 and 8 times the kernel's
-    sub-panel count (converged rules: what is left is rounding)"""
-    m = fp.subpanels(case["alpha"], case["bound"])
-    return max(float(abs(mp.mpf(cm_rule_fp64(case, fp.PANELS * m * k)) - exact_call)) for k in (2, 4, 8))
+    return np.exp(mu * iu - (T / case["nu"]) * np.log(base))
 
 
 def cm_bar(case, e64):
