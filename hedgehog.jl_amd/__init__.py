@@ -19,8 +19,8 @@ from .greeks import (AssetSpotLens, AssetVolLens, BatchGreekProblem, Correlation
                      ForwardAD, GreekProblem, GreekResult, PropertyLens, SecondOrderGreekProblem, SpotLens,
                      VolLens,
                      ZeroRateSpineLens, optic, set)
-from .lsm import (LSM, EulerPaths, HestonExactPaths, LSMSolution, simulate_euler_paths,
-                  simulate_heston_exact_paths, solve_lsm)
+from .lsm import (LSM, EulerPaths, HestonExactPaths, LSMSolution, SpotPaths, simulate_euler_paths,
+                  simulate_heston_exact_paths, simulate_spot_paths, solve_lsm)
 from .montecarlo import (AbstractPricingMethod, Antithetic, BatesDynamics, BlackScholesExact, EulerMaruyama,
                          HestonBroadieKaya, HestonDynamics, HestonQE, LognormalDynamics, MertonDynamics, MertonExact, MethodError,
                          MonteCarlo, NoVarianceReduction, NormalLaw, SimulationConfig, VarianceGammaDynamics,

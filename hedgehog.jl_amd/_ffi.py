@@ -127,6 +127,15 @@ class hh_localvol(C.Structure):
                 ("n_times", C.c_uint32), ("n_x", C.c_uint32)]
 
 
+HH_SOURCE_EULER, HH_SOURCE_JUMP, HH_SOURCE_QE, HH_SOURCE_BATES, HH_SOURCE_LOCALVOL, HH_SOURCE_VG = range(6)
+
+
+class hh_path_source(C.Structure):
+    """A member of the log-spot path family (enum hh_path_source_kind) and the structs its kernel reads; the others NULL."""
+    _fields_ = [("kind", C.c_int32), ("jump", C.POINTER(hh_jump)), ("qe", C.POINTER(hh_qe)),
+                ("localvol", C.POINTER(hh_localvol)), ("vg", C.POINTER(hh_vg))]
+
+
 HH_BK_ROOT_SECANT, HH_BK_ROOT_ORDER2 = 0, 1
 HH_BK_BRACKET_MIDPOINT, HH_BK_BRACKET_ROOTS = 0, 1
 HH_BK_CAPS_AS_WRITTEN, HH_BK_CAPS_ROOTS_DEFAULT = 0, 1
@@ -188,6 +197,10 @@ SYMBOLS = [
     ("hh_euler_grid", C.c_int, [_vp, C.POINTER(hh_model), C.POINTER(hh_config), C.c_int32, _vp, _vp, C.c_int32, C.POINTER(hh_result)]),
     ("hh_lsm_solve_euler", C.c_int, [_vp, C.POINTER(hh_model), C.POINTER(hh_config), C.c_int32, C.c_int32, C.c_double,
                                      C.POINTER(hh_lsm_result), _vp, _vp, _vp]),
+    ("hh_mc_path_grid", C.c_int, [_vp, C.POINTER(hh_path_source), C.POINTER(hh_model), C.POINTER(hh_config), C.c_uint32, _vp,
+                                  C.c_int32, C.POINTER(hh_result)]),
+    ("hh_lsm_solve_path", C.c_int, [_vp, C.POINTER(hh_path_source), C.POINTER(hh_model), C.POINTER(hh_config), C.c_uint32,
+                                    C.c_int32, C.c_double, C.POINTER(hh_lsm_result), _vp, _vp, _vp]),
     ("hh_mc_path_stats", C.c_int, [_vp, C.POINTER(hh_model), C.POINTER(hh_config), C.c_uint32, C.c_int32, _vp, C.c_int32,
                                    C.POINTER(hh_result)]),
     ("hh_mc_solve_path", C.c_int, [_vp, C.POINTER(hh_model), C.POINTER(hh_config), C.c_uint32, C.c_int32,
@@ -611,6 +624,17 @@ def make_vg(theta=0.0, nu=1.0):
     g = hh_vg()
     g.theta, g.nu = theta, nu
     return g
+
+
+def make_path_source(kind, jump=None, qe=None, localvol=None, vg=None):
+    """hh_path_source of `kind` over the structs given (each kept alive by the descriptor)"""
+    src = hh_path_source()
+    src.kind = kind
+    src._keep = (jump, qe, localvol, vg)
+    for name, v in zip(("jump", "qe", "localvol", "vg"), src._keep):
+        if v is not None:
+            setattr(src, name, C.pointer(v))
+    return src
 
 
 def make_assets(spots, sigmas, weights, corr, index_kind=HH_INDEX_WEIGHTED_SUM):

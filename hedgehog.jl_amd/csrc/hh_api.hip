@@ -1549,6 +1549,7 @@ struct PathFamily {
   const hh_vg* vg = nullptr;
   double* var_T = nullptr;  // host, nullable: the variance at expiry of every member (the QE step)
   bool missing = false;     // a struct the kernel needs came as NULL: the entry point's "NULL argument"
+  bool date_rows = false;   // the kernel's date-row sibling: the grid into ctx->lsm_grid, no statistics (hh_mc_path_grid)
   // path_stats_kernel: lognormal or Heston dynamics by Euler–Maruyama
   PathFamily(const char* w, int32_t last, int32_t ext) : kernel(kEuler), who(w), last_kind(last), extremes(ext) {}
   // jump_stats_kernel, the Merton form: lognormal dynamics
@@ -1574,10 +1575,24 @@ struct PathFamily {
   hh::PathStatsLayout layout(const hh_config* c) const {
     return hh::PathStatsLayout(c->n_paths, c->antithetic != 0 || kernel == kCoupled, path_stat_rows(extremes));
   }
+  // this member in its date-row form
+  PathFamily rows() const {
+    PathFamily f = *this;
+    f.date_rows = true;
+    return f;
+  }
 };
 
+// the dates of a call lie on every `every`-th step (`word`: what the entry point calls it)
+static int check_every(hh_ctx* ctx, const char* who, const char* word, uint32_t every, uint32_t n_steps) {
+  if (every == 0 || n_steps % every != 0)
+    return fail(ctx, HH_ERR_INVALID, "%s: %s (%u) must be >= 1 and divide n_steps (%u)", who, word, every, n_steps);
+  return HH_OK;
+}
+
 // The checks of every entry point, then the statistics of every trajectory into ctx->path_stats (one timing slot) and,
-// where f.var_T, the variances at expiry into ctx->heston_var.
+// where f.var_T, the variances at expiry into ctx->heston_var.  f.date_rows: monitor_every is the entry point's
+// exercise_every, and the rows of every such step go into ctx->lsm_grid ([n_steps/monitor_every + 1][n_total]) instead.
 static int run_path_stats(hh_ctx* ctx, const PathFamily& f, const hh_model* m, const hh_config* c, uint32_t monitor_every,
                           int32_t include_start) {
   const char* who = f.who;
@@ -1626,9 +1641,11 @@ static int run_path_stats(hh_ctx* ctx, const PathFamily& f, const hh_model* m, c
     return fail(ctx, HH_ERR_INVALID, "%s: unknown extremes %d", who, f.extremes);
   if (c->n_paths == 0 || c->n_steps == 0 || c->n_paths > kMaxPaths / 2 || c->n_steps > kMaxEulerSteps)
     return fail(ctx, HH_ERR_INVALID, "%s: 1 <= n_paths <= 2^31 - 128, 1 <= n_steps <= %u", who, kMaxEulerSteps);
-  if (monitor_every == 0 || c->n_steps % monitor_every != 0)
-    return fail(ctx, HH_ERR_INVALID, "%s: monitor_every (%u) must be >= 1 and divide n_steps (%u)", who, monitor_every,
-                c->n_steps);
+  int rc;
+  if ((rc = check_every(ctx, who, f.date_rows ? "exercise_every" : "monitor_every", monitor_every, c->n_steps))) return rc;
+  if (f.date_rows && c->n_steps / monitor_every > kMaxGridSteps)
+    return fail(ctx, HH_ERR_INVALID, "%s: n_steps / exercise_every = %u dates is above %u", who, c->n_steps / monitor_every,
+                kMaxGridSteps);
   if (coupled && ((c->n_steps & 1u) || (monitor_every & 1u)))
     return fail(ctx, HH_ERR_INVALID, "%s: n_steps (%u, the fine grid) and monitor_every (%u) must be even: the coarse grid "
                 "has half the steps and the same dates", who, c->n_steps, monitor_every);
@@ -1640,7 +1657,6 @@ static int run_path_stats(hh_ctx* ctx, const PathFamily& f, const hh_model* m, c
              (hest && (!(std::fabs(m->rho) <= 1.0) || !std::isfinite(m->V0) || !std::isfinite(m->kappa) ||
                        !std::isfinite(m->theta))))
     return fail(ctx, HH_ERR_INVALID, "%s: S0, T > 0, |rho| <= 1, model scalars finite", who);
-  int rc;
   if (f.assets && (rc = check_assets(ctx, who, f.assets))) return rc;
   if (f.localvol && (rc = check_localvol(ctx, who, f.localvol))) return rc;
   if (f.jump && (rc = check_jump(ctx, who, f.jump, m->T / (double)c->n_steps))) return rc;
@@ -1649,7 +1665,11 @@ static int run_path_stats(hh_ctx* ctx, const PathFamily& f, const hh_model* m, c
   if (f.jump && f.qe) m_c.r_drift = m->r_drift - hh::merton_compensator(*f.jump);
   if (f.qe && (rc = check_qe(ctx, who, &m_c, c, f.qe))) return rc;
   const hh::PathStatsLayout at = f.layout(c);
-  if ((rc = ensure(ctx, ctx->path_stats, at.total))) return rc;
+  const bool rows = f.date_rows;
+  if (rows) rc = ensure(ctx, ctx->lsm_grid, hh_lsm_grid_elems(c->n_paths, c->n_steps / monitor_every, c->antithetic));
+  else rc = ensure(ctx, ctx->path_stats, at.total);
+  if (rc) return rc;
+  double* const dst = rows ? ctx->lsm_grid.p : ctx->path_stats.p;
   if (f.qe && f.var_T && (rc = ensure(ctx, ctx->heston_var, (size_t)at.n_total))) return rc;
   const uint64_t* seeds_dev = nullptr;
   if ((rc = stage_path_seeds(ctx, c, &seeds_dev))) return rc;
@@ -1660,31 +1680,31 @@ static int run_path_stats(hh_ctx* ctx, const PathFamily& f, const hh_model* m, c
   double* const var_dev = f.var_T ? ctx->heston_var.p : nullptr;
   switch (f.kernel) {
     case PathFamily::kEuler:
-      HH_HIP(ctx, hh::launch_path_stats(*m, *c, seeds_dev, monitor_every, start, f.extremes == HH_EXTREMES_BRIDGE,
-                                        ctx->path_stats, ctx->stream));
+      HH_HIP(ctx, hh::launch_path_stats(*m, *c, seeds_dev, monitor_every, start, f.extremes == HH_EXTREMES_BRIDGE, dst,
+                                        ctx->stream, rows));
       break;
     case PathFamily::kJump:
-      HH_HIP(ctx, hh::launch_jump_stats(*m, *c, *f.jump, seeds_dev, monitor_every, start, ctx->path_stats, ctx->stream));
+      HH_HIP(ctx, hh::launch_jump_stats(*m, *c, *f.jump, seeds_dev, monitor_every, start, dst, ctx->stream, rows));
       break;
     case PathFamily::kQe:
-      HH_HIP(ctx, hh::launch_qe_stats(*m, *c, *f.qe, seeds_dev, monitor_every, start, ctx->path_stats, var_dev, ctx->stream));
+      HH_HIP(ctx, hh::launch_qe_stats(*m, *c, *f.qe, seeds_dev, monitor_every, start, dst, var_dev, ctx->stream, rows));
       break;
     case PathFamily::kBates:
-      HH_HIP(ctx, hh::launch_bates_stats(*m, *c, *f.qe, *f.jump, seeds_dev, monitor_every, start, ctx->path_stats, var_dev,
-                                         ctx->stream));
+      HH_HIP(ctx, hh::launch_bates_stats(*m, *c, *f.qe, *f.jump, seeds_dev, monitor_every, start, dst, var_dev, ctx->stream,
+                                         rows));
       break;
     case PathFamily::kAssets:
       HH_HIP(ctx, hh::launch_assets_stats(*m, *c, *f.assets, seeds_dev, monitor_every, start, ctx->path_stats, ctx->stream));
       break;
     case PathFamily::kLocalVol:
       HH_HIP(ctx, hh::launch_localvol_stats(*m, *c, lv_args, seeds_dev, monitor_every, start, f.extremes == HH_EXTREMES_BRIDGE,
-                                            ctx->path_stats, ctx->stream));
+                                            dst, ctx->stream, rows));
       break;
     case PathFamily::kCoupled:
       HH_HIP(ctx, hh::launch_coupled_stats(*m, *c, seeds_dev, monitor_every, start, ctx->path_stats, ctx->stream));
       break;
     case PathFamily::kVg:
-      HH_HIP(ctx, hh::launch_vg_stats(*m, *c, *f.vg, seeds_dev, monitor_every, start, ctx->path_stats, ctx->stream));
+      HH_HIP(ctx, hh::launch_vg_stats(*m, *c, *f.vg, seeds_dev, monitor_every, start, dst, ctx->stream, rows));
       break;
   }
   return end_timing(ctx);
@@ -1825,6 +1845,74 @@ int hh_mc_solve_path_ex(hh_ctx* ctx, const hh_model* m, const hh_config* c, uint
                         double* path_values, double* stats) {
   return solve_path_call(ctx, {"hh_mc_solve_path_ex", HH_PAYOFF_LOOKBACK_FIXED, extremes}, m, c, monitor_every,
                          include_start, payoffs, n_payoffs, out, path_values, stats);
+}
+
+// ---- date rows of the family, and LSM on them (hedgehog_mc.h, "Date rows of the log-spot path family") ----
+
+// The family member a source names, in its date-row form, handed to `run`: each kind through the constructor its
+// path_stats entry point uses, so run_path_stats makes that entry point's checks in that entry point's words.
+static int with_source_family(hh_ctx* ctx, const char* who, const hh_path_source* src,
+                              const std::function<int(const PathFamily&)>& run) {
+  if (!src) return fail(ctx, HH_ERR_INVALID, "%s: NULL argument", who);
+  switch (src->kind) {
+    case HH_SOURCE_EULER: return run(PathFamily(who, 0, HH_EXTREMES_MONITORED).rows());
+    case HH_SOURCE_JUMP: return run(PathFamily(who, 0, src->jump).rows());
+    case HH_SOURCE_QE: return run(PathFamily(who, 0, src->qe, nullptr).rows());
+    case HH_SOURCE_BATES: return run(PathFamily(who, 0, src->qe, src->jump, nullptr).rows());
+    case HH_SOURCE_LOCALVOL: return run(PathFamily(who, 0, src->localvol, HH_EXTREMES_MONITORED).rows());
+    case HH_SOURCE_VG: return run(PathFamily(who, 0, src->vg).rows());
+  }
+  return fail(ctx, HH_ERR_INVALID, "%s: unknown source kind %d", who, src->kind);
+}
+
+// cfg with its steps counted in exercise dates (exercise_every has passed check_every): what the grid's consumers
+// (grid_results, the induction and its scalar checks) are told
+static hh_config dates_config(const hh_config* c, uint32_t exercise_every) {
+  hh_config g = *c;
+  g.n_steps = c->n_steps / exercise_every;
+  return g;
+}
+
+int hh_mc_path_grid(hh_ctx* ctx, const hh_path_source* source, const hh_model* m, const hh_config* c,
+                    uint32_t exercise_every, double* spot_grid, int32_t grid_on_device, hh_result* out) {
+  if (!ctx) return HH_ERR_INVALID;
+  std::lock_guard<std::recursive_mutex> lock__(ctx->mu);
+  return with_source_family(ctx, "hh_mc_path_grid", source, [&](const PathFamily& f) -> int {
+    if (!m || !c || f.missing) return fail(ctx, HH_ERR_INVALID, "%s: NULL argument", f.who);
+    const WallClock clock;
+    HH_HIP(ctx, hipSetDevice(ctx->device));
+    HH_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+    int rc = run_path_stats(ctx, f, m, c, exercise_every, 1);
+    if (rc) return rc;
+    HH_HIP(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+    const hh_config g = dates_config(c, exercise_every);
+    if ((rc = grid_results(ctx, &g, spot_grid, nullptr, grid_on_device, /*bk_counters=*/false, out, clock))) return rc;
+    return release_host_operands(ctx);
+  });
+}
+
+int hh_lsm_solve_path(hh_ctx* ctx, const hh_path_source* source, const hh_model* m, const hh_config* c,
+                      uint32_t exercise_every, int32_t degree, double date_discount, hh_lsm_result* out,
+                      int32_t* stop_time, double* stop_value, double* spot_grid) {
+  if (!ctx) return HH_ERR_INVALID;
+  std::lock_guard<std::recursive_mutex> lock__(ctx->mu);
+  return with_source_family(ctx, "hh_lsm_solve_path", source, [&](const PathFamily& f) -> int {
+    if (!m || !c || !out || f.missing) return fail(ctx, HH_ERR_INVALID, "%s: NULL argument", f.who);
+    const WallClock clock;
+    // the schedule first, then the induction's scalars on its dates, then everything the source's entry point checks
+    int rc = check_every(ctx, f.who, "exercise_every", exercise_every, c->n_steps);
+    if (rc) return rc;
+    const hh_config g = dates_config(c, exercise_every);
+    if ((rc = lsm_check_scalars(ctx, m, &g, degree, date_discount))) return rc;
+    HH_HIP(ctx, hipSetDevice(ctx->device));
+    HH_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+    if ((rc = run_path_stats(ctx, f, m, c, exercise_every, 1))) return rc;
+    const uint64_t ntot = c->n_paths * (c->antithetic ? 2 : 1);
+    rc = lsm_on_grid(ctx, ctx->lsm_grid, ntot, g.n_steps, m, degree, date_discount, out, stop_time, stop_value, clock);
+    if (rc) return rc;
+    if ((rc = release_host_operands(ctx))) return rc;
+    return copy_back_spot_grid(ctx, &g, spot_grid);
+  });
 }
 
 // ---- multilevel Monte Carlo (hedgehog_mc.h, "Multilevel Monte Carlo"; kernels: hh_path.hip) ----

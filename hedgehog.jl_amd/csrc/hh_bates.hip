@@ -23,7 +23,11 @@
 namespace hh {
 namespace {
 
-template <bool ANTI, bool MART>
+// Sink (hh_path_stats.h): Monitor, the five statistics — or DateRows, the date-row form: `stats` is then the grid
+// [n_steps/monitor_every + 1][n_total], row j the spot after step j·monitor_every, and include_start is not read.  The
+// walk, its draws and its constants are stated here once for both.
+// The date-row form writes spots alone: no variance rows, var_T is not read.
+template <bool ANTI, bool MART, class Sink = Monitor<ANTI>>
 __global__ __launch_bounds__(256) void bates_stats_kernel(const SimArgs<0> a, const QeArgs q, const JumpArgs j,
                                                           const double S0, const uint32_t monitor_every,
                                                           const int include_start, double* __restrict__ stats,
@@ -33,7 +37,8 @@ __global__ __launch_bounds__(256) void bates_stats_kernel(const SimArgs<0> a, co
   const PathStatsLayout at(a.n_paths, ANTI, HH_PATH_STATS);
   const uint32_t n_steps = a.n_steps;
   QeState st{a.x0.v, a.v0.v}, sa{a.x0.v, a.v0.v};
-  Monitor<ANTI> mon(monitor_every, include_start);
+  Sink mon(monitor_every, include_start);
+  mon.bind(stats, i, a.n_paths);
   mon.start(S0, a.x0.v);
   const uint64_t key = a.seeds[i];
   const uint32_t k0 = (uint32_t)key, k1 = (uint32_t)(key >> 32);
@@ -44,12 +49,14 @@ __global__ __launch_bounds__(256) void bates_stats_kernel(const SimArgs<0> a, co
     jump_step<ANTI>(j, key, k, uj, st.x, sa.x);
     mon.date(st.x, sa.x);
   }
-  // each member's rows, then its var_T (Monitor::store writes the rows alone)
-  mon.r.store(stats, at, i);
-  if (var_T) var_T[i] = st.v;
-  if constexpr (ANTI) {
-    mon.ra.store(stats, at, a.n_paths + i);
-    if (var_T) var_T[a.n_paths + i] = sa.v;
+  if constexpr (Sink::kStats) {
+    // each member's rows, then its var_T (Monitor::store writes the rows alone)
+    mon.r.store(stats, at, i);
+    if (var_T) var_T[i] = st.v;
+    if constexpr (ANTI) {
+      mon.ra.store(stats, at, a.n_paths + i);
+      if (var_T) var_T[a.n_paths + i] = sa.v;
+    }
   }
 }
 
@@ -62,13 +69,16 @@ QeArgs bates_launch_args(const hh_model& m, const hh_config& c, const hh_qe& qe,
 
 int launch_bates_stats(const hh_model& m, const hh_config& c, const hh_qe& qe, const hh_jump& jump,
                        const uint64_t* seeds_dev, uint32_t monitor_every, bool include_start, double* stats,
-                       double* var_T, hipStream_t s) {
+                       double* var_T, hipStream_t s, bool date_rows) {
   const StatsLaunch l(m, c, seeds_dev);
   const QeArgs q = bates_launch_args(m, c, qe, jump);
   const JumpArgs j = jump_args(jump, m.T / (double)c.n_steps);
   const bool anti = c.antithetic != 0, mart = qe.martingale != 0;
   auto kernel = anti ? (mart ? bates_stats_kernel<true, true> : bates_stats_kernel<true, false>)
                      : (mart ? bates_stats_kernel<false, true> : bates_stats_kernel<false, false>);
+  if (date_rows)
+    kernel = anti ? (mart ? bates_stats_kernel<true, true, DateRows<true>> : bates_stats_kernel<true, false, DateRows<true>>)
+                  : (mart ? bates_stats_kernel<false, true, DateRows<false>> : bates_stats_kernel<false, false, DateRows<false>>);
   hipLaunchKernelGGL(kernel, l.grid, l.block, 0, s, l.a, q, j, m.S0, monitor_every, (int)include_start, stats, var_T);
   return (int)hipGetLastError();
 }

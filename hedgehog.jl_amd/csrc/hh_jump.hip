@@ -62,7 +62,10 @@ __global__ __launch_bounds__(kTile) void merton_exact_kernel(const SimArgs<0> a,
 // block (k >> 1, 0, 0, kDomJump) — words 0, 1 for an even step, 2, 3 for an odd one (JumpUniforms) — and jump_step,
 // after the step and before the date.  The mirror takes -dW, the same N_k and -z.  a.gdrift carries the compensator;
 // with mean = 0 no lane ever jumps and every operation left is path_stats_kernel's.
-template <bool ANTI>
+// Sink (hh_path_stats.h): Monitor, the five statistics — or DateRows, the date-row form: `stats` is then the grid
+// [n_steps/monitor_every + 1][n_total], row j the spot after step j·monitor_every, and include_start is not read.  The
+// walk, its draws and its constants are stated here once for both.
+template <bool ANTI, class Sink = Monitor<ANTI>>
 __global__ __launch_bounds__(256) void jump_stats_kernel(const SimArgs<0> a, const JumpArgs j, const double S0,
                                                          const uint32_t monitor_every, const int include_start,
                                                          double* __restrict__ stats) {
@@ -75,7 +78,8 @@ __global__ __launch_bounds__(256) void jump_stats_kernel(const SimArgs<0> a, con
   State st, sa;
   M::init(st, a);
   if constexpr (ANTI) M::init(sa, a);
-  Monitor<ANTI> mon(monitor_every, include_start);
+  Sink mon(monitor_every, include_start);
+  mon.bind(stats, i, a.n_paths);
   mon.start(S0, a.x0.v);
   const uint64_t key = a.seeds[i];
   const uint32_t k0 = (uint32_t)key, k1 = (uint32_t)(key >> 32);
@@ -111,11 +115,12 @@ int launch_merton_exact(const hh_model& m, const hh_config& c, const hh_jump& ju
 }
 
 int launch_jump_stats(const hh_model& m, const hh_config& c, const hh_jump& jump, const uint64_t* seeds_dev,
-                      uint32_t monitor_every, bool include_start, double* stats, hipStream_t s) {
+                      uint32_t monitor_every, bool include_start, double* stats, hipStream_t s, bool date_rows) {
   StatsLaunch l(m, c, seeds_dev);
   l.a.gdrift.v = l.a.gdrift.v - merton_compensator(jump);  // (r − σ²/2) − λκ̄, in that order: λ = 0 leaves the lognormal drift
   const JumpArgs j = jump_args(jump, l.a.dt);
-  auto kernel = c.antithetic ? jump_stats_kernel<true> : jump_stats_kernel<false>;
+  auto kernel = c.antithetic ? (date_rows ? jump_stats_kernel<true, DateRows<true>> : jump_stats_kernel<true>)
+                             : (date_rows ? jump_stats_kernel<false, DateRows<false>> : jump_stats_kernel<false>);
   hipLaunchKernelGGL(kernel, l.grid, l.block, 0, s, l.a, j, m.S0, monitor_every, (int)include_start, stats);
   return (int)hipGetLastError();
 }

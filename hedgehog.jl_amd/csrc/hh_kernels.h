@@ -294,8 +294,11 @@ struct StatsLaunch {
 // antithetic, n_paths, n_steps), reduced per trajectory to the HH_PATH_STATS numbers of PathStatsLayout over the
 // monitoring dates monitor_every, 2·monitor_every, …, n_steps (a divisor of n_steps) and, include_start, step 0.
 // bridge: the HH_PATH_STATS_BRIDGE numbers — the five, bit for bit, then the continuous extremes over all steps.
+// date_rows (this launcher and the five below that take it): the kernel's date-row sibling — `stats` is then the grid
+// [n_steps/monitor_every + 1][n_total] of hh_lsm_grid_elems, row j the spot after step j·monitor_every, row 0 = S0 always;
+// include_start, bridge and var_T are not read.  The argument blocks and constants are formed by the same lines.
 int launch_path_stats(const hh_model& m, const hh_config& c, const uint64_t* seeds_dev, uint32_t monitor_every,
-                      bool include_start, bool bridge, double* stats, hipStream_t s);
+                      bool include_start, bool bridge, double* stats, hipStream_t s, bool date_rows = false);
 // … and n_payoffs payoffs evaluated on them: one record per payoff and chunk, as launch_basket_payoffs leaves them
 struct PathPayoffArgs {
   const double* stats;            // PathStatsLayout(n_paths, antithetic, rows of `extremes`)
@@ -329,7 +332,7 @@ inline uint32_t merton_records(uint64_t n_paths) {
 int launch_merton_exact(const hh_model& m, const hh_config& c, const hh_jump& jump, const DevicePtrs& p, hipStream_t s);
 // launch_path_stats' lognormal, monitored form under jumps: the same five rows
 int launch_jump_stats(const hh_model& m, const hh_config& c, const hh_jump& jump, const uint64_t* seeds_dev,
-                      uint32_t monitor_every, bool include_start, double* stats, hipStream_t s);
+                      uint32_t monitor_every, bool include_start, double* stats, hipStream_t s, bool date_rows = false);
 // Variance Gamma (hh_vg.hip, hh_fourier.hip; include/hedgehog_mc.h, "Variance Gamma").  The scalars are checked by the
 // entry points.  The terminal law: a lane takes kVgPerLane trajectories whatever the call, a workgroup leaves one record
 constexpr int kVgPerLane = 8;
@@ -341,7 +344,7 @@ inline uint32_t vg_records(uint64_t n_paths) {
 int launch_vg_exact(const hh_model& m, const hh_config& c, const hh_vg& vg, const DevicePtrs& p, hipStream_t s);
 // the five monitored rows of launch_path_stats on the gamma clock: one gamma variate of shape dt/ν per step
 int launch_vg_stats(const hh_model& m, const hh_config& c, const hh_vg& vg, const uint64_t* seeds_dev,
-                    uint32_t monitor_every, bool include_start, double* stats, hipStream_t s);
+                    uint32_t monitor_every, bool include_start, double* stats, hipStream_t s, bool date_rows = false);
 // Heston paths by the quadratic-exponential scheme (hh_qe.hip; include/hedgehog_mc.h, "Heston paths by the
 // quadratic-exponential scheme").  The scalars are checked by the entry points, which ask qe_launch_args for the
 // host-formed constants (A decides whether the martingale correction is admitted).
@@ -349,21 +352,23 @@ struct QeArgs;
 QeArgs qe_launch_args(const hh_model& m, const hh_config& c, const hh_qe& qe);
 // launch_path_stats' monitored form with the QE step: the same five rows; var_T (nullable): n_total doubles
 int launch_qe_stats(const hh_model& m, const hh_config& c, const hh_qe& qe, const uint64_t* seeds_dev,
-                    uint32_t monitor_every, bool include_start, double* stats, double* var_T, hipStream_t s);
+                    uint32_t monitor_every, bool include_start, double* stats, double* var_T, hipStream_t s,
+                    bool date_rows = false);
 // Bates (hh_bates.hip, hh_fourier.hip; include/hedgehog_mc.h, "Bates (1996): Heston variance with Merton jumps").  The
 // scalars are checked by the entry points.  qe_launch_args with r_c = r_drift − merton_compensator(jump) for r:
 QeArgs bates_launch_args(const hh_model& m, const hh_config& c, const hh_qe& qe, const hh_jump& jump);
 // launch_qe_stats with a jump count per step and, on the lane that has one, a jump: the same five rows and var_T
 int launch_bates_stats(const hh_model& m, const hh_config& c, const hh_qe& qe, const hh_jump& jump,
                        const uint64_t* seeds_dev, uint32_t monitor_every, bool include_start, double* stats,
-                       double* var_T, hipStream_t s);
+                       double* var_T, hipStream_t s, bool date_rows = false);
 // Local volatility on a tabulated surface (hh_localvol.hip; include/hedgehog_mc.h, "Local volatility on a tabulated
 // surface"): launch_path_stats' lognormal forms — the five monitored rows, or the seven under `bridge` — with the σ of
 // every step read from the surface.  m.sigma is not read.  The entry points have checked the surface and staged lv's
 // three arrays (hh_localvol.h); lv.n_times·lv.n_x doubles of dynamic LDS, at most HH_LV_MAX_NODES.
 struct LocalVolArgs;
 int launch_localvol_stats(const hh_model& m, const hh_config& c, const LocalVolArgs& lv, const uint64_t* seeds_dev,
-                          uint32_t monitor_every, bool include_start, bool bridge, double* stats, hipStream_t s);
+                          uint32_t monitor_every, bool include_start, bool bridge, double* stats, hipStream_t s,
+                          bool date_rows = false);
 // Several correlated lognormal assets (hh_assets.hip; include/hedgehog_mc.h, "Several correlated lognormal assets"):
 // launch_path_stats' five monitored rows for the index of `assets`.  m: T, r_drift; c: antithetic, n_paths, n_steps.
 // The entry points have checked the assets (hh_assets.h: corr_defect, cholesky); the factor is formed again here.

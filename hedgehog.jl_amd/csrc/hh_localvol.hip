@@ -23,10 +23,14 @@ namespace {
 // after path_stats_kernel<GbmModel<0>, ANTI, BRIDGE>.  The lanes past n_paths take part in the table's load and in the
 // barrier and leave only then.  BRIDGE: the σ of the step, frozen over it, is the bridge's coefficient (Extremes); the
 // mirror takes the bridge draws swapped, as there.
-template <bool ANTI, bool BRIDGE>
+// Sink (hh_path_stats.h): Monitor, the five statistics — or DateRows, the date-row form: `stats` is then the grid
+// [n_steps/monitor_every + 1][n_total], row j the spot after step j·monitor_every, and include_start is not read.  The
+// walk, its draws and its constants are stated here once for both.
+template <bool ANTI, bool BRIDGE, class Sink = Monitor<ANTI>>
 __global__ __launch_bounds__(256) void localvol_stats_kernel(const SimArgs<0> a, const LocalVolArgs lv, const double S0,
                                                              const uint32_t monitor_every, const int include_start,
                                                              double* __restrict__ stats) {
+  static_assert(Sink::kStats || !BRIDGE, "the continuous extremes are statistics: no date-row form");
   extern __shared__ double tab[];
   const uint32_t n_nodes = lv.n_times * lv.n_x;
   for (uint32_t q = threadIdx.x; q < n_nodes; q += 256u) tab[q] = lv.vols[q];
@@ -37,7 +41,8 @@ __global__ __launch_bounds__(256) void localvol_stats_kernel(const SimArgs<0> a,
   const uint32_t n_steps = a.n_steps;
   const bool two_rows = lv.n_times > 1u;
   double x = a.x0.v, xa = a.x0.v;
-  Monitor<ANTI> mon(monitor_every, include_start);
+  Sink mon(monitor_every, include_start);
+  mon.bind(stats, i, a.n_paths);
   mon.start(S0, a.x0.v);
   Extremes e, ea;
   if constexpr (BRIDGE) {
@@ -83,7 +88,8 @@ __global__ __launch_bounds__(256) void localvol_stats_kernel(const SimArgs<0> a,
 }  // namespace
 
 int launch_localvol_stats(const hh_model& m, const hh_config& c, const LocalVolArgs& lv, const uint64_t* seeds_dev,
-                          uint32_t monitor_every, bool include_start, bool bridge, double* stats, hipStream_t s) {
+                          uint32_t monitor_every, bool include_start, bool bridge, double* stats, hipStream_t s,
+                          bool date_rows) {
   const StatsLaunch l(m, c, seeds_dev);
   const size_t lds = (size_t)lv.n_times * lv.n_x * sizeof(double);  // <= HH_LV_MAX_NODES·8 = 64 KiB: the entry points check
   auto go = [&](auto anti, auto br) {
@@ -91,7 +97,11 @@ int launch_localvol_stats(const hh_model& m, const hh_config& c, const LocalVolA
                        lv, m.S0, monitor_every, (int)include_start, stats);
   };
   auto with_form = [&](auto anti) {
-    if (bridge) go(anti, std::true_type{});
+    constexpr bool kAnti = decltype(anti)::value;
+    if (date_rows)
+      hipLaunchKernelGGL((localvol_stats_kernel<kAnti, false, DateRows<kAnti>>), l.grid, l.block, lds, s, l.a, lv, m.S0,
+                         monitor_every, 1, stats);
+    else if (bridge) go(anti, std::true_type{});
     else go(anti, std::false_type{});
   };
   if (c.antithetic) with_form(std::true_type{});

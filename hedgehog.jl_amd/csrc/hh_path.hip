@@ -25,10 +25,15 @@ namespace {
 // block and two logarithms per step (euler_bridge_draws), shared with the mirror: -dW has the negated bridge, the
 // excess of its maximum is the excess of the original's minimum, so the mirror's maximum takes L2 and its minimum L1.
 // The trajectory and the five statistics are the other form's, operation for operation.
-template <class M, bool ANTI, bool BRIDGE>
+// Sink (hh_path_stats.h): Monitor, the five statistics — or DateRows, the date-row form: `stats` is then the grid
+// [n_steps/monitor_every + 1][n_total], row j the spot after step j·monitor_every, and include_start is not read.  The
+// walk, its draws and its constants are stated here once for both.
+// At monitor_every = 1 the date rows are euler_grid_kernel's spot grid bit for bit.
+template <class M, bool ANTI, bool BRIDGE, class Sink = Monitor<ANTI>>
 __global__ __launch_bounds__(256) void path_stats_kernel(const SimArgs<0> a, const double S0,
                                                          const uint32_t monitor_every, const int include_start,
                                                          double* __restrict__ stats) {
+  static_assert(Sink::kStats || !BRIDGE, "the continuous extremes are statistics: no date-row form");
   using State = typename M::State;
   constexpr int NC = M::NCOMP;
   const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
@@ -38,7 +43,8 @@ __global__ __launch_bounds__(256) void path_stats_kernel(const SimArgs<0> a, con
   State st, sa;
   M::init(st, a);
   if constexpr (ANTI) M::init(sa, a);
-  Monitor<ANTI> mon(monitor_every, include_start);
+  Sink mon(monitor_every, include_start);
+  mon.bind(stats, i, a.n_paths);
   mon.start(S0, a.x0.v);
   Extremes e, ea;
   if constexpr (BRIDGE) {
@@ -307,14 +313,18 @@ int launch_level_payoffs(const PathPayoffArgs& b, uint32_t n_payoffs, hipStream_
 }
 
 int launch_path_stats(const hh_model& m, const hh_config& c, const uint64_t* seeds_dev, uint32_t monitor_every,
-                      bool include_start, bool bridge, double* stats, hipStream_t s) {
+                      bool include_start, bool bridge, double* stats, hipStream_t s, bool date_rows) {
   const StatsLaunch l(m, c, seeds_dev);
   auto go = [&](auto model, auto anti, auto br) {
     hipLaunchKernelGGL((path_stats_kernel<decltype(model), decltype(anti)::value, decltype(br)::value>), l.grid, l.block, 0,
                        s, l.a, m.S0, monitor_every, (int)include_start, stats);
   };
   auto with_form = [&](auto model, auto anti) {
-    if (bridge) go(model, anti, std::true_type{});
+    constexpr bool kAnti = decltype(anti)::value;
+    if (date_rows)
+      hipLaunchKernelGGL((path_stats_kernel<decltype(model), kAnti, false, DateRows<kAnti>>), l.grid, l.block, 0, s, l.a, m.S0,
+                         monitor_every, 1, stats);
+    else if (bridge) go(model, anti, std::true_type{});
     else go(model, anti, std::false_type{});
   };
   auto with_anti = [&](auto model) {

@@ -1,8 +1,10 @@
 // The monitored statistics of a trajectory and its mirror (enum hh_path_stat), stated once for the kernels that keep
 // them on log spots: path_stats_kernel (hh_path.hip), jump_stats_kernel (hh_jump.hip), qe_stats_kernel (hh_qe.hip),
-// bates_stats_kernel (hh_bates.hip) and localvol_stats_kernel (hh_localvol.hip).  Running is the arithmetic of the five
-// rows, Monitor the dates they are taken on, Extremes the two rows of the bridge form; a kernel supplies its states, its
-// step and the call after it.  assets_stats_kernel (hh_assets.hip) uses Running and writes the dates out itself (its head
+// bates_stats_kernel (hh_bates.hip), localvol_stats_kernel (hh_localvol.hip) and vg_stats_kernel (hh_vg.hip).  Running is
+// the arithmetic of the five rows, Monitor the dates they are taken on, Extremes the two rows of the bridge form; a kernel
+// supplies its states, its step and the call after it.  DateRows is the second sink of the same walks: each kernel takes its
+// sink as its last template parameter (Monitor by default) and, instantiated on DateRows, leaves the dates themselves
+// (hh_mc_path_grid).  assets_stats_kernel (hh_assets.hip) uses Running and writes the dates out itself (its head
 // comment says why).  Internal.
 #pragma once
 #include "hh_sim.h"
@@ -61,12 +63,15 @@ struct Monitor {
   // (the members in the reverse of the order the kernels once declared them as locals: promoted to registers in this
   // order, eleven of the thirteen path_stats_kernel forms and every jump, QE and Bates kernel compile to the code they
   // compiled to with those locals)
+  static constexpr bool kStats = true;  // keeps the five rows (DateRows: writes the dates out)
   const uint32_t every;
   uint32_t left;
   bool started;
   Running ra, r;
   __device__ __forceinline__ Monitor(uint32_t monitor_every, int include_start)
       : every(monitor_every), left(monitor_every), started(include_start != 0) {}
+  // where a sink writes as it goes (DateRows); the statistics go out at the end, through store
+  __device__ __forceinline__ void bind(double*, uint64_t, uint64_t) {}
   // step 0, taken when include_start alone: (S0, log S0), from which the mirror starts as well
   __device__ __forceinline__ void start(double S0, double x0) {
     if (!started) return;
@@ -95,6 +100,41 @@ struct Monitor {
     r.store(stats, at, i);
     if constexpr (ANTI) ra.store(stats, at, n_paths + i);
   }
+};
+
+// The other sink of the family's walks, with Monitor's start / date / store: every date's exp(x) goes OUT, into the
+// step-major grid [n_steps/every + 1][n_total] of hh_lsm_grid_elems, and nothing is kept.  Row 0 is S0 as euler_grid_kernel
+// writes it (a plain store, whatever include_start says), row j the state after step j·every, the mirror of trajectory i
+// in column n_paths + i.  One lane writes one column: a wave's store is 512 contiguous bytes per date and member.  The
+// grid is written once and read once by the induction, far beyond what the caches hold: nontemporal stores, as there.
+// The lane carries the address of its column in the next row and adds n_total (size_t) per date; the countdown is
+// Monitor's uniform branch.
+template <bool ANTI>
+struct DateRows {
+  static constexpr bool kStats = false;
+  const uint32_t every;
+  uint32_t left;
+  double* next = nullptr;  // column i of the next row
+  size_t n_total = 0, mirror = 0;
+  __device__ __forceinline__ DateRows(uint32_t exercise_every, int) : every(exercise_every), left(exercise_every) {}
+  __device__ __forceinline__ void bind(double* __restrict__ grid, uint64_t i, uint64_t n_paths) {
+    next = grid + i;
+    n_total = (size_t)(ANTI ? 2 * n_paths : n_paths);
+    mirror = (size_t)n_paths;
+  }
+  __device__ __forceinline__ void start(double S0, double) {
+    next[0] = S0;
+    if constexpr (ANTI) next[mirror] = S0;
+    next += n_total;
+  }
+  __device__ __forceinline__ void date(const double& x, const double& xa) {
+    if (--left != 0u) return;
+    left = every;
+    __builtin_nontemporal_store(exp(x), next);
+    if constexpr (ANTI) __builtin_nontemporal_store(exp(xa), next + mirror);
+    next += n_total;
+  }
+  __device__ __forceinline__ void store(double* __restrict__, const PathStatsLayout&, uint64_t, uint64_t) const {}
 };
 
 // The running extremes of the scheme's CONTINUOUS interpolation, in log space (the bridge form of path_stats_kernel and

@@ -91,7 +91,10 @@ __global__ __launch_bounds__(kTile) void vg_exact_kernel(const SimArgs<0> a, con
 // Trajectory i under seeds[i].  Step k: the gamma variate of shape dt/ν from VgStepDraws' blocks, the normal the
 // lognormal path_stats_kernel draws for step k (euler_scalar_normals, domain 0: one block per two steps, an odd n_steps
 // leaving the last block half read), x ← x + vg_increment, then the date.  The mirror takes the same variate and −z.
-template <bool ANTI>
+// Sink (hh_path_stats.h): Monitor, the five statistics — or DateRows, the date-row form: `stats` is then the grid
+// [n_steps/monitor_every + 1][n_total], row j the spot after step j·monitor_every, and include_start is not read.  The
+// walk, its draws and its constants are stated here once for both.
+template <bool ANTI, class Sink = Monitor<ANTI>>
 __global__ __launch_bounds__(256) void vg_stats_kernel(const SimArgs<0> a, const VgArgs v, const double S0,
                                                        const uint32_t monitor_every, const int include_start,
                                                        double* __restrict__ stats) {
@@ -100,7 +103,8 @@ __global__ __launch_bounds__(256) void vg_stats_kernel(const SimArgs<0> a, const
   const PathStatsLayout at(a.n_paths, ANTI, HH_PATH_STATS);
   const uint32_t n_steps = a.n_steps;
   double x = a.x0.v, xa = a.x0.v;
-  Monitor<ANTI> mon(monitor_every, include_start);
+  Sink mon(monitor_every, include_start);
+  mon.bind(stats, i, a.n_paths);
   mon.start(S0, a.x0.v);
   const uint64_t key = a.seeds[i];
   const uint32_t k0 = (uint32_t)key, k1 = (uint32_t)(key >> 32);
@@ -133,10 +137,11 @@ int launch_vg_exact(const hh_model& m, const hh_config& c, const hh_vg& vg, cons
 }
 
 int launch_vg_stats(const hh_model& m, const hh_config& c, const hh_vg& vg, const uint64_t* seeds_dev,
-                    uint32_t monitor_every, bool include_start, double* stats, hipStream_t s) {
+                    uint32_t monitor_every, bool include_start, double* stats, hipStream_t s, bool date_rows) {
   StatsLaunch l(m, c, seeds_dev);
   const VgArgs v = vg_args(m.sigma, m.r_drift, vg, l.a.dt);
-  auto kernel = c.antithetic ? vg_stats_kernel<true> : vg_stats_kernel<false>;
+  auto kernel = c.antithetic ? (date_rows ? vg_stats_kernel<true, DateRows<true>> : vg_stats_kernel<true>)
+                             : (date_rows ? vg_stats_kernel<false, DateRows<false>> : vg_stats_kernel<false>);
   hipLaunchKernelGGL(kernel, l.grid, l.block, 0, s, l.a, v, m.S0, monitor_every, (int)include_start, stats);
   return (int)hipGetLastError();
 }

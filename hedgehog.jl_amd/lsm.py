@@ -9,7 +9,13 @@ For every log-state problem (the Euler ones, and HestonNoise) the reference's ex
 combinations (LognormalDynamics or HestonDynamics + EulerMaruyama, `hh_lsm_solve_euler`) are reached
 only when the caller names the path state: path_state="spot" regresses on exp(log S) as for the exact
 Heston paths, path_state="log" hands log S to the regression and the payoff, the reference as run.
-Without it they raise MethodError."""
+Without it they raise MethodError.
+
+Every other spot-path model of routes.py — Merton jumps on Euler paths, HestonQE, Bates, local volatility, Variance Gamma —
+is priced on the date rows of its own path kernel (`hh_lsm_solve_path`): LSM(dynamics, strategy, config, degree) with the
+route's own dynamics, inputs and strategy.  `exercise_every=m` exercises on every m-th simulation step (a Bermudan
+schedule of steps/m dates; m divides steps), there and on the Euler sources under path_state="spot".  Stopping times count
+EXERCISE DATES, date j lying at T·j·m/steps, and spot_paths holds those dates' rows alone."""
 from __future__ import annotations
 
 import ctypes as C
@@ -20,10 +26,11 @@ import numpy as np
 
 from . import _ffi
 from .dates import MILLISECONDS_IN_YEAR_365, yearfrac
-from .domain import (American, BlackScholesInputs, HestonInputs, PricingProblem, VanillaOption, df,
+from .domain import (American, BlackScholesInputs, Call, European, HestonInputs, PricingProblem, Spot, VanillaOption, df,
                      get_vol, zero_rate)
+from .dual import Dual
 from .montecarlo import (AbstractPricingMethod, Antithetic, BlackScholesExact, EulerMaruyama,
-                         HestonBroadieKaya, HestonDynamics, LognormalDynamics, MethodError, MonteCarlo)
+                         HestonBroadieKaya, HestonDynamics, LognormalDynamics, MethodError, MonteCarlo, routes)
 
 _PATH_STATES = {"spot": _ffi.HH_PATH_SPOT, "log": _ffi.HH_PATH_LOG}
 
@@ -120,21 +127,82 @@ def _lsm_structs(prob: PricingProblem, mc: MonteCarlo, euler: bool = False):
     return model, c, T
 
 
+def _exercise_dates(steps: int, exercise_every) -> int:
+    every = int(exercise_every)
+    if every != exercise_every or every < 1 or steps % every:
+        raise MethodError(f"exercise_every ({exercise_every!r}) must be a whole number >= 1 that divides steps ({steps})")
+    return steps // every
+
+
+def _source_structs(prob: PricingProblem, mc: MonteCarlo, route, exercise_every):
+    """(hh_path_source, hh_model, hh_config, T, n_dates) of the date rows of `route` (routes.py) for prob's payoff: the
+    structs of the route's path solve to that expiry — formed by the route, with its refusals — under the payoff's strike and
+    sign, on the seeds of mc.config in host memory."""
+    payoff, m = prob.payoff, prob.market_inputs
+    n_dates = _exercise_dates(mc.config.steps, exercise_every)
+    model, c, extras = route.form_structs(VanillaOption(1.0, payoff.expiry, European(), Call(), Spot()), m, mc)
+    if isinstance(payoff.strike, Dual):
+        raise MethodError(route.no_duals)
+    model.strike, model.cp = float(payoff.strike), payoff.call_put()
+    c.seeds, c.seeds_on_device, c.seeds_len = mc.config.seeds.ctypes.data, 0, mc.config.seeds.size
+    return routes().path_source(route, extras), model, c, float(model.T), n_dates
+
+
+def _date_discount(m, T, steps, exercise_every) -> float:
+    """df over one exercise period, T·exercise_every/steps from the reference date (:107 at exercise_every = 1)"""
+    return float(df(m.rate, m.referenceDate + (T * exercise_every / steps) * MILLISECONDS_IN_YEAR_365))
+
+
+def _solve_lsm_path(prob, method, source, model, c, T, n_dates, exercise_every, spot_paths, stopping_info) -> LSMSolution:
+    """hh_lsm_solve_path: the grid of `source` on every exercise_every-th step, then the backward induction on it"""
+    mc = method.mc_method
+    ntot = mc.config.trajectories * (2 if c.antithetic else 1)
+    tau = np.empty(ntot, dtype=np.int32) if stopping_info else None
+    val = np.empty(ntot) if stopping_info else None
+    grid = np.empty((n_dates + 1, ntot)) if spot_paths else None
+    res = _ffi.hh_lsm_result()
+    ctx = _ffi.get_context(mc.device)
+    ctx.check(ctx.lib.hh_lsm_solve_path(ctx.handle, C.byref(source), C.byref(model), C.byref(c), int(exercise_every),
+                                        method.degree, _date_discount(prob.market_inputs, T, mc.config.steps, int(exercise_every)),
+                                        C.byref(res), tau.ctypes.data if stopping_info else None,
+                                        val.ctypes.data if stopping_info else None, grid.ctypes.data if spot_paths else None))
+    return LSMSolution(prob, method, res.price, (tau, val) if stopping_info else None, grid, std_error=res.std_error, result=res)
+
+
 def solve_lsm(prob: PricingProblem, method: LSM, spot_paths: bool = False,
-              stopping_info: bool = True, path_state=None) -> LSMSolution:
+              stopping_info: bool = True, path_state=None, exercise_every=1) -> LSMSolution:
     """path_state: None (the exact sources only), "spot" or "log" (module docstring).  On an exact source
-    "spot" is what it does anyway and "log" raises MethodError.  With path_state="log", spot_paths holds log S."""
+    "spot" is what it does anyway and "log" raises MethodError.  With path_state="log", spot_paths holds log S.
+    exercise_every: exercise on every m-th step — on the spot-path models of routes.py, and (m > 1) on the Euler sources
+    under path_state="spot"; stopping_info[0] then counts exercise dates, not steps, and spot_paths holds steps/m + 1 rows."""
     payoff, m = prob.payoff, prob.market_inputs
     if not (isinstance(payoff, VanillaOption) and isinstance(payoff.exercise_style, American)):
         raise MethodError("solve(::PricingProblem, ::LSM) needs an American VanillaOption")
     mc = method.mc_method
     state = None if path_state is None else _path_state_code(path_state)
+    route = routes().lsm_route_of(m, mc)
+    if route is not None:
+        if state == _ffi.HH_PATH_LOG:
+            raise MethodError('path_state="log" applies to the Euler path sources only')
+        return _solve_lsm_path(prob, method, *_source_structs(prob, mc, route, exercise_every), exercise_every, spot_paths,
+                               stopping_info)
     euler = state is not None and _is_euler(mc)
     if state == _ffi.HH_PATH_LOG and not euler:
         raise MethodError('path_state="log" applies to the Euler path sources only')
     model, c, T = _lsm_structs(prob, mc, euler=euler)
     cfg = mc.config
     nsteps = cfg.steps
+    if exercise_every != 1:  # a Bermudan schedule: the Euler source's date rows
+        n_dates = _exercise_dates(nsteps, exercise_every)
+        if state == _ffi.HH_PATH_LOG:
+            raise MethodError('exercise_every > 1 regresses on spot rows: path_state="log" exercises on every step')
+        if not euler:
+            raise MethodError('exercise_every > 1 needs path rows on a subset of the steps: the Euler sources under path_state="spot", '
+                              "or a spot-path model (Merton, HestonQE, Bates, local volatility, Variance Gamma)")
+        if mc.devices is not None:
+            raise MethodError("LSM on Euler paths is not sharded over several GPUs")
+        source = _ffi.make_path_source(routes().EULER.source)
+        return _solve_lsm_path(prob, method, source, model, c, T, n_dates, exercise_every, spot_paths, stopping_info)
     # discount = df(rate, add_yearfrac(referenceDate, T / nsteps))      # :107
     step_discount = float(df(m.rate, m.referenceDate + (T / nsteps) * MILLISECONDS_IN_YEAR_365))
     ntot = cfg.trajectories * (2 if c.antithetic else 1)
@@ -225,3 +293,40 @@ def simulate_euler_paths(prob: PricingProblem, mc: MonteCarlo, path_state: str =
     ctx.check(ctx.lib.hh_euler_grid(ctx.handle, C.byref(model), C.byref(c), state, spot.ctypes.data,
                                     var.ctypes.data if var is not None else None, 0, C.byref(res)))
     return EulerPaths(spot, var, np.linspace(0.0, T, steps + 1), res)
+
+
+@dataclass(frozen=True)
+class SpotPaths:
+    """The spots of a spot-path model's trajectories on every exercise_every-th step, as a (steps/exercise_every + 1, n)
+    matrix whose row j lies at times[j]; row 0 is the spot.  Antithetic: n = 2·trajectories, the mirror of trajectory i in
+    column trajectories + i."""
+    spot: Any
+    times: Any
+    result: Any = field(default=None, compare=False, repr=False)
+
+
+def simulate_spot_paths(prob: PricingProblem, mc: MonteCarlo, exercise_every=1) -> SpotPaths:
+    """The date rows of solve(prob, mc)'s trajectories through hh_mc_path_grid, on the same seeds: Merton jumps on Euler
+    paths, HestonQE, Bates, local volatility, Variance Gamma — the route's own dynamics, inputs and strategy — and the Euler
+    paths of the plain models.  The last row is that solve's sample at expiry."""
+    m = prob.market_inputs
+    route = routes().lsm_route_of(m, mc)
+    if route is not None:
+        source, model, c, T, n_dates = _source_structs(prob, mc, route, exercise_every)
+    elif _is_euler(mc):
+        if mc.devices is not None:
+            raise MethodError("LSM on Euler paths is not sharded over several GPUs")
+        model, c, T = _lsm_structs(prob, mc, euler=True)
+        n_dates = _exercise_dates(mc.config.steps, exercise_every)
+        source = _ffi.make_path_source(routes().EULER.source)
+    else:
+        raise MethodError("simulate_spot_paths needs a spot-path model on its own dynamics, inputs and strategy (Merton + "
+                          "EulerMaruyama, HestonQE, Bates, local volatility, Variance Gamma) or LognormalDynamics / "
+                          "HestonDynamics + EulerMaruyama")
+    ntot = mc.config.trajectories * (2 if c.antithetic else 1)
+    spot = np.empty((n_dates + 1, ntot))
+    res = _ffi.hh_result()
+    ctx = _ffi.get_context(mc.device)
+    ctx.check(ctx.lib.hh_mc_path_grid(ctx.handle, C.byref(source), C.byref(model), C.byref(c), int(exercise_every),
+                                      spot.ctypes.data, 0, C.byref(res)))
+    return SpotPaths(spot, np.linspace(0.0, T, n_dates + 1), res)

@@ -67,6 +67,7 @@ class Route:
     entry_ex: str = None             # the entry point (with extremes) of a lookback or a continuously monitored payoff
     tail: tuple = ()                 # NULLs after the statistics (var_T)
     law: bool = False                # `entry` samples the law at expiry: one European vanilla, no paths
+    source: int = None               # enum hh_path_source_kind: the route's paths as date rows (hh_mc_path_grid, LSM on them)
     solve_all: Callable = None       # (payoffs, market_inputs, method, ensemble): a grouping of its own, for one payoff or many
     # ---- what it refuses, and in which words ----
     early: tuple = ()                # of the four checks above, in the route's order; `admitted` elsewhere: with the structs
@@ -84,7 +85,17 @@ class Route:
     checks_first: bool = False       # per expiry), "singles"; checks_first: the first payoff's refusals before any grouping
     multi: bool = False              # an hh_mc_solve_multi form
 
+    def takes_lsm(self, m, mc):
+        """Is `mc` — the MonteCarlo method inside an LSM — this route's own triple?  Then LSM regresses on its date rows."""
+        if self.source is None or self.admits is None or not self.claims((), m, mc):
+            return False
+        D, M, S = self.admits
+        return isinstance(mc.dynamics, D) and isinstance(m, M) and isinstance(mc.strategy, S)
+
     def refuse_method(self, payoffs, m, method):
+        mc = getattr(method, "mc_method", None)  # an LSM: on the route's own triple it is one of the route's methods
+        if mc is not None and self.takes_lsm(m, mc):
+            return
         if self.other_methods and not isinstance(method, self.methods) and self.claims(payoffs, m, method):
             raise MethodError(self.other_methods.format(type(method).__name__))
 
@@ -149,7 +160,7 @@ LOCALVOL = Route(
     admits=(LocalVolDynamics, LocalVolInputs, EulerMaruyama),
     not_admitted="no local-volatility solve for {dyn} + {strat} on {m}: use " + LOCALVOL_ROUTES,
     base=_on_lognormal(), dual_fields=("spot",), extras=lambda m, method: (m.surface.c_struct(),),
-    entry="hh_mc_solve_path_lv", takes_extremes=True, early=(admitted, european_discrete, one_device),
+    entry="hh_mc_solve_path_lv", takes_extremes=True, source=_ffi.HH_SOURCE_LOCALVOL, early=(admitted, european_discrete, one_device),
     no_replay="local-volatility solves draw their own noise: no replay",
     one_device="local-volatility solves run on one device (MonteCarlo.devices is not supported)",
     no_duals="local-volatility solves carry no dual partials (ForwardAD): use FiniteDifference — its solves share their seeds, "
@@ -162,7 +173,7 @@ BATES = Route(
     admits=(BatesDynamics, BatesInputs, HestonQE), not_admitted="no Bates solve for {dyn} + {strat} on {m}: use " + BATES_ROUTES,
     base=lambda m, method: (m.heston(), dataclasses.replace(method, dynamics=HestonDynamics(), strategy=EulerMaruyama())),
     strategy=_ffi.HH_QE, dual_fields=JUMPS, extras=lambda m, method: _qe(m, method) + _jump(m, method),
-    entry="hh_mc_solve_path_bates", tail=(None,), early=(admitted, european_discrete, one_device),
+    entry="hh_mc_solve_path_bates", tail=(None,), source=_ffi.HH_SOURCE_BATES, early=(admitted, european_discrete, one_device),
     no_replay="Bates solves draw their own noise: no replay",
     one_device="path-dependent payoffs run on one device (MonteCarlo.devices is not supported)",
     no_duals="Bates solves carry no dual partials (ForwardAD): use FiniteDifference — its solves share their seeds",
@@ -177,7 +188,7 @@ QE = Route(
     not_admitted="HestonQE simulates HestonDynamics() on HestonInputs, not {dyn} on {m}: use EulerMaruyama or the model's exact "
                  "strategy there",
     base=lambda m, method: (m, dataclasses.replace(method, strategy=EulerMaruyama())), strategy=_ffi.HH_QE, extras=_qe,
-    entry="hh_mc_solve_path_qe", tail=(None,), early=(european_discrete, one_device),
+    entry="hh_mc_solve_path_qe", tail=(None,), source=_ffi.HH_SOURCE_QE, early=(european_discrete, one_device),
     no_replay="HestonQE solves draw their own noise: no replay (EulerMaruyama takes one)",
     one_device="path-dependent payoffs run on one device (MonteCarlo.devices is not supported)",
     no_duals="HestonQE solves carry no dual partials (ForwardAD): use FiniteDifference — its solves share their seeds",
@@ -192,7 +203,7 @@ MERTON = Route(  # Merton jumps on Euler paths
     admits=(MertonDynamics, MertonInputs, (EulerMaruyama, MertonExact)),
     not_admitted="no sde_problem / marginal_law for {dyn} + {strat} on {m}",
     base=_on_lognormal(compat_sqrt_alpha=False), dual_fields=JUMPS, extras=_jump,
-    entry="hh_mc_solve_path_jump", early=(one_device,),
+    entry="hh_mc_solve_path_jump", source=_ffi.HH_SOURCE_JUMP, early=(one_device,),
     no_replay="Merton solves draw their own noise: no replay",
     one_device="path-dependent payoffs run on one device (MonteCarlo.devices is not supported)",
     no_duals="Merton solves carry no dual partials: use FiniteDifference",
@@ -201,7 +212,7 @@ MERTON = Route(  # Merton jumps on Euler paths
 
 MERTON_LAW = dataclasses.replace(  # MertonExact: the law at expiry (and whatever else a Merton pair names: not admitted)
     MERTON, name="Merton law", claims=lambda payoffs, m, method: is_merton(m, method),
-    base=_on_lognormal(compat_sqrt_alpha=False, strategy=BlackScholesExact()), entry="hh_mc_solve_jump", law=True,
+    base=_on_lognormal(compat_sqrt_alpha=False, strategy=BlackScholesExact()), entry="hh_mc_solve_jump", law=True, source=None,
     early=(euler_paths,),  # asked for paths (a basket's path groups): refused
     one_device="Merton solves run on one device (MonteCarlo.devices is not supported)", no_bridge=None,
     no_paths="MertonExact samples the law at expiry: path-dependent payoffs need EulerMaruyama paths", rest="singles")
@@ -211,7 +222,7 @@ VG = Route(  # Variance Gamma: every payoff on the path statistics, exact in law
     admits=(VarianceGammaDynamics, VarianceGammaInputs, VarianceGammaExact),
     not_admitted="no Variance Gamma solve for {dyn} + {strat} on {m}: use " + VG_ROUTES,
     base=_on_lognormal(compat_sqrt_alpha=False, strategy=BlackScholesExact()), dual_fields=("theta", "nu"), extras=_vg,
-    entry="hh_mc_solve_path_vg", early=(admitted, european_discrete, one_device),
+    entry="hh_mc_solve_path_vg", source=_ffi.HH_SOURCE_VG, early=(admitted, european_discrete, one_device),
     no_replay="Variance Gamma solves draw their own noise (gamma variates by rejection): no replay; use " + VG_ROUTES,
     one_device="Variance Gamma solves run on one device (MonteCarlo.devices is not supported): use " + VG_ROUTES,
     no_duals="Variance Gamma solves carry no dual partials (ForwardAD): use FiniteDifference with SpotLens, VolLens, "
@@ -224,11 +235,11 @@ VG = Route(  # Variance Gamma: every payoff on the path statistics, exact in law
 
 VG_LAW = dataclasses.replace(  # one European vanilla on the spot: the law at expiry, one gamma variate per trajectory
     VG, name="Variance Gamma law", claims=lambda payoffs, m, method: is_vg(m, method) and _one_european_vanilla(payoffs),
-    entry="hh_mc_solve_vg", law=True, early=(), rest="singles")
+    entry="hh_mc_solve_vg", law=True, source=None, early=(), rest="singles")
 
 EULER = Route(  # a path-dependent payoff on the Euler paths of the plain models; vanillas of its basket: the plain route's
     "Euler paths", lambda payoffs, m, method: any(isinstance(p, PATH_PAYOFFS) for p in payoffs),
-    entry="hh_mc_solve_path", entry_ex="hh_mc_solve_path_ex", early=(euler_paths, one_device),
+    entry="hh_mc_solve_path", entry_ex="hh_mc_solve_path_ex", source=_ffi.HH_SOURCE_EULER, early=(euler_paths, one_device),
     no_replay="path-dependent payoffs draw their own noise: no replay",
     one_device="path-dependent payoffs run on one device (MonteCarlo.devices is not supported)",
     no_duals="path-dependent payoffs carry no dual partials: use FiniteDifference")
@@ -248,6 +259,20 @@ def route_of(payoffs, market_inputs, method, routes=ROUTES) -> Route:
 
 def path_route_of(payoffs, market_inputs, method) -> Route:
     return route_of(payoffs, market_inputs, method, SPOT_PATHS) or EULER
+
+
+def lsm_route_of(market_inputs, mc) -> Route:
+    """The route whose date rows an LSM on `mc` regresses on: the one that takes the triple as its own, or None (the Euler and
+    exact sources of lsm.py, and every refusal there)."""
+    for route in SPOT_PATHS:
+        if route.takes_lsm(market_inputs, mc):
+            return route
+
+
+def path_source(route, extras):
+    """hh_path_source of a route over the structs it brought (Route.extras), each in the field of its type"""
+    fields = {_ffi.hh_jump: "jump", _ffi.hh_qe: "qe", _ffi.hh_localvol: "localvol", _ffi.hh_vg: "vg"}
+    return _ffi.make_path_source(route.source, **{fields[type(x)]: x for x in extras})
 
 
 def refuse_other_methods(payoffs, market_inputs, method):

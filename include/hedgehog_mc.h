@@ -873,8 +873,8 @@ int hh_carr_madan_jump(hh_ctx* ctx, const hh_model* model, const hh_jump* jump, 
  * noise, n_partials > 0, the correction with A > 0 (run without it).
  * Not provided: bridge extremes (the QE step's interpolation is not a frozen-coefficient bridge), REPLAY noise, dual
  * partials (bump the inputs: the solves share their seeds), accumulate and multi-GPU forms, the hh_mc_solve_multi form,
- * LSM on these paths, a spot / variance grid, weights other than ½, the TG scheme, the correction for A > 0, a Julia
- * binding.
+ * a variance grid (the spot rows and LSM on them: hh_mc_path_grid, hh_lsm_solve_path), weights other than ½, the TG
+ * scheme, the correction for A > 0, a Julia binding.
  */
 #define HH_QE_MAX_PSI 1e9   /* largest σ²/(2κθ), the maximum of ψ over v >= 0, these entry points admit */
 typedef struct hh_qe { double psi_c; int32_t martingale; int32_t reserved; } hh_qe;   /* 16 bytes */
@@ -935,8 +935,8 @@ int hh_mc_solve_path_qe(hh_ctx* ctx, const hh_model* model, const hh_qe* qe, con
  * it); everything the QE entry points reject, the step's constants being formed on r_c; everything hh_mc_solve_path_ex
  * or hh_carr_madan_basket reject.  HH_ERR_UNSUPPORTED: dynamics other than HH_HESTON, a strategy other than HH_QE,
  * REPLAY noise, n_partials > 0, the martingale correction with A > 0.
- * Not provided: a terminal-law form on Broadie–Kaya, bridge extremes, a gradient of hh_carr_madan_bates, LSM on these
- * paths, multi-GPU and accumulate forms, the hh_mc_solve_multi form, dual partials (bump the inputs: the solves share
+ * Not provided: a terminal-law form on Broadie–Kaya, bridge extremes, a gradient of hh_carr_madan_bates, a variance grid
+ * (the spot rows and LSM on them: hh_mc_path_grid, hh_lsm_solve_path), multi-GPU and accumulate forms, the hh_mc_solve_multi form, dual partials (bump the inputs: the solves share
  * their seeds), a Julia binding.
  */
 int hh_mc_path_stats_bates(hh_ctx* ctx, const hh_model* model, const hh_qe* qe, const hh_jump* jump,
@@ -1063,8 +1063,8 @@ int hh_mc_solve_path_assets(hh_ctx* ctx, const hh_model* model, const hh_assets*
  * or <= 0; x_lo not finite; h not finite or <= 0; everything hh_mc_solve_path_ex rejects (model->sigma excepted).
  * HH_ERR_UNSUPPORTED: dynamics other than HH_LOGNORMAL, a strategy other than HH_EULER_MARUYAMA, REPLAY noise,
  * n_partials > 0.
- * Not provided: REPLAY noise, dual partials (bump the inputs: the solves share their seeds), LSM / American exercise,
- * accumulate, hh_mc_solve_multi and multi-GPU forms, local volatility on the Crank–Nicolson grid, stochastic-local
+ * Not provided: REPLAY noise, dual partials (bump the inputs: the solves share their seeds), accumulate,
+ * hh_mc_solve_multi and multi-GPU forms (American exercise: hh_lsm_solve_path), local volatility on the Crank–Nicolson grid, stochastic-local
  * volatility, tables above 64 KiB, non-uniform log-spot grids, a Julia binding.
  */
 #define HH_LV_MAX_NODES 8192          /* n_times · n_x doubles = 64 KiB of LDS */
@@ -1320,8 +1320,8 @@ int hh_ctx_read_timings(hh_ctx* ctx, double* ms, int32_t cap, int32_t* n_out);
  * n_partials > 0, a strategy other than HH_EXACT_LAW.  After any refusal the context stays usable.
  * Not provided: NIG and CGMY, the difference-of-gammas form, bridge or continuous monitoring, REPLAY and quasi-Monte
  * Carlo, dual partials (bump the inputs: the solves of a finite difference share their seeds), multilevel coupling,
- * LSM / American exercise, accumulate, hh_mc_solve_multi and multi-GPU forms, a gradient of hh_carr_madan_vg, a Julia
- * binding.
+ * accumulate, hh_mc_solve_multi and multi-GPU forms (American exercise: hh_lsm_solve_path), a gradient of
+ * hh_carr_madan_vg, a Julia binding.
  */
 #define HH_VG_MAX_ATTEMPTS 64    /* the rejection loop of one gamma variate stops here at the latest */
 typedef struct hh_vg { double theta, nu; } hh_vg;                        /* 16 bytes */
@@ -1335,6 +1335,66 @@ int hh_mc_solve_path_vg(hh_ctx* ctx, const hh_model* model, const hh_vg* vg, con
 int hh_carr_madan_vg(hh_ctx* ctx, const hh_model* model, const hh_vg* vg, double alpha, double bound,
                      const double* strikes, const double* cps, const double* Ts, const double* r_drifts,
                      const double* discounts, uint32_t n_payoffs, double* prices_out);
+
+/*
+ * Date rows of the log-spot path family, and American / Bermudan exercise on them (kernels: each *_stats_kernel of the
+ * family instantiated on the second sink, *_stats_kernel<…, DateRows<ANTI>>; hh_path_stats.h).
+ *
+ * A SOURCE names one of the family's six kernels and carries the structs it reads beside model and cfg:
+ *   HH_SOURCE_EULER     hh_mc_path_stats        lognormal or Heston dynamics, HH_EULER_MARUYAMA      no struct
+ *   HH_SOURCE_JUMP      hh_mc_solve_path_jump   lognormal dynamics, HH_EULER_MARUYAMA                jump
+ *   HH_SOURCE_QE        hh_mc_path_stats_qe     Heston dynamics, HH_QE                               qe
+ *   HH_SOURCE_BATES     hh_mc_path_stats_bates  Heston dynamics, HH_QE                               qe, jump
+ *   HH_SOURCE_LOCALVOL  hh_mc_path_stats_lv     lognormal dynamics, HH_EULER_MARUYAMA                localvol
+ *   HH_SOURCE_VG        hh_mc_path_stats_vg     lognormal dynamics, HH_EXACT_LAW                     vg
+ * The trajectories are those of the entry point named, on the same seeds (seeds[i] keys trajectory i; path_offset is not
+ * read), under HH_EXTREMES_MONITORED: the same draws, step and host-formed constants — the two kernels of a source run
+ * one statement of the walk.  A struct the kind does not list is not read.
+ *
+ * hh_mc_path_grid — the spots on every exercise_every-th step.  n_dates = n_steps / exercise_every, exercise_every >= 1
+ * a divisor of n_steps.  spot_grid (host, or device when grid_on_device) takes hh_lsm_grid_elems(n_paths, n_dates,
+ * antithetic) doubles, step-major as hh_euler_grid's:
+ *   row 0   S0 in every column
+ *   row j   exp(x) after step j·exercise_every, j = 1 .. n_dates — S = exp(x) is formed on those steps alone
+ *   column i < n_paths: trajectory i;  column n_paths + i (antithetic): its mirror
+ * With the statistics of the source's path_stats call at monitor_every = exercise_every, include_start = 0: S_T is row
+ * n_dates, MAX_S / MIN_S the extremes over rows 1 .. n_dates, SUM_S those rows added in date order, bit for bit.  The
+ * rows at exercise_every = m are rows 0, m, 2m, … of the grid at exercise_every = 1; HH_SOURCE_EULER at exercise_every
+ * = 1 is hh_euler_grid's HH_PATH_SPOT grid.  out (nullable): n_paths_done and the times.  Timing: one slot.
+ *
+ * hh_lsm_solve_path — that grid into the context, then the backward induction of hh_lsm_solve_grid over its n_dates
+ * exercise dates: hh_lsm_solve_euler's path behind another source, so HH_OPT_LSM_FORM, the one-launch form's fall-back
+ * and hh_lsm_result are as there.  date_discount is the discount over ONE EXERCISE PERIOD, T·exercise_every/n_steps
+ * (hh_lsm_solve_euler's step_discount at exercise_every = 1).  stop_time (nullable, n_total) is hh_lsm_solve_grid's on that
+ * grid: it counts EXERCISE DATES — the grid's rows — not simulation steps, date j lying at time j·T/n_dates.
+ * stop_value, spot_grid (nullable, host): as hh_lsm_solve_euler's, the grid being the one above.
+ * exercise_every = n_steps leaves one date: the European price, date_discount times the mean payoff at expiry.
+ *
+ * Both are synchronous.  Errors, checked on the host before any launch, in the words of the source's path_stats entry
+ * point wherever it makes the same check.  HH_ERR_INVALID: a NULL source, model, cfg (out for hh_lsm_solve_path) or a
+ * struct the kind lists; an unknown kind; exercise_every = 0 or not a divisor of n_steps; n_dates > 65534; everything
+ * the source's path_stats entry point rejects (scalars, jump, qe, surface, vg); for hh_lsm_solve_path what
+ * hh_lsm_solve_euler rejects (degree outside 1 .. 8, cp not ±1, date_discount not finite or <= 0).
+ * HH_ERR_UNSUPPORTED: REPLAY noise, n_partials > 0, dynamics or a strategy that are not the kernel's own.
+ * hh_lsm_solve_path checks exercise_every first, then the induction's scalars on its n_dates (in hh_lsm_solve_euler's
+ * words), then everything the source's entry point checks; where several things are wrong the first of these is reported.
+ * Not provided: sharded and multi-GPU forms, the log path state (the regression on log S is hh_lsm_solve_euler's, on
+ * every step), variance rows for QE and Bates, the bridge form, the coupled and the several-asset kernels.
+ */
+enum hh_path_source_kind { HH_SOURCE_EULER = 0, HH_SOURCE_JUMP = 1, HH_SOURCE_QE = 2, HH_SOURCE_BATES = 3,
+                           HH_SOURCE_LOCALVOL = 4, HH_SOURCE_VG = 5 };
+typedef struct hh_path_source {       /* 40 bytes */
+  int32_t kind;                       /* enum hh_path_source_kind */
+  const hh_jump* jump;
+  const hh_qe* qe;
+  const hh_localvol* localvol;
+  const hh_vg* vg;
+} hh_path_source;
+int hh_mc_path_grid(hh_ctx* ctx, const hh_path_source* source, const hh_model* model, const hh_config* cfg,
+                    uint32_t exercise_every, double* spot_grid, int32_t grid_on_device, hh_result* out);
+int hh_lsm_solve_path(hh_ctx* ctx, const hh_path_source* source, const hh_model* model, const hh_config* cfg,
+                      uint32_t exercise_every, int32_t degree, double date_discount, hh_lsm_result* out,
+                      int32_t* stop_time, double* stop_value, double* spot_grid);
 
 /*
  * A SimulationConfig's seed vector in the device memory of ctx, uploaded once and kept — repeated solves on one
