@@ -26,8 +26,8 @@ from .montecarlo import (AbstractPricingMethod, Antithetic, BatesDynamics, Black
                          MonteCarlo, NoVarianceReduction, NormalLaw, SimulationConfig, VarianceGammaDynamics,
                          VarianceGammaExact, marginal_law,
                          solve_montecarlo, solve_montecarlo_many, solve_path_payoffs)
-from .multiasset import (BestOf, GeometricMean, IndexOption, MultiAssetDynamics, MultiAssetInputs, WeightedSum, WorstOf,
-                         solve_index_options)
+from .multiasset import (AssetPaths, BestOf, GeometricMean, IndexOption, MultiAssetDynamics, MultiAssetInputs, WeightedSum,
+                         WorstOf, simulate_asset_paths, solve_index_lsm, solve_index_options)
 from .localvol import (LocalVolDynamics, LocalVolInputs, LocalVolSurface, dupire_from, dupire_local_vol, get_local_vol,
                        refuse_other_methods, solve_localvol_payoffs)
 from .qmc import (BrownianBridge, Incremental, QuasiMonteCarlo, QuasiMonteCarloSolution, SobolConfig, solve_qmc)
@@ -77,6 +77,9 @@ def solve(*args, **kw):
                                   multilevel Monte Carlo on coupled Euler levels of steps·2^l steps: European vanillas and the
                                   path-dependent payoffs under a Monitoring, lognormal or Heston (no reference method)
         solve(prob::PricingProblem{<:VanillaOption{…,American,…}}, ::LSM)     least_squares_montecarlo.jl:99
+        solve(prob::PricingProblem{IndexOption{…, VanillaOption{…,American,…}}, MultiAssetInputs},
+              ::LSM(MultiAssetDynamics(), EulerMaruyama(), config, degree); exercise_every=m)
+                                  American / Bermudan baskets and rainbows: a regression basis in several variables
         solve(prob::PricingProblem{<:VanillaOption}, ::CoxRossRubinsteinMethod) cox_ross_rubinstein.jl:99
         solve(prob::BasketPricingProblem, ::CoxRossRubinsteinMethod)         basket.jl:35
         solve(prob::PricingProblem{<:VanillaOption} | ::BasketPricingProblem, ::CrankNicolsonMethod)

@@ -121,6 +121,17 @@ class hh_assets(C.Structure):
                 ("weights", C.c_double * HH_MAX_ASSETS), ("corr", C.c_double * (HH_MAX_ASSETS * HH_MAX_ASSETS))]
 
 
+HH_LSM_MAX_BASIS = 45
+HH_LSM_STATES_LOG_ASSETS = 0
+
+
+class hh_lsm_states(C.Structure):
+    """How a column's m state rows give the exercise value and the regressors of the several-variable induction (enum
+    hh_lsm_states_kind): log-states of assets, the index kind and weights, cp and strike."""
+    _fields_ = [("kind", C.c_int32), ("n_states", C.c_uint32), ("index_kind", C.c_int32), ("reserved", C.c_int32),
+                ("cp", C.c_double), ("strike", C.c_double), ("weights", C.c_double * HH_MAX_ASSETS)]
+
+
 class hh_localvol(C.Structure):
     """A local-volatility surface: σ at (times[j], x_lo + i·h), row-major [n_times][n_x], in host memory."""
     _fields_ = [("times", _dp), ("vols", _dp), ("x_lo", C.c_double), ("h", C.c_double),
@@ -242,6 +253,13 @@ SYMBOLS = [
                                           C.c_int32, _vp, C.c_int32, C.POINTER(hh_result)]),
     ("hh_mc_solve_path_assets", C.c_int, [_vp, C.POINTER(hh_model), C.POINTER(hh_assets), C.POINTER(hh_config), C.c_uint32,
                                           C.c_int32, C.POINTER(hh_path_payoff), C.c_uint32, C.POINTER(hh_result), _vp, _vp]),
+    ("hh_assets_rows_elems", C.c_size_t, [C.c_uint64, C.c_uint32, C.c_uint32, C.c_int32]),
+    ("hh_assets_path_rows", C.c_int, [_vp, C.POINTER(hh_model), C.POINTER(hh_assets), C.POINTER(hh_config), C.c_uint32, _vp,
+                                      C.c_int32, C.POINTER(hh_result)]),
+    ("hh_lsm_solve_states", C.c_int, [_vp, C.POINTER(hh_lsm_states), _vp, C.c_uint64, C.c_uint32, C.c_int32, C.c_double,
+                                      C.POINTER(hh_lsm_result), _vp, _vp, _vp]),
+    ("hh_lsm_solve_assets", C.c_int, [_vp, C.POINTER(hh_model), C.POINTER(hh_assets), C.POINTER(hh_config), C.c_uint32,
+                                      C.c_int32, C.c_double, C.POINTER(hh_lsm_result), _vp, _vp, _vp]),
     ("hh_mc_path_stats_lv", C.c_int, [_vp, C.POINTER(hh_model), C.POINTER(hh_localvol), C.POINTER(hh_config), C.c_uint32,
                                       C.c_int32, C.c_int32, _vp, C.c_int32, C.POINTER(hh_result)]),
     ("hh_mc_solve_path_lv", C.c_int, [_vp, C.POINTER(hh_model), C.POINTER(hh_localvol), C.POINTER(hh_config), C.c_uint32,

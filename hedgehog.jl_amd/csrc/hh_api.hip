@@ -12,6 +12,7 @@
 #include "hh_assets.h"
 #include "hh_kernels.h"
 #include "hh_localvol.h"
+#include "hh_lsm_basis.h"
 #include "hh_qe.h"
 
 #include "hh_ctx.h"
@@ -1592,7 +1593,8 @@ static int check_every(hh_ctx* ctx, const char* who, const char* word, uint32_t 
 
 // The checks of every entry point, then the statistics of every trajectory into ctx->path_stats (one timing slot) and,
 // where f.var_T, the variances at expiry into ctx->heston_var.  f.date_rows: monitor_every is the entry point's
-// exercise_every, and the rows of every such step go into ctx->lsm_grid ([n_steps/monitor_every + 1][n_total]) instead.
+// exercise_every, and the rows of every such step go into ctx->lsm_grid ([n_steps/monitor_every + 1][n_total]) instead —
+// of the several-asset walk its state rows, [n_steps/monitor_every + 1][n_assets][n_total].
 static int run_path_stats(hh_ctx* ctx, const PathFamily& f, const hh_model* m, const hh_config* c, uint32_t monitor_every,
                           int32_t include_start) {
   const char* who = f.who;
@@ -1666,7 +1668,9 @@ static int run_path_stats(hh_ctx* ctx, const PathFamily& f, const hh_model* m, c
   if (f.qe && (rc = check_qe(ctx, who, &m_c, c, f.qe))) return rc;
   const hh::PathStatsLayout at = f.layout(c);
   const bool rows = f.date_rows;
-  if (rows) rc = ensure(ctx, ctx->lsm_grid, hh_lsm_grid_elems(c->n_paths, c->n_steps / monitor_every, c->antithetic));
+  if (rows && f.assets)  // the several-asset walk's rows are its d log-states per date (hh_assets_path_rows)
+    rc = ensure(ctx, ctx->lsm_grid, hh_assets_rows_elems(c->n_paths, c->n_steps / monitor_every, f.assets->n_assets, c->antithetic));
+  else if (rows) rc = ensure(ctx, ctx->lsm_grid, hh_lsm_grid_elems(c->n_paths, c->n_steps / monitor_every, c->antithetic));
   else rc = ensure(ctx, ctx->path_stats, at.total);
   if (rc) return rc;
   double* const dst = rows ? ctx->lsm_grid.p : ctx->path_stats.p;
@@ -1694,7 +1698,8 @@ static int run_path_stats(hh_ctx* ctx, const PathFamily& f, const hh_model* m, c
                                          rows));
       break;
     case PathFamily::kAssets:
-      HH_HIP(ctx, hh::launch_assets_stats(*m, *c, *f.assets, seeds_dev, monitor_every, start, ctx->path_stats, ctx->stream));
+      if (rows) HH_HIP(ctx, hh::launch_assets_rows(*m, *c, *f.assets, seeds_dev, monitor_every, dst, ctx->stream));
+      else HH_HIP(ctx, hh::launch_assets_stats(*m, *c, *f.assets, seeds_dev, monitor_every, start, ctx->path_stats, ctx->stream));
       break;
     case PathFamily::kLocalVol:
       HH_HIP(ctx, hh::launch_localvol_stats(*m, *c, lv_args, seeds_dev, monitor_every, start, f.extremes == HH_EXTREMES_BRIDGE,
@@ -1913,6 +1918,154 @@ int hh_lsm_solve_path(hh_ctx* ctx, const hh_path_source* source, const hh_model*
     if ((rc = release_host_operands(ctx))) return rc;
     return copy_back_spot_grid(ctx, &g, spot_grid);
   });
+}
+
+// ---- state rows of the several-asset walk, and LSM on several state rows (hedgehog_mc.h, "American exercise on several
+// state rows"; kernels: hh_assets.hip, hh_lsm_multi.hip) ----
+
+size_t hh_assets_rows_elems(uint64_t n_paths, uint32_t n_dates, uint32_t n_assets, int32_t antithetic) {
+  return (size_t)(n_dates + 1) * n_assets * n_paths * (antithetic ? 2 : 1);
+}
+
+int hh_assets_path_rows(hh_ctx* ctx, const hh_model* m, const hh_assets* assets, const hh_config* c, uint32_t exercise_every,
+                        double* rows, int32_t rows_on_device, hh_result* out) {
+  if (!ctx) return HH_ERR_INVALID;
+  std::lock_guard<std::recursive_mutex> lock__(ctx->mu);
+  const PathFamily f = PathFamily("hh_assets_path_rows", 0, assets).rows();
+  if (!m || !c || !rows || f.missing) return fail(ctx, HH_ERR_INVALID, "%s: NULL argument", f.who);
+  const WallClock clock;
+  HH_HIP(ctx, hipSetDevice(ctx->device));
+  HH_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+  int rc = run_path_stats(ctx, f, m, c, exercise_every, 1);
+  if (rc) return rc;
+  HH_HIP(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+  const size_t bytes = hh_assets_rows_elems(c->n_paths, c->n_steps / exercise_every, assets->n_assets, c->antithetic) * sizeof(double);
+  HH_HIP(ctx, hipMemcpyAsync(rows, ctx->lsm_grid, bytes, rows_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost,
+                             ctx->stream));
+  HH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  if ((rc = release_host_operands(ctx))) return rc;
+  if (!out) return HH_OK;
+  std::memset(out, 0, sizeof(*out));
+  out->n_paths_done = c->n_paths;
+  return solve_times(ctx, clock, &out->kernel_ms, &out->total_ms);
+}
+
+// the descriptor and the basis of an induction on state rows, after lsm_check_scalars
+static int check_lsm_states(hh_ctx* ctx, const char* who, const hh_lsm_states* d, int32_t degree) {
+  if (d->kind != HH_LSM_STATES_LOG_ASSETS) return fail(ctx, HH_ERR_INVALID, "%s: unknown descriptor kind %d", who, d->kind);
+  if (d->n_states < 1u || d->n_states > (uint32_t)HH_MAX_ASSETS)
+    return fail(ctx, HH_ERR_INVALID, "%s: n_states (%u) must lie in 1 .. %d", who, d->n_states, HH_MAX_ASSETS);
+  if (d->index_kind < HH_INDEX_WEIGHTED_SUM || d->index_kind > HH_INDEX_WORST_OF)
+    return fail(ctx, HH_ERR_INVALID, "%s: unknown index_kind %d", who, d->index_kind);
+  if (!std::isfinite(d->strike)) return fail(ctx, HH_ERR_INVALID, "%s: the strike must be finite", who);
+  for (uint32_t i = 0; i < d->n_states; ++i)
+    if (!std::isfinite(d->weights[i])) return fail(ctx, HH_ERR_INVALID, "%s: asset %u: the weight must be finite", who, i);
+  if (hh::lsm_basis_count((int)d->n_states, degree) == 0)
+    return fail(ctx, HH_ERR_UNSUPPORTED, "%s: %u state rows at degree %d need more than %d basis functions", who, d->n_states,
+                degree, HH_LSM_MAX_BASIS);
+  return HH_OK;
+}
+
+// The induction on state rows already in device memory: launches, reduction and the copies back.  The caller recorded
+// ctx->ev0 and has checked everything.
+static int lsm_on_states(hh_ctx* ctx, const hh_lsm_states* d, const double* rows_dev, uint64_t ntot, uint32_t n_dates,
+                         int32_t degree, double date_discount, hh_lsm_result* out, int32_t* stop_time, double* stop_value,
+                         double* coef, const WallClock& clock) {
+  const hh::LsmMultiScratch at(ntot, n_dates);
+  const uint32_t ch = hh::lsm_chunks(ntot);
+  int rc;
+  if ((rc = ensure(ctx, ctx->lsm_val, (size_t)ntot))) return rc;
+  if ((rc = ensure(ctx, ctx->lsm_tau, (size_t)ntot))) return rc;
+  if ((rc = ensure(ctx, ctx->lsm_scratch, at.total))) return rc;
+  if ((rc = ensure(ctx, ctx->records, (size_t)ch * hh::kRecStride))) return rc;
+  double* counters = ctx->accum_host + HH_ACC_LEN;  // pinned, behind the accumulator (lsm_on_grid)
+  counters[0] = counters[1] = 0.0;
+  HH_HIP(ctx, hh::launch_lsm_multi(*d, rows_dev, ntot, n_dates, degree, date_discount, ctx->lsm_tau, ctx->lsm_val,
+                                   ctx->lsm_scratch, ctx->records, ctx->stream));
+  HH_HIP(ctx, hh::launch_reduce_records(ctx->records, ch, (double)ntot, ctx->accum, ctx->stream));
+  HH_HIP(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+  HH_HIP(ctx, hipMemcpyAsync(ctx->accum_host, ctx->accum, HH_ACC_LEN * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  HH_HIP(ctx, hipMemcpyAsync(counters, ctx->lsm_scratch + at.counters, 2 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  if (stop_time)
+    HH_HIP(ctx, hipMemcpyAsync(stop_time, ctx->lsm_tau, ntot * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+  if (stop_value)
+    HH_HIP(ctx, hipMemcpyAsync(stop_value, ctx->lsm_val, ntot * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  if (coef) {  // [date][kLsmMultiPad] on the device, [date][B] for the caller
+    const size_t B = (size_t)hh::lsm_basis_count((int)d->n_states, degree);
+    HH_HIP(ctx, hipMemcpy2DAsync(coef, B * sizeof(double), ctx->lsm_scratch + at.coef, hh::kLsmMultiPad * sizeof(double),
+                                 B * sizeof(double), n_dates, hipMemcpyDeviceToHost, ctx->stream));
+  }
+  HH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  if ((rc = hh_lsm_finalize(ctx->accum_host, out))) return finalize_failed(ctx, rc);
+  out->rows_regressed = (uint32_t)counters[0];
+  out->rows_skipped = (uint32_t)counters[1];
+  out->form = hh::kLsmFormPerDate;
+  return solve_times(ctx, clock, &out->kernel_ms, &out->total_ms);
+}
+
+// the induction's scalars in lsm_check_scalars' words: a model that carries cp alone, a config that carries the sizes
+static int check_lsm_states_scalars(hh_ctx* ctx, double cp, uint64_t n_paths, uint32_t n_dates, int32_t degree,
+                                    double date_discount) {
+  hh_model mm{};
+  mm.S0 = 1.0;
+  mm.T = 1.0;
+  mm.cp = cp;
+  hh_config g{};
+  g.n_paths = n_paths;
+  g.n_steps = n_dates;
+  return lsm_check_scalars(ctx, &mm, &g, degree, date_discount);
+}
+
+int hh_lsm_solve_states(hh_ctx* ctx, const hh_lsm_states* desc, const double* rows_dev, uint64_t n_total, uint32_t n_dates,
+                        int32_t degree, double date_discount, hh_lsm_result* out, int32_t* stop_time, double* stop_value,
+                        double* coef) {
+  if (!ctx) return HH_ERR_INVALID;
+  std::lock_guard<std::recursive_mutex> lock__(ctx->mu);
+  static const char who[] = "hh_lsm_solve_states";
+  if (!desc || !rows_dev || !out) return fail(ctx, HH_ERR_INVALID, "%s: NULL argument", who);
+  const WallClock clock;
+  int rc = check_lsm_states_scalars(ctx, desc->cp, n_total, n_dates, degree, date_discount);
+  if (rc) return rc;
+  if ((rc = check_lsm_states(ctx, who, desc, degree))) return rc;
+  HH_HIP(ctx, hipSetDevice(ctx->device));
+  HH_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+  return lsm_on_states(ctx, desc, rows_dev, n_total, n_dates, degree, date_discount, out, stop_time, stop_value, coef, clock);
+}
+
+int hh_lsm_solve_assets(hh_ctx* ctx, const hh_model* m, const hh_assets* assets, const hh_config* c, uint32_t exercise_every,
+                        int32_t degree, double date_discount, hh_lsm_result* out, int32_t* stop_time, double* stop_value,
+                        double* rows) {
+  if (!ctx) return HH_ERR_INVALID;
+  std::lock_guard<std::recursive_mutex> lock__(ctx->mu);
+  const PathFamily f = PathFamily("hh_lsm_solve_assets", 0, assets).rows();
+  if (!m || !c || !out || f.missing) return fail(ctx, HH_ERR_INVALID, "%s: NULL argument", f.who);
+  const WallClock clock;
+  // the schedule first, then the induction's scalars on its dates, then everything the walk's entry point checks
+  int rc = check_every(ctx, f.who, "exercise_every", exercise_every, c->n_steps);
+  if (rc) return rc;
+  const uint32_t n_dates = c->n_steps / exercise_every;
+  if ((rc = check_lsm_states_scalars(ctx, m->cp, c->n_paths, n_dates, degree, date_discount))) return rc;
+  hh_lsm_states d{};
+  d.kind = HH_LSM_STATES_LOG_ASSETS;
+  d.n_states = assets->n_assets;
+  d.index_kind = assets->index_kind;
+  d.cp = m->cp;
+  d.strike = m->strike;
+  for (uint32_t i = 0; i < assets->n_assets && i < (uint32_t)HH_MAX_ASSETS; ++i) d.weights[i] = assets->weights[i];
+  if ((rc = check_lsm_states(ctx, f.who, &d, degree))) return rc;
+  HH_HIP(ctx, hipSetDevice(ctx->device));
+  HH_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+  if ((rc = run_path_stats(ctx, f, m, c, exercise_every, 1))) return rc;
+  const uint64_t ntot = c->n_paths * (c->antithetic ? 2 : 1);
+  rc = lsm_on_states(ctx, &d, ctx->lsm_grid, ntot, n_dates, degree, date_discount, out, stop_time, stop_value, nullptr, clock);
+  if (rc) return rc;
+  if ((rc = release_host_operands(ctx))) return rc;
+  if (rows) {
+    HH_HIP(ctx, hipMemcpyAsync(rows, ctx->lsm_grid, hh_assets_rows_elems(c->n_paths, n_dates, assets->n_assets, c->antithetic) * sizeof(double),
+                               hipMemcpyDeviceToHost, ctx->stream));
+    HH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  }
+  return HH_OK;
 }
 
 // ---- multilevel Monte Carlo (hedgehog_mc.h, "Multilevel Monte Carlo"; kernels: hh_path.hip) ----

@@ -77,4 +77,48 @@ inline AssetArgs asset_args(const hh_assets& as, double r_drift, double T, uint3
   return a;
 }
 
+// ---- what the kernels share (hh_assets.hip: the statistics and the state rows; hh_lsm_multi.hip: the exercise value on a
+// stored row) — device code, seen by hipcc alone ----
+#if defined(__HIPCC__)
+}  // namespace hh
+#include "hh_path_stats.h"  // vmax, vmin
+namespace hh {
+namespace {
+
+// the pair (I, x) of the index on a date — what Running::first / next take as (S, log S)
+template <int D, int KIND>
+__device__ __forceinline__ void index_of(const AssetArgs& c, const double (&x)[D], double& I, double& xi) {
+  if constexpr (KIND == HH_INDEX_WEIGHTED_SUM) {
+    I = c.w[0] * exp(x[0]);
+#pragma unroll
+    for (int i = 1; i < D; ++i) I = fma(c.w[i], exp(x[i]), I);
+    xi = log(I);
+  } else if constexpr (KIND == HH_INDEX_GEOMETRIC) {
+    xi = c.w[0] * x[0];
+#pragma unroll
+    for (int i = 1; i < D; ++i) xi = fma(c.w[i], x[i], xi);
+    I = exp(xi);
+  } else {  // best-of, worst-of: log w_i is in the initial state
+    xi = x[0];
+#pragma unroll
+    for (int i = 1; i < D; ++i) xi = KIND == HH_INDEX_BEST_OF ? vmax(xi, x[i]) : vmin(xi, x[i]);
+    I = exp(xi);
+  }
+}
+
+// x_i += drift_i + Σ_{j<=i} A_ij·(±z_j), the sum as a chain of fma in j
+template <int D, bool MIRROR>
+__device__ __forceinline__ void step_assets(const AssetArgs& c, double (&x)[D], const double (&z)[2 * ((D + 1) / 2)]) {
+#pragma unroll
+  for (int i = 0; i < D; ++i) {
+    double acc = c.drift[i];
+#pragma unroll
+    for (int j = 0; j <= i; ++j) acc = fma(c.A[tri(i, j)], MIRROR ? -z[j] : z[j], acc);
+    x[i] = x[i] + acc;
+  }
+}
+
+}  // namespace
+#endif  // __HIPCC__
+
 }  // namespace hh

@@ -374,6 +374,17 @@ int launch_localvol_stats(const hh_model& m, const hh_config& c, const LocalVolA
 // The entry points have checked the assets (hh_assets.h: corr_defect, cholesky); the factor is formed again here.
 int launch_assets_stats(const hh_model& m, const hh_config& c, const hh_assets& assets, const uint64_t* seeds_dev,
                         uint32_t monitor_every, bool include_start, double* stats, hipStream_t s);
+// The state rows of that walk (assets_rows_kernel): the d log-states on every exercise_every-th step into
+// rows[n_steps/exercise_every + 1][d][n_total], row 0 = x0; the same draws, step and constants as launch_assets_stats.
+int launch_assets_rows(const hh_model& m, const hh_config& c, const hh_assets& assets, const uint64_t* seeds_dev,
+                       uint32_t exercise_every, double* rows, hipStream_t s);
+// LSM on several state rows per date (hh_lsm_multi.hip): the whole induction, one launch per date, on rows
+// [n_dates + 1][desc.n_states][ntot]; scratch: LsmMultiScratch(ntot, n_dates).total doubles (hh_layout.h), whose coef
+// region holds the fitted coefficients [date][kLsmMultiPad] afterwards; records: lsm_chunks(ntot) x kRecStride.
+int launch_lsm_multi(const hh_lsm_states& desc, const double* rows, uint64_t ntot, uint32_t n_dates, int degree,
+                     double date_discount, int32_t* tau, double* val, double* scratch, double* records, hipStream_t s);
+// the final Σ, Σ² kernel of the inductions: per-workgroup sums of exp(ln_disc·tau)·val into lsm_chunks(ntot) records
+int launch_lsm_final(const int32_t* tau, const double* val, uint64_t ntot, double ln_disc, double* records, hipStream_t s);
 // form: kLsmFormPersistent = the whole backward induction in ONE launch when the ensemble fits the
 // chip (else it falls back by itself), kLsmFormPerDate = one launch per exercise date.  *form_used
 // says which was enqueued; after a persistent launch the caller synchronises and reads the word at

@@ -74,6 +74,36 @@ struct LsmScratch {
   }
 };
 
+// ---- LSM on several state rows (hh_lsm_multi.hip) ---------------------------------------------------------------
+
+constexpr int kLsmMultiPad = 48;         // a padded basis: three tiles of 16 (HH_LSM_MAX_BASIS = 45 functions)
+constexpr int kLsmMultiStats = 1 + 2 * HH_MAX_ASSETS;  // n, Σv_i (μ_i), Σv_i² (isd_i) of a date
+constexpr int kLsmMultiTileDoubles = 6 * 256;  // a chunk's Gram record: the 6 tile products of the upper block triangle
+constexpr int kLsmMultiRowBlock = 8;     // dates whose Gram records are held at a time
+
+// offsets in doubles; the chunk rule is the one-variable induction's (lsm_q, lsm_nch)
+struct LsmMultiScratch {
+  size_t rec_stats, rowstat, rec_gram, G, recB, coef, have_fit, disc_pow, counters, total;
+  uint32_t rows, nch;
+  int q;
+  LsmMultiScratch(uint64_t ntot, uint32_t n_dates) : rows(n_dates + 1), nch(lsm_nch(ntot)), q(lsm_q(ntot)) {
+    const size_t r = rows, ch = nch;
+    LayoutCursor c;
+    rec_stats = c.take(r * ch * kLsmMultiStats);                        // [date][chunk][17]
+    rowstat = c.take(r * kLsmMultiStats);                               // [date][17]
+    rec_gram = c.take((size_t)kLsmMultiRowBlock * ch * kLsmMultiTileDoubles);  // [date of the block][chunk][6][256]
+    G = c.take(r * kLsmMultiPad * kLsmMultiPad);                        // [date][48][48]
+    recB = c.take(r * ch * kLsmMultiPad);                               // [date][chunk][48]
+    // zeroed together when an induction starts, [coef, total): the coefficients [date][48], the fit flags (an int32 per
+    // date), the discount table [date] and the counters (rows regressed, rows skipped)
+    coef = c.take(r * kLsmMultiPad);
+    have_fit = c.take((r + 1) / 2);
+    disc_pow = c.take(r);
+    counters = c.take(2);
+    total = c.at;
+  }
+};
+
 // ---- path statistics (hh_path.hip) ----------------------------------------------------------------------------
 
 // What path_stats_kernel leaves of every trajectory and path_payoff_kernel reads: one row per statistic (enum

@@ -1424,6 +1424,12 @@ int launch_lsm(const double* grid, uint64_t ntot, uint32_t n_steps, double strik
   return (int)hipGetLastError();
 }
 
+// the final kernel alone, for the induction on several state rows (hh_lsm_multi.hip)
+int launch_lsm_final(const int32_t* tau, const double* val, uint64_t ntot, double ln_disc, double* records, hipStream_t s) {
+  hipLaunchKernelGGL(lsm_final_kernel, dim3(lsm_chunks(ntot)), dim3(256), 0, s, tau, val, ntot, ln_disc, records);
+  return (int)hipGetLastError();
+}
+
 // device address of the word the persistent form sets when a workgroup gave up waiting
 const unsigned int* lsm_persistent_status(const double* scratch, const LsmScratch& at) {
   return reinterpret_cast<const unsigned int*>(scratch + at.sync);

@@ -15,7 +15,11 @@ Every other spot-path model of routes.py — Merton jumps on Euler paths, Heston
 is priced on the date rows of its own path kernel (`hh_lsm_solve_path`): LSM(dynamics, strategy, config, degree) with the
 route's own dynamics, inputs and strategy.  `exercise_every=m` exercises on every m-th simulation step (a Bermudan
 schedule of steps/m dates; m divides steps), there and on the Euler sources under path_state="spot".  Stopping times count
-EXERCISE DATES, date j lying at T·j·m/steps, and spot_paths holds those dates' rows alone."""
+EXERCISE DATES, date j lying at T·j·m/steps, and spot_paths holds those dates' rows alone.
+
+An American IndexOption on MultiAssetInputs under LSM(MultiAssetDynamics(), EulerMaruyama(), config, degree) is
+multiasset.solve_index_lsm's: the assets' state rows and a regression on all monomials of the standardised spots up to
+`degree` (`hh_lsm_solve_assets`); spot_paths is then the (dates + 1, assets, columns) array of simulate_asset_paths."""
 from __future__ import annotations
 
 import ctypes as C
@@ -176,9 +180,15 @@ def solve_lsm(prob: PricingProblem, method: LSM, spot_paths: bool = False,
     exercise_every: exercise on every m-th step — on the spot-path models of routes.py, and (m > 1) on the Euler sources
     under path_state="spot"; stopping_info[0] then counts exercise dates, not steps, and spot_paths holds steps/m + 1 rows."""
     payoff, m = prob.payoff, prob.market_inputs
+    mc = method.mc_method
+    if routes().own_lsm_route_of(m, mc) is not None:  # several assets: an index, state rows and a basis in several variables
+        from .multiasset import solve_index_lsm
+        if path_state is not None:
+            raise MethodError("path_state applies to the Euler path sources only: an index of several assets is regressed on "
+                              "its assets' spots")
+        return solve_index_lsm(prob, method, spot_paths, stopping_info, exercise_every)
     if not (isinstance(payoff, VanillaOption) and isinstance(payoff.exercise_style, American)):
         raise MethodError("solve(::PricingProblem, ::LSM) needs an American VanillaOption")
-    mc = method.mc_method
     state = None if path_state is None else _path_state_code(path_state)
     route = routes().lsm_route_of(m, mc)
     if route is not None:

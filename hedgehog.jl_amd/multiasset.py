@@ -9,15 +9,24 @@ The inner payoff — a European vanilla on the spot, an AsianOption, BarrierOpti
 read as written on the index.  One call of hh_mc_solve_path_assets simulates the assets and prices every payoff of one
 index; in a BasketPricingProblem each distinct index takes one such pass, all on the same seeds.  The solves carry no dual
 partials: Greeks come from FiniteDifference through AssetSpotLens, AssetVolLens and CorrelationLens (greeks.py).
+
+American and Bermudan exercise ("American exercise on several state rows"):
+    option = IndexOption(WorstOf(), VanillaOption(100.0, expiry, American(), Put(), Spot()))
+    solve(PricingProblem(option, inputs), LSM(MultiAssetDynamics(), EulerMaruyama(), config, degree), exercise_every=m)
+regresses the continuation value on all monomials of the d standardised spots of total degree <= degree — C(d + degree,
+degree) <= 45 functions — on every m-th step (hh_lsm_solve_assets).  simulate_asset_paths returns the rows.
 """
 from __future__ import annotations
 
+import ctypes as C
 import math
-from dataclasses import dataclass
+from dataclasses import dataclass, field
 from typing import Any
 
+import numpy as np
+
 from . import _ffi
-from .dates import to_ticks, yearfrac
+from .dates import MILLISECONDS_IN_YEAR_365, to_ticks, yearfrac
 from .domain import (PATH_PAYOFFS, American, AsianOption, ContinuousMonitoring, European, FlatRateCurve, GeometricAverage, RateCurve,
                      Spot, VanillaOption, df, zero_rate)
 from .dual import Dual, value_of
@@ -25,6 +34,8 @@ from .montecarlo import Antithetic, MethodError, MonteCarlo, path_monitoring, ro
 
 ROUTES = ("MonteCarlo(MultiAssetDynamics(), EulerMaruyama(), config) or MultiAssetAnalytic() on "
           "PricingProblem(IndexOption(index, payoff), MultiAssetInputs(…))")
+LSM_ROUTE = ("LSM(MultiAssetDynamics(), EulerMaruyama(), config, degree) on PricingProblem(IndexOption(index, VanillaOption(K, "
+             "expiry, American(), cp, Spot())), MultiAssetInputs(…))")
 
 
 class MultiAssetDynamics:
@@ -289,3 +300,108 @@ def solve_index_options(options, market_inputs, method, ensemble: bool = True):
         for i, sol in zip(idx, _solve_group(route, key, [options[i] for i in idx], market_inputs, method, ensemble)):
             sols[i] = sol
     return sols
+
+
+# ---- American exercise: state rows and the several-variable induction ---------------------------------------------------------
+
+def basis_count(d: int, degree: int) -> int:
+    """C(d + degree, degree): the monomials of d variables of total degree <= degree"""
+    return math.comb(d + degree, degree)
+
+
+def _require_rows_route(prob, mc, exercise_every, american: bool):
+    """every refusal of the state-row calls that needs no device, in the route's words; -> (route, index option, dates)"""
+    rt = routes()
+    route = rt.MULTIASSET
+    option, m = prob.payoff, prob.market_inputs
+    rt.admitted(route, [option], m, mc)
+    if not isinstance(option, IndexOption):
+        raise MethodError(f"a {type(option).__name__} names no index of the assets of MultiAssetInputs: wrap it in "
+                          "IndexOption(index, payoff)")
+    q = option.payoff
+    if not isinstance(q, VanillaOption):
+        raise MethodError(f"a path-dependent inner payoff ({type(q).__name__}) has no exercise decision to regress: " + LSM_ROUTE)
+    if isinstance(getattr(q, "monitoring", None), ContinuousMonitoring):
+        raise MethodError(route.no_continuous)
+    if not isinstance(q.underlying, Spot) or (american and not isinstance(q.exercise_style, American)):
+        raise MethodError("LSM on an index of several assets needs an American VanillaOption on Spot: " + LSM_ROUTE)
+    if mc.devices is not None:
+        raise MethodError(route.one_device)
+    flat = list(m.spots) + list(m.sigmas) + [t for row in m.correlation for t in row] + [zero_rate(m.rate, 0.0), q.strike]
+    flat += list(option.index.weights or ())
+    if any(isinstance(t, Dual) for t in flat):
+        raise MethodError(route.no_duals)
+    every = int(exercise_every)
+    steps = mc.config.steps
+    if every != exercise_every or every < 1 or steps % every:
+        raise MethodError(f"exercise_every ({exercise_every!r}) must be a whole number >= 1 that divides steps ({steps})")
+    index_weights(option.index, m.n_assets)
+    return route, option, steps // every
+
+
+def _rows_structs(option, m, mc):
+    """hh_model, hh_assets and hh_config of the walk to the option's expiry, on the seeds of mc.config in host memory"""
+    cfg = mc.config
+    q = option.payoff
+    model = _ffi.hh_model()
+    model.T = float(yearfrac(m.referenceDate, option.expiry))
+    model.r_drift = float(zero_rate(m.rate, 0.0))
+    model.discount = float(df(m.rate, option.expiry))
+    model.strike, model.cp = float(q.strike), q.call_put()
+    c = _ffi.hh_config()
+    c.dynamics, c.strategy, c.noise_mode = _ffi.HH_LOGNORMAL, _ffi.HH_EULER_MARUYAMA, _ffi.HH_NOISE_GENERATE
+    c.antithetic = int(isinstance(cfg.variance_reduction, Antithetic))
+    c.n_steps, c.n_paths = cfg.steps, cfg.trajectories
+    c.seeds, c.seeds_on_device, c.seeds_len = cfg.seeds.ctypes.data, 0, cfg.seeds.size
+    return model, pack_assets(option.index, m), c
+
+
+@dataclass(frozen=True)
+class AssetPaths:
+    """The spots of the assets' trajectories on every exercise_every-th step: spot[date][asset][column], row j at times[j],
+    date 0 the spots.  Antithetic: 2·trajectories columns, the mirror of trajectory i in column trajectories + i.  Under
+    BestOf and WorstOf the rows are w_i·S_i — the weight is folded into the state the walk carries."""
+    spot: Any
+    times: Any
+    result: Any = field(default=None, compare=False, repr=False)
+
+
+def simulate_asset_paths(prob, mc, exercise_every=1) -> AssetPaths:
+    """The assets' spots on the dates of solve(prob, LSM(mc, degree), exercise_every=…), on the same seeds, through
+    hh_assets_path_rows: the device returns log-states, exp is taken here.  Under BestOf and WorstOf the rows are w_i·S_i.
+    The inner payoff may be European or American: its expiry alone is read."""
+    route, option, n_dates = _require_rows_route(prob, mc, exercise_every, american=False)
+    model, assets, c = _rows_structs(option, prob.market_inputs, mc)
+    ntot = mc.config.trajectories * (2 if c.antithetic else 1)
+    rows = np.empty((n_dates + 1, prob.market_inputs.n_assets, ntot))
+    res = _ffi.hh_result()
+    ctx = _ffi.get_context(mc.device)
+    ctx.check(ctx.lib.hh_assets_path_rows(ctx.handle, C.byref(model), C.byref(assets), C.byref(c), int(exercise_every),
+                                          rows.ctypes.data, 0, C.byref(res)))
+    return AssetPaths(np.exp(rows), np.linspace(0.0, float(model.T), n_dates + 1), res)
+
+
+def solve_index_lsm(prob, method, spot_paths: bool = False, stopping_info: bool = True, exercise_every=1):
+    """An American (exercise_every > 1: Bermudan) IndexOption by Longstaff–Schwartz on the assets' state rows:
+    hh_lsm_solve_assets.  stopping_info[0] counts exercise dates; spot_paths: AssetPaths.spot of the same trajectories."""
+    from .lsm import LSMSolution
+    mc = method.mc_method
+    route, option, n_dates = _require_rows_route(prob, mc, exercise_every, american=True)
+    m = prob.market_inputs
+    B = basis_count(m.n_assets, method.degree)
+    if not 1 <= method.degree <= 8 or B > _ffi.HH_LSM_MAX_BASIS:
+        raise MethodError(f"LSM on {m.n_assets} assets at degree {method.degree} needs {B} basis functions: at most "
+                          f"{_ffi.HH_LSM_MAX_BASIS}, degree 1 … 8 ({LSM_ROUTE})")
+    model, assets, c = _rows_structs(option, m, mc)
+    ntot = mc.config.trajectories * (2 if c.antithetic else 1)
+    tau = np.empty(ntot, dtype=np.int32) if stopping_info else None
+    val = np.empty(ntot) if stopping_info else None
+    rows = np.empty((n_dates + 1, m.n_assets, ntot)) if spot_paths else None
+    date_discount = float(df(m.rate, m.referenceDate + (float(model.T) * int(exercise_every) / mc.config.steps) * MILLISECONDS_IN_YEAR_365))
+    res = _ffi.hh_lsm_result()
+    ctx = _ffi.get_context(mc.device)
+    ctx.check(ctx.lib.hh_lsm_solve_assets(ctx.handle, C.byref(model), C.byref(assets), C.byref(c), int(exercise_every), method.degree,
+                                          date_discount, C.byref(res), tau.ctypes.data if stopping_info else None,
+                                          val.ctypes.data if stopping_info else None, rows.ctypes.data if spot_paths else None))
+    return LSMSolution(prob, method, res.price, (tau, val) if stopping_info else None, np.exp(rows) if spot_paths else None,
+                       std_error=res.std_error, result=res)

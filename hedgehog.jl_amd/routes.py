@@ -69,6 +69,7 @@ class Route:
     law: bool = False                # `entry` samples the law at expiry: one European vanilla, no paths
     source: int = None               # enum hh_path_source_kind: the route's paths as date rows (hh_mc_path_grid, LSM on them)
     solve_all: Callable = None       # (payoffs, market_inputs, method, ensemble): a grouping of its own, for one payoff or many
+    own_lsm: bool = False            # an LSM on the route's own triple has an induction of its own (no date rows of one spot)
     # ---- what it refuses, and in which words ----
     early: tuple = ()                # of the four checks above, in the route's order; `admitted` elsewhere: with the structs
     no_replay: str = None
@@ -87,7 +88,7 @@ class Route:
 
     def takes_lsm(self, m, mc):
         """Is `mc` — the MonteCarlo method inside an LSM — this route's own triple?  Then LSM regresses on its date rows."""
-        if self.source is None or self.admits is None or not self.claims((), m, mc):
+        if (self.source is None and not self.own_lsm) or self.admits is None or not self.claims((), m, mc):
             return False
         D, M, S = self.admits
         return isinstance(mc.dynamics, D) and isinstance(m, M) and isinstance(mc.strategy, S)
@@ -145,7 +146,7 @@ MULTIASSET = Route(
     "multi-asset", is_multiasset,
     admits=(MultiAssetDynamics, MultiAssetInputs, EulerMaruyama),
     not_admitted="no multi-asset solve for {dyn} + {strat} on {m}: use " + ASSET_ROUTES,
-    entry="hh_mc_solve_path_assets", solve_all=solve_index_options,
+    entry="hh_mc_solve_path_assets", solve_all=solve_index_options, own_lsm=True,
     no_replay="multi-asset solves draw their own noise: no replay",
     one_device="multi-asset solves run on one device (MonteCarlo.devices is not supported)",
     no_duals="multi-asset solves carry no dual partials (ForwardAD): use FiniteDifference with AssetSpotLens, AssetVolLens or "
@@ -267,6 +268,11 @@ def lsm_route_of(market_inputs, mc) -> Route:
     for route in SPOT_PATHS:
         if route.takes_lsm(market_inputs, mc):
             return route
+
+
+def own_lsm_route_of(market_inputs, mc) -> Route:
+    """The route that prices an LSM on `mc` by an induction of its own (several assets: several state rows per date), or None"""
+    return MULTIASSET if MULTIASSET.takes_lsm(market_inputs, mc) else None
 
 
 def path_source(route, extras):

@@ -1001,7 +1001,8 @@ int hh_carr_madan_bates(hh_ctx* ctx, const hh_model* model, const hh_jump* jump,
  * discount not finite; everything else hh_mc_solve_path_ex rejects.  HH_ERR_UNSUPPORTED: dynamics other than
  * HH_LOGNORMAL, a strategy other than HH_EULER_MARUYAMA, REPLAY noise, n_partials > 0.
  * Not provided: barriers on single assets, payoffs that read more than one index (one call per index, on the same
- * seeds), dividends and quantos, stochastic volatility per asset, American exercise, continuous (bridge) monitoring,
+ * seeds), dividends and quantos, stochastic volatility per asset, American exercise through these two entry points (it is hh_lsm_solve_assets', further
+ * down), continuous (bridge) monitoring,
  * REPLAY noise, dual partials (bump the inputs: the solves share their seeds), accumulate, hh_mc_solve_multi and
  * multi-GPU forms, more than HH_MAX_ASSETS assets, a Julia binding.
  */
@@ -1379,7 +1380,8 @@ int hh_carr_madan_vg(hh_ctx* ctx, const hh_model* model, const hh_vg* vg, double
  * hh_lsm_solve_path checks exercise_every first, then the induction's scalars on its n_dates (in hh_lsm_solve_euler's
  * words), then everything the source's entry point checks; where several things are wrong the first of these is reported.
  * Not provided: sharded and multi-GPU forms, the log path state (the regression on log S is hh_lsm_solve_euler's, on
- * every step), variance rows for QE and Bates, the bridge form, the coupled and the several-asset kernels.
+ * every step), variance rows for QE and Bates, the bridge form, the coupled kernel (the several-asset walk has state rows of its own:
+ * "American exercise on several state rows").
  */
 enum hh_path_source_kind { HH_SOURCE_EULER = 0, HH_SOURCE_JUMP = 1, HH_SOURCE_QE = 2, HH_SOURCE_BATES = 3,
                            HH_SOURCE_LOCALVOL = 4, HH_SOURCE_VG = 5 };
@@ -1395,6 +1397,86 @@ int hh_mc_path_grid(hh_ctx* ctx, const hh_path_source* source, const hh_model* m
 int hh_lsm_solve_path(hh_ctx* ctx, const hh_path_source* source, const hh_model* model, const hh_config* cfg,
                       uint32_t exercise_every, int32_t degree, double date_discount, hh_lsm_result* out,
                       int32_t* stop_time, double* stop_value, double* spot_grid);
+
+/*
+ * American exercise on several state rows: the state rows of the several-asset walk, and Longstaff–Schwartz with a
+ * regression basis in several variables on them (kernels: assets_rows_kernel, hh_assets.hip; the induction,
+ * hh_lsm_multi.hip; the basis, csrc/hh_lsm_basis.h — a host program can include it).
+ *
+ * hh_assets_path_rows — the walk of hh_mc_path_stats_assets (the same draws, step and host-formed constants) with no
+ * statistics: on every exercise_every-th step the d = n_assets log-states x_i as the walk holds them, log w_i folded in
+ * under best-of and worst-of.  n_dates = n_steps / exercise_every.  rows (host, or device when rows_on_device) takes
+ * hh_assets_rows_elems(n_paths, n_dates, n_assets, antithetic) = (n_dates + 1)·d·n_total doubles,
+ *   rows[(date·d + asset)·n_total + column]      date-major, then asset-major, n_total = n_paths·(1 + antithetic) columns
+ *   date 0: x0_i in every column;  date j: the states after step j·exercise_every;  column n_paths + i: the mirror of i
+ * Log-states, not spots: the index of "Several correlated lognormal assets" formed on a stored row is the pair (I, x) the
+ * statistics kernel forms on that date, bit for bit, for every index kind — the rows do not depend on the kind beyond x0.
+ * The non-mirrored half of an antithetic grid equals the plain grid column for column.  out (nullable): n_paths_done and
+ * the times.  Timing: one slot.
+ *
+ * hh_lsm_solve_states — the backward induction on a DEVICE grid rows_dev[n_dates + 1][m][n_total] of m = desc->n_states
+ * state rows per date the caller supplies; the counterpart of hh_lsm_solve_grid.  desc says how a column's m states give
+ * the exercise value and the m regressors.  HH_LSM_STATES_LOG_ASSETS, the one kind: the states are log-states of assets,
+ *   exercise value  pay = cp·(I − strike), I the index of kind index_kind and weights[] on the m states (above)
+ *   regressors      v_i = exp(x_i), in asset order
+ * Per date t = n_dates − 1 down to 1, on the columns IN THE MONEY, pay > 0, alone (the one-variable rule; the others
+ * add exact zeros to every sum):
+ *   statistics   n, Σv_i, Σv_i²;  μ_i = Σv_i/n, var_i = Σv_i²/n − μ_i·μ_i, isd_i = 1/sqrt(var_i) if var_i > 0 else 1
+ *                (n = 0: the date is skipped, no fit);  z_i = (v_i − μ_i)·isd_i
+ *   basis        all monomials φ = Π z_i^{e_i} of total degree <= degree in GRADED LEXICOGRAPHIC order: by total degree,
+ *                within a degree the exponent tuples (e_0, …, e_{m−1}) in descending lexicographic order — m = 2, degree
+ *                2: 1, z_0, z_1, z_0², z_0·z_1, z_1².  B = C(m + degree, degree) <= HH_LSM_MAX_BASIS functions: m = 5 .. 8 at
+ *                degree <= 2, m = 4 at <= 3, m = 3 at <= 4, m = 2 and m = 1 at <= 8.  A value is
+ *                1·z_0 (e_0 times)·z_1 (e_1 times)·…, one rounded product after the other, by ONE function for the Gram
+ *                sums, the moment sums and the fitted value.
+ *   Gram sums    G_jk = Σ φ_j·φ_k          moment sums  b_j = Σ φ_j·y,  y = date_discount^(τ − t)·val
+ *   solve        G c = b by LDLᵀ without pivoting; a pivot not above 1e-13·G_cc is dropped, its coefficient 0
+ *   exercise     where pay > 0 and pay > c_0·φ_0 + fma(c_j, φ_j, ·) in basis order:  τ = t, val = pay
+ * from τ = n_dates, val = max(pay, 0) at expiry; price = mean(date_discount^τ·val), by hh_lsm_solve_grid's final kernel
+ * into hh_lsm_result (form = HH_LSM_FORM_PER_DATE: there is no other).  Every sum has a fixed tree (hh_lsm_multi.hip
+ * states it: chunks of 512·Q columns by hh_lsm_solve_grid's chunk rule, wave butterflies or the matrix instruction's
+ * batches of four columns, waves in order, chunks in order), no atomics: the same inputs give the same bits on every
+ * run.  stop_time (nullable, host, n_total) counts EXERCISE DATES — the grid's dates; stop_value (nullable, host,
+ * n_total); coef (nullable, host, n_dates·B): the fitted coefficients, coef[t·B + j] of date t, zeros where no fit ran
+ * (date 0, a date with no column in the money) and for a dropped pivot.
+ *
+ * hh_lsm_solve_assets — hh_assets_path_rows into the context, then hh_lsm_solve_states on them with
+ * {HH_LSM_STATES_LOG_ASSETS, n_assets, index_kind, cp and strike of the model, the assets' weights}.  date_discount is
+ * the discount over ONE EXERCISE PERIOD.  rows (nullable, host): the state rows.  exercise_every = n_steps leaves one
+ * date: the European price, date_discount times the mean payoff at expiry.
+ *
+ * All synchronous.  Errors, checked on the host before any launch, in hh_mc_path_stats_assets' and hh_lsm_solve_path's
+ * words wherever the check is the same; a refusal uses no timing slot.  HH_ERR_INVALID: a NULL ctx, model, assets, cfg,
+ * desc, rows / rows_dev or out (hh_assets_path_rows: rows); exercise_every = 0 or not a divisor of n_steps; n_dates >
+ * 65534; an unknown descriptor kind or index kind; n_states outside 1 .. HH_MAX_ASSETS; cp not ±1; strike or a weight
+ * not finite; degree outside 1 .. 8; date_discount not finite or <= 0; n_total = 0 or above 2^31 − 128; everything
+ * hh_mc_path_stats_assets rejects.  HH_ERR_UNSUPPORTED: C(m + degree, degree) > HH_LSM_MAX_BASIS; REPLAY noise,
+ * n_partials > 0, dynamics or a strategy that are not the walk's own.  hh_lsm_solve_assets checks exercise_every first,
+ * then the induction's scalars, then everything hh_assets_path_rows checks.
+ * Not provided: variance rows and a regression on (S, V) (a second descriptor kind on the same induction), a persistent
+ * or cooperative form, sharded and multi-GPU forms, REPLAY or Sobol' noise, dual partials, basis families other than
+ * monomials (sorted assets, the payoff as a regressor, Laguerre), more than HH_LSM_MAX_BASIS functions, barriers on
+ * single assets, a Julia binding.
+ */
+#define HH_LSM_MAX_BASIS 45
+enum hh_lsm_states_kind { HH_LSM_STATES_LOG_ASSETS = 0 };
+typedef struct hh_lsm_states {        /* 88 bytes */
+  int32_t kind;                       /* enum hh_lsm_states_kind */
+  uint32_t n_states;                  /* m, 1 .. HH_MAX_ASSETS */
+  int32_t index_kind;                 /* enum hh_index_kind */
+  int32_t reserved;
+  double cp, strike;
+  double weights[HH_MAX_ASSETS];
+} hh_lsm_states;
+size_t hh_assets_rows_elems(uint64_t n_paths, uint32_t n_dates, uint32_t n_assets, int32_t antithetic);
+int hh_assets_path_rows(hh_ctx* ctx, const hh_model* model, const hh_assets* assets, const hh_config* cfg,
+                        uint32_t exercise_every, double* rows, int32_t rows_on_device, hh_result* out);
+int hh_lsm_solve_states(hh_ctx* ctx, const hh_lsm_states* desc, const double* rows_dev, uint64_t n_total,
+                        uint32_t n_dates, int32_t degree, double date_discount, hh_lsm_result* out, int32_t* stop_time,
+                        double* stop_value, double* coef);
+int hh_lsm_solve_assets(hh_ctx* ctx, const hh_model* model, const hh_assets* assets, const hh_config* cfg,
+                        uint32_t exercise_every, int32_t degree, double date_discount, hh_lsm_result* out,
+                        int32_t* stop_time, double* stop_value, double* rows);
 
 /*
  * A SimulationConfig's seed vector in the device memory of ctx, uploaded once and kept — repeated solves on one
