@@ -16,7 +16,7 @@ from .dates import Date, DateTime, add_years, to_ticks, yearfrac
 from .dual import Dual, partials_of, value_of
 from .greeks import (AssetSpotLens, AssetVolLens, BatchGreekProblem, CorrelationLens, FDBackward, FDCentral, FDForward,
                      FiniteDifference,
-                     ForwardAD, GreekProblem, GreekResult, PropertyLens, SecondOrderGreekProblem, SpotLens,
+                     ForwardAD, GreekProblem, GreekResult, Pathwise, PropertyLens, SecondOrderGreekProblem, SpotLens,
                      VolLens,
                      ZeroRateSpineLens, optic, set)
 from .lsm import (LSM, EulerPaths, HestonExactPaths, LSMSolution, SpotPaths, simulate_euler_paths,
@@ -51,6 +51,8 @@ def solve(*args, **kw):
                                                   (Euler paths; barriers and lookbacks also ContinuousMonitoring())
         solve(gprob::GreekProblem, ::ForwardAD, method)                      greeks_problem.jl:249
         solve(gprob::GreekProblem, ::FiniteDifference, method)               greeks_problem.jl:318
+        solve(gprob::GreekProblem | ::BatchGreekProblem, ::Pathwise, ::MonteCarlo(…, EulerMaruyama(), …))
+                                  pathwise Greeks of Asian / lookback / vanilla payoffs, one pass (no reference method)
         solve(gprob::SecondOrderGreekProblem, ::FiniteDifference, method)    greeks_problem.jl:396
         solve(gprob::BatchGreekProblem, ::GreekMethod, method)               greeks_problem.jl:559
         solve(prob::BasketPricingProblem, method::MonteCarlo | ::CarrMadan)  basket.jl:35
@@ -128,9 +130,12 @@ def solve(*args, **kw):
             return _g.solve_greek_ad(args[0], args[2], solve)
         if isinstance(args[1], FiniteDifference):
             return _g.solve_greek_fd(args[0], args[1], args[2], solve)
+        if isinstance(args[1], Pathwise):
+            lens = args[0].wrt
+            return GreekResult(_g.solve_pathwise(args[0].pricing_problem, (lens,), args[2], solve, kw)[lens])
     if len(args) == 3 and isinstance(args[0], SecondOrderGreekProblem) and \
             isinstance(args[1], FiniteDifference):
         return _g.solve_second_order_fd(args[0], args[1], args[2], solve)
     if len(args) == 3 and isinstance(args[0], BatchGreekProblem):
-        return _g.solve_batch(args[0], args[1], args[2], solve)
+        return _g.solve_batch(args[0], args[1], args[2], solve, **(kw if isinstance(args[1], Pathwise) else {}))
     raise MethodError("no method matching solve(" + ", ".join(type(a).__name__ for a in args) + ")")

@@ -29,6 +29,10 @@ HH_STAT_CMAX_S, HH_STAT_CMIN_S = 5, 6
 HH_EXTREMES_MONITORED, HH_EXTREMES_BRIDGE = 0, 1
 HH_PATH_STATS = 5
 HH_PATH_STATS_BRIDGE = 7
+HH_TANGENT_K_MAX, HH_TANGENT_K_MIN, HH_TANGENT_SUM_KS = 5, 6, 7  # enum hh_tangent_date_row
+HH_TANGENT_DSUM_S, HH_TANGENT_DSUM_X, HH_TANGENT_DMAX_S, HH_TANGENT_DMIN_S, HH_TANGENT_DS_T = 0, 1, 2, 3, 4
+HH_BASIS_V0, HH_BASIS_KAPPA, HH_BASIS_THETA, HH_BASIS_SIGMA = 0, 1, 2, 3
+HH_TANGENT_DATE_ROWS, HH_TANGENT_ROWS_PER_SLOT, HH_TANGENT_MAX_BASIS = 3, 5, 4
 HH_MAX_PATH_PAYOFFS = 1024
 HH_JUMP_MAX_MEAN = 64.0
 HH_JUMP_MAX_COUNT = 255
@@ -220,6 +224,11 @@ SYMBOLS = [
                                       C.c_int32, C.POINTER(hh_result)]),
     ("hh_mc_solve_path_ex", C.c_int, [_vp, C.POINTER(hh_model), C.POINTER(hh_config), C.c_uint32, C.c_int32, C.c_int32,
                                       C.POINTER(hh_path_payoff), C.c_uint32, C.POINTER(hh_result), _vp, _vp]),
+    ("hh_path_tangent_rows", C.c_size_t, [C.c_uint32]),
+    ("hh_mc_path_stats_tangent", C.c_int, [_vp, C.POINTER(hh_model), C.POINTER(hh_config), C.c_uint32, C.c_int32, _vp,
+                                           C.c_int32, _vp, C.POINTER(hh_result)]),
+    ("hh_mc_solve_path_tangent", C.c_int, [_vp, C.POINTER(hh_model), C.POINTER(hh_config), C.c_uint32, C.c_int32,
+                                           C.POINTER(hh_path_payoff), C.c_uint32, C.POINTER(hh_result), _vp]),
     ("hh_mc_path_stats_coupled", C.c_int, [_vp, C.POINTER(hh_model), C.POINTER(hh_config), C.c_uint32, C.c_int32, _vp,
                                            C.c_int32, C.POINTER(hh_result)]),
     ("hh_mc_solve_path_coupled", C.c_int, [_vp, C.POINTER(hh_model), C.POINTER(hh_config), C.c_uint32, C.c_int32,

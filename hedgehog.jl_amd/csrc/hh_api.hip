@@ -1551,6 +1551,7 @@ struct PathFamily {
   double* var_T = nullptr;  // host, nullable: the variance at expiry of every member (the QE step)
   bool missing = false;     // a struct the kernel needs came as NULL: the entry point's "NULL argument"
   bool date_rows = false;   // the kernel's date-row sibling: the grid into ctx->lsm_grid, no statistics (hh_mc_path_grid)
+  bool tangent = false;     // path_tangent_kernel: the statistics with their tangents, cfg->n_partials directions (kEuler)
   // path_stats_kernel: lognormal or Heston dynamics by Euler–Maruyama
   PathFamily(const char* w, int32_t last, int32_t ext) : kernel(kEuler), who(w), last_kind(last), extremes(ext) {}
   // jump_stats_kernel, the Merton form: lognormal dynamics
@@ -1582,7 +1583,18 @@ struct PathFamily {
     f.date_rows = true;
     return f;
   }
+  // this member (kEuler) with the tangents of the statistics
+  PathFamily tangents() const {
+    PathFamily f = *this;
+    f.tangent = true;
+    return f;
+  }
 };
+
+// the rows of the tangent form: the carried slots are those of the call's seeds (hh_mc_solve's map)
+static hh::PathTangentLayout tangent_layout(const hh_model* m, const hh_config* c) {
+  return hh::PathTangentLayout(c->n_paths, c->antithetic != 0, hh::partial_map(*m, *c).n_active);
+}
 
 // the dates of a call lie on every `every`-th step (`word`: what the entry point calls it)
 static int check_every(hh_ctx* ctx, const char* who, const char* word, uint32_t every, uint32_t n_steps) {
@@ -1633,7 +1645,11 @@ static int run_path_stats(hh_ctx* ctx, const PathFamily& f, const hh_model* m, c
       break;
   }
   if (!ok) return fail(ctx, HH_ERR_UNSUPPORTED, "%s needs %s", who, needs);
-  if (c->noise_mode == HH_NOISE_REPLAY || c->n_partials != 0)
+  if (f.tangent && c->noise_mode == HH_NOISE_REPLAY)
+    return fail(ctx, HH_ERR_UNSUPPORTED, "%s: GENERATE noise: the pathwise tangent has no REPLAY form", who);
+  if (f.tangent && (c->n_partials == 0 || c->n_partials > HH_MAX_PARTIALS))
+    return fail(ctx, HH_ERR_INVALID, "%s: n_partials (%u) must be 1 .. %d", who, c->n_partials, HH_MAX_PARTIALS);
+  if (c->noise_mode == HH_NOISE_REPLAY || (c->n_partials != 0 && !f.tangent))
     return fail(ctx, HH_ERR_UNSUPPORTED, "%s: GENERATE noise, no dual partials", who);
   const bool coupled = f.kernel == PathFamily::kCoupled;
   if (coupled && c->antithetic)
@@ -1671,6 +1687,7 @@ static int run_path_stats(hh_ctx* ctx, const PathFamily& f, const hh_model* m, c
   if (rows && f.assets)  // the several-asset walk's rows are its d log-states per date (hh_assets_path_rows)
     rc = ensure(ctx, ctx->lsm_grid, hh_assets_rows_elems(c->n_paths, c->n_steps / monitor_every, f.assets->n_assets, c->antithetic));
   else if (rows) rc = ensure(ctx, ctx->lsm_grid, hh_lsm_grid_elems(c->n_paths, c->n_steps / monitor_every, c->antithetic));
+  else if (f.tangent) rc = ensure(ctx, ctx->path_stats, tangent_layout(m, c).total);
   else rc = ensure(ctx, ctx->path_stats, at.total);
   if (rc) return rc;
   double* const dst = rows ? ctx->lsm_grid.p : ctx->path_stats.p;
@@ -1684,6 +1701,10 @@ static int run_path_stats(hh_ctx* ctx, const PathFamily& f, const hh_model* m, c
   double* const var_dev = f.var_T ? ctx->heston_var.p : nullptr;
   switch (f.kernel) {
     case PathFamily::kEuler:
+      if (f.tangent) {
+        HH_HIP(ctx, hh::launch_path_tangent(*m, *c, seeds_dev, monitor_every, start, dst, ctx->stream));
+        break;
+      }
       HH_HIP(ctx, hh::launch_path_stats(*m, *c, seeds_dev, monitor_every, start, f.extremes == HH_EXTREMES_BRIDGE, dst,
                                         ctx->stream, rows));
       break;
@@ -1850,6 +1871,103 @@ int hh_mc_solve_path_ex(hh_ctx* ctx, const hh_model* m, const hh_config* c, uint
                         double* path_values, double* stats) {
   return solve_path_call(ctx, {"hh_mc_solve_path_ex", HH_PAYOFF_LOOKBACK_FIXED, extremes}, m, c, monitor_every,
                          include_start, payoffs, n_payoffs, out, path_values, stats);
+}
+
+// ---- pathwise derivatives (hedgehog_mc.h, "Pathwise derivatives of path-dependent payoffs") ----
+
+size_t hh_path_tangent_rows(uint32_t n_active) {
+  return (size_t)HH_PATH_STATS + HH_TANGENT_DATE_ROWS + (size_t)HH_TANGENT_ROWS_PER_SLOT * n_active;
+}
+
+int hh_mc_path_stats_tangent(hh_ctx* ctx, const hh_model* m, const hh_config* c, uint32_t monitor_every,
+                             int32_t include_start, double* rows, int32_t rows_on_device, int32_t* basis_out,
+                             hh_result* out) {
+  if (!ctx) return HH_ERR_INVALID;
+  std::lock_guard<std::recursive_mutex> lock__(ctx->mu);
+  const PathFamily f = PathFamily("hh_mc_path_stats_tangent", 0, HH_EXTREMES_MONITORED).tangents();
+  if (!m || !c || !rows) return fail(ctx, HH_ERR_INVALID, "%s: NULL argument", f.who);
+  const WallClock clock;
+  HH_HIP(ctx, hipSetDevice(ctx->device));
+  HH_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+  int rc = run_path_stats(ctx, f, m, c, monitor_every, include_start);
+  if (rc) return rc;
+  HH_HIP(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+  const hh::PartialMap pm = hh::partial_map(*m, *c);
+  const hh::PathTangentLayout at = tangent_layout(m, c);
+  HH_HIP(ctx, hipMemcpyAsync(rows, ctx->path_stats, at.total * sizeof(double),
+                             rows_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, ctx->stream));
+  HH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  if ((rc = release_host_operands(ctx))) return rc;
+  if (basis_out)
+    for (int j = 0; j < hh::kMaxBasis; ++j) basis_out[j] = j < pm.n_active ? pm.basis[j] : -1;
+  if (!out) return HH_OK;
+  std::memset(out, 0, sizeof(*out));
+  out->n_paths_done = c->n_paths;
+  return solve_times(ctx, clock, &out->kernel_ms, &out->total_ms);
+}
+
+int hh_mc_solve_path_tangent(hh_ctx* ctx, const hh_model* m, const hh_config* c, uint32_t monitor_every,
+                             int32_t include_start, const hh_path_payoff* payoffs, uint32_t n_payoffs, hh_result* out,
+                             double* rows) {
+  if (!ctx) return HH_ERR_INVALID;
+  std::lock_guard<std::recursive_mutex> lock__(ctx->mu);
+  const PathFamily f = PathFamily("hh_mc_solve_path_tangent", HH_PAYOFF_LOOKBACK_FIXED, HH_EXTREMES_MONITORED).tangents();
+  const char* who = f.who;
+  if (!m || !c || !payoffs || !out) return fail(ctx, HH_ERR_INVALID, "%s: NULL argument", who);
+  int rc = check_path_payoffs(ctx, f, payoffs, n_payoffs);
+  if (rc) return rc;
+  for (uint32_t k = 0; k < n_payoffs; ++k)
+    if (payoffs[k].kind == HH_PAYOFF_BARRIER || payoffs[k].kind == HH_PAYOFF_DIGITAL_CASH ||
+        payoffs[k].kind == HH_PAYOFF_DIGITAL_ASSET)
+      return fail(ctx, HH_ERR_UNSUPPORTED,
+                  "%s: payoff %u (kind %d) is discontinuous: its pathwise derivative omits the jump term — use "
+                  "FiniteDifference", who, k, payoffs[k].kind);
+  const WallClock clock;
+  HH_HIP(ctx, hipSetDevice(ctx->device));
+  HH_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+  if ((rc = run_path_stats(ctx, f, m, c, monitor_every, include_start))) return rc;
+
+  const hh::PartialMap pm = hh::partial_map(*m, *c);
+  const hh::PathTangentLayout at = tangent_layout(m, c);
+  hh::PathTangentArgs b{};
+  b.rows = ctx->path_stats;
+  b.n_paths = c->n_paths;
+  b.n_chunks = hh::basket_chunks(c->n_paths);
+  b.antithetic = c->antithetic;
+  const uint32_t n_dates = c->n_steps / monitor_every;  // the dates after the start: steps every, 2·every, …, n_steps
+  b.n_mon = (double)(n_dates + (include_start ? 1u : 0u));
+  b.sum_k = (double)monitor_every * (0.5 * (double)n_dates * ((double)n_dates + 1.0));
+  b.n_steps = (double)c->n_steps;
+  b.dt = m->T / (double)c->n_steps;
+  b.n_partials = (int)c->n_partials;
+  b.n_active = pm.n_active;
+  for (uint32_t k = 0; k < c->n_partials; ++k) {
+    for (int j = 0; j < pm.n_active; ++j) b.w[k][j] = pm.w[k][j];
+    b.xd0[k] = m->dS0 ? m->dS0[k] / m->S0 : 0.0;
+    b.dr[k] = m->dr_drift ? m->dr_drift[k] : 0.0;
+    b.dK[k] = pm.dK[k];
+  }
+  if ((rc = stage_host(ctx, ctx->path_payoffs, (size_t)n_payoffs, payoffs, (size_t)n_payoffs, &b.payoffs))) return rc;
+  const size_t n_acc = (size_t)n_payoffs * HH_ACC_LEN;
+  if ((rc = ensure(ctx, ctx->basket_records, (size_t)n_payoffs * b.n_chunks * hh::kRecStride))) return rc;
+  if ((rc = ensure(ctx, ctx->basket_accum, n_acc))) return rc;
+  b.records = ctx->basket_records;
+  if ((rc = begin_timing(ctx))) return rc;
+  HH_HIP(ctx, hh::launch_path_payoff_tangent(b, n_payoffs, ctx->stream));
+  HH_HIP(ctx, hh::launch_reduce_records(ctx->basket_records, b.n_chunks, (double)c->n_paths, ctx->basket_accum,
+                                        ctx->stream, n_payoffs));
+  if ((rc = end_timing(ctx))) return rc;
+  HH_HIP(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+  std::vector<double> host(n_acc);
+  HH_HIP(ctx, hipMemcpyAsync(host.data(), ctx->basket_accum, n_acc * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  if (rows)
+    HH_HIP(ctx, hipMemcpyAsync(rows, ctx->path_stats, at.total * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  HH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  if ((rc = release_host_operands(ctx))) return rc;
+  double kernel_ms, total_ms;
+  if ((rc = solve_times(ctx, clock, &kernel_ms, &total_ms))) return rc;
+  rc = finalize_results(m, 0, c, host.data(), n_payoffs, kernel_ms, total_ms, out);
+  return rc ? fail(ctx, rc, "finalize failed: the accumulator holds no trajectories") : HH_OK;
 }
 
 // ---- date rows of the family, and LSM on them (hedgehog_mc.h, "Date rows of the log-spot path family") ----

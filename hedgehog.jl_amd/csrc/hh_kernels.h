@@ -312,6 +312,36 @@ struct PathPayoffArgs {
   int extremes;                   // enum hh_path_extremes: which rows a payoff's MAX / MIN are
 };
 int launch_path_payoffs(const PathPayoffArgs& b, uint32_t n_payoffs, hipStream_t s);
+// Pathwise derivatives of the path payoffs (hh_path.hip; include/hedgehog_mc.h, "Pathwise derivatives of path-dependent
+// payoffs").  How c.n_partials directions split into carried basis slots and closed-form passive parts (hh_mc_solve's
+// map), and the argument block with a unit seed on every carried parameter, as hh_mc_solve forms it (P = n_active >= 1).
+PartialMap partial_map(const hh_model& m, const hh_config& c);
+template <int P>
+SimArgs<P> make_basis_args(const hh_model& m, const hh_config& c, const DevicePtrs& p);
+// launch_path_stats' monitored trajectories with the tangents of partial_map(m, c)'s carried slots: PathTangentLayout(
+// c.n_paths, c.antithetic, n_active) into `rows`
+int launch_path_tangent(const hh_model& m, const hh_config& c, const uint64_t* seeds_dev, uint32_t monitor_every,
+                        bool include_start, double* rows, hipStream_t s);
+// … and the payoffs with their derivatives on them: one record per payoff and chunk — Σp, Σp² as launch_path_payoffs
+// leaves them, and Σ∂p_k, assembled, in slots HH_ACC_DSUM + k
+struct PathTangentArgs {
+  const double* rows;             // PathTangentLayout(n_paths, antithetic, n_active)
+  const hh_path_payoff* payoffs;  // device, [n_payoffs]
+  double* records;                // [n_payoffs][n_chunks][kRecStride]
+  double n_mon;                   // monitoring dates of a trajectory
+  double sum_k;                   // Σ k_j over them
+  double n_steps;                 // the last date's step index
+  double dt;                      // as make_args forms it
+  uint64_t n_paths;
+  uint32_t n_chunks;              // basket_chunks(n_paths)
+  int antithetic;
+  int n_partials, n_active;
+  double w[HH_MAX_PARTIALS][kMaxBasis];  // seed of direction k on the parameter of slot b
+  double xd0[HH_MAX_PARTIALS];           // dS0_k / S0
+  double dr[HH_MAX_PARTIALS];            // drift-rate seed of direction k
+  double dK[HH_MAX_PARTIALS];            // strike seed of direction k
+};
+int launch_path_payoff_tangent(const PathTangentArgs& b, uint32_t n_payoffs, hipStream_t s);
 // Multilevel Monte Carlo (hh_path.hip; include/hedgehog_mc.h, "Multilevel Monte Carlo").  launch_path_stats' monitored,
 // non-antithetic trajectories (c.n_steps even: the FINE grid) in columns [0, n_paths) and, in [n_paths, 2·n_paths), those
 // of c.n_steps/2 steps on the summed increments; monitor_every even, counted in fine steps.  PathStatsLayout(n_paths, true).

@@ -587,6 +587,17 @@ SimArgs<0> make_args0(const hh_model& m, const hh_config& c, const DevicePtrs& p
   return make_args<0>(m, c0, p, classify_partials(m, c0));
 }
 
+PartialMap partial_map(const hh_model& m, const hh_config& c) { return classify_partials(m, c); }
+
+template <int P>
+SimArgs<P> make_basis_args(const hh_model& m, const hh_config& c, const DevicePtrs& p) {
+  return make_args<P>(m, c, p, classify_partials(m, c));
+}
+template SimArgs<1> make_basis_args<1>(const hh_model&, const hh_config&, const DevicePtrs&);
+template SimArgs<2> make_basis_args<2>(const hh_model&, const hh_config&, const DevicePtrs&);
+template SimArgs<3> make_basis_args<3>(const hh_model&, const hh_config&, const DevicePtrs&);
+template SimArgs<4> make_basis_args<4>(const hh_model&, const hh_config&, const DevicePtrs&);
+
 template <class M, int P, bool REPLAY, bool ANTI>
 static int launch_euler_t(const SimArgs<P>& a, hipStream_t s) {
   hipLaunchKernelGGL((euler_kernel<M, P, REPLAY, ANTI>), dim3(a.n_tiles), dim3(kTile), 0, s, a);

@@ -117,6 +117,23 @@ struct PathStatsLayout {
   constexpr size_t row(int stat) const { return (size_t)stat * n_total; }
 };
 
+// What path_tangent_kernel leaves of every trajectory and path_payoff_tangent_kernel reads (include/hedgehog_mc.h,
+// "Pathwise derivatives of path-dependent payoffs"): the five value rows of PathStatsLayout, the three date rows, then
+// five tangent rows per carried basis slot — rows[row][column], the same columns.  Offsets in doubles.
+struct PathTangentLayout {
+  size_t n_total, total;
+  int n_active;
+  constexpr PathTangentLayout(uint64_t n_paths, bool antithetic, int n_active_)
+      : n_total((size_t)n_paths * (antithetic ? 2 : 1)),
+        total((size_t)(HH_PATH_STATS + HH_TANGENT_DATE_ROWS + HH_TANGENT_ROWS_PER_SLOT * n_active_) * n_total),
+        n_active(n_active_) {}
+  constexpr size_t row(int r) const { return (size_t)r * n_total; }
+  // tangent row `which` (enum hh_path_tangent_row) of carried slot b
+  constexpr size_t slot_row(int b, int which) const {
+    return (size_t)(HH_PATH_STATS + HH_TANGENT_DATE_ROWS + HH_TANGENT_ROWS_PER_SLOT * b + which) * n_total;
+  }
+};
+
 // ---- Broadie–Kaya (hh_bk.hip) ----------------------------------------------------------------------------------
 
 // Columns of cached series terms.  A lane's column belongs to a workgroup SLOT that a workgroup of the

@@ -11,6 +11,9 @@
 //
 // The 40 bytes per trajectory that go through memory between the two are about 1 % of the simulation's time at
 // 252 steps; in exchange one simulation serves every payoff of a call and the caller can have the statistics.
+// Their pathwise-derivative siblings (include/hedgehog_mc.h, "Pathwise derivatives of path-dependent payoffs"; DESIGN
+// §5.21): path_tangent_kernel walks the same trajectories on dual states and keeps the tangent of every statistic along
+// the carried basis slots, path_payoff_tangent_kernel evaluates the Lipschitz payoffs and their derivatives on them.
 #include "hh_path_stats.h"  // Monitor: the five statistics and their dates, shared by the family; Extremes
 #include "hh_sim.h"
 
@@ -90,6 +93,50 @@ __global__ __launch_bounds__(256) void path_stats_kernel(const SimArgs<0> a, con
     e.store(stats, at, i);
     if constexpr (ANTI) ea.store(stats, at, a.n_paths + i);
   }
+}
+
+// path_stats_kernel's monitored (non-bridge) walk, statement for statement, on dual states: M = GbmModel<P> or
+// HestonModel<P, SPLIT> propagates the tangents along the P carried basis slots of `a` (make_basis_args: a unit seed on
+// each carried parameter) through its fused per-step map, and TangentMonitor keeps the statistics with their tangents.
+// The draws, the mirror on −dW and the Philox pairing of scalar noise are that kernel's: rows 0-4 are its rows bit for
+// bit.  P = 0: no carried slot — the eight value and date rows alone.  PathTangentLayout(n_paths, ANTI, P).  No LDS.
+template <class M, int P, bool ANTI>
+__global__ __launch_bounds__(256) void path_tangent_kernel(const SimArgs<P> a, const double S0,
+                                                           const uint32_t monitor_every, const int include_start,
+                                                           double* __restrict__ rows) {
+  using State = typename M::State;
+  constexpr int NC = M::NCOMP;
+  const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= a.n_paths) return;
+  const PathTangentLayout at(a.n_paths, ANTI, P);
+  const uint32_t n_steps = a.n_steps;
+  State st, sa;
+  M::init(st, a);
+  if constexpr (ANTI) M::init(sa, a);
+  TangentMonitor<P, ANTI> mon(monitor_every, include_start);
+  mon.start(S0, a.x0.v);
+  const uint64_t key = a.seeds[i];  // montecarlo.jl:331
+  auto advance = [&](double d1, double d2) {
+    M::step(st, a, d1, d2);
+    if constexpr (ANTI) M::step(sa, a, -d1, -d2);
+    mon.date(st.x, sa.x);
+  };
+  if constexpr (NC == 2) {
+    for (uint32_t s = 0; s < n_steps; ++s) {
+      double d1, d2;
+      euler_pair_increments(key, s, a, d1, d2);
+      advance(d1, d2);
+    }
+  } else {
+    // scalar noise: one Philox block feeds two consecutive steps
+    for (uint32_t s = 0; s < n_steps; s += 2) {
+      double z1, z2;
+      euler_scalar_normals(key, s >> 1, z1, z2);
+      advance(a.sqrt_dt * z1, 0.0);
+      if (s + 1 < n_steps) advance(a.sqrt_dt * z2, 0.0);
+    }
+  }
+  mon.store(rows, at, i, a.n_paths);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -182,6 +229,191 @@ __global__ __launch_bounds__(256) void path_payoff_kernel(const PathPayoffArgs b
     if (k0 + g >= n_payoffs) break;  // uniform over the workgroup
     if (g) __syncthreads();          // the reduction's LDS staging is reused
     block_reduce_store<2, 4, 0>(acc[g], b.records + ((size_t)(k0 + g) * b.n_chunks + chunk) * kRecStride);
+  }
+}
+
+// ------------------------------------------------------------------------------------------
+// payoffs and their pathwise derivatives on the tangent rows
+// ------------------------------------------------------------------------------------------
+
+// What a member's payoff derivative is made of.  Every rule of the header's table is linear in the tangents of the five
+// statistics and in the strike seed:  ∂p_k = Σ_s c[s]·dStat_s[k] − cK·dK_k  (s: enum hh_path_tangent_row), and the
+// tangent of a statistic is  Σ_b w[k][b]·(row s of slot b) + xd0_k·A_s + (dr_k·dt)·B_s  with the passive factors A_s, B_s
+// of the header.  So per member and payoff seven numbers hold every direction:
+//   basis[b] = Σ_s c[s]·(row s of slot b),   pa = Σ_s c[s]·A_s,   pb = Σ_s c[s]·B_s,   pk = cK
+// and they are linear too: their sums over the trajectories are assembled into the directions once per record.
+constexpr int kTanSums = kMaxBasis + 3;  // basis[0..3], pa, pb, pk
+
+struct MemberRows {
+  double t[HH_PATH_STATS];  // the five statistics
+  double k_max, k_min, sum_ks;
+  double d[kMaxBasis][HH_TANGENT_ROWS_PER_SLOT];
+};
+
+__device__ __forceinline__ void load_member(const PathTangentArgs& b, const PathTangentLayout& at, uint64_t col,
+                                            MemberRows& r) {
+#pragma unroll
+  for (int s = 0; s < HH_PATH_STATS; ++s) r.t[s] = b.rows[at.row(s) + col];
+  r.k_max = b.rows[at.row(HH_TANGENT_K_MAX) + col];
+  r.k_min = b.rows[at.row(HH_TANGENT_K_MIN) + col];
+  r.sum_ks = b.rows[at.row(HH_TANGENT_SUM_KS) + col];
+#pragma unroll
+  for (int j = 0; j < kMaxBasis; ++j)
+#pragma unroll
+    for (int s = 0; s < HH_TANGENT_ROWS_PER_SLOT; ++s)
+      r.d[j][s] = j < b.n_active ? b.rows[at.slot_row(j, s) + col] : 0.0;  // uniform
+}
+
+// p: path_payoff_of's value, itm = p > 0 (every admitted kind's own comparison).  q is uniform: scalar branches.
+__device__ __forceinline__ void payoff_tangent_of(const hh_path_payoff& q, const MemberRows& r, const PathTangentArgs& b,
+                                                  double& p, double (&out)[kTanSums]) {
+  p = path_payoff_of(q, r.t, b.n_mon);
+  const double itm = p > 0.0 ? 1.0 : 0.0;
+  double c[HH_TANGENT_ROWS_PER_SLOT] = {0.0, 0.0, 0.0, 0.0, 0.0}, cK = 0.0;
+  switch (q.kind) {
+    case HH_PAYOFF_ASIAN_ARITH:
+      c[HH_TANGENT_DSUM_S] = itm * q.cp / b.n_mon;
+      cK = itm * q.cp;
+      break;
+    case HH_PAYOFF_ASIAN_GEOM:
+      c[HH_TANGENT_DSUM_X] = itm * q.cp * exp(r.t[HH_STAT_SUM_X] / b.n_mon) / b.n_mon;
+      cK = itm * q.cp;
+      break;
+    case HH_PAYOFF_LOOKBACK_FLOAT:
+      if (q.cp > 0.0) {
+        c[HH_TANGENT_DS_T] = 1.0;
+        c[HH_TANGENT_DMIN_S] = -1.0;
+      } else {
+        c[HH_TANGENT_DMAX_S] = 1.0;
+        c[HH_TANGENT_DS_T] = -1.0;
+      }
+      break;
+    case HH_PAYOFF_LOOKBACK_FIXED:
+      if (q.cp > 0.0) {
+        c[HH_TANGENT_DMAX_S] = itm;
+        cK = itm;
+      } else {
+        c[HH_TANGENT_DMIN_S] = -itm;
+        cK = -itm;
+      }
+      break;
+    default:  // HH_PAYOFF_VANILLA (the entry point admits no other kind)
+      c[HH_TANGENT_DS_T] = itm * q.cp;
+      cK = itm * q.cp;
+      break;
+  }
+  const double A[HH_TANGENT_ROWS_PER_SLOT] = {r.t[HH_STAT_SUM_S], b.n_mon, r.t[HH_STAT_MAX_S], r.t[HH_STAT_MIN_S],
+                                              r.t[HH_STAT_S_T]};
+  const double B[HH_TANGENT_ROWS_PER_SLOT] = {r.sum_ks, b.sum_k, r.t[HH_STAT_MAX_S] * r.k_max,
+                                              r.t[HH_STAT_MIN_S] * r.k_min, r.t[HH_STAT_S_T] * b.n_steps};
+#pragma unroll
+  for (int j = 0; j < kMaxBasis; ++j) {
+    double v = 0.0;
+#pragma unroll
+    for (int s = 0; s < HH_TANGENT_ROWS_PER_SLOT; ++s) v = fma(c[s], r.d[j][s], v);
+    out[j] = v;
+  }
+  double pa = 0.0, pb = 0.0;
+#pragma unroll
+  for (int s = 0; s < HH_TANGENT_ROWS_PER_SLOT; ++s) {
+    pa = fma(c[s], A[s], pa);
+    pb = fma(c[s], B[s], pb);
+  }
+  out[kMaxBasis] = pa;
+  out[kMaxBasis + 1] = pb;
+  out[kMaxBasis + 2] = cK;
+}
+
+// block_reduce_store<2, 4, 0>'s adds in its order for Σp, Σp² — the record's first two slots are path_payoff_kernel's
+// bit for bit — and the same tree for the seven tangent sums, which thread 0 assembles into the n_partials directions:
+// slot HH_ACC_DSUM + k = Σ_b w[k][b]·Σbasis[b] + xd0_k·Σpa + (dr_k·dt)·Σpb − dK_k·Σpk.
+__device__ __forceinline__ void tangent_reduce_store(double (&acc)[2 + kTanSums], const PathTangentArgs& b,
+                                                     double* __restrict__ rec) {
+  constexpr int N = 2 + kTanSums;
+#pragma unroll
+  for (int i = 0; i < N; ++i) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) acc[i] += __shfl_down(acc[i], off, 64);
+  }
+  __shared__ double sm[4][N];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (lane == 0) {
+#pragma unroll
+    for (int i = 0; i < N; ++i) sm[wave][i] = acc[i];
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double t[N];
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+      t[i] = sm[0][i];
+#pragma unroll
+      for (int w = 1; w < 4; ++w) t[i] += sm[w][i];
+    }
+#pragma unroll
+    for (int i = 0; i < kRecStride; ++i) rec[i] = 0.0;
+    rec[HH_ACC_SUM] = t[0];
+    rec[HH_ACC_SUMSQ] = t[1];
+    for (int k = 0; k < b.n_partials; ++k) {
+      double d = 0.0;
+#pragma unroll
+      for (int j = 0; j < kMaxBasis; ++j) d = fma(b.w[k][j], t[2 + j], d);
+      d = fma(b.xd0[k], t[2 + kMaxBasis], d);
+      d = fma(b.dr[k] * b.dt, t[2 + kMaxBasis + 1], d);
+      d = fma(-b.dK[k], t[2 + kMaxBasis + 2], d);
+      rec[HH_ACC_DSUM + k] = d;
+    }
+  }
+}
+
+// path_payoff_kernel's block -> (chunk, payoff group) map, payoffs per load and lane order, on path_tangent_kernel's
+// rows.  Each payoff keeps its own accumulators and record: its price sums are hh_mc_solve_path's bit for bit, whatever
+// else is in the call.  Antithetic: the pair average of the payoff and of each of its seven tangent numbers.
+__global__ __launch_bounds__(256) void path_payoff_tangent_kernel(const PathTangentArgs b, const uint32_t n_payoffs) {
+  const uint32_t per_xcd = (b.n_chunks + 7u) / 8u;
+  const uint32_t xcd = blockIdx.x & 7u, idx = blockIdx.x >> 3;
+  const uint32_t grp = idx / per_xcd, chunk = (idx % per_xcd) * 8u + xcd;
+  if (chunk >= b.n_chunks) return;  // padding of the last group of eight
+  const uint32_t k0 = grp * kPathKB;
+  hh_path_payoff q[kPathKB];
+#pragma unroll
+  for (int g = 0; g < kPathKB; ++g) q[g] = b.payoffs[min(k0 + g, n_payoffs - 1)];
+  const bool anti = b.antithetic != 0;
+  const PathTangentLayout at(b.n_paths, anti, b.n_active);
+  double acc[kPathKB][2 + kTanSums];
+#pragma unroll
+  for (int g = 0; g < kPathKB; ++g)
+#pragma unroll
+    for (int s = 0; s < 2 + kTanSums; ++s) acc[g][s] = 0.0;
+  const uint64_t i0 = (uint64_t)chunk * kBasketChunk;
+  for (uint32_t j = threadIdx.x; j < (uint32_t)kBasketChunk; j += 256) {
+    const uint64_t i = i0 + j;
+    if (i >= b.n_paths) break;
+    MemberRows r, ra;
+    load_member(b, at, i, r);
+    if (anti) load_member(b, at, b.n_paths + i, ra);
+#pragma unroll
+    for (int g = 0; g < kPathKB; ++g) {
+      double p, d[kTanSums];
+      payoff_tangent_of(q[g], r, b, p, d);
+      if (anti) {
+        double pa, da[kTanSums];
+        payoff_tangent_of(q[g], ra, b, pa, da);
+        p = (p + pa) / 2;  // montecarlo.jl:431
+#pragma unroll
+        for (int s = 0; s < kTanSums; ++s) d[s] = (d[s] + da[s]) / 2;
+      }
+      acc[g][0] += p;
+      acc[g][1] = fma(p, p, acc[g][1]);
+#pragma unroll
+      for (int s = 0; s < kTanSums; ++s) acc[g][2 + s] += d[s];
+    }
+  }
+#pragma unroll
+  for (int g = 0; g < kPathKB; ++g) {
+    if (k0 + g >= n_payoffs) break;  // uniform over the workgroup
+    if (g) __syncthreads();          // the reduction's LDS staging is reused
+    tangent_reduce_store(acc[g], b, b.records + ((size_t)(k0 + g) * b.n_chunks + chunk) * kRecStride);
   }
 }
 
@@ -334,6 +566,50 @@ int launch_path_stats(const hh_model& m, const hh_config& c, const uint64_t* see
   if (c.dynamics == HH_LOGNORMAL) with_anti(GbmModel<0>{});
   else if (c.em_split) with_anti(HestonModel<0, true>{});
   else with_anti(HestonModel<0, false>{});
+  return (int)hipGetLastError();
+}
+
+// The carried slots decide the instantiation: P = n_active (lognormal dynamics carry sigma alone: P <= 1).  P = 0 takes
+// launch_path_stats' argument block.  No form spills, so the slots are never split over passes.
+int launch_path_tangent(const hh_model& m, const hh_config& c, const uint64_t* seeds_dev, uint32_t monitor_every,
+                        bool include_start, double* rows, hipStream_t s) {
+  const StatsLaunch l(m, c, seeds_dev);
+  DevicePtrs p{};
+  p.seeds = seeds_dev;
+  auto with_p = [&](auto p_c) {
+    constexpr int P = decltype(p_c)::value;
+    SimArgs<P> a;
+    if constexpr (P == 0) a = l.a;
+    else a = make_basis_args<P>(m, c, p);
+    auto go = [&](auto model, auto anti) {
+      hipLaunchKernelGGL((path_tangent_kernel<decltype(model), P, decltype(anti)::value>), l.grid, l.block, 0, s, a, m.S0,
+                         monitor_every, (int)include_start, rows);
+    };
+    auto with_anti = [&](auto model) {
+      if (c.antithetic) go(model, std::true_type{});
+      else go(model, std::false_type{});
+    };
+    if constexpr (P <= 1) {
+      if (c.dynamics == HH_LOGNORMAL) return with_anti(GbmModel<P>{});
+    }
+    if (c.em_split) with_anti(HestonModel<P, true>{});
+    else with_anti(HestonModel<P, false>{});
+  };
+  switch (partial_map(m, c).n_active) {
+    case 0: with_p(std::integral_constant<int, 0>{}); break;
+    case 1: with_p(std::integral_constant<int, 1>{}); break;
+    case 2: with_p(std::integral_constant<int, 2>{}); break;
+    case 3: with_p(std::integral_constant<int, 3>{}); break;
+    default: with_p(std::integral_constant<int, 4>{}); break;
+  }
+  return (int)hipGetLastError();
+}
+
+int launch_path_payoff_tangent(const PathTangentArgs& b, uint32_t n_payoffs, hipStream_t s) {
+  const uint32_t n_groups = (n_payoffs + kPathKB - 1) / kPathKB;
+  if ((uint64_t)((b.n_chunks + 7u) / 8u) * 8u * n_groups > 0x7fffffffull) return (int)hipErrorInvalidConfiguration;
+  const dim3 grid(((b.n_chunks + 7u) / 8u) * 8u * n_groups), block(256);
+  hipLaunchKernelGGL(path_payoff_tangent_kernel, grid, block, 0, s, b, n_payoffs);
   return (int)hipGetLastError();
 }
 

@@ -137,6 +137,113 @@ struct DateRows {
   __device__ __forceinline__ void store(double* __restrict__, const PathStatsLayout&, uint64_t, uint64_t) const {}
 };
 
+// The statistics of one member WITH their tangents along P carried basis slots (path_tangent_kernel, hh_path.hip;
+// PathTangentLayout).  The five values go through Running, in its order: rows 0-4 are Monitor's bit for bit.  Beside them
+// the date rows — k_max, k_min: the step index of the date that holds the extreme; sum_ks = Σ k_j·S_j — and per slot
+// Σ S·dx, Σ dx, S·dx at the two extremes and at the last date, dx = ∂x/∂(the slot's parameter) on that date.
+// TIE RULE: an extreme's tangent and index follow its value: they are replaced exactly when the new S is STRICTLY
+// greater (less) than the running extreme, so the first of equal dates holds it.  The comparison is made once, before
+// Running::next, whose vmax / vmin still give the value.
+template <int P>
+struct RunningTangent {
+  static constexpr int N = P > 0 ? P : 1;
+  Running r;
+  double k_max = 0.0, k_min = 0.0, sum_ks = 0.0;
+  double dsum_s[N], dsum_x[N], dmax_s[N], dmin_s[N], ds_t[N];
+  __device__ __forceinline__ void first(double S, double x, double k, const double (&dx)[N]) {
+    r.first(S, x);
+    k_max = k;
+    k_min = k;
+    sum_ks = k * S;
+#pragma unroll
+    for (int b = 0; b < P; ++b) {
+      const double t = S * dx[b];
+      dsum_s[b] = t;
+      dsum_x[b] = dx[b];
+      dmax_s[b] = t;
+      dmin_s[b] = t;
+      ds_t[b] = t;
+    }
+  }
+  __device__ __forceinline__ void next(double S, double x, double k, const double (&dx)[N]) {
+    const bool up = S > r.max_s, dn = S < r.min_s;
+    r.next(S, x);
+    k_max = up ? k : k_max;
+    k_min = dn ? k : k_min;
+    sum_ks = fma(k, S, sum_ks);
+#pragma unroll
+    for (int b = 0; b < P; ++b) {
+      const double t = S * dx[b];
+      dsum_s[b] = dsum_s[b] + t;
+      dsum_x[b] = dsum_x[b] + dx[b];
+      dmax_s[b] = up ? t : dmax_s[b];
+      dmin_s[b] = dn ? t : dmin_s[b];
+      ds_t[b] = t;
+    }
+  }
+  // plain stores, for the reason Running::store gives: path_payoff_tangent_kernel reads the rows straight back
+  __device__ __forceinline__ void store(double* __restrict__ rows, const PathTangentLayout& at, uint64_t col) const {
+    rows[at.row(HH_STAT_SUM_S) + col] = r.sum_s;
+    rows[at.row(HH_STAT_SUM_X) + col] = r.sum_x;
+    rows[at.row(HH_STAT_MAX_S) + col] = r.max_s;
+    rows[at.row(HH_STAT_MIN_S) + col] = r.min_s;
+    rows[at.row(HH_STAT_S_T) + col] = r.s_t;
+    rows[at.row(HH_TANGENT_K_MAX) + col] = k_max;
+    rows[at.row(HH_TANGENT_K_MIN) + col] = k_min;
+    rows[at.row(HH_TANGENT_SUM_KS) + col] = sum_ks;
+#pragma unroll
+    for (int b = 0; b < P; ++b) {
+      rows[at.slot_row(b, HH_TANGENT_DSUM_S) + col] = dsum_s[b];
+      rows[at.slot_row(b, HH_TANGENT_DSUM_X) + col] = dsum_x[b];
+      rows[at.slot_row(b, HH_TANGENT_DMAX_S) + col] = dmax_s[b];
+      rows[at.slot_row(b, HH_TANGENT_DMIN_S) + col] = dmin_s[b];
+      rows[at.slot_row(b, HH_TANGENT_DS_T) + col] = ds_t[b];
+    }
+  }
+};
+
+// Monitor with the tangents: its dates, its include_start rule and its "first term starts the sum" rule, on the dual log
+// spots of the trajectory and (ANTI) of the mirror.  k counts the steps taken, as a double (exact: n_steps < 2^53).  The
+// start's basis tangents are zero: no carried parameter reaches log S0.
+template <int P, bool ANTI>
+struct TangentMonitor {
+  static constexpr int N = P > 0 ? P : 1;
+  const uint32_t every;
+  uint32_t left;
+  bool started;
+  double k = 0.0;
+  RunningTangent<P> ra, r;
+  __device__ __forceinline__ TangentMonitor(uint32_t monitor_every, int include_start)
+      : every(monitor_every), left(monitor_every), started(include_start != 0) {}
+  __device__ __forceinline__ void start(double S0, double x0) {
+    if (!started) return;
+    double zero[N];
+#pragma unroll
+    for (int b = 0; b < N; ++b) zero[b] = 0.0;
+    r.first(S0, x0, 0.0, zero);
+    if constexpr (ANTI) ra.first(S0, x0, 0.0, zero);
+  }
+  __device__ __forceinline__ void date(const DualT<P>& x, const DualT<P>& xa) {
+    if (--left != 0u) return;
+    left = every;
+    k += (double)every;
+    const double S = exp(x.v);
+    if (started) r.next(S, x.v, k, x.d);
+    else r.first(S, x.v, k, x.d);
+    if constexpr (ANTI) {
+      const double Sa = exp(xa.v);
+      if (started) ra.next(Sa, xa.v, k, xa.d);
+      else ra.first(Sa, xa.v, k, xa.d);
+    }
+    started = true;
+  }
+  __device__ __forceinline__ void store(double* __restrict__ rows, const PathTangentLayout& at, uint64_t i,
+                                        uint64_t n_paths) const {
+    r.store(rows, at, i);
+    if constexpr (ANTI) ra.store(rows, at, n_paths + i);
+  }
+};
+
 // The running extremes of the scheme's CONTINUOUS interpolation, in log space (the bridge form of path_stats_kernel and
 // localvol_stats_kernel).  Between x0 and x1 an Euler step with frozen diffusion coefficient g is a Brownian bridge of
 // variance q = g²·dt, whose maximum and minimum have the laws that one uniform each inverts:

@@ -160,6 +160,16 @@ def set(prob, lens, val):  # noqa: A001 - the reference's name (Accessors.set)
 # ---- methods ----
 class GreekMethod: pass
 class ForwardAD(GreekMethod): pass
+
+
+class Pathwise(GreekMethod):
+    """The pathwise (forward-mode) derivative of a Lipschitz path payoff on Euler–Maruyama paths: an AsianOption or a
+    LookbackOption under a Monitoring, or a European VanillaOption, through MonteCarlo(LognormalDynamics() |
+    HestonDynamics(), EulerMaruyama(), config).  The lenses ForwardAD takes on the plain route; a batch of up to 8 is ONE
+    simulation pass (hh_mc_solve_path_tangent), where FiniteDifference runs two bumped passes per lens.  No reference
+    method.  Barriers and digitals are refused: the pathwise derivative of a discontinuous payoff omits the jump term."""
+
+
 class FDScheme: pass
 class FDForward(FDScheme): pass
 class FDBackward(FDScheme): pass
@@ -269,23 +279,43 @@ def solve_second_order_fd(gprob: SecondOrderGreekProblem, method: FiniteDifferen
     return GreekResult(d)
 
 
-def solve_batch(gprob: BatchGreekProblem, method, pricing_method, solve):
+def _seed_batch(prob, lenses):
+    """`prob` with direction k seeded through lens k: one partial per lens"""
+    n = len(lenses)
+    p = prob
+    for k, lens in enumerate(lenses):
+        x0 = lens(p)
+        if isinstance(x0, Dual):  # two lenses on the same input
+            x0 = Dual(x0.value, tuple(a + (1.0 if j == k else 0.0)
+                                      for j, a in enumerate(x0.partials)))
+        else:
+            x0 = _seed(x0, k, n)
+        p = set(p, lens, x0)
+    return p
+
+
+def solve_pathwise(prob, lenses, pricing_method, solve, kw):
+    """Pathwise(): {lens: greek} of up to 8 lenses out of one tangent pass (montecarlo.solve_path_tangent)."""
+    from .montecarlo import MethodError, MonteCarlo, solve_path_tangent
+    if not isinstance(pricing_method, MonteCarlo):
+        raise MethodError(f"Pathwise() differentiates MonteCarlo(…, EulerMaruyama(), …) paths, not {type(pricing_method).__name__}")
+    if kw:
+        raise MethodError(f"Pathwise() draws its own noise and takes no {sorted(kw)}: no replay")
+    if not 0 < len(lenses) <= 8:
+        raise MethodError("Pathwise() takes 1 .. 8 lenses per pass")
+    price = solve_path_tangent(_seed_batch(prob, lenses), pricing_method, solve).price
+    return {lens: price.partials[k] for k, lens in enumerate(lenses)}
+
+
+def solve_batch(gprob: BatchGreekProblem, method, pricing_method, solve, **kw):
     """greeks_problem.jl:559-568 -> {lens: greek}; ForwardAD through MonteCarlo is one fused pass."""
     from .montecarlo import MonteCarlo
     lenses, prob = tuple(gprob.lenses), gprob.pricing_problem
+    if isinstance(method, Pathwise):
+        return solve_pathwise(prob, lenses, pricing_method, solve, kw)
     if isinstance(method, ForwardAD) and isinstance(pricing_method, MonteCarlo) and \
             0 < len(lenses) <= 8:
-        n = len(lenses)
-        p = prob
-        for k, lens in enumerate(lenses):
-            x0 = lens(p)
-            if isinstance(x0, Dual):  # two lenses on the same input
-                x0 = Dual(x0.value, tuple(a + (1.0 if j == k else 0.0)
-                                          for j, a in enumerate(x0.partials)))
-            else:
-                x0 = _seed(x0, k, n)
-            p = set(p, lens, x0)
-        price = solve(p, pricing_method).price
+        price = solve(_seed_batch(prob, lenses), pricing_method).price
         return {lens: price.partials[k] for k, lens in enumerate(lenses)}
     if isinstance(method, FiniteDifference) and isinstance(pricing_method, MonteCarlo) and \
             isinstance(method.scheme, FDCentral) and 0 < 2 * len(lenses) <= 16:

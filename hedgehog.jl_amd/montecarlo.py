@@ -504,6 +504,46 @@ def run_paths(route, payoffs, market_inputs, method, ensemble, structs, inner=No
                                std_error=res[k].std_error, result=res[k]) for k, p in enumerate(payoffs)]
 
 
+def solve_path_tangent(prob: PricingProblem, method: MonteCarlo, solve) -> MonteCarloSolution:
+    """Pathwise(): `prob` carries Duals (greeks._seed_batch); its price comes back as a Dual from ONE tangent pass
+    (hh_mc_solve_path_tangent: include/hedgehog_mc.h, "Pathwise derivatives of path-dependent payoffs").  An AsianOption or
+    a LookbackOption under a Monitoring on the plain Euler route; a European vanilla is ForwardAD's fused pass."""
+    from .greeks import _replace
+    payoff, m = prob.payoff, prob.market_inputs
+    if isinstance(payoff, (BarrierOption, DigitalOption)):
+        raise MethodError(f"Pathwise() is not offered for {type(payoff).__name__}: the pathwise derivative of a discontinuous "
+                          "payoff omits the jump term — use FiniteDifference")
+    if isinstance(getattr(payoff, "monitoring", None), ContinuousMonitoring):
+        raise MethodError("Pathwise() is not offered under ContinuousMonitoring() (no tangent of the bridge extremes): monitor "
+                          "on the dates of a Monitoring, or use FiniteDifference")
+    route = routes().route_of([payoff], m, method)
+    if route.name not in ("Euler paths", "plain European") or not isinstance(method.strategy, EulerMaruyama):
+        raise MethodError(f"Pathwise() is offered on the plain Euler route — MonteCarlo(LognormalDynamics() | HestonDynamics(), "
+                          f"EulerMaruyama(), config) — not on {route.name} with {type(method.strategy).__name__}: use FiniteDifference")
+    if method.devices is not None:
+        raise MethodError("Pathwise() runs on one device (MonteCarlo.devices is not supported)")
+    if route.name == "plain European":  # the terminal payoff: hh_mc_solve's fused pass carries these partials already
+        return solve(prob, method)
+    if not isinstance(payoff, (AsianOption, LookbackOption)):
+        raise MethodError(f"Pathwise() has no rule for {type(payoff).__name__}")
+    steps = method.config.steps
+    every, start = path_monitoring(payoff, steps)
+    strike = 1.0 if payoff.strike is None else payoff.strike  # a floating lookback reads none
+    european = VanillaOption(strike, payoff.expiry, European(), Call(), Spot())
+    model, c, keep, P, _ = _model_and_config(PricingProblem(european, m), method)
+    if P == 0:
+        raise MethodError("Pathwise(): no Dual in the problem — nothing to differentiate")
+    packed = (_ffi.hh_path_payoff * 1)(pack_path_payoff(payoff if payoff.strike is None else _replace(payoff, "strike", value_of(payoff.strike))))
+    cfg = method.config
+    ctx = _ffi.get_context(method.device)
+    c.seeds, c.seeds_on_device, c.seeds_len = cfg.device_seeds(ctx), 1, cfg.seeds.size
+    res = (_ffi.hh_result * 1)()
+    ctx.check(ctx.lib.hh_mc_solve_path_tangent(ctx.handle, C.byref(model), C.byref(c), every, int(start), packed, 1, res, None))
+    del keep
+    return MonteCarloSolution(prob, method, Dual(res[0].price, tuple(res[0].dprice[k] for k in range(P))), None,
+                              std_error=res[0].std_error, result=res[0])
+
+
 def _solve_multi_gpu(prob, method, model, c, P, discount, ensemble, replay, replay_layout):
     """solve(prob, method) with `method.devices`: the trajectories sharded over those GPUs by ONE
     library call from this thread (hh_mgpu_solve: contiguous ranges, one RCCL all-reduce of the

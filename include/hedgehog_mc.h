@@ -707,6 +707,67 @@ int hh_mc_solve_path_ex(hh_ctx* ctx, const hh_model* model, const hh_config* cfg
                         hh_result* out, double* path_values, double* stats);
 
 /*
+ * Pathwise derivatives of path-dependent payoffs: hh_mc_path_stats_tangent, hh_mc_solve_path_tangent.  The forward-mode
+ * (pathwise) derivative of every LIPSCHITZ payoff of the calls above — vanilla, both Asians, both lookbacks, on the
+ * monitored extremes — along up to HH_MAX_PARTIALS directions, out of ONE simulation pass: the trajectories, dates and
+ * statistics of hh_mc_path_stats, and beside every statistic its tangent.
+ *
+ * cfg as for hh_mc_path_stats, but n_partials = 1 .. HH_MAX_PARTIALS; the directions are hh_model's d* seed arrays, as
+ * for hh_mc_solve.  Of the parameters only those that reach the diffusion are carried per trajectory, with a unit seed
+ * each: V0, kappa, theta, sigma under Heston, sigma alone under lognormal dynamics, and of these the ones some direction
+ * has a non-zero seed on — the n_active BASIS slots, in that order (hh_mc_path_stats_tangent reports them in basis_out
+ * as enum hh_tangent_basis).  Spot, drift rate, strike and discount are finished in closed form and cost nothing per step.
+ *
+ * Rows.  rows[row][column], hh_path_tangent_rows(n_active) = 5 + 3 + 5·n_active rows of n_total doubles, columns as above:
+ *   0 .. 4                            the HH_PATH_STATS statistics, hh_mc_path_stats' bit for bit
+ *   HH_TANGENT_K_MAX, HH_TANGENT_K_MIN  the step index, as a double, of the date that holds MAX_S / MIN_S (0 = the start)
+ *   HH_TANGENT_SUM_KS                 Σ_dates k_j·S_j, k_j the step index of date j
+ *   8 + 5·b + (enum hh_path_tangent_row), for carried slot b, with dx_j = ∂ log S_j / ∂ (parameter of slot b):
+ *     HH_TANGENT_DSUM_S  Σ S_j·dx_j      HH_TANGENT_DSUM_X  Σ dx_j      HH_TANGENT_DS_T  S_T·dx_T
+ *     HH_TANGENT_DMAX_S, HH_TANGENT_DMIN_S   S·dx of the date that holds the extreme
+ * TIE RULE: the tangent and the index of an extreme follow its value — they are replaced exactly when a date's S is
+ * STRICTLY greater (less) than the running extreme, so of equal values the FIRST date holds the extreme.  The start's
+ * basis tangents are zero.  n_active = 0 (seeds on spot, rate, strike, discount only): the eight rows alone.
+ *
+ * hh_mc_solve_path_tangent evaluates the payoffs on the five value rows exactly as hh_mc_solve_path(_ex) does — price,
+ * std_error and both sums are that call's bit for bit — and their almost-everywhere derivatives.  The tangent of a
+ * statistic in direction k is Σ_b seed_k(slot b)·(its row of slot b) plus the passive part from
+ * dx_j = dS0_k/S0 + dr_k·(k_j·dt):   dSUM_S += xd0·SUM_S + dr·dt·SUM_KS;   dSUM_X += n_mon·xd0 + dr·dt·Σk_j;
+ * dMAX_S += MAX_S·(xd0 + dr·dt·K_MAX), likewise the minimum;   dS_T += S_T·(xd0 + dr·dt·n_steps).  Payoff rules
+ * (dK = model->dstrike[k], the strike seed of EVERY payoff of the call; itm = the payoff is > 0):
+ *   HH_PAYOFF_VANILLA         1[itm]·cp·(dS_T − dK)
+ *   HH_PAYOFF_ASIAN_ARITH     1[itm]·cp·(dSUM_S / n_mon − dK)
+ *   HH_PAYOFF_ASIAN_GEOM      1[itm]·cp·(G·dSUM_X / n_mon − dK),  G = exp(SUM_X / n_mon)
+ *   HH_PAYOFF_LOOKBACK_FLOAT  call: dS_T − dMIN_S;               put: dMAX_S − dS_T
+ *   HH_PAYOFF_LOOKBACK_FIXED  call: 1[itm]·(dMAX_S − dK);        put: 1[itm]·(dK − dMIN_S)
+ * Antithetic: the pair average.  out[k].dprice[j] = discount·mean(∂payoff_j) + ddiscount_j·mean(payoff).
+ *   hh_mc_path_stats_tangent  rows: host memory, or device memory when rows_on_device, sized for the call's n_active
+ *                             (4 is always enough); basis_out (nullable): 4 int32, the carried parameters, −1 beyond
+ *                             n_active; out (nullable): n_paths_done, kernel_ms, total_ms.
+ *   hh_mc_solve_path_tangent  out[k] as hh_mc_solve_path's with dprice filled; rows (nullable, host): as above.
+ * Synchronous, one device.  hh_ctx_enable_timing: the tangent kernel, then the payoff kernel with its record reduction.
+ * HH_ERR_UNSUPPORTED: HH_PAYOFF_BARRIER, HH_PAYOFF_DIGITAL_CASH, HH_PAYOFF_DIGITAL_ASSET (the pathwise derivative of a
+ * discontinuous payoff omits the jump term: use a finite difference); REPLAY noise; every dynamics/strategy other than
+ * lognormal or Heston by HH_EULER_MARUYAMA.  HH_ERR_INVALID: n_partials = 0 or above HH_MAX_PARTIALS, NULL arguments, and
+ * everything hh_mc_solve_path rejects.  Not provided: the bridge extremes, the other path families, multilevel, LSM,
+ * multi-GPU, REPLAY / Sobol' noise, second order; rho has no seed in hh_model.
+ */
+enum hh_tangent_date_row { HH_TANGENT_K_MAX = 5, HH_TANGENT_K_MIN = 6, HH_TANGENT_SUM_KS = 7 };
+enum hh_path_tangent_row { HH_TANGENT_DSUM_S = 0, HH_TANGENT_DSUM_X = 1, HH_TANGENT_DMAX_S = 2, HH_TANGENT_DMIN_S = 3,
+                           HH_TANGENT_DS_T = 4 };
+enum hh_tangent_basis { HH_BASIS_V0 = 0, HH_BASIS_KAPPA = 1, HH_BASIS_THETA = 2, HH_BASIS_SIGMA = 3 };
+#define HH_TANGENT_DATE_ROWS 3
+#define HH_TANGENT_ROWS_PER_SLOT 5
+#define HH_TANGENT_MAX_BASIS 4
+size_t hh_path_tangent_rows(uint32_t n_active);
+int hh_mc_path_stats_tangent(hh_ctx* ctx, const hh_model* model, const hh_config* cfg, uint32_t monitor_every,
+                             int32_t include_start, double* rows, int32_t rows_on_device, int32_t* basis_out,
+                             hh_result* out);
+int hh_mc_solve_path_tangent(hh_ctx* ctx, const hh_model* model, const hh_config* cfg, uint32_t monitor_every,
+                             int32_t include_start, const hh_path_payoff* payoffs, uint32_t n_payoffs, hh_result* out,
+                             double* rows);
+
+/*
  * Multilevel Monte Carlo (Giles 2008): one level's correction E[P_fine − P_coarse], sampled on a fine and a coarse
  * Euler–Maruyama trajectory driven by the same Brownian increments.  The reference has no multilevel method; the
  * conventions below are this library's.  The host method (MultilevelMonteCarlo) chooses levels and trajectory counts;
