@@ -19,8 +19,8 @@ from .greeks import (AssetSpotLens, AssetVolLens, BatchGreekProblem, Correlation
                      ForwardAD, GreekProblem, GreekResult, Pathwise, PropertyLens, SecondOrderGreekProblem, SpotLens,
                      VolLens,
                      ZeroRateSpineLens, optic, set)
-from .lsm import (LSM, EulerPaths, HestonExactPaths, LSMSolution, SpotPaths, simulate_euler_paths,
-                  simulate_heston_exact_paths, simulate_spot_paths, solve_lsm)
+from .lsm import (LSM, EulerPaths, HestonExactPaths, LSMSolution, SpotPaths, StatePaths, simulate_euler_paths,
+                  simulate_heston_exact_paths, simulate_spot_paths, simulate_state_paths, solve_lsm)
 from .montecarlo import (AbstractPricingMethod, Antithetic, BatesDynamics, BlackScholesExact, EulerMaruyama,
                          HestonBroadieKaya, HestonDynamics, HestonQE, LognormalDynamics, MertonDynamics, MertonExact, MethodError,
                          MonteCarlo, NoVarianceReduction, NormalLaw, SimulationConfig, VarianceGammaDynamics,
@@ -82,6 +82,8 @@ def solve(*args, **kw):
         solve(prob::PricingProblem{IndexOption{…, VanillaOption{…,American,…}}, MultiAssetInputs},
               ::LSM(MultiAssetDynamics(), EulerMaruyama(), config, degree); exercise_every=m)
                                   American / Bermudan baskets and rainbows: a regression basis in several variables
+        solve(prob::PricingProblem{<:VanillaOption{…,American,…}}, ::LSM; exercise_every=m, regressors="spot_variance")
+                                  Heston Euler (path_state="spot"), HestonQE, Bates: the regression on spot AND variance
         solve(prob::PricingProblem{<:VanillaOption}, ::CoxRossRubinsteinMethod) cox_ross_rubinstein.jl:99
         solve(prob::BasketPricingProblem, ::CoxRossRubinsteinMethod)         basket.jl:35
         solve(prob::PricingProblem{<:VanillaOption} | ::BasketPricingProblem, ::CrankNicolsonMethod)

@@ -127,6 +127,7 @@ class hh_assets(C.Structure):
 
 HH_LSM_MAX_BASIS = 45
 HH_LSM_STATES_LOG_ASSETS = 0
+HH_LSM_STATES_LOG_SPOT_VARIANCE = 1
 
 
 class hh_lsm_states(C.Structure):
@@ -269,6 +270,10 @@ SYMBOLS = [
                                       C.POINTER(hh_lsm_result), _vp, _vp, _vp]),
     ("hh_lsm_solve_assets", C.c_int, [_vp, C.POINTER(hh_model), C.POINTER(hh_assets), C.POINTER(hh_config), C.c_uint32,
                                       C.c_int32, C.c_double, C.POINTER(hh_lsm_result), _vp, _vp, _vp]),
+    ("hh_mc_path_states", C.c_int, [_vp, C.POINTER(hh_path_source), C.POINTER(hh_model), C.POINTER(hh_config), C.c_uint32, _vp,
+                                    C.c_int32, C.POINTER(hh_result)]),
+    ("hh_lsm_solve_path_states", C.c_int, [_vp, C.POINTER(hh_path_source), C.POINTER(hh_model), C.POINTER(hh_config),
+                                           C.c_uint32, C.c_int32, C.c_double, C.POINTER(hh_lsm_result), _vp, _vp, _vp, _vp]),
     ("hh_mc_path_stats_lv", C.c_int, [_vp, C.POINTER(hh_model), C.POINTER(hh_localvol), C.POINTER(hh_config), C.c_uint32,
                                       C.c_int32, C.c_int32, _vp, C.c_int32, C.POINTER(hh_result)]),
     ("hh_mc_solve_path_lv", C.c_int, [_vp, C.POINTER(hh_model), C.POINTER(hh_localvol), C.POINTER(hh_config), C.c_uint32,

@@ -1551,6 +1551,8 @@ struct PathFamily {
   double* var_T = nullptr;  // host, nullable: the variance at expiry of every member (the QE step)
   bool missing = false;     // a struct the kernel needs came as NULL: the entry point's "NULL argument"
   bool date_rows = false;   // the kernel's date-row sibling: the grid into ctx->lsm_grid, no statistics (hh_mc_path_grid)
+  bool state_rows = false;  // with date_rows: the state-row sibling instead — (x, v) per date (hh_mc_path_states; kEuler
+                            // under Heston dynamics, kQe, kBates)
   bool tangent = false;     // path_tangent_kernel: the statistics with their tangents, cfg->n_partials directions (kEuler)
   // path_stats_kernel: lognormal or Heston dynamics by Euler–Maruyama
   PathFamily(const char* w, int32_t last, int32_t ext) : kernel(kEuler), who(w), last_kind(last), extremes(ext) {}
@@ -1583,6 +1585,12 @@ struct PathFamily {
     f.date_rows = true;
     return f;
   }
+  // this member (a walk that holds a variance) in its state-row form
+  PathFamily states() const {
+    PathFamily f = rows();
+    f.state_rows = true;
+    return f;
+  }
   // this member (kEuler) with the tangents of the statistics
   PathFamily tangents() const {
     PathFamily f = *this;
@@ -1606,7 +1614,8 @@ static int check_every(hh_ctx* ctx, const char* who, const char* word, uint32_t 
 // The checks of every entry point, then the statistics of every trajectory into ctx->path_stats (one timing slot) and,
 // where f.var_T, the variances at expiry into ctx->heston_var.  f.date_rows: monitor_every is the entry point's
 // exercise_every, and the rows of every such step go into ctx->lsm_grid ([n_steps/monitor_every + 1][n_total]) instead —
-// of the several-asset walk its state rows, [n_steps/monitor_every + 1][n_assets][n_total].
+// of the several-asset walk its state rows, [n_steps/monitor_every + 1][n_assets][n_total], under f.state_rows the rows
+// (x, v), [n_steps/monitor_every + 1][2][n_total].
 static int run_path_stats(hh_ctx* ctx, const PathFamily& f, const hh_model* m, const hh_config* c, uint32_t monitor_every,
                           int32_t include_start) {
   const char* who = f.who;
@@ -1686,6 +1695,8 @@ static int run_path_stats(hh_ctx* ctx, const PathFamily& f, const hh_model* m, c
   const bool rows = f.date_rows;
   if (rows && f.assets)  // the several-asset walk's rows are its d log-states per date (hh_assets_path_rows)
     rc = ensure(ctx, ctx->lsm_grid, hh_assets_rows_elems(c->n_paths, c->n_steps / monitor_every, f.assets->n_assets, c->antithetic));
+  else if (rows && f.state_rows)
+    rc = ensure(ctx, ctx->lsm_grid, hh_assets_rows_elems(c->n_paths, c->n_steps / monitor_every, 2, c->antithetic));
   else if (rows) rc = ensure(ctx, ctx->lsm_grid, hh_lsm_grid_elems(c->n_paths, c->n_steps / monitor_every, c->antithetic));
   else if (f.tangent) rc = ensure(ctx, ctx->path_stats, tangent_layout(m, c).total);
   else rc = ensure(ctx, ctx->path_stats, at.total);
@@ -1706,17 +1717,18 @@ static int run_path_stats(hh_ctx* ctx, const PathFamily& f, const hh_model* m, c
         break;
       }
       HH_HIP(ctx, hh::launch_path_stats(*m, *c, seeds_dev, monitor_every, start, f.extremes == HH_EXTREMES_BRIDGE, dst,
-                                        ctx->stream, rows));
+                                        ctx->stream, rows, f.state_rows));
       break;
     case PathFamily::kJump:
       HH_HIP(ctx, hh::launch_jump_stats(*m, *c, *f.jump, seeds_dev, monitor_every, start, dst, ctx->stream, rows));
       break;
     case PathFamily::kQe:
-      HH_HIP(ctx, hh::launch_qe_stats(*m, *c, *f.qe, seeds_dev, monitor_every, start, dst, var_dev, ctx->stream, rows));
+      HH_HIP(ctx, hh::launch_qe_stats(*m, *c, *f.qe, seeds_dev, monitor_every, start, dst, var_dev, ctx->stream, rows,
+                                      f.state_rows));
       break;
     case PathFamily::kBates:
       HH_HIP(ctx, hh::launch_bates_stats(*m, *c, *f.qe, *f.jump, seeds_dev, monitor_every, start, dst, var_dev, ctx->stream,
-                                         rows));
+                                         rows, f.state_rows));
       break;
     case PathFamily::kAssets:
       if (rows) HH_HIP(ctx, hh::launch_assets_rows(*m, *c, *f.assets, seeds_dev, monitor_every, dst, ctx->stream));
@@ -1974,9 +1986,21 @@ int hh_mc_solve_path_tangent(hh_ctx* ctx, const hh_model* m, const hh_config* c,
 
 // The family member a source names, in its date-row form, handed to `run`: each kind through the constructor its
 // path_stats entry point uses, so run_path_stats makes that entry point's checks in that entry point's words.
+// states: the state-row form instead, of the three sources whose walk holds a variance.
 static int with_source_family(hh_ctx* ctx, const char* who, const hh_path_source* src,
-                              const std::function<int(const PathFamily&)>& run) {
+                              const std::function<int(const PathFamily&)>& run, bool states = false) {
   if (!src) return fail(ctx, HH_ERR_INVALID, "%s: NULL argument", who);
+  if (states) switch (src->kind) {
+    case HH_SOURCE_EULER: return run(PathFamily(who, 0, HH_EXTREMES_MONITORED).states());
+    case HH_SOURCE_QE: return run(PathFamily(who, 0, src->qe, nullptr).states());
+    case HH_SOURCE_BATES: return run(PathFamily(who, 0, src->qe, src->jump, nullptr).states());
+    case HH_SOURCE_JUMP:
+    case HH_SOURCE_LOCALVOL:
+    case HH_SOURCE_VG:
+      return fail(ctx, HH_ERR_UNSUPPORTED, "%s: source kind %d: the walk has no variance (state rows are those of "
+                  "HH_SOURCE_EULER under Heston dynamics, HH_SOURCE_QE and HH_SOURCE_BATES)", who, src->kind);
+    default: return fail(ctx, HH_ERR_INVALID, "%s: unknown source kind %d", who, src->kind);
+  }
   switch (src->kind) {
     case HH_SOURCE_EULER: return run(PathFamily(who, 0, HH_EXTREMES_MONITORED).rows());
     case HH_SOURCE_JUMP: return run(PathFamily(who, 0, src->jump).rows());
@@ -2070,14 +2094,21 @@ int hh_assets_path_rows(hh_ctx* ctx, const hh_model* m, const hh_assets* assets,
 
 // the descriptor and the basis of an induction on state rows, after lsm_check_scalars
 static int check_lsm_states(hh_ctx* ctx, const char* who, const hh_lsm_states* d, int32_t degree) {
-  if (d->kind != HH_LSM_STATES_LOG_ASSETS) return fail(ctx, HH_ERR_INVALID, "%s: unknown descriptor kind %d", who, d->kind);
-  if (d->n_states < 1u || d->n_states > (uint32_t)HH_MAX_ASSETS)
-    return fail(ctx, HH_ERR_INVALID, "%s: n_states (%u) must lie in 1 .. %d", who, d->n_states, HH_MAX_ASSETS);
-  if (d->index_kind < HH_INDEX_WEIGHTED_SUM || d->index_kind > HH_INDEX_WORST_OF)
-    return fail(ctx, HH_ERR_INVALID, "%s: unknown index_kind %d", who, d->index_kind);
-  if (!std::isfinite(d->strike)) return fail(ctx, HH_ERR_INVALID, "%s: the strike must be finite", who);
-  for (uint32_t i = 0; i < d->n_states; ++i)
-    if (!std::isfinite(d->weights[i])) return fail(ctx, HH_ERR_INVALID, "%s: asset %u: the weight must be finite", who, i);
+  if (d->kind != HH_LSM_STATES_LOG_ASSETS && d->kind != HH_LSM_STATES_LOG_SPOT_VARIANCE)
+    return fail(ctx, HH_ERR_INVALID, "%s: unknown descriptor kind %d", who, d->kind);
+  if (d->kind == HH_LSM_STATES_LOG_SPOT_VARIANCE) {  // index_kind and weights are not read
+    if (d->n_states != 2u)
+      return fail(ctx, HH_ERR_INVALID, "%s: n_states (%u) must be 2 under HH_LSM_STATES_LOG_SPOT_VARIANCE", who, d->n_states);
+    if (!std::isfinite(d->strike)) return fail(ctx, HH_ERR_INVALID, "%s: the strike must be finite", who);
+  } else {
+    if (d->n_states < 1u || d->n_states > (uint32_t)HH_MAX_ASSETS)
+      return fail(ctx, HH_ERR_INVALID, "%s: n_states (%u) must lie in 1 .. %d", who, d->n_states, HH_MAX_ASSETS);
+    if (d->index_kind < HH_INDEX_WEIGHTED_SUM || d->index_kind > HH_INDEX_WORST_OF)
+      return fail(ctx, HH_ERR_INVALID, "%s: unknown index_kind %d", who, d->index_kind);
+    if (!std::isfinite(d->strike)) return fail(ctx, HH_ERR_INVALID, "%s: the strike must be finite", who);
+    for (uint32_t i = 0; i < d->n_states; ++i)
+      if (!std::isfinite(d->weights[i])) return fail(ctx, HH_ERR_INVALID, "%s: asset %u: the weight must be finite", who, i);
+  }
   if (hh::lsm_basis_count((int)d->n_states, degree) == 0)
     return fail(ctx, HH_ERR_UNSUPPORTED, "%s: %u state rows at degree %d need more than %d basis functions", who, d->n_states,
                 degree, HH_LSM_MAX_BASIS);
@@ -2184,6 +2215,78 @@ int hh_lsm_solve_assets(hh_ctx* ctx, const hh_model* m, const hh_assets* assets,
     HH_HIP(ctx, hipStreamSynchronize(ctx->stream));
   }
   return HH_OK;
+}
+
+// ---- state rows of the stochastic-volatility walks, and LSM on (S, V) (hedgehog_mc.h, "American exercise under
+// stochastic volatility"; kernels: each walk's *_stats_kernel<…, StateRows<ANTI>>, hh_lsm_multi.hip) ----
+
+// the Euler source walks lognormal dynamics too, and that walk holds no variance
+static int check_walk_has_variance(hh_ctx* ctx, const PathFamily& f, const hh_config* c) {
+  if (f.kernel == PathFamily::kEuler && c->dynamics == HH_LOGNORMAL)
+    return fail(ctx, HH_ERR_UNSUPPORTED, "%s: LognormalDynamics on HH_SOURCE_EULER: the walk has no variance (state rows "
+                "need HestonDynamics there)", f.who);
+  return HH_OK;
+}
+
+int hh_mc_path_states(hh_ctx* ctx, const hh_path_source* source, const hh_model* m, const hh_config* c,
+                      uint32_t exercise_every, double* rows, int32_t rows_on_device, hh_result* out) {
+  if (!ctx) return HH_ERR_INVALID;
+  std::lock_guard<std::recursive_mutex> lock__(ctx->mu);
+  return with_source_family(ctx, "hh_mc_path_states", source, [&](const PathFamily& f) -> int {
+    if (!m || !c || !rows || f.missing) return fail(ctx, HH_ERR_INVALID, "%s: NULL argument", f.who);
+    int rc = check_walk_has_variance(ctx, f, c);
+    if (rc) return rc;
+    const WallClock clock;
+    HH_HIP(ctx, hipSetDevice(ctx->device));
+    HH_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+    if ((rc = run_path_stats(ctx, f, m, c, exercise_every, 1))) return rc;
+    HH_HIP(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+    const size_t bytes = hh_assets_rows_elems(c->n_paths, c->n_steps / exercise_every, 2, c->antithetic) * sizeof(double);
+    HH_HIP(ctx, hipMemcpyAsync(rows, ctx->lsm_grid, bytes, rows_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost,
+                               ctx->stream));
+    HH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if ((rc = release_host_operands(ctx))) return rc;
+    if (!out) return HH_OK;
+    std::memset(out, 0, sizeof(*out));
+    out->n_paths_done = c->n_paths;
+    return solve_times(ctx, clock, &out->kernel_ms, &out->total_ms);
+  }, /*states=*/true);
+}
+
+int hh_lsm_solve_path_states(hh_ctx* ctx, const hh_path_source* source, const hh_model* m, const hh_config* c,
+                             uint32_t exercise_every, int32_t degree, double date_discount, hh_lsm_result* out,
+                             int32_t* stop_time, double* stop_value, double* coef, double* rows) {
+  if (!ctx) return HH_ERR_INVALID;
+  std::lock_guard<std::recursive_mutex> lock__(ctx->mu);
+  return with_source_family(ctx, "hh_lsm_solve_path_states", source, [&](const PathFamily& f) -> int {
+    if (!m || !c || !out || f.missing) return fail(ctx, HH_ERR_INVALID, "%s: NULL argument", f.who);
+    const WallClock clock;
+    // the schedule first, then the induction's scalars on its dates, then everything the source's entry point checks
+    int rc = check_every(ctx, f.who, "exercise_every", exercise_every, c->n_steps);
+    if (rc) return rc;
+    const uint32_t n_dates = c->n_steps / exercise_every;
+    if ((rc = check_lsm_states_scalars(ctx, m->cp, c->n_paths, n_dates, degree, date_discount))) return rc;
+    hh_lsm_states d{};
+    d.kind = HH_LSM_STATES_LOG_SPOT_VARIANCE;
+    d.n_states = 2;
+    d.cp = m->cp;
+    d.strike = m->strike;
+    if ((rc = check_lsm_states(ctx, f.who, &d, degree))) return rc;
+    if ((rc = check_walk_has_variance(ctx, f, c))) return rc;
+    HH_HIP(ctx, hipSetDevice(ctx->device));
+    HH_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+    if ((rc = run_path_stats(ctx, f, m, c, exercise_every, 1))) return rc;
+    const uint64_t ntot = c->n_paths * (c->antithetic ? 2 : 1);
+    rc = lsm_on_states(ctx, &d, ctx->lsm_grid, ntot, n_dates, degree, date_discount, out, stop_time, stop_value, coef, clock);
+    if (rc) return rc;
+    if ((rc = release_host_operands(ctx))) return rc;
+    if (rows) {
+      HH_HIP(ctx, hipMemcpyAsync(rows, ctx->lsm_grid, hh_assets_rows_elems(c->n_paths, n_dates, 2, c->antithetic) * sizeof(double),
+                                 hipMemcpyDeviceToHost, ctx->stream));
+      HH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    return HH_OK;
+  }, /*states=*/true);
 }
 
 // ---- multilevel Monte Carlo (hedgehog_mc.h, "Multilevel Monte Carlo"; kernels: hh_path.hip) ----

@@ -26,7 +26,8 @@ namespace {
 // Sink (hh_path_stats.h): Monitor, the five statistics — or DateRows, the date-row form: `stats` is then the grid
 // [n_steps/monitor_every + 1][n_total], row j the spot after step j·monitor_every, and include_start is not read.  The
 // walk, its draws and its constants are stated here once for both.
-// The date-row form writes spots alone: no variance rows, var_T is not read.
+// The date-row form writes spots alone: no variance rows, var_T is not read.  StateRows: `stats` is the state rows
+// [n_steps/monitor_every + 1][2][n_total], (x, v) after step j·monitor_every; var_T is not read (it is the last v row).
 template <bool ANTI, bool MART, class Sink = Monitor<ANTI>>
 __global__ __launch_bounds__(256) void bates_stats_kernel(const SimArgs<0> a, const QeArgs q, const JumpArgs j,
                                                           const double S0, const uint32_t monitor_every,
@@ -39,7 +40,8 @@ __global__ __launch_bounds__(256) void bates_stats_kernel(const SimArgs<0> a, co
   QeState st{a.x0.v, a.v0.v}, sa{a.x0.v, a.v0.v};
   Sink mon(monitor_every, include_start);
   mon.bind(stats, i, a.n_paths);
-  mon.start(S0, a.x0.v);
+  if constexpr (Sink::kStates) mon.start(a.x0.v, a.v0.v);
+  else mon.start(S0, a.x0.v);
   const uint64_t key = a.seeds[i];
   const uint32_t k0 = (uint32_t)key, k1 = (uint32_t)(key >> 32);
   JumpUniforms ju;
@@ -47,7 +49,8 @@ __global__ __launch_bounds__(256) void bates_stats_kernel(const SimArgs<0> a, co
     qe_pair_step<ANTI, MART>(st, sa, q, key, k);
     const double uj = (k & 1u) == 0u ? ju.even(k >> 1, k0, k1) : ju.odd();
     jump_step<ANTI>(j, key, k, uj, st.x, sa.x);
-    mon.date(st.x, sa.x);
+    if constexpr (Sink::kStates) mon.date(st.x, sa.x, st.v, sa.v);
+    else mon.date(st.x, sa.x);
   }
   if constexpr (Sink::kStats) {
     // each member's rows, then its var_T (Monitor::store writes the rows alone)
@@ -69,7 +72,7 @@ QeArgs bates_launch_args(const hh_model& m, const hh_config& c, const hh_qe& qe,
 
 int launch_bates_stats(const hh_model& m, const hh_config& c, const hh_qe& qe, const hh_jump& jump,
                        const uint64_t* seeds_dev, uint32_t monitor_every, bool include_start, double* stats,
-                       double* var_T, hipStream_t s, bool date_rows) {
+                       double* var_T, hipStream_t s, bool date_rows, bool state_rows) {
   const StatsLaunch l(m, c, seeds_dev);
   const QeArgs q = bates_launch_args(m, c, qe, jump);
   const JumpArgs j = jump_args(jump, m.T / (double)c.n_steps);
@@ -79,6 +82,9 @@ int launch_bates_stats(const hh_model& m, const hh_config& c, const hh_qe& qe, c
   if (date_rows)
     kernel = anti ? (mart ? bates_stats_kernel<true, true, DateRows<true>> : bates_stats_kernel<true, false, DateRows<true>>)
                   : (mart ? bates_stats_kernel<false, true, DateRows<false>> : bates_stats_kernel<false, false, DateRows<false>>);
+  if (state_rows)
+    kernel = anti ? (mart ? bates_stats_kernel<true, true, StateRows<true>> : bates_stats_kernel<true, false, StateRows<true>>)
+                  : (mart ? bates_stats_kernel<false, true, StateRows<false>> : bates_stats_kernel<false, false, StateRows<false>>);
   hipLaunchKernelGGL(kernel, l.grid, l.block, 0, s, l.a, q, j, m.S0, monitor_every, (int)include_start, stats, var_T);
   return (int)hipGetLastError();
 }

@@ -297,8 +297,12 @@ struct StatsLaunch {
 // date_rows (this launcher and the five below that take it): the kernel's date-row sibling — `stats` is then the grid
 // [n_steps/monitor_every + 1][n_total] of hh_lsm_grid_elems, row j the spot after step j·monitor_every, row 0 = S0 always;
 // include_start, bridge and var_T are not read.  The argument blocks and constants are formed by the same lines.
+// state_rows (this launcher under Heston dynamics, launch_qe_stats, launch_bates_stats — the walks that hold a variance):
+// the kernel's state-row sibling — `stats` is then rows[n_steps/monitor_every + 1][2][n_total] of hh_assets_rows_elems at
+// d = 2, (x, v) after step j·monitor_every as the walk holds them, row 0 = (log S0, V0); it goes before date_rows.
 int launch_path_stats(const hh_model& m, const hh_config& c, const uint64_t* seeds_dev, uint32_t monitor_every,
-                      bool include_start, bool bridge, double* stats, hipStream_t s, bool date_rows = false);
+                      bool include_start, bool bridge, double* stats, hipStream_t s, bool date_rows = false,
+                      bool state_rows = false);
 // … and n_payoffs payoffs evaluated on them: one record per payoff and chunk, as launch_basket_payoffs leaves them
 struct PathPayoffArgs {
   const double* stats;            // PathStatsLayout(n_paths, antithetic, rows of `extremes`)
@@ -383,14 +387,14 @@ QeArgs qe_launch_args(const hh_model& m, const hh_config& c, const hh_qe& qe);
 // launch_path_stats' monitored form with the QE step: the same five rows; var_T (nullable): n_total doubles
 int launch_qe_stats(const hh_model& m, const hh_config& c, const hh_qe& qe, const uint64_t* seeds_dev,
                     uint32_t monitor_every, bool include_start, double* stats, double* var_T, hipStream_t s,
-                    bool date_rows = false);
+                    bool date_rows = false, bool state_rows = false);
 // Bates (hh_bates.hip, hh_fourier.hip; include/hedgehog_mc.h, "Bates (1996): Heston variance with Merton jumps").  The
 // scalars are checked by the entry points.  qe_launch_args with r_c = r_drift − merton_compensator(jump) for r:
 QeArgs bates_launch_args(const hh_model& m, const hh_config& c, const hh_qe& qe, const hh_jump& jump);
 // launch_qe_stats with a jump count per step and, on the lane that has one, a jump: the same five rows and var_T
 int launch_bates_stats(const hh_model& m, const hh_config& c, const hh_qe& qe, const hh_jump& jump,
                        const uint64_t* seeds_dev, uint32_t monitor_every, bool include_start, double* stats,
-                       double* var_T, hipStream_t s, bool date_rows = false);
+                       double* var_T, hipStream_t s, bool date_rows = false, bool state_rows = false);
 // Local volatility on a tabulated surface (hh_localvol.hip; include/hedgehog_mc.h, "Local volatility on a tabulated
 // surface"): launch_path_stats' lognormal forms — the five monitored rows, or the seven under `bridge` — with the σ of
 // every step read from the surface.  m.sigma is not read.  The entry points have checked the surface and staged lv's

@@ -3,8 +3,10 @@
 // standardised regressors, B = C(m + p, p) <= 45 of them, in the graded lexicographic order of hh_lsm_basis.h.  It reads a
 // device grid rows[date][state][column] of m state rows per date and a by-value descriptor that says how a column's m
 // states give (a) the exercise value and (b) the m regressors; it knows nothing else of where the rows come from.  The
-// one descriptor today is "log-states of assets" (hh_assets_path_rows): exercise value cp·(I − K) with I from index_of
-// (hh_assets.h), regressors v_i = exp(x_i).  A descriptor is one more case in column_of and nowhere else.
+// two descriptors are "log-states of assets" (hh_assets_path_rows): exercise value cp·(I − K) with I from index_of
+// (hh_assets.h), regressors v_i = exp(x_i) — and "log spot and variance" (hh_mc_path_states, m = 2): exercise value
+// cp·(exp(x_0) − K), regressors exp(x_0) and x_1, the variance as stored.  A descriptor is one more case in column_of and
+// nowhere else.
 //
 // FORM: one launch per date, and that is the whole of it — there is no persistent / cooperative form of this induction
 // (hh_lsm.hip has one for a single row; here B² running sums per workgroup would have to cross the chip per date).
@@ -68,11 +70,21 @@ struct StatesDesc {
   int32_t index_kind;  // HH_LSM_STATES_LOG_ASSETS: enum hh_index_kind
   double cp, strike;
   AssetArgs c;         // … and the weights of the index, where index_of reads them (c.w); nothing else is set
+                       // (HH_LSM_STATES_LOG_SPOT_VARIANCE reads neither)
 };
 
 template <int M>
 __device__ __forceinline__ void column_of(const StatesDesc& d, const double (&x)[M], double& pay, double (&v)[M]) {
-  // HH_LSM_STATES_LOG_ASSETS, the one kind: the index as the statistics kernel forms it on these states
+  // HH_LSM_STATES_LOG_SPOT_VARIANCE (m = 2: the descriptor check admits no other): the spot and the variance as stored
+  if constexpr (M == 2) {
+    if (d.kind == HH_LSM_STATES_LOG_SPOT_VARIANCE) {  // uniform
+      v[0] = exp(x[0]);
+      v[1] = x[1];
+      pay = d.cp * (v[0] - d.strike);
+      return;
+    }
+  }
+  // HH_LSM_STATES_LOG_ASSETS: the index as the statistics kernel forms it on these states
   double I, xi;
   switch (d.index_kind) {  // uniform
     case HH_INDEX_WEIGHTED_SUM: index_of<M, HH_INDEX_WEIGHTED_SUM>(d.c, x, I, xi); break;

@@ -32,11 +32,15 @@ namespace {
 // [n_steps/monitor_every + 1][n_total], row j the spot after step j·monitor_every, and include_start is not read.  The
 // walk, its draws and its constants are stated here once for both.
 // At monitor_every = 1 the date rows are euler_grid_kernel's spot grid bit for bit.
+// StateRows (HestonModel alone: the walk that holds a variance): `stats` is the state rows [n_steps/monitor_every + 1][2]
+// [n_total], (x, v) after step j·monitor_every as the step leaves them — at monitor_every = 1 euler_grid_kernel's log
+// states and its variance grid bit for bit.
 template <class M, bool ANTI, bool BRIDGE, class Sink = Monitor<ANTI>>
 __global__ __launch_bounds__(256) void path_stats_kernel(const SimArgs<0> a, const double S0,
                                                          const uint32_t monitor_every, const int include_start,
                                                          double* __restrict__ stats) {
   static_assert(Sink::kStats || !BRIDGE, "the continuous extremes are statistics: no date-row form");
+  static_assert(!Sink::kStates || M::NCOMP == 2, "state rows need a walk that holds a variance");
   using State = typename M::State;
   constexpr int NC = M::NCOMP;
   const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
@@ -48,7 +52,8 @@ __global__ __launch_bounds__(256) void path_stats_kernel(const SimArgs<0> a, con
   if constexpr (ANTI) M::init(sa, a);
   Sink mon(monitor_every, include_start);
   mon.bind(stats, i, a.n_paths);
-  mon.start(S0, a.x0.v);
+  if constexpr (Sink::kStates) mon.start(a.x0.v, a.v0.v);
+  else mon.start(S0, a.x0.v);
   Extremes e, ea;
   if constexpr (BRIDGE) {
     e.first(a.x0.v);
@@ -71,7 +76,8 @@ __global__ __launch_bounds__(256) void path_stats_kernel(const SimArgs<0> a, con
       M::step(st, a, d1, d2);
       if constexpr (ANTI) M::step(sa, a, -d1, -d2);
     }
-    mon.date(st.x.v, sa.x.v);
+    if constexpr (Sink::kStates) mon.date(st.x.v, sa.x.v, st.v.v, sa.v.v);
+    else mon.date(st.x.v, sa.x.v);
   };
   if constexpr (NC == 2) {
     for (uint32_t s = 0; s < n_steps; ++s) {
@@ -545,14 +551,22 @@ int launch_level_payoffs(const PathPayoffArgs& b, uint32_t n_payoffs, hipStream_
 }
 
 int launch_path_stats(const hh_model& m, const hh_config& c, const uint64_t* seeds_dev, uint32_t monitor_every,
-                      bool include_start, bool bridge, double* stats, hipStream_t s, bool date_rows) {
+                      bool include_start, bool bridge, double* stats, hipStream_t s, bool date_rows, bool state_rows) {
   const StatsLaunch l(m, c, seeds_dev);
+  if (state_rows && c.dynamics != HH_HESTON) return (int)hipErrorInvalidValue;  // the entry point has refused it
   auto go = [&](auto model, auto anti, auto br) {
     hipLaunchKernelGGL((path_stats_kernel<decltype(model), decltype(anti)::value, decltype(br)::value>), l.grid, l.block, 0,
                        s, l.a, m.S0, monitor_every, (int)include_start, stats);
   };
   auto with_form = [&](auto model, auto anti) {
     constexpr bool kAnti = decltype(anti)::value;
+    if constexpr (decltype(model)::NCOMP == 2) {
+      if (state_rows) {
+        hipLaunchKernelGGL((path_stats_kernel<decltype(model), kAnti, false, StateRows<kAnti>>), l.grid, l.block, 0, s, l.a,
+                           m.S0, monitor_every, 1, stats);
+        return;
+      }
+    }
     if (date_rows)
       hipLaunchKernelGGL((path_stats_kernel<decltype(model), kAnti, false, DateRows<kAnti>>), l.grid, l.block, 0, s, l.a, m.S0,
                          monitor_every, 1, stats);

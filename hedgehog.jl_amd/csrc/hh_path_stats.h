@@ -4,7 +4,8 @@
 // the arithmetic of the five rows, Monitor the dates they are taken on, Extremes the two rows of the bridge form; a kernel
 // supplies its states, its step and the call after it.  DateRows is the second sink of the same walks: each kernel takes its
 // sink as its last template parameter (Monitor by default) and, instantiated on DateRows, leaves the dates themselves
-// (hh_mc_path_grid).  assets_stats_kernel (hh_assets.hip) uses Running and writes the dates out itself (its head
+// (hh_mc_path_grid); the three walks that hold a variance take StateRows as well and leave (x, v) per date
+// (hh_mc_path_states).  assets_stats_kernel (hh_assets.hip) uses Running and writes the dates out itself (its head
 // comment says why).  Internal.
 #pragma once
 #include "hh_sim.h"
@@ -64,6 +65,7 @@ struct Monitor {
   // order, eleven of the thirteen path_stats_kernel forms and every jump, QE and Bates kernel compile to the code they
   // compiled to with those locals)
   static constexpr bool kStats = true;  // keeps the five rows (DateRows: writes the dates out)
+  static constexpr bool kStates = false;  // reads the log spots alone (StateRows: the variance beside them)
   const uint32_t every;
   uint32_t left;
   bool started;
@@ -112,6 +114,7 @@ struct Monitor {
 template <bool ANTI>
 struct DateRows {
   static constexpr bool kStats = false;
+  static constexpr bool kStates = false;
   const uint32_t every;
   uint32_t left;
   double* next = nullptr;  // column i of the next row
@@ -133,6 +136,51 @@ struct DateRows {
     __builtin_nontemporal_store(exp(x), next);
     if constexpr (ANTI) __builtin_nontemporal_store(exp(xa), next + mirror);
     next += n_total;
+  }
+  __device__ __forceinline__ void store(double* __restrict__, const PathStatsLayout&, uint64_t, uint64_t) const {}
+};
+
+// The third sink, of the walks that hold a variance beside the log spot (HestonModel's Euler step, the QE step, Bates):
+// every date's STATE goes out, x and v as the walk holds them — the raw registers: no exp, and on Euler the variance
+// before any clipping (the step clips where it reads) — into the date-major, then state-major rows
+// rows[(date·2 + state)·n_total + column] of hh_assets_rows_elems at d = 2, state 0 = x, state 1 = v: the layout of
+// assets_rows_kernel, so the several-variable induction reads them as it reads those.  Row 0 is (log S0, V0) by plain
+// stores, the later rows nontemporal, the mirror of trajectory i in column n_paths + i: DateRows' access pattern, two
+// rows per date — a wave's store is 512 contiguous bytes per date, state and member.  A kernel hands the variances to
+// start / date behind `if constexpr (Sink::kStates)`: the other sinks' instantiations do not see them.
+template <bool ANTI>
+struct StateRows {
+  static constexpr bool kStats = false;
+  static constexpr bool kStates = true;
+  const uint32_t every;
+  uint32_t left;
+  double* next = nullptr;  // column i of state 0 of the next date
+  size_t n_total = 0, mirror = 0;
+  __device__ __forceinline__ StateRows(uint32_t exercise_every, int) : every(exercise_every), left(exercise_every) {}
+  __device__ __forceinline__ void bind(double* __restrict__ rows, uint64_t i, uint64_t n_paths) {
+    next = rows + i;
+    n_total = (size_t)(ANTI ? 2 * n_paths : n_paths);
+    mirror = (size_t)n_paths;
+  }
+  __device__ __forceinline__ void start(double x0, double v0) {
+    next[0] = x0;
+    next[n_total] = v0;
+    if constexpr (ANTI) {
+      next[mirror] = x0;
+      next[n_total + mirror] = v0;
+    }
+    next += 2 * n_total;
+  }
+  __device__ __forceinline__ void date(const double& x, const double& xa, const double& v, const double& va) {
+    if (--left != 0u) return;
+    left = every;
+    __builtin_nontemporal_store(x, next);
+    __builtin_nontemporal_store(v, next + n_total);
+    if constexpr (ANTI) {
+      __builtin_nontemporal_store(xa, next + mirror);
+      __builtin_nontemporal_store(va, next + n_total + mirror);
+    }
+    next += 2 * n_total;
   }
   __device__ __forceinline__ void store(double* __restrict__, const PathStatsLayout&, uint64_t, uint64_t) const {}
 };

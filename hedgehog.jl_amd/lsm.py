@@ -19,7 +19,12 @@ EXERCISE DATES, date j lying at T·j·m/steps, and spot_paths holds those dates'
 
 An American IndexOption on MultiAssetInputs under LSM(MultiAssetDynamics(), EulerMaruyama(), config, degree) is
 multiasset.solve_index_lsm's: the assets' state rows and a regression on all monomials of the standardised spots up to
-`degree` (`hh_lsm_solve_assets`); spot_paths is then the (dates + 1, assets, columns) array of simulate_asset_paths."""
+`degree` (`hh_lsm_solve_assets`); spot_paths is then the (dates + 1, assets, columns) array of simulate_asset_paths.
+
+Under stochastic volatility the spot alone does not carry the continuation value.  regressors="spot_variance" regresses on
+all monomials of the standardised spot AND variance up to `degree` (`hh_lsm_solve_path_states`: the walk's (log S, V) rows,
+then the several-variable induction at m = 2) — on HestonDynamics + EulerMaruyama under path_state="spot", on HestonQE and
+on Bates.  The default, regressors="spot", is every path above, unchanged.  simulate_state_paths returns the rows."""
 from __future__ import annotations
 
 import ctypes as C
@@ -173,14 +178,79 @@ def _solve_lsm_path(prob, method, source, model, c, T, n_dates, exercise_every, 
     return LSMSolution(prob, method, res.price, (tau, val) if stopping_info else None, grid, std_error=res.std_error, result=res)
 
 
+_REGRESSORS = ("spot", "spot_variance")
+
+
+def _state_structs(prob: PricingProblem, mc: MonteCarlo, exercise_every, path_state="spot"):
+    """(hh_path_source, hh_model, hh_config, T, n_dates) of the (log S, V) rows of mc's walk: a spot-path route whose walk
+    holds a variance (HestonQE, Bates) on its own triple, or HestonDynamics + EulerMaruyama; everything else is refused in
+    the routes' words."""
+    m = prob.market_inputs
+    if routes().own_lsm_route_of(m, mc) is not None:
+        raise MethodError("an index of several assets is regressed on its assets' spots: its walk has no variance; "
+                          'regressors="spot_variance" needs ' + routes().STATE_ROWS)
+    route = routes().lsm_route_of(m, mc)
+    if route is not None and not route.state_rows:
+        raise MethodError(f'the walk of {route.name} has no variance: regressors="spot_variance" needs ' + routes().STATE_ROWS)
+    if path_state is not None and _path_state_code(path_state) == _ffi.HH_PATH_LOG:
+        raise MethodError('regressors="spot_variance" regresses on the spot and the variance: path_state="log" is not offered with it')
+    if route is not None:
+        return _source_structs(prob, mc, route, exercise_every)
+    if not (isinstance(mc.strategy, EulerMaruyama) and isinstance(mc.dynamics, HestonDynamics)):
+        raise MethodError(f"the walk of {type(mc.dynamics).__name__} + {type(mc.strategy).__name__} has no variance rows: "
+                          'regressors="spot_variance" needs ' + routes().STATE_ROWS)
+    if path_state is None:
+        raise MethodError('LSM on Euler paths needs a named path state: regressors="spot_variance" goes with path_state="spot"')
+    if mc.devices is not None:
+        raise MethodError("LSM on Euler paths is not sharded over several GPUs")
+    n_dates = _exercise_dates(mc.config.steps, exercise_every)
+    model, c, T = _lsm_structs(prob, mc, euler=True)
+    return _ffi.make_path_source(routes().EULER.source), model, c, T, n_dates
+
+
+def _states_of(rows: np.ndarray):
+    """(spots, variances) of the device's rows[date][state][column]: exp is taken here, the variance is the walk's own"""
+    return np.exp(rows[:, 0, :]), np.ascontiguousarray(rows[:, 1, :])
+
+
+def _solve_lsm_states(prob, method, source, model, c, T, n_dates, exercise_every, spot_paths, stopping_info) -> LSMSolution:
+    """hh_lsm_solve_path_states: the (log S, V) rows of `source` on every exercise_every-th step, then the several-variable
+    induction on (S, V).  spot_paths: the (dates + 1, columns) spots, as the spot regression returns them."""
+    mc = method.mc_method
+    from .multiasset import basis_count  # C(2 + degree, degree) <= HH_LSM_MAX_BASIS
+    if not 1 <= method.degree <= 8 or basis_count(2, method.degree) > _ffi.HH_LSM_MAX_BASIS:
+        raise MethodError(f"LSM on (S, V) at degree {method.degree}: 1 <= degree <= 8 (C(2 + degree, degree) <= "
+                          f"{_ffi.HH_LSM_MAX_BASIS} basis functions)")
+    ntot = mc.config.trajectories * (2 if c.antithetic else 1)
+    tau = np.empty(ntot, dtype=np.int32) if stopping_info else None
+    val = np.empty(ntot) if stopping_info else None
+    rows = np.empty((n_dates + 1, 2, ntot)) if spot_paths else None
+    res = _ffi.hh_lsm_result()
+    ctx = _ffi.get_context(mc.device)
+    ctx.check(ctx.lib.hh_lsm_solve_path_states(
+        ctx.handle, C.byref(source), C.byref(model), C.byref(c), int(exercise_every), method.degree,
+        _date_discount(prob.market_inputs, T, mc.config.steps, int(exercise_every)), C.byref(res),
+        tau.ctypes.data if stopping_info else None, val.ctypes.data if stopping_info else None, None,
+        rows.ctypes.data if spot_paths else None))
+    return LSMSolution(prob, method, res.price, (tau, val) if stopping_info else None, _states_of(rows)[0] if spot_paths else None,
+                       std_error=res.std_error, result=res)
+
+
 def solve_lsm(prob: PricingProblem, method: LSM, spot_paths: bool = False,
-              stopping_info: bool = True, path_state=None, exercise_every=1) -> LSMSolution:
+              stopping_info: bool = True, path_state=None, exercise_every=1, regressors="spot") -> LSMSolution:
     """path_state: None (the exact sources only), "spot" or "log" (module docstring).  On an exact source
     "spot" is what it does anyway and "log" raises MethodError.  With path_state="log", spot_paths holds log S.
     exercise_every: exercise on every m-th step — on the spot-path models of routes.py, and (m > 1) on the Euler sources
     under path_state="spot"; stopping_info[0] then counts exercise dates, not steps, and spot_paths holds steps/m + 1 rows."""
     payoff, m = prob.payoff, prob.market_inputs
     mc = method.mc_method
+    if regressors not in _REGRESSORS:
+        raise ValueError(f'regressors must be "spot" or "spot_variance", not {regressors!r}')
+    if regressors == "spot_variance":  # the walk's (log S, V) rows and the induction in two variables
+        structs = _state_structs(prob, mc, exercise_every, path_state)
+        if not (isinstance(payoff, VanillaOption) and isinstance(payoff.exercise_style, American)):
+            raise MethodError("solve(::PricingProblem, ::LSM) needs an American VanillaOption")
+        return _solve_lsm_states(prob, method, *structs, exercise_every, spot_paths, stopping_info)
     if routes().own_lsm_route_of(m, mc) is not None:  # several assets: an index, state rows and a basis in several variables
         from .multiasset import solve_index_lsm
         if path_state is not None:
@@ -340,3 +410,29 @@ def simulate_spot_paths(prob: PricingProblem, mc: MonteCarlo, exercise_every=1) 
     ctx.check(ctx.lib.hh_mc_path_grid(ctx.handle, C.byref(source), C.byref(model), C.byref(c), int(exercise_every),
                                       spot.ctypes.data, 0, C.byref(res)))
     return SpotPaths(spot, np.linspace(0.0, T, n_dates + 1), res)
+
+
+@dataclass(frozen=True)
+class StatePaths:
+    """The spots and variances of a stochastic-volatility walk on every exercise_every-th step, as two (steps/exercise_every
+    + 1, n) matrices whose row j lies at times[j]; row 0 is (spot, V0).  `variance` is the walk's own state: under
+    EulerMaruyama the full-truncation scheme's unclipped variance, which can be negative.  Antithetic: n = 2·trajectories,
+    the mirror of trajectory i in column trajectories + i."""
+    spot: Any
+    variance: Any
+    times: Any
+    result: Any = field(default=None, compare=False, repr=False)
+
+
+def simulate_state_paths(prob: PricingProblem, mc: MonteCarlo, exercise_every=1) -> StatePaths:
+    """The (log S, V) rows of solve(prob, mc)'s trajectories through hh_mc_path_states, on the same seeds: HestonDynamics +
+    EulerMaruyama, HestonQE and Bates.  The last spot row is that solve's sample at expiry."""
+    source, model, c, T, n_dates = _state_structs(prob, mc, exercise_every)
+    ntot = mc.config.trajectories * (2 if c.antithetic else 1)
+    rows = np.empty((n_dates + 1, 2, ntot))
+    res = _ffi.hh_result()
+    ctx = _ffi.get_context(mc.device)
+    ctx.check(ctx.lib.hh_mc_path_states(ctx.handle, C.byref(source), C.byref(model), C.byref(c), int(exercise_every),
+                                        rows.ctypes.data, 0, C.byref(res)))
+    spot, var = _states_of(rows)
+    return StatePaths(spot, var, np.linspace(0.0, T, n_dates + 1), res)

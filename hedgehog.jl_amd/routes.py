@@ -70,6 +70,7 @@ class Route:
     source: int = None               # enum hh_path_source_kind: the route's paths as date rows (hh_mc_path_grid, LSM on them)
     solve_all: Callable = None       # (payoffs, market_inputs, method, ensemble): a grouping of its own, for one payoff or many
     own_lsm: bool = False            # an LSM on the route's own triple has an induction of its own (no date rows of one spot)
+    state_rows: bool = False         # the walk holds a variance: (log S, V) rows (hh_mc_path_states) and an LSM on (S, V)
     # ---- what it refuses, and in which words ----
     early: tuple = ()                # of the four checks above, in the route's order; `admitted` elsewhere: with the structs
     no_replay: str = None
@@ -174,7 +175,7 @@ BATES = Route(
     admits=(BatesDynamics, BatesInputs, HestonQE), not_admitted="no Bates solve for {dyn} + {strat} on {m}: use " + BATES_ROUTES,
     base=lambda m, method: (m.heston(), dataclasses.replace(method, dynamics=HestonDynamics(), strategy=EulerMaruyama())),
     strategy=_ffi.HH_QE, dual_fields=JUMPS, extras=lambda m, method: _qe(m, method) + _jump(m, method),
-    entry="hh_mc_solve_path_bates", tail=(None,), source=_ffi.HH_SOURCE_BATES, early=(admitted, european_discrete, one_device),
+    entry="hh_mc_solve_path_bates", tail=(None,), source=_ffi.HH_SOURCE_BATES, state_rows=True, early=(admitted, european_discrete, one_device),
     no_replay="Bates solves draw their own noise: no replay",
     one_device="path-dependent payoffs run on one device (MonteCarlo.devices is not supported)",
     no_duals="Bates solves carry no dual partials (ForwardAD): use FiniteDifference — its solves share their seeds",
@@ -189,7 +190,7 @@ QE = Route(
     not_admitted="HestonQE simulates HestonDynamics() on HestonInputs, not {dyn} on {m}: use EulerMaruyama or the model's exact "
                  "strategy there",
     base=lambda m, method: (m, dataclasses.replace(method, strategy=EulerMaruyama())), strategy=_ffi.HH_QE, extras=_qe,
-    entry="hh_mc_solve_path_qe", tail=(None,), source=_ffi.HH_SOURCE_QE, early=(european_discrete, one_device),
+    entry="hh_mc_solve_path_qe", tail=(None,), source=_ffi.HH_SOURCE_QE, state_rows=True, early=(european_discrete, one_device),
     no_replay="HestonQE solves draw their own noise: no replay (EulerMaruyama takes one)",
     one_device="path-dependent payoffs run on one device (MonteCarlo.devices is not supported)",
     no_duals="HestonQE solves carry no dual partials (ForwardAD): use FiniteDifference — its solves share their seeds",
@@ -268,6 +269,9 @@ def lsm_route_of(market_inputs, mc) -> Route:
     for route in SPOT_PATHS:
         if route.takes_lsm(market_inputs, mc):
             return route
+
+
+STATE_ROWS = "HestonDynamics() + EulerMaruyama() (under path_state=\"spot\"), HestonQE and Bates"  # the walks with a variance
 
 
 def own_lsm_route_of(market_inputs, mc) -> Route:

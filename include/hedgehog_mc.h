@@ -1441,8 +1441,10 @@ int hh_carr_madan_vg(hh_ctx* ctx, const hh_model* model, const hh_vg* vg, double
  * hh_lsm_solve_path checks exercise_every first, then the induction's scalars on its n_dates (in hh_lsm_solve_euler's
  * words), then everything the source's entry point checks; where several things are wrong the first of these is reported.
  * Not provided: sharded and multi-GPU forms, the log path state (the regression on log S is hh_lsm_solve_euler's, on
- * every step), variance rows for QE and Bates, the bridge form, the coupled kernel (the several-asset walk has state rows of its own:
- * "American exercise on several state rows").
+ * every step), the bridge form, the coupled kernel (the several-asset walk has state rows of its own: "American exercise
+ * on several state rows").
+ * Provided elsewhere: variance rows for QE and Bates, and for Heston Euler — hh_mc_path_states, "American exercise under
+ * stochastic volatility".
  */
 enum hh_path_source_kind { HH_SOURCE_EULER = 0, HH_SOURCE_JUMP = 1, HH_SOURCE_QE = 2, HH_SOURCE_BATES = 3,
                            HH_SOURCE_LOCALVOL = 4, HH_SOURCE_VG = 5 };
@@ -1477,9 +1479,13 @@ int hh_lsm_solve_path(hh_ctx* ctx, const hh_path_source* source, const hh_model*
  *
  * hh_lsm_solve_states — the backward induction on a DEVICE grid rows_dev[n_dates + 1][m][n_total] of m = desc->n_states
  * state rows per date the caller supplies; the counterpart of hh_lsm_solve_grid.  desc says how a column's m states give
- * the exercise value and the m regressors.  HH_LSM_STATES_LOG_ASSETS, the one kind: the states are log-states of assets,
+ * the exercise value and the m regressors.  HH_LSM_STATES_LOG_ASSETS: the states are log-states of assets,
  *   exercise value  pay = cp·(I − strike), I the index of kind index_kind and weights[] on the m states (above)
  *   regressors      v_i = exp(x_i), in asset order
+ * HH_LSM_STATES_LOG_SPOT_VARIANCE (n_states = 2; index_kind and weights are not read): state 0 is a log spot, state 1 a
+ * variance ("American exercise under stochastic volatility" below),
+ *   exercise value  pay = cp·(exp(x_0) − strike)
+ *   regressors      v_0 = exp(x_0), v_1 = x_1 — the variance as stored
  * Per date t = n_dates − 1 down to 1, on the columns IN THE MONEY, pay > 0, alone (the one-variable rule; the others
  * add exact zeros to every sum):
  *   statistics   n, Σv_i, Σv_i²;  μ_i = Σv_i/n, var_i = Σv_i²/n − μ_i·μ_i, isd_i = 1/sqrt(var_i) if var_i > 0 else 1
@@ -1509,18 +1515,18 @@ int hh_lsm_solve_path(hh_ctx* ctx, const hh_path_source* source, const hh_model*
  * All synchronous.  Errors, checked on the host before any launch, in hh_mc_path_stats_assets' and hh_lsm_solve_path's
  * words wherever the check is the same; a refusal uses no timing slot.  HH_ERR_INVALID: a NULL ctx, model, assets, cfg,
  * desc, rows / rows_dev or out (hh_assets_path_rows: rows); exercise_every = 0 or not a divisor of n_steps; n_dates >
- * 65534; an unknown descriptor kind or index kind; n_states outside 1 .. HH_MAX_ASSETS; cp not ±1; strike or a weight
+ * 65534; an unknown descriptor kind or index kind; n_states outside 1 .. HH_MAX_ASSETS (HH_LSM_STATES_LOG_SPOT_VARIANCE:
+ * other than 2); cp not ±1; strike or a weight
  * not finite; degree outside 1 .. 8; date_discount not finite or <= 0; n_total = 0 or above 2^31 − 128; everything
  * hh_mc_path_stats_assets rejects.  HH_ERR_UNSUPPORTED: C(m + degree, degree) > HH_LSM_MAX_BASIS; REPLAY noise,
  * n_partials > 0, dynamics or a strategy that are not the walk's own.  hh_lsm_solve_assets checks exercise_every first,
  * then the induction's scalars, then everything hh_assets_path_rows checks.
- * Not provided: variance rows and a regression on (S, V) (a second descriptor kind on the same induction), a persistent
- * or cooperative form, sharded and multi-GPU forms, REPLAY or Sobol' noise, dual partials, basis families other than
+ * Not provided: a persistent or cooperative form, sharded and multi-GPU forms, REPLAY or Sobol' noise, dual partials, basis families other than
  * monomials (sorted assets, the payoff as a regressor, Laguerre), more than HH_LSM_MAX_BASIS functions, barriers on
  * single assets, a Julia binding.
  */
 #define HH_LSM_MAX_BASIS 45
-enum hh_lsm_states_kind { HH_LSM_STATES_LOG_ASSETS = 0 };
+enum hh_lsm_states_kind { HH_LSM_STATES_LOG_ASSETS = 0, HH_LSM_STATES_LOG_SPOT_VARIANCE = 1 };
 typedef struct hh_lsm_states {        /* 88 bytes */
   int32_t kind;                       /* enum hh_lsm_states_kind */
   uint32_t n_states;                  /* m, 1 .. HH_MAX_ASSETS */
@@ -1538,6 +1544,51 @@ int hh_lsm_solve_states(hh_ctx* ctx, const hh_lsm_states* desc, const double* ro
 int hh_lsm_solve_assets(hh_ctx* ctx, const hh_model* model, const hh_assets* assets, const hh_config* cfg,
                         uint32_t exercise_every, int32_t degree, double date_discount, hh_lsm_result* out,
                         int32_t* stop_time, double* stop_value, double* rows);
+
+/*
+ * American exercise under stochastic volatility: the state rows (log spot, variance) of the walks that hold a variance,
+ * and Longstaff–Schwartz with a regression on (S, V) on them (kernels: path_stats_kernel<HestonModel, …>, qe_stats_kernel
+ * and bates_stats_kernel instantiated on the third sink, StateRows<ANTI>, hh_path_stats.h; the induction, hh_lsm_multi.hip).
+ *
+ * hh_mc_path_states — the walk the source names ("Date rows of the log-spot path family": the same draws, step and
+ * host-formed constants as its path_stats entry point) with no statistics: on every exercise_every-th step the lane's
+ * log spot x and variance v.  Admitted sources: HH_SOURCE_EULER under Heston dynamics, HH_SOURCE_QE, HH_SOURCE_BATES.
+ * n_dates = n_steps / exercise_every.  rows (host, or device when rows_on_device) takes hh_assets_rows_elems(n_paths,
+ * n_dates, 2, antithetic) = (n_dates + 1)·2·n_total doubles, hh_assets_path_rows' layout at d = 2:
+ *   rows[(date·2 + state)·n_total + column]      state 0 = x, state 1 = v, n_total = n_paths·(1 + antithetic) columns
+ *   date 0: (log S0, V0) in every column;  date j: the state after step j·exercise_every;  column n_paths + i: the mirror
+ * RAW STATE: x and v are stored as the walk holds them.  No exp is formed; under HH_SOURCE_EULER v is the full-truncation
+ * scheme's unclipped variance, which can be negative (the step clips where it reads it) — hh_euler_grid's var_grid, and at
+ * exercise_every = 1 the x rows are hh_euler_grid's HH_PATH_LOG rows, both bit for bit.  Under QE and Bates v >= 0 and the
+ * last v row is var_T of the source's path_stats entry point.  The x rows added in date order are HH_STAT_SUM_X of that
+ * entry point at monitor_every = exercise_every, include_start = 0; the rows at exercise_every = m are rows 0, m, 2m, …
+ * of the rows at exercise_every = 1; the non-mirrored half of an antithetic grid equals the plain grid.  out (nullable):
+ * n_paths_done and the times.  Timing: one slot.
+ *
+ * hh_lsm_solve_path_states — those rows into the context, then hh_lsm_solve_states on them with
+ * {HH_LSM_STATES_LOG_SPOT_VARIANCE, 2, cp and strike of the model}: the exercise value cp·(exp(x) − strike), the
+ * regressors S = exp(x) and v, the variance as stored.  date_discount is the discount over ONE EXERCISE PERIOD.
+ * stop_time, stop_value (nullable, host, n_total), coef (nullable, host, n_dates·C(2 + degree, degree)): as
+ * hh_lsm_solve_states'.  rows (nullable, host): the state rows.  exercise_every = n_steps leaves one date: the European
+ * price, date_discount times the mean payoff at expiry.
+ *
+ * Both are synchronous.  Errors, checked on the host before any launch, in the words of the source's path_stats entry
+ * point and of hh_lsm_solve_assets wherever the check is the same; a refusal uses no timing slot.  HH_ERR_INVALID: a NULL
+ * ctx, source, model, cfg, rows (hh_mc_path_states), out (hh_lsm_solve_path_states) or a struct the kind lists; an
+ * unknown source kind; exercise_every = 0 or not a divisor of n_steps; n_dates > 65534; cp not ±1; a strike not finite;
+ * degree outside 1 .. 8; date_discount not finite or <= 0; everything the source's path_stats entry point rejects.
+ * HH_ERR_UNSUPPORTED: HH_SOURCE_JUMP, HH_SOURCE_LOCALVOL, HH_SOURCE_VG, and lognormal dynamics on HH_SOURCE_EULER — the
+ * walk has no variance; REPLAY noise, n_partials > 0, dynamics or a strategy that are not the kernel's own.
+ * hh_lsm_solve_path_states checks exercise_every first, then the induction's scalars, then everything hh_mc_path_states
+ * checks.
+ * Not provided: a log-spot or payoff regressor and Laguerre bases, variance rows of the exact Heston and Broadie–Kaya
+ * sources, a persistent form of the induction, REPLAY or Sobol' noise, dual partials, multi-GPU, a Julia binding.
+ */
+int hh_mc_path_states(hh_ctx* ctx, const hh_path_source* source, const hh_model* model, const hh_config* cfg,
+                      uint32_t exercise_every, double* rows, int32_t rows_on_device, hh_result* out);
+int hh_lsm_solve_path_states(hh_ctx* ctx, const hh_path_source* source, const hh_model* model, const hh_config* cfg,
+                             uint32_t exercise_every, int32_t degree, double date_discount, hh_lsm_result* out,
+                             int32_t* stop_time, double* stop_value, double* coef, double* rows);
 
 /*
  * A SimulationConfig's seed vector in the device memory of ctx, uploaded once and kept — repeated solves on one
