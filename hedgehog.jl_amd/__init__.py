@@ -19,8 +19,9 @@ from .greeks import (AssetSpotLens, AssetVolLens, BatchGreekProblem, Correlation
                      ForwardAD, GreekProblem, GreekResult, Pathwise, PropertyLens, SecondOrderGreekProblem, SpotLens,
                      VolLens,
                      ZeroRateSpineLens, optic, set)
-from .lsm import (LSM, EulerPaths, HestonExactPaths, LSMSolution, SpotPaths, StatePaths, simulate_euler_paths,
-                  simulate_heston_exact_paths, simulate_spot_paths, simulate_state_paths, solve_lsm)
+from .lsm import (LSM, BoundsSolution, DualBounds, EulerPaths, ExercisePolicy, HestonExactPaths, LSMSolution, SpotPaths,
+                  StatePaths, fit_policy, policy_value, simulate_euler_paths, simulate_heston_exact_paths, simulate_spot_paths,
+                  simulate_state_paths, solve_dual_bounds, solve_lsm, upper_bound)
 from .montecarlo import (AbstractPricingMethod, Antithetic, BatesDynamics, BlackScholesExact, EulerMaruyama,
                          HestonBroadieKaya, HestonDynamics, HestonQE, LognormalDynamics, MertonDynamics, MertonExact, MethodError,
                          MonteCarlo, NoVarianceReduction, NormalLaw, SimulationConfig, VarianceGammaDynamics,
@@ -84,6 +85,9 @@ def solve(*args, **kw):
                                   American / Bermudan baskets and rainbows: a regression basis in several variables
         solve(prob::PricingProblem{<:VanillaOption{…,American,…}}, ::LSM; exercise_every=m, regressors="spot_variance")
                                   Heston Euler (path_state="spot"), HestonQE, Bates: the regression on spot AND variance
+        solve(prob::PricingProblem{<:VanillaOption{…,American,…}, HestonInputs},
+              ::DualBounds(LSM(HestonDynamics(), EulerMaruyama(), config, degree), outer=, inner=, fresh=, inner_seed=); exercise_every=m)
+                                  the bracket: the fitted policy on fresh paths (lower), the Andersen–Broadie dual (upper)
         solve(prob::PricingProblem{<:VanillaOption}, ::CoxRossRubinsteinMethod) cox_ross_rubinstein.jl:99
         solve(prob::BasketPricingProblem, ::CoxRossRubinsteinMethod)         basket.jl:35
         solve(prob::PricingProblem{<:VanillaOption} | ::BasketPricingProblem, ::CrankNicolsonMethod)
@@ -120,6 +124,8 @@ def solve(*args, **kw):
         return solve_merton_analytic(args[0], args[1])
     if len(args) == 2 and isinstance(args[0], PricingProblem) and isinstance(args[1], LSM):
         return solve_lsm(args[0], args[1], **kw)
+    if len(args) == 2 and isinstance(args[0], PricingProblem) and isinstance(args[1], DualBounds):
+        return solve_dual_bounds(args[0], args[1], **kw)
     if len(args) == 2 and isinstance(args[0], PricingProblem) and isinstance(args[1], CoxRossRubinsteinMethod):
         return solve_crr(args[0], args[1])
     if len(args) == 2 and isinstance(args[0], PricingProblem) and isinstance(args[1], CrankNicolsonMethod):

@@ -15,7 +15,7 @@ LIB = os.path.join(HERE, "lib", "libhedgehog_mc.so")
 OBJ = os.path.join(HERE, "lib", "obj")
 SOURCES = ["hh_api.hip", "hh_mgpu.hip", "hh_kernels.hip", "hh_multi.hip", "hh_bk.hip", "hh_lsm.hip", "hh_fourier.hip", "hh_crr.hip",
            "hh_path.hip", "hh_jump.hip", "hh_qe.hip", "hh_bates.hip", "hh_fd.hip", "hh_assets.hip",
-           "hh_localvol.hip", "hh_sobol.hip", "hh_vg.hip", "hh_lsm_multi.hip"]
+           "hh_localvol.hip", "hh_sobol.hip", "hh_vg.hip", "hh_lsm_multi.hip", "hh_bounds.hip"]
 # (source, object, extra flags): hh_bk.hip is built without the machine-code LICM pass — see the head of that file
 UNITS = [(s, s.replace(".hip", ".o"), ["-mllvm", "-disable-machine-licm"] if s == "hh_bk.hip" else []) for s in SOURCES]
 CFLAGS = ["-fPIC", "-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off", "-Wall",

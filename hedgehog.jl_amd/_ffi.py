@@ -97,6 +97,13 @@ class hh_lsm_result(C.Structure):
                 ("form", C.c_int32), ("persistent_fallbacks", C.c_int32)]
 
 
+class hh_bounds_result(C.Structure):
+    """hh_lsm_upper_bound's result: the dual upper bound, its standard error, the sizes and the two kernels' times."""
+    _fields_ = [("upper", C.c_double), ("upper_se", C.c_double), ("n_outer", C.c_uint64),
+                ("n_inner", C.c_uint32), ("reserved", C.c_uint32),
+                ("nested_ms", C.c_double), ("outer_ms", C.c_double), ("total_ms", C.c_double)]
+
+
 class hh_path_payoff(C.Structure):
     _fields_ = [("kind", C.c_int32), ("barrier_type", C.c_int32), ("strike", C.c_double), ("cp", C.c_double),
                 ("barrier", C.c_double), ("rebate", C.c_double), ("cash", C.c_double)]
@@ -274,6 +281,17 @@ SYMBOLS = [
                                     C.c_int32, C.POINTER(hh_result)]),
     ("hh_lsm_solve_path_states", C.c_int, [_vp, C.POINTER(hh_path_source), C.POINTER(hh_model), C.POINTER(hh_config),
                                            C.c_uint32, C.c_int32, C.c_double, C.POINTER(hh_lsm_result), _vp, _vp, _vp, _vp]),
+    ("hh_lsm_policy_elems", C.c_size_t, [C.c_uint32, C.c_uint32, C.c_int32]),
+    ("hh_lsm_fit_states", C.c_int, [_vp, C.POINTER(hh_lsm_states), _vp, C.c_uint64, C.c_uint32, C.c_int32, C.c_double,
+                                    C.POINTER(hh_lsm_result), _vp, _vp, _vp]),
+    ("hh_lsm_fit_path_states", C.c_int, [_vp, C.POINTER(hh_path_source), C.POINTER(hh_model), C.POINTER(hh_config), C.c_uint32,
+                                         C.c_int32, C.c_double, C.POINTER(hh_lsm_result), _vp]),
+    ("hh_lsm_policy_value", C.c_int, [_vp, C.POINTER(hh_lsm_states), _vp, C.c_int32, _vp, C.c_uint64, C.c_uint32, C.c_double,
+                                      C.POINTER(hh_lsm_result), _vp, _vp]),
+    ("hh_lsm_policy_value_path", C.c_int, [_vp, C.POINTER(hh_path_source), C.POINTER(hh_model), C.POINTER(hh_config), C.c_uint32,
+                                           _vp, C.c_int32, C.c_double, C.POINTER(hh_lsm_result)]),
+    ("hh_lsm_upper_bound", C.c_int, [_vp, C.POINTER(hh_model), C.POINTER(hh_config), C.c_uint32, _vp, C.c_int32, C.c_double,
+                                     C.c_uint32, C.c_uint64, C.POINTER(hh_bounds_result), _vp, _vp, _vp]),
     ("hh_mc_path_stats_lv", C.c_int, [_vp, C.POINTER(hh_model), C.POINTER(hh_localvol), C.POINTER(hh_config), C.c_uint32,
                                       C.c_int32, C.c_int32, _vp, C.c_int32, C.POINTER(hh_result)]),
     ("hh_mc_solve_path_lv", C.c_int, [_vp, C.POINTER(hh_model), C.POINTER(hh_localvol), C.POINTER(hh_config), C.c_uint32,

@@ -2119,7 +2119,7 @@ static int check_lsm_states(hh_ctx* ctx, const char* who, const hh_lsm_states* d
 // ctx->ev0 and has checked everything.
 static int lsm_on_states(hh_ctx* ctx, const hh_lsm_states* d, const double* rows_dev, uint64_t ntot, uint32_t n_dates,
                          int32_t degree, double date_discount, hh_lsm_result* out, int32_t* stop_time, double* stop_value,
-                         double* coef, const WallClock& clock) {
+                         double* coef, const WallClock& clock, double* policy = nullptr) {
   const hh::LsmMultiScratch at(ntot, n_dates);
   const uint32_t ch = hh::lsm_chunks(ntot);
   int rc;
@@ -2144,7 +2144,30 @@ static int lsm_on_states(hh_ctx* ctx, const hh_lsm_states* d, const double* rows
     HH_HIP(ctx, hipMemcpy2DAsync(coef, B * sizeof(double), ctx->lsm_scratch + at.coef, hh::kLsmMultiPad * sizeof(double),
                                  B * sizeof(double), n_dates, hipMemcpyDeviceToHost, ctx->stream));
   }
+  // the policy (hh_lsm_fit_states): one more copy — the statistics the induction standardised by, and the coefficients
+  const size_t rows = (size_t)n_dates + 1;
+  std::vector<double> rowstat, coef_pad;
+  if (policy) {
+    rowstat.resize(rows * hh::kLsmMultiStats);
+    coef_pad.resize(rows * hh::kLsmMultiPad);
+    HH_HIP(ctx, hipMemcpyAsync(rowstat.data(), ctx->lsm_scratch + at.rowstat, rowstat.size() * sizeof(double),
+                               hipMemcpyDeviceToHost, ctx->stream));
+    HH_HIP(ctx, hipMemcpyAsync(coef_pad.data(), ctx->lsm_scratch + at.coef, coef_pad.size() * sizeof(double),
+                               hipMemcpyDeviceToHost, ctx->stream));
+  }
   HH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  if (policy) {  // [date][μ_i, isd_i, coef_j]; a date that was not regressed (0, n_dates): μ = 0, isd = 1, coef = 0
+    const size_t m = d->n_states, B = (size_t)hh::lsm_basis_count((int)m, degree), stride = 2 * m + B;
+    for (size_t t = 0; t < rows; ++t) {
+      const bool regressed = t >= 1 && t < n_dates;
+      const double* rs = rowstat.data() + t * hh::kLsmMultiStats;
+      for (size_t i = 0; i < m; ++i) {
+        policy[t * stride + i] = regressed ? rs[1 + i] : 0.0;
+        policy[t * stride + m + i] = regressed ? rs[1 + HH_MAX_ASSETS + i] : 1.0;
+      }
+      for (size_t j = 0; j < B; ++j) policy[t * stride + 2 * m + j] = regressed ? coef_pad[t * hh::kLsmMultiPad + j] : 0.0;
+    }
+  }
   if ((rc = hh_lsm_finalize(ctx->accum_host, out))) return finalize_failed(ctx, rc);
   out->rows_regressed = (uint32_t)counters[0];
   out->rows_skipped = (uint32_t)counters[1];
@@ -2253,13 +2276,15 @@ int hh_mc_path_states(hh_ctx* ctx, const hh_path_source* source, const hh_model*
   }, /*states=*/true);
 }
 
-int hh_lsm_solve_path_states(hh_ctx* ctx, const hh_path_source* source, const hh_model* m, const hh_config* c,
-                             uint32_t exercise_every, int32_t degree, double date_discount, hh_lsm_result* out,
-                             int32_t* stop_time, double* stop_value, double* coef, double* rows) {
+// hh_lsm_solve_path_states and, with a policy, hh_lsm_fit_path_states (`who`; need_policy: its policy may not be NULL)
+static int lsm_path_states_call(hh_ctx* ctx, const char* who, const hh_path_source* source, const hh_model* m,
+                                const hh_config* c, uint32_t exercise_every, int32_t degree, double date_discount,
+                                hh_lsm_result* out, int32_t* stop_time, double* stop_value, double* coef, double* rows,
+                                double* policy, bool need_policy) {
   if (!ctx) return HH_ERR_INVALID;
   std::lock_guard<std::recursive_mutex> lock__(ctx->mu);
-  return with_source_family(ctx, "hh_lsm_solve_path_states", source, [&](const PathFamily& f) -> int {
-    if (!m || !c || !out || f.missing) return fail(ctx, HH_ERR_INVALID, "%s: NULL argument", f.who);
+  return with_source_family(ctx, who, source, [&](const PathFamily& f) -> int {
+    if (!m || !c || !out || f.missing || (need_policy && !policy)) return fail(ctx, HH_ERR_INVALID, "%s: NULL argument", f.who);
     const WallClock clock;
     // the schedule first, then the induction's scalars on its dates, then everything the source's entry point checks
     int rc = check_every(ctx, f.who, "exercise_every", exercise_every, c->n_steps);
@@ -2277,7 +2302,8 @@ int hh_lsm_solve_path_states(hh_ctx* ctx, const hh_path_source* source, const hh
     HH_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
     if ((rc = run_path_stats(ctx, f, m, c, exercise_every, 1))) return rc;
     const uint64_t ntot = c->n_paths * (c->antithetic ? 2 : 1);
-    rc = lsm_on_states(ctx, &d, ctx->lsm_grid, ntot, n_dates, degree, date_discount, out, stop_time, stop_value, coef, clock);
+    rc = lsm_on_states(ctx, &d, ctx->lsm_grid, ntot, n_dates, degree, date_discount, out, stop_time, stop_value, coef, clock,
+                       policy);
     if (rc) return rc;
     if ((rc = release_host_operands(ctx))) return rc;
     if (rows) {
@@ -2287,6 +2313,241 @@ int hh_lsm_solve_path_states(hh_ctx* ctx, const hh_path_source* source, const hh
     }
     return HH_OK;
   }, /*states=*/true);
+}
+
+int hh_lsm_solve_path_states(hh_ctx* ctx, const hh_path_source* source, const hh_model* m, const hh_config* c,
+                             uint32_t exercise_every, int32_t degree, double date_discount, hh_lsm_result* out,
+                             int32_t* stop_time, double* stop_value, double* coef, double* rows) {
+  return lsm_path_states_call(ctx, "hh_lsm_solve_path_states", source, m, c, exercise_every, degree, date_discount, out,
+                              stop_time, stop_value, coef, rows, nullptr, false);
+}
+
+// ---- dual bounds: the policy as an array, its value on other rows, the nested upper bound (hedgehog_mc.h, "Dual bounds for
+// American exercise"; kernels: policy_value_kernel of hh_lsm_multi.hip, hh_bounds.hip) ----
+
+size_t hh_lsm_policy_elems(uint32_t n_dates, uint32_t m, int32_t degree) {
+  const int B = m <= (uint32_t)HH_MAX_ASSETS ? hh::lsm_basis_count((int)m, degree) : 0;
+  return B ? ((size_t)n_dates + 1) * (2 * (size_t)m + (size_t)B) : 0;
+}
+
+int hh_lsm_fit_states(hh_ctx* ctx, const hh_lsm_states* desc, const double* rows_dev, uint64_t n_total, uint32_t n_dates,
+                      int32_t degree, double date_discount, hh_lsm_result* out, int32_t* stop_time, double* stop_value,
+                      double* policy) {
+  if (!ctx) return HH_ERR_INVALID;
+  std::lock_guard<std::recursive_mutex> lock__(ctx->mu);
+  static const char who[] = "hh_lsm_fit_states";
+  if (!desc || !rows_dev || !out || !policy) return fail(ctx, HH_ERR_INVALID, "%s: NULL argument", who);
+  const WallClock clock;
+  int rc = check_lsm_states_scalars(ctx, desc->cp, n_total, n_dates, degree, date_discount);
+  if (rc) return rc;
+  if ((rc = check_lsm_states(ctx, who, desc, degree))) return rc;
+  HH_HIP(ctx, hipSetDevice(ctx->device));
+  HH_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+  return lsm_on_states(ctx, desc, rows_dev, n_total, n_dates, degree, date_discount, out, stop_time, stop_value, nullptr, clock,
+                       policy);
+}
+
+int hh_lsm_fit_path_states(hh_ctx* ctx, const hh_path_source* source, const hh_model* m, const hh_config* c,
+                           uint32_t exercise_every, int32_t degree, double date_discount, hh_lsm_result* out, double* policy) {
+  return lsm_path_states_call(ctx, "hh_lsm_fit_path_states", source, m, c, exercise_every, degree, date_discount, out, nullptr,
+                              nullptr, nullptr, nullptr, policy, true);
+}
+
+// every entry of a caller's policy is finite (after check_lsm_states: the basis exists)
+static int check_policy(hh_ctx* ctx, const char* who, const double* policy, uint32_t n_dates, uint32_t m, int32_t degree) {
+  const size_t n = hh_lsm_policy_elems(n_dates, m, degree), stride = n / ((size_t)n_dates + 1);
+  for (size_t k = 0; k < n; ++k)
+    if (!std::isfinite(policy[k]))
+      return fail(ctx, HH_ERR_INVALID, "%s: policy entry %zu of date %zu is not finite", who, k % stride, k / stride);
+  return HH_OK;
+}
+
+// the descriptor of the (log S, V) rows under the model's payoff
+static hh_lsm_states spot_variance_states(const hh_model* m) {
+  hh_lsm_states d{};
+  d.kind = HH_LSM_STATES_LOG_SPOT_VARIANCE;
+  d.n_states = 2;
+  d.cp = m->cp;
+  d.strike = m->strike;
+  return d;
+}
+
+// The policy and, behind it, D^k for k = 0 .. n_dates into ctx->lsm_policy; *disc_dev: where the powers start.
+static int stage_policy(hh_ctx* ctx, const double* policy, size_t n_policy, uint32_t n_dates, double date_discount,
+                        const double** policy_dev, const double** disc_dev) {
+  std::vector<double> host(policy, policy + n_policy);
+  for (uint32_t k = 0; k <= n_dates; ++k) host.push_back(std::pow(date_discount, (double)k));
+  int rc = ensure(ctx, ctx->lsm_policy, host.size());
+  if (rc) return rc;
+  HH_HIP(ctx, hipMemcpyAsync(ctx->lsm_policy, host.data(), host.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  HH_HIP(ctx, hipStreamSynchronize(ctx->stream));  // `host` goes with this frame
+  *policy_dev = ctx->lsm_policy;
+  if (disc_dev) *disc_dev = ctx->lsm_policy + n_policy;
+  return HH_OK;
+}
+
+// A checked policy run forward on state rows in device memory: launches, reduction and the copies back.  The caller
+// recorded ctx->ev0.
+static int policy_on_states(hh_ctx* ctx, const hh_lsm_states* d, const double* policy, int32_t degree, const double* rows_dev,
+                            uint64_t ntot, uint32_t n_dates, double date_discount, hh_lsm_result* out, int32_t* stop_time,
+                            double* stop_value, const WallClock& clock) {
+  const uint32_t ch = hh::lsm_chunks(ntot);
+  int rc;
+  if ((rc = ensure(ctx, ctx->lsm_val, (size_t)ntot))) return rc;
+  if ((rc = ensure(ctx, ctx->lsm_tau, (size_t)ntot))) return rc;
+  if ((rc = ensure(ctx, ctx->records, (size_t)ch * hh::kRecStride))) return rc;
+  const double* policy_dev = nullptr;
+  if ((rc = stage_policy(ctx, policy, hh_lsm_policy_elems(n_dates, d->n_states, degree), n_dates, date_discount, &policy_dev,
+                         nullptr)))
+    return rc;
+  if ((rc = begin_timing(ctx))) return rc;
+  HH_HIP(ctx, hh::launch_policy_value(*d, rows_dev, ntot, n_dates, degree, date_discount, policy_dev, ctx->lsm_tau, ctx->lsm_val,
+                                      ctx->records, ctx->stream));
+  if ((rc = end_timing(ctx))) return rc;
+  HH_HIP(ctx, hh::launch_reduce_records(ctx->records, ch, (double)ntot, ctx->accum, ctx->stream));
+  HH_HIP(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+  HH_HIP(ctx, hipMemcpyAsync(ctx->accum_host, ctx->accum, HH_ACC_LEN * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  if (stop_time)
+    HH_HIP(ctx, hipMemcpyAsync(stop_time, ctx->lsm_tau, ntot * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+  if (stop_value)
+    HH_HIP(ctx, hipMemcpyAsync(stop_value, ctx->lsm_val, ntot * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  HH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  if ((rc = hh_lsm_finalize(ctx->accum_host, out))) return finalize_failed(ctx, rc);
+  out->form = hh::kLsmFormPerDate;
+  return solve_times(ctx, clock, &out->kernel_ms, &out->total_ms);
+}
+
+int hh_lsm_policy_value(hh_ctx* ctx, const hh_lsm_states* desc, const double* policy, int32_t degree, const double* rows_dev,
+                        uint64_t n_total, uint32_t n_dates, double date_discount, hh_lsm_result* out, int32_t* stop_time,
+                        double* stop_value) {
+  if (!ctx) return HH_ERR_INVALID;
+  std::lock_guard<std::recursive_mutex> lock__(ctx->mu);
+  static const char who[] = "hh_lsm_policy_value";
+  if (!desc || !policy || !rows_dev || !out) return fail(ctx, HH_ERR_INVALID, "%s: NULL argument", who);
+  const WallClock clock;
+  int rc = check_lsm_states_scalars(ctx, desc->cp, n_total, n_dates, degree, date_discount);
+  if (rc) return rc;
+  if ((rc = check_lsm_states(ctx, who, desc, degree))) return rc;
+  if ((rc = check_policy(ctx, who, policy, n_dates, desc->n_states, degree))) return rc;
+  HH_HIP(ctx, hipSetDevice(ctx->device));
+  HH_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+  return policy_on_states(ctx, desc, policy, degree, rows_dev, n_total, n_dates, date_discount, out, stop_time, stop_value,
+                          clock);
+}
+
+int hh_lsm_policy_value_path(hh_ctx* ctx, const hh_path_source* source, const hh_model* m, const hh_config* c,
+                             uint32_t exercise_every, const double* policy, int32_t degree, double date_discount,
+                             hh_lsm_result* out) {
+  if (!ctx) return HH_ERR_INVALID;
+  std::lock_guard<std::recursive_mutex> lock__(ctx->mu);
+  return with_source_family(ctx, "hh_lsm_policy_value_path", source, [&](const PathFamily& f) -> int {
+    if (!m || !c || !policy || !out || f.missing) return fail(ctx, HH_ERR_INVALID, "%s: NULL argument", f.who);
+    const WallClock clock;
+    // hh_lsm_solve_path_states' order: the schedule, the induction's scalars, the policy, then what the walk's entry point checks
+    int rc = check_every(ctx, f.who, "exercise_every", exercise_every, c->n_steps);
+    if (rc) return rc;
+    const uint32_t n_dates = c->n_steps / exercise_every;
+    if ((rc = check_lsm_states_scalars(ctx, m->cp, c->n_paths, n_dates, degree, date_discount))) return rc;
+    const hh_lsm_states d = spot_variance_states(m);
+    if ((rc = check_lsm_states(ctx, f.who, &d, degree))) return rc;
+    if ((rc = check_policy(ctx, f.who, policy, n_dates, 2, degree))) return rc;
+    if ((rc = check_walk_has_variance(ctx, f, c))) return rc;
+    HH_HIP(ctx, hipSetDevice(ctx->device));
+    HH_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+    if ((rc = run_path_stats(ctx, f, m, c, exercise_every, 1))) return rc;
+    const uint64_t ntot = c->n_paths * (c->antithetic ? 2 : 1);
+    rc = policy_on_states(ctx, &d, policy, degree, ctx->lsm_grid, ntot, n_dates, date_discount, out, nullptr, nullptr, clock);
+    if (rc) return rc;
+    return release_host_operands(ctx);
+  }, /*states=*/true);
+}
+
+int hh_lsm_upper_bound(hh_ctx* ctx, const hh_model* m, const hh_config* c, uint32_t exercise_every, const double* policy,
+                       int32_t degree, double date_discount, uint32_t n_inner, uint64_t inner_seed, hh_bounds_result* out,
+                       double* cont, double* cont_se, double* pathwise_max) {
+  if (!ctx) return HH_ERR_INVALID;
+  std::lock_guard<std::recursive_mutex> lock__(ctx->mu);
+  const PathFamily f = PathFamily("hh_lsm_upper_bound", 0, HH_EXTREMES_MONITORED).states();
+  const char* who = f.who;
+  if (!m || !c || !policy || !out) return fail(ctx, HH_ERR_INVALID, "%s: NULL argument", who);
+  const WallClock clock;
+  int rc = check_every(ctx, who, "exercise_every", exercise_every, c->n_steps);
+  if (rc) return rc;
+  const uint32_t n_dates = c->n_steps / exercise_every;
+  if ((rc = check_lsm_states_scalars(ctx, m->cp, c->n_paths, n_dates, degree, date_discount))) return rc;
+  const hh_lsm_states d = spot_variance_states(m);
+  if ((rc = check_lsm_states(ctx, who, &d, degree))) return rc;
+  if (n_inner == 0 || n_inner % 64u)
+    return fail(ctx, HH_ERR_INVALID, "%s: n_inner (%u) must be a multiple of 64 and >= 64 (a wave walks 64 inner paths at a time)",
+                who, n_inner);
+  if ((rc = check_policy(ctx, who, policy, n_dates, 2, degree))) return rc;
+  if ((uint64_t)n_dates * c->n_paths > 0x80000000ull)
+    return fail(ctx, HH_ERR_INVALID, "%s: n_dates·n_outer = %llu pairs are above 2^31", who,
+                (unsigned long long)n_dates * (unsigned long long)c->n_paths);
+  if (c->dynamics != HH_HESTON || c->strategy != HH_EULER_MARUYAMA)
+    return fail(ctx, HH_ERR_UNSUPPORTED, "%s needs HestonDynamics + EulerMaruyama: the nested walks restart the Heston Euler step "
+                "(no QE, Bates, several-asset or one-variable form)", who);
+  if (c->antithetic)
+    return fail(ctx, HH_ERR_UNSUPPORTED, "%s: no antithetic outer paths (the martingale is built per outer column)", who);
+  HH_HIP(ctx, hipSetDevice(ctx->device));
+  HH_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+  if ((rc = run_path_stats(ctx, f, m, c, exercise_every, 1))) return rc;  // REPLAY noise, n_partials and the scalars: its words
+  const uint64_t n_outer = c->n_paths;
+  const size_t n_cont = (size_t)n_dates * n_outer;
+  const uint32_t ch = hh::lsm_chunks(n_outer);
+  if ((rc = ensure(ctx, ctx->bounds_cont, 2 * n_cont))) return rc;
+  if ((rc = ensure(ctx, ctx->lsm_val, (size_t)n_outer))) return rc;
+  if ((rc = ensure(ctx, ctx->lsm_tau, (size_t)n_outer))) return rc;
+  if ((rc = ensure(ctx, ctx->records, (size_t)ch * hh::kRecStride))) return rc;
+  hh::BoundsLaunch b{};
+  b.rows = ctx->lsm_grid;
+  b.n_dates = n_dates;
+  b.n_inner = n_inner;
+  b.degree = degree;
+  b.inner_seed = inner_seed;
+  if ((rc = stage_policy(ctx, policy, hh_lsm_policy_elems(n_dates, 2, degree), n_dates, date_discount, &b.policy, &b.disc_pow)))
+    return rc;
+  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+  struct EventGuard {
+    hipEvent_t* e;
+    ~EventGuard() { for (int k = 0; k < 3; ++k) if (e[k]) (void)hipEventDestroy(e[k]); }
+  } guard{ev};
+  for (int k = 0; k < 3; ++k) HH_HIP(ctx, hipEventCreate(&ev[k]));
+  double* const cont_dev = ctx->bounds_cont;
+  double* const se_dev = ctx->bounds_cont + n_cont;
+  if ((rc = begin_timing(ctx))) return rc;
+  HH_HIP(ctx, hipEventRecord(ev[0], ctx->stream));
+  HH_HIP(ctx, hh::launch_nested_continuation(*m, *c, b, cont_dev, se_dev, ctx->stream));
+  HH_HIP(ctx, hipEventRecord(ev[1], ctx->stream));
+  if ((rc = end_timing(ctx))) return rc;
+  HH_HIP(ctx, hh::launch_dual_outer(*m, *c, b, cont_dev, ctx->lsm_val, ctx->stream));
+  HH_HIP(ctx, hipEventRecord(ev[2], ctx->stream));
+  // the mean of pathwise_max and its standard error by the inductions' final kernel at τ = 0, and the record reduction
+  HH_HIP(ctx, hipMemsetAsync(ctx->lsm_tau, 0, n_outer * sizeof(int32_t), ctx->stream));
+  HH_HIP(ctx, hh::launch_lsm_final(ctx->lsm_tau, ctx->lsm_val, n_outer, 0.0, ctx->records, ctx->stream));
+  HH_HIP(ctx, hh::launch_reduce_records(ctx->records, ch, (double)n_outer, ctx->accum, ctx->stream));
+  HH_HIP(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+  HH_HIP(ctx, hipMemcpyAsync(ctx->accum_host, ctx->accum, HH_ACC_LEN * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  if (cont) HH_HIP(ctx, hipMemcpyAsync(cont, cont_dev, n_cont * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  if (cont_se) HH_HIP(ctx, hipMemcpyAsync(cont_se, se_dev, n_cont * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  if (pathwise_max)
+    HH_HIP(ctx, hipMemcpyAsync(pathwise_max, ctx->lsm_val, n_outer * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  HH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  if ((rc = release_host_operands(ctx))) return rc;
+  hh_lsm_result mean{};
+  if ((rc = hh_lsm_finalize(ctx->accum_host, &mean))) return finalize_failed(ctx, rc);
+  std::memset(out, 0, sizeof(*out));
+  out->upper = mean.price;
+  out->upper_se = mean.std_error;
+  out->n_outer = n_outer;
+  out->n_inner = n_inner;
+  float ms = 0.f;
+  HH_HIP(ctx, hipEventElapsedTime(&ms, ev[0], ev[1]));
+  out->nested_ms = ms;
+  HH_HIP(ctx, hipEventElapsedTime(&ms, ev[1], ev[2]));
+  out->outer_ms = ms;
+  out->total_ms = clock.ms();
+  return HH_OK;
 }
 
 // ---- multilevel Monte Carlo (hedgehog_mc.h, "Multilevel Monte Carlo"; kernels: hh_path.hip) ----

@@ -59,6 +59,8 @@ struct hh_ctx {
   DevBuf<double> lsm_val;
   DevBuf<int32_t> lsm_tau;
   DevBuf<double> lsm_scratch;
+  DevBuf<double> lsm_policy;   // a policy [n_dates + 1][2m + B], then D^k, k = 0 .. n_dates (hh_lsm_policy_value, hh_lsm_upper_bound)
+  DevBuf<double> bounds_cont;  // [2][n_dates][n_outer]: the nested continuation values, then their standard errors
   // sharded LSM in progress (hh_lsm_shard_begin .. hh_lsm_shard_finish)
   struct {
     bool active = false;

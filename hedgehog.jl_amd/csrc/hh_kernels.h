@@ -417,6 +417,27 @@ int launch_assets_rows(const hh_model& m, const hh_config& c, const hh_assets& a
 // region holds the fitted coefficients [date][kLsmMultiPad] afterwards; records: lsm_chunks(ntot) x kRecStride.
 int launch_lsm_multi(const hh_lsm_states& desc, const double* rows, uint64_t ntot, uint32_t n_dates, int degree,
                      double date_discount, int32_t* tau, double* val, double* scratch, double* records, hipStream_t s);
+// A policy run forward on such rows (hh_lsm_multi.hip; include/hedgehog_mc.h, "Dual bounds for American exercise"):
+// policy [n_dates + 1][2m + B] on the device; tau, val: ntot entries; records as launch_lsm_multi's.
+int launch_policy_value(const hh_lsm_states& desc, const double* rows, uint64_t ntot, uint32_t n_dates, int degree,
+                        double date_discount, const double* policy, int32_t* tau, double* val, double* records,
+                        hipStream_t s);
+// The dual upper bound's two kernels (hh_bounds.hip) on the (log S, V) rows [n_dates + 1][2][n_outer] of a plain Heston Euler
+// walk (m, c: its model and config, n_outer = c.n_paths; exercise_every = c.n_steps / n_dates).  disc_pow: D^k, k = 0 ..
+// n_dates, on the device.  launch_nested_continuation writes cont and cont_se ([n_dates][n_outer]); launch_dual_outer
+// reads cont and writes pathwise_max (n_outer).  n_dates·n_outer <= 2^31.
+struct BoundsLaunch {
+  const double* rows;
+  const double* policy;    // [n_dates + 1][4 + B], device
+  const double* disc_pow;
+  uint32_t n_dates, n_inner;
+  int degree;
+  uint64_t inner_seed;
+};
+int launch_nested_continuation(const hh_model& m, const hh_config& c, const BoundsLaunch& b, double* cont, double* cont_se,
+                               hipStream_t s);
+int launch_dual_outer(const hh_model& m, const hh_config& c, const BoundsLaunch& b, const double* cont, double* pathwise_max,
+                      hipStream_t s);
 // the final Σ, Σ² kernel of the inductions: per-workgroup sums of exp(ln_disc·tau)·val into lsm_chunks(ntot) records
 int launch_lsm_final(const int32_t* tau, const double* val, uint64_t ntot, double ln_disc, double* records, hipStream_t s);
 // form: kLsmFormPersistent = the whole backward induction in ONE launch when the ensemble fits the

@@ -519,6 +519,65 @@ __global__ __launch_bounds__(256) void multi_disc_kernel(double ln_disc, uint32_
   if (k <= n) out[k] = exp(ln_disc * (double)k);
 }
 
+// ---- a policy run forward (include/hedgehog_mc.h, "Dual bounds for American exercise") -----------------------------------
+
+struct PolicyArgs {
+  const double* rows;    // [n_dates + 1][m][ntot]
+  const double* policy;  // [n_dates + 1][2m + B]: μ_i, isd_i, coef_j of every date
+  uint64_t ntot;
+  uint32_t n_dates;
+  int32_t B, p;          // p: the degree
+  StatesDesc d;
+  int32_t* tau;
+  double* val;
+  uint32_t expo[kPad];
+};
+
+// One lane per column, dates 1 .. n_dates in order: the first date the policy exercises, else expiry.  The fitted value is
+// multi_step_kernel's, statement for statement — z_i from (μ_i, isd_i), c_0·φ_0, then fma in basis order, φ by lsm_phi — so
+// on the rows a policy was fitted on a column stops where the induction stopped it.  Memory-bound: a date's m rows are
+// read once, a wave's 64 columns one line each; the date's policy sits at a wave-uniform address (scalar loads).  A lane
+// that has stopped leaves; no sum is formed here (launch_lsm_final has the induction's).
+template <int M>
+__global__ __launch_bounds__(256) void policy_value_kernel(const PolicyArgs a) {
+  constexpr int P = lsm_max_degree(M);
+  const uint64_t col = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (col >= a.ntot) return;
+  const int stride = 2 * M + a.B;
+  int tau = (int)a.n_dates;
+  double val = 0.0;
+  double xn[M];  // the next date's states, asked for one date ahead: the loads travel while this date is evaluated
+#pragma unroll
+  for (int i = 0; i < M; ++i) xn[i] = a.rows[((size_t)M + i) * a.ntot + col];
+  for (uint32_t t = 1; t <= a.n_dates; ++t) {
+    double x[M], v[M], z[M], pay;
+#pragma unroll
+    for (int i = 0; i < M; ++i) x[i] = xn[i];
+    if (t < a.n_dates) {  // uniform
+      const double* r = a.rows + ((size_t)(t + 1) * M) * a.ntot + col;
+#pragma unroll
+      for (int i = 0; i < M; ++i) xn[i] = r[(size_t)i * a.ntot];
+    }
+    column_of<M>(a.d, x, pay, v);
+    if (t == a.n_dates) {  // uniform
+      val = pay > 0.0 ? pay : 0.0;
+      break;
+    }
+    const double* __restrict__ pol = a.policy + (size_t)t * stride;
+#pragma unroll
+    for (int i = 0; i < M; ++i) z[i] = (v[i] - pol[i]) * pol[M + i];
+    double cont = pol[2 * M] * lsm_phi<M, P>(1.0, z, a.expo[0], a.p);
+    for (int j = 1; j < a.B; ++j) cont = fma(pol[2 * M + j], lsm_phi<M, P>(1.0, z, a.expo[j], a.p), cont);
+    if (pay > 0.0 && pay > cont) {
+      tau = (int)t;
+      val = pay;
+      break;
+    }
+  }
+  a.tau[col] = tau;
+  a.val[col] = val;
+}
+
 template <class F>
 inline void with_m(int m, F&& f) {
   switch (m) {
@@ -586,6 +645,28 @@ int launch_lsm_multi(const hh_lsm_states& desc, const double* rows, uint64_t nto
   e = hipGetLastError();
   if (e != hipSuccess) return (int)e;
   return launch_lsm_final(tau, val, ntot, ln_disc, records, s);
+}
+
+// A policy ([n_dates + 1][2m + B], device) run forward on `rows`: tau / val of every column, then the induction's final
+// Σ, Σ² kernel into records (lsm_chunks(ntot) × kRecStride).  The entry points have checked every argument.
+int launch_policy_value(const hh_lsm_states& desc, const double* rows, uint64_t ntot, uint32_t n_dates, int degree,
+                        double date_discount, const double* policy, int32_t* tau, double* val, double* records,
+                        hipStream_t s) {
+  const int m = (int)desc.n_states;
+  PolicyArgs a{};
+  a.B = lsm_basis_fill(m, degree, a.expo);
+  if (a.B == 0) return (int)hipErrorInvalidValue;
+  a.rows = rows; a.policy = policy; a.ntot = ntot; a.n_dates = n_dates; a.p = degree;
+  a.d.kind = desc.kind; a.d.index_kind = desc.index_kind; a.d.cp = desc.cp; a.d.strike = desc.strike;
+  for (int i = 0; i < m; ++i) a.d.c.w[i] = desc.weights[i];
+  a.tau = tau; a.val = val;
+  with_m(m, [&](auto mc) {
+    constexpr int M = decltype(mc)::value;
+    hipLaunchKernelGGL(policy_value_kernel<M>, dim3((unsigned)((ntot + 255) / 256)), dim3(256), 0, s, a);
+  });
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return (int)e;
+  return launch_lsm_final(tau, val, ntot, log(date_discount), records, s);
 }
 
 }  // namespace hh

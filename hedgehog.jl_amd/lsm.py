@@ -24,7 +24,13 @@ multiasset.solve_index_lsm's: the assets' state rows and a regression on all mon
 Under stochastic volatility the spot alone does not carry the continuation value.  regressors="spot_variance" regresses on
 all monomials of the standardised spot AND variance up to `degree` (`hh_lsm_solve_path_states`: the walk's (log S, V) rows,
 then the several-variable induction at m = 2) — on HestonDynamics + EulerMaruyama under path_state="spot", on HestonQE and
-on Bates.  The default, regressors="spot", is every path above, unchanged.  simulate_state_paths returns the rows."""
+on Bates.  The default, regressors="spot", is every path above, unchanged.  simulate_state_paths returns the rows.
+
+Each of these prices is in sample: the policy is valued on the trajectories it was fitted on.  fit_policy keeps the (S, V)
+policy as an ExercisePolicy (`hh_lsm_fit_path_states`), policy_value runs it forward on other seeds — a lower bound
+(`hh_lsm_policy_value_path`) — and upper_bound builds the Andersen–Broadie martingale from nested Heston Euler walks
+(`hh_lsm_upper_bound`); solve(prob, DualBounds(LSM(...), outer=, inner=, fresh=, inner_seed=), exercise_every=m) does the three
+and returns the bracket (BoundsSolution)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -312,6 +318,221 @@ def solve_lsm(prob: PricingProblem, method: LSM, spot_paths: bool = False,
                                        step_discount, C.byref(res), *outs))
     return LSMSolution(prob, method, res.price, (tau, val) if stopping_info else None, grid,
                        std_error=res.std_error, result=res)
+
+
+# ---- dual bounds: the policy as an object, its value on other seeds, the nested upper bound -------------------------------------
+
+@dataclass(frozen=True)
+class ExercisePolicy:
+    """What an LSM fit decides by, free of the paths it was fitted on (hh_lsm_fit_path_states): `array` is the (dates + 1,
+    2·m + B) matrix of the header's "Dual bounds for American exercise" — per date μ_i, isd_i of the m regressors, then the B
+    coefficients; `discount` is the discount over one exercise period.  Any finite array of that shape is a policy.
+    fit_seeds: the seeds the fit ran on (None for a hand-made policy); in_sample: the fit's LSMSolution."""
+    array: Any
+    m: int
+    degree: int
+    dates: int
+    discount: float
+    exercise_every: int = 1
+    fit_seeds: Any = field(default=None, compare=False, repr=False)
+    in_sample: Any = field(default=None, compare=False, repr=False)
+
+    def __post_init__(self):
+        from .multiasset import basis_count
+        a = np.ascontiguousarray(self.array, dtype=np.float64)
+        if a.shape != (self.dates + 1, 2 * self.m + basis_count(self.m, self.degree)):
+            raise ValueError(f"a policy of {self.dates} dates, m = {self.m}, degree {self.degree} is a "
+                             f"({self.dates + 1}, {2 * self.m + basis_count(self.m, self.degree)}) array, not {a.shape}")
+        if not np.all(np.isfinite(a)):
+            raise ValueError("a policy holds finite numbers only")
+        object.__setattr__(self, "array", a)
+
+
+@dataclass(frozen=True)
+class DualBounds(AbstractPricingMethod):
+    """solve(prob, DualBounds(LSM(...), outer=, inner=, fresh=, inner_seed=), exercise_every=m): the LSM policy fitted on the
+    LSM config's seeds, valued on the `fresh` seeds (a lower bound) and bounded from above on the `outer` seeds with `inner`
+    nested walks per date and outer column (Andersen–Broadie).  fresh, outer: seed arrays, or a count n — then the n seeds
+    after the largest one used so far.  inner: a multiple of 64."""
+    lsm: LSM
+    outer: Any = 4096
+    inner: int = 256
+    fresh: Any = None
+    inner_seed: int = 1
+
+    def __init__(self, lsm, outer=4096, inner=256, fresh=None, inner_seed=1):
+        for k, v in (("lsm", lsm), ("outer", outer), ("inner", int(inner)), ("fresh", fresh), ("inner_seed", int(inner_seed))):
+            object.__setattr__(self, k, v)
+
+    @property
+    def mc_method(self):  # what routes.refuse_other_methods looks an LSM's walk up by
+        return getattr(self.lsm, "mc_method", None)
+
+
+@dataclass(frozen=True)
+class BoundsSolution:
+    """lower ± lower_se: the fitted policy on fresh paths; upper ± upper_se: the dual bound; in_sample: the LSM price on the
+    fitted paths (neither bound); gap = upper − lower, gap_se = sqrt(upper_se² + lower_se²) — the seed sets are disjoint."""
+    problem: Any
+    method: Any
+    lower: float
+    lower_se: float
+    upper: float
+    upper_se: float
+    in_sample: float
+    in_sample_se: float
+    gap: float
+    gap_se: float
+    policy: Any = field(default=None, compare=False, repr=False)
+    result: Any = field(default=None, compare=False, repr=False)
+
+
+def _american_vanilla(prob):
+    if not (isinstance(prob.payoff, VanillaOption) and isinstance(prob.payoff.exercise_style, American)):
+        raise MethodError("an exercise policy needs an American VanillaOption")
+
+
+def _policy_degree(degree):
+    from .multiasset import basis_count  # C(2 + degree, degree) <= HH_LSM_MAX_BASIS
+    if not 1 <= degree <= 8 or basis_count(2, degree) > _ffi.HH_LSM_MAX_BASIS:
+        raise MethodError(f"LSM on (S, V) at degree {degree}: 1 <= degree <= 8 (C(2 + degree, degree) <= "
+                          f"{_ffi.HH_LSM_MAX_BASIS} basis functions)")
+
+
+def _with_seeds(method: LSM, seeds) -> LSM:
+    """`method` on other seeds: as many trajectories as seeds"""
+    import dataclasses
+    mc = method.mc_method
+    seeds = np.ascontiguousarray(seeds, dtype=np.uint64)
+    cfg = mc.config.replace(trajectories=int(seeds.size), seeds=seeds)
+    return LSM(dataclasses.replace(mc, config=cfg), method.degree)
+
+
+def _refuse_shared_seeds(what, seeds, fit_seeds):
+    if fit_seeds is not None and np.intersect1d(np.asarray(seeds, dtype=np.uint64), np.asarray(fit_seeds, dtype=np.uint64)).size:
+        raise MethodError(f"{what} seeds coincide with the seeds the policy was fitted on: the value of a policy on its own paths "
+                          "is no lower bound (look-ahead bias) — hand in other seeds")
+
+
+def fit_policy(prob: PricingProblem, method: LSM, exercise_every=1, regressors="spot_variance", path_state="spot") -> ExercisePolicy:
+    """The LSM induction of solve(prob, method, regressors="spot_variance", …) with its policy kept (hh_lsm_fit_path_states):
+    HestonDynamics + EulerMaruyama, HestonQE and Bates."""
+    if regressors != "spot_variance":
+        raise MethodError('fit_policy keeps the policy of the regression on (S, V): regressors="spot_variance" (the one-variable '
+                          "inductions keep none)")
+    mc = method.mc_method
+    source, model, c, T, n_dates = _state_structs(prob, mc, exercise_every, path_state)
+    _american_vanilla(prob)
+    _policy_degree(method.degree)
+    D = _date_discount(prob.market_inputs, T, mc.config.steps, int(exercise_every))
+    from .multiasset import basis_count
+    array = np.empty((n_dates + 1, 4 + basis_count(2, method.degree)))
+    res = _ffi.hh_lsm_result()
+    ctx = _ffi.get_context(mc.device)
+    ctx.check(ctx.lib.hh_lsm_fit_path_states(ctx.handle, C.byref(source), C.byref(model), C.byref(c), int(exercise_every),
+                                             method.degree, D, C.byref(res), array.ctypes.data))
+    sol = LSMSolution(prob, method, res.price, None, None, std_error=res.std_error, result=res)
+    return ExercisePolicy(array, 2, method.degree, n_dates, D, int(exercise_every), np.array(mc.config.seeds, dtype=np.uint64), sol)
+
+
+def _check_policy_fits(policy: ExercisePolicy, method: LSM, n_dates, exercise_every, D):
+    if not isinstance(policy, ExercisePolicy):
+        raise TypeError("policy must be an ExercisePolicy")
+    if policy.m != 2:
+        raise MethodError(f"a policy in {policy.m} regressors does not decide on (S, V) rows: m = 2")
+    if (policy.dates, policy.degree) != (n_dates, method.degree):
+        raise MethodError(f"the policy has {policy.dates} dates at degree {policy.degree}; the method asks for {n_dates} dates "
+                          f"(steps / exercise_every) at degree {method.degree}")
+    if abs(policy.discount - D) > 1e-12 * D:
+        raise MethodError(f"the policy discounts an exercise period by {policy.discount!r}, the problem by {D!r}")
+
+
+def policy_value(prob: PricingProblem, method: LSM, policy: ExercisePolicy, seeds=None, exercise_every=None,
+                 path_state="spot") -> LSMSolution:
+    """The policy run forward on the walk of `method` on `seeds` (default: the method's own) through hh_lsm_policy_value_path:
+    with seeds other than the fit's, an out-of-sample LOWER bound.  Seeds the policy was fitted on are refused."""
+    every = policy.exercise_every if exercise_every is None and isinstance(policy, ExercisePolicy) else (exercise_every or 1)
+    if seeds is not None:
+        method = _with_seeds(method, seeds)
+    mc = method.mc_method
+    source, model, c, T, n_dates = _state_structs(prob, mc, every, path_state)
+    _american_vanilla(prob)
+    _policy_degree(method.degree)
+    D = _date_discount(prob.market_inputs, T, mc.config.steps, int(every))
+    _check_policy_fits(policy, method, n_dates, every, D)
+    _refuse_shared_seeds("policy_value:", mc.config.seeds[:mc.config.trajectories], policy.fit_seeds)
+    res = _ffi.hh_lsm_result()
+    ctx = _ffi.get_context(mc.device)
+    ctx.check(ctx.lib.hh_lsm_policy_value_path(ctx.handle, C.byref(source), C.byref(model), C.byref(c), int(every),
+                                               policy.array.ctypes.data, method.degree, D, C.byref(res)))
+    return LSMSolution(prob, method, res.price, None, None, std_error=res.std_error, result=res)
+
+
+def upper_bound(prob: PricingProblem, method: LSM, policy: ExercisePolicy, outer, inner=256, inner_seed=1, exercise_every=None,
+                want_cont=False):
+    """The dual upper bound of `policy` on the outer seeds (hh_lsm_upper_bound): HestonDynamics + EulerMaruyama, plain paths.
+    Returns the hh_bounds_result, and with want_cont (cont, cont_se, pathwise_max) beside it."""
+    every = policy.exercise_every if exercise_every is None and isinstance(policy, ExercisePolicy) else (exercise_every or 1)
+    routes().bounds_route_of(prob.market_inputs, method.mc_method)
+    method = _with_seeds(method, outer)
+    mc = method.mc_method
+    if isinstance(mc.config.variance_reduction, Antithetic):
+        raise MethodError("DualBounds: antithetic outer paths are not offered (the martingale is built per outer column): use "
+                          "NoVarianceReduction()")
+    if int(inner) <= 0 or int(inner) % 64:
+        raise MethodError(f"DualBounds: inner ({inner}) must be a multiple of 64 and >= 64")
+    source, model, c, T, n_dates = _state_structs(prob, mc, every, "spot")
+    _american_vanilla(prob)
+    _policy_degree(method.degree)
+    D = _date_discount(prob.market_inputs, T, mc.config.steps, int(every))
+    _check_policy_fits(policy, method, n_dates, every, D)
+    n = mc.config.trajectories
+    cont = np.empty((n_dates, n)) if want_cont else None
+    cont_se = np.empty((n_dates, n)) if want_cont else None
+    pmax = np.empty(n) if want_cont else None
+    res = _ffi.hh_bounds_result()
+    ctx = _ffi.get_context(mc.device)
+    ctx.check(ctx.lib.hh_lsm_upper_bound(ctx.handle, C.byref(model), C.byref(c), int(every), policy.array.ctypes.data,
+                                         method.degree, D, int(inner), int(inner_seed) & (2**64 - 1), C.byref(res),
+                                         cont.ctypes.data if want_cont else None, cont_se.ctypes.data if want_cont else None,
+                                         pmax.ctypes.data if want_cont else None))
+    return (res, cont, cont_se, pmax) if want_cont else res
+
+
+def _seed_set(spec, used_max, what):
+    """a seed array as given, or the `spec` seeds after used_max"""
+    if spec is None:
+        raise MethodError(f"DualBounds needs {what}: a seed array, or a count")
+    if np.ndim(spec) == 0:
+        n = int(spec)
+        if n < 1:
+            raise MethodError(f"DualBounds: {what} must hold at least one seed")
+        return np.arange(used_max + 1, used_max + 1 + n, dtype=np.uint64)
+    return np.ascontiguousarray(spec, dtype=np.uint64)
+
+
+def solve_dual_bounds(prob: PricingProblem, method: DualBounds, exercise_every=1, path_state="spot") -> BoundsSolution:
+    """fit on the LSM config's seeds, value on `fresh`, bound on `outer` (module docstring of DualBounds)"""
+    lsm = method.lsm
+    if not isinstance(lsm, LSM):
+        raise MethodError("DualBounds(LSM(...), outer=, inner=, fresh=, inner_seed=)")
+    routes().bounds_route_of(prob.market_inputs, lsm.mc_method)  # a route that cannot serve says so before anything runs
+    if isinstance(lsm.mc_method.config.variance_reduction, Antithetic):
+        raise MethodError("DualBounds: antithetic outer paths are not offered (the martingale is built per outer column): use "
+                          "NoVarianceReduction()")
+    if int(method.inner) <= 0 or int(method.inner) % 64:
+        raise MethodError(f"DualBounds: inner ({method.inner}) must be a multiple of 64 and >= 64")
+    fit_seeds = np.asarray(lsm.mc_method.config.seeds, dtype=np.uint64)
+    fresh = _seed_set(method.fresh if method.fresh is not None else lsm.mc_method.config.trajectories, int(fit_seeds.max()), "fresh")
+    outer = _seed_set(method.outer, int(max(fit_seeds.max(), fresh.max())), "outer")
+    _refuse_shared_seeds("DualBounds: the fresh", fresh, fit_seeds)
+    _refuse_shared_seeds("DualBounds: the outer", outer, fit_seeds)
+    policy = fit_policy(prob, lsm, exercise_every, "spot_variance", path_state)
+    low = policy_value(prob, lsm, policy, seeds=fresh, path_state=path_state)
+    up = upper_bound(prob, lsm, policy, outer, method.inner, method.inner_seed)
+    ins = policy.in_sample
+    return BoundsSolution(prob, method, low.price, low.std_error, up.upper, up.upper_se, ins.price, ins.std_error,
+                          up.upper - low.price, float(np.hypot(up.upper_se, low.std_error)), policy, up)
 
 
 @dataclass(frozen=True)

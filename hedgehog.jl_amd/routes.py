@@ -71,6 +71,7 @@ class Route:
     solve_all: Callable = None       # (payoffs, market_inputs, method, ensemble): a grouping of its own, for one payoff or many
     own_lsm: bool = False            # an LSM on the route's own triple has an induction of its own (no date rows of one spot)
     state_rows: bool = False         # the walk holds a variance: (log S, V) rows (hh_mc_path_states) and an LSM on (S, V)
+    nested_walk: bool = False        # the walk restarts from stored (log S, V) states: the dual upper bound (hh_lsm_upper_bound)
     # ---- what it refuses, and in which words ----
     early: tuple = ()                # of the four checks above, in the route's order; `admitted` elsewhere: with the structs
     no_replay: str = None
@@ -241,7 +242,8 @@ VG_LAW = dataclasses.replace(  # one European vanilla on the spot: the law at ex
 
 EULER = Route(  # a path-dependent payoff on the Euler paths of the plain models; vanillas of its basket: the plain route's
     "Euler paths", lambda payoffs, m, method: any(isinstance(p, PATH_PAYOFFS) for p in payoffs),
-    entry="hh_mc_solve_path", entry_ex="hh_mc_solve_path_ex", source=_ffi.HH_SOURCE_EULER, early=(euler_paths, one_device),
+    entry="hh_mc_solve_path", entry_ex="hh_mc_solve_path_ex", source=_ffi.HH_SOURCE_EULER, nested_walk=True,
+    early=(euler_paths, one_device),
     no_replay="path-dependent payoffs draw their own noise: no replay",
     one_device="path-dependent payoffs run on one device (MonteCarlo.devices is not supported)",
     no_duals="path-dependent payoffs carry no dual partials: use FiniteDifference")
@@ -272,6 +274,29 @@ def lsm_route_of(market_inputs, mc) -> Route:
 
 
 STATE_ROWS = "HestonDynamics() + EulerMaruyama() (under path_state=\"spot\"), HestonQE and Bates"  # the walks with a variance
+
+
+NESTED_WALKS = "HestonDynamics() + EulerMaruyama()"  # the walks hh_lsm_upper_bound restarts from stored states
+
+
+def bounds_route_of(market_inputs, mc) -> Route:
+    """The route whose walk serves DualBounds on `mc`: the lower bound needs state rows, the upper bound a nested walk.  A route
+    that cannot serve raises MethodError naming what is missing."""
+    if own_lsm_route_of(market_inputs, mc) is not None:
+        raise MethodError("DualBounds: the several-asset walk has no variance rows and no nested walk; the bounds need " + NESTED_WALKS)
+    route = lsm_route_of(market_inputs, mc)
+    if route is None:
+        if isinstance(mc.strategy, EulerMaruyama) and isinstance(mc.dynamics, HestonDynamics):
+            return EULER
+        raise MethodError(f"DualBounds: {type(mc.dynamics).__name__} + {type(mc.strategy).__name__} has no variance rows and no "
+                          "nested walk; the bounds need " + NESTED_WALKS)
+    if not route.state_rows:
+        raise MethodError(f"DualBounds: the walk of {route.name} has no variance rows (and no nested walk); the bounds need "
+                          + NESTED_WALKS)
+    if not route.nested_walk:
+        raise MethodError(f"DualBounds: {route.name} has state rows (fit_policy and policy_value serve it) but no nested walk: "
+                          "the upper bound needs " + NESTED_WALKS)
+    return route
 
 
 def own_lsm_route_of(market_inputs, mc) -> Route:

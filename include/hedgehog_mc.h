@@ -1591,6 +1591,88 @@ int hh_lsm_solve_path_states(hh_ctx* ctx, const hh_path_source* source, const hh
                              int32_t* stop_time, double* stop_value, double* coef, double* rows);
 
 /*
+ * Dual bounds for American exercise: the fitted policy as an array, its value on other paths (a lower bound) and the
+ * Andersen–Broadie (2004) upper bound by nested simulation (kernels: policy_value_kernel, hh_lsm_multi.hip;
+ * nested_continuation_kernel and dual_outer_kernel, hh_bounds.hip).
+ *
+ * A POLICY is a date-major host array of hh_lsm_policy_elems(n_dates, m, degree) = (n_dates + 1)·(2m + B) doubles, B =
+ * C(m + degree, degree) (0 where hh_lsm_solve_states admits no such basis):
+ *   policy[t·(2m + B) + i]            μ_i of date t, i < m
+ *   policy[t·(2m + B) + m + i]        isd_i of date t
+ *   policy[t·(2m + B) + 2m + j]       coef_j of date t, j < B, the layout of hh_lsm_solve_states' coef
+ * Dates where no fit ran (date 0, date n_dates, a date with no column in the money) hold μ = 0, isd = 1, coef = 0.  THE
+ * RULE a policy states, at date t = 1 .. n_dates − 1 on a column with exercise value pay and regressors v_i:
+ *   z_i = (v_i − μ_i)·isd_i;  fit = c_0·φ_0 + fma(c_j, φ_j, ·) in basis order (φ by csrc/hh_lsm_basis.h's lsm_phi);
+ *   exercise where pay > 0 and pay > fit;  at date n_dates: stop with max(pay, 0).
+ * Any finite array is a policy, not only a fitted one: all zeros exercises at the first date in the money, c_0 = 1e300 on
+ * every date never exercises before expiry.
+ *
+ * hh_lsm_fit_states — hh_lsm_solve_states' induction, unchanged, and one more copy: μ_i and isd_i of every regressed date
+ * beside the coefficients.  out, stop_time, stop_value and the coef part of policy are hh_lsm_solve_states' on the same
+ * rows bit for bit.  hh_lsm_fit_path_states — hh_mc_path_states' rows into the context, then that fit under
+ * {HH_LSM_STATES_LOG_SPOT_VARIANCE, 2, cp and strike of the model}: hh_lsm_solve_path_states with the policy.
+ *
+ * hh_lsm_policy_value — THE RULE run forward on the device rows rows_dev[n_dates + 1][m][n_total], one lane per column
+ * from date 1: the first date the policy exercises, else expiry.  stop_time, stop_value (nullable, host, n_total) and out
+ * (price = mean(date_discount^τ·val), by the inductions' final kernel) as hh_lsm_solve_states'; rows_regressed and
+ * rows_skipped are 0.  On the rows a policy was fitted on it reproduces the induction's stop_time, stop_value and price
+ * bit for bit; on rows of other seeds the price is a LOWER bound in expectation (the policy does not see them).  No
+ * atomics: the same inputs give the same bits.  hh_lsm_policy_value_path — hh_mc_path_states' rows (HH_SOURCE_EULER under
+ * Heston dynamics, HH_SOURCE_QE, HH_SOURCE_BATES) on cfg's seeds into the context, then that valuation at m = 2.  Timing:
+ * one slot for the valuation (the forward kernel and the final kernel), before it one for the rows of the _path form.
+ *
+ * hh_lsm_upper_bound — the dual bound.  Outer pass: hh_mc_path_states' rows of HH_SOURCE_EULER under Heston dynamics on
+ * cfg_outer's n_outer = n_paths seeds, plain (no antithetic pairs), kept on the device.  Nested pass: for every date t = 0 ..
+ * n_dates − 1 and outer column i, n_inner (a multiple of 64) walks restart from the stored (x, v) of (t, i), take steps
+ * t·exercise_every .. n_steps − 1 of the same Euler step, follow THE RULE from date t + 1 and keep y = date_discount^(τ − t)
+ * ·val;  cont[t·n_outer + i] = Ĉ = Σy/n_inner and cont_se[…] = sqrt(max(Σy² − n_inner·Ĉ², 0)/(n_inner·(n_inner − 1))).
+ * INNER KEYS: walk j of (t, i) draws step s from Philox key
+ *   key = mix(mix(inner_seed + 0x9E3779B97F4A7C15·(i + 1)) ^ (t·2^32 + j)),
+ *   mix(z): z = (z ^ z >> 30)·0xBF58476D1CE4E5B9; z = (z ^ z >> 27)·0x94D049BB133111EB; z ^ z >> 31   (mod 2^64)
+ * at counter (s + 2^31, 0, 0, domain 0): an outer walk's counters are (s, 0, 0, 0) with s < 2^31, so no inner draw is an
+ * outer draw whatever the seeds.  Outer recursion, per column, D = date_discount, M_0 = 0:
+ *   L_t = pay_t where the policy exercises at t (t = n_dates: max(pay_t, 0)), else Ĉ[t];
+ *   M_t = M_{t−1} + D^t·L_t − D^{t−1}·Ĉ[t−1];   pathwise_max[i] = max over t = 0 .. n_dates of D^t·max(pay_t, 0) − M_t
+ * upper = mean(pathwise_max), upper_se its standard error, by the inductions' final kernel and record reduction.  By
+ * Jensen's inequality the inner noise biases upper UPWARD only: it stays an upper bound in expectation for every n_inner.
+ * cont, cont_se (n_dates·n_outer), pathwise_max (n_outer): nullable, host.  The same inputs give the same bits.  Timing:
+ * one slot for the rows, one for the nested kernel.
+ *
+ * All synchronous.  Errors, checked on the host before any launch, in hh_lsm_solve_path_states' words wherever the check
+ * is the same; a refusal uses no timing slot.  HH_ERR_INVALID: a NULL ctx, desc, rows_dev, source, model, cfg, policy or
+ * out; exercise_every = 0 or not a divisor of n_steps; degree, date_discount, cp, strike, the descriptor and the sizes as
+ * hh_lsm_solve_states checks them; n_inner = 0 or not a multiple of 64; a policy entry that is not finite; n_dates·n_outer
+ * above 2^31.  HH_ERR_UNSUPPORTED: more than HH_LSM_MAX_BASIS basis functions; the sources hh_mc_path_states refuses;
+ * for hh_lsm_upper_bound everything but Heston dynamics by Euler–Maruyama, antithetic outer paths, REPLAY noise,
+ * n_partials > 0.
+ * Not provided: nested walks for QE, Bates, the several-asset walk and the one-variable spot grid; antithetic, sharded or
+ * multi-GPU forms; sub-simulation savings (skipping Ĉ where exercise is clearly suboptimal); a Julia binding.
+ */
+typedef struct hh_bounds_result {     /* 56 bytes */
+  double upper, upper_se;
+  uint64_t n_outer;
+  uint32_t n_inner, reserved;
+  double nested_ms, outer_ms;         /* nested_continuation_kernel, dual_outer_kernel */
+  double total_ms;
+} hh_bounds_result;
+size_t hh_lsm_policy_elems(uint32_t n_dates, uint32_t m, int32_t degree);
+int hh_lsm_fit_states(hh_ctx* ctx, const hh_lsm_states* desc, const double* rows_dev, uint64_t n_total, uint32_t n_dates,
+                      int32_t degree, double date_discount, hh_lsm_result* out, int32_t* stop_time, double* stop_value,
+                      double* policy);
+int hh_lsm_fit_path_states(hh_ctx* ctx, const hh_path_source* source, const hh_model* model, const hh_config* cfg,
+                           uint32_t exercise_every, int32_t degree, double date_discount, hh_lsm_result* out,
+                           double* policy);
+int hh_lsm_policy_value(hh_ctx* ctx, const hh_lsm_states* desc, const double* policy, int32_t degree,
+                        const double* rows_dev, uint64_t n_total, uint32_t n_dates, double date_discount,
+                        hh_lsm_result* out, int32_t* stop_time, double* stop_value);
+int hh_lsm_policy_value_path(hh_ctx* ctx, const hh_path_source* source, const hh_model* model, const hh_config* cfg,
+                             uint32_t exercise_every, const double* policy, int32_t degree, double date_discount,
+                             hh_lsm_result* out);
+int hh_lsm_upper_bound(hh_ctx* ctx, const hh_model* model, const hh_config* cfg_outer, uint32_t exercise_every,
+                       const double* policy, int32_t degree, double date_discount, uint32_t n_inner, uint64_t inner_seed,
+                       hh_bounds_result* out, double* cont, double* cont_se, double* pathwise_max);
+
+/*
  * A SimulationConfig's seed vector in the device memory of ctx, uploaded once and kept — repeated solves on one
  * config (finite-difference Greeks, calibration loops) would otherwise move 8 MB per 10^6 trajectories at
  * every call, about a third of a GENERATE solve of that size.  The reference reads seeds[i] at every solve
